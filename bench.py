@@ -15,10 +15,15 @@ with 100 (README.md:57, BASELINE.json configs[0]).  All three are timed in every
 run and reported under `by_ntransitions`; the headline (`value`, `roofline`) is the
 one --ntransitions selects (default 100) and says so in `config`.
 
-Timed region: W warm-up steps, then blocks of EXACTLY K steps, each block bracketed
-by a barrier + stream synchronisation on both sides; blocks are repeated until at
-least --min-seconds of device work has been timed (so that an external sampler sees
-the GPU busy); `ms_per_step` is the mean over all timed steps.
+Timed region: after WARM_SECONDS of the same work on a scratch ensemble (the clocks come
+up), W warm-up steps, then EXACTLY K timed steps (--steps K), bracketed by a
+barrier + stream synchronisation on both sides; `ms_per_step` is their mean.  Only when
+--min-seconds / --headline-seconds are given is the K-step block repeated until that much
+device work has been timed (so that an external sampler sees the GPU busy).
+
+--dump-outputs DIR: after the headline setting's last timed step, the ensemble state a
+caller of that path reads back (positions, log-prior, log-likelihood, counters) is written
+as DIR/<name>.npy in float64.  Inputs are seeded, so equal arguments give equal outputs.
 
 Prints ONE JSON line (rank 0).  `roofline` is for the half-generation kernel:
 algorithmic bytes per launch = rows * ntransitions * 8(3D+4) over the
@@ -49,10 +54,11 @@ D = 8
 NT_SET = (1, 16, 100)
 NT_HEADLINE = 100
 SEED = 1
-HBM_PEAK_GBS = 8000.0   # MI355X spec peak, /opt/skills/guides/MI355X_MICROARCH.md
+HBM_PEAK_GBS = 8000.0   # MI355X spec peak
 SIMDS = 1024            # 256 CUs x 4
-CLOCK_HZ = 2.4e9        # max engine clock, same guide
+CLOCK_HZ = 2.4e9        # max engine clock
 SMC_N, SMC_D = 32768, 16
+WARM_SECONDS = 0.5      # device warm-up before the timed settings (not on the measured ensemble)
 
 
 def build_model(k):
@@ -540,6 +546,35 @@ def cold_spec_child():
     print(json.dumps({"cold_spec": res}), flush=True)
 
 
+DUMP_BYTES = 64 << 20   # --dump-outputs: at most this much in all
+
+
+def dump_outputs(d, ens, counters, rank, world, sharded):
+    """--dump-outputs: the state kabc_ais_get_state returns after the last timed step -- walkers [N][D],
+    logprior [N], loglik [N] in walker-id order -- and counters = (proposals, cost_evals, accepted) since
+    the ensemble was created, all float64.  A sharded rank writes its owned rows as <name>_rank<r>.npy
+    (counters: rank 0, unsuffixed).  Beyond the byte budget a fixed, seeded sample of the rows is written, with its indices in rows.npy."""
+    import numpy as np
+    x, lp, ll = ens.state()[:3]
+    sfx = f"_rank{rank}" if sharded and world > 1 else ""
+    arrays = {"walkers": x, "logprior": lp, "loglik": ll}
+    budget = DUMP_BYTES // (world if sharded else 1)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > budget:
+        n = x.shape[0]
+        m = (budget - 4096) // (total // n + 8)   # (+ the index per row; 4 KiB for the headers and counters)
+        rows = np.sort(np.random.default_rng(SEED).choice(n, m, replace=False))
+        arrays = {name: a[rows] for name, a in arrays.items()}
+        arrays["rows"] = rows.astype(np.float64)
+    arrays = {name + sfx: a for name, a in arrays.items()}
+    if rank == 0:   # (global: summed over the ranks)
+        arrays["counters"] = np.array([counters["proposals"], counters["cost_evals"], counters["accepted"]],
+                                      dtype=np.float64)
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def main():
     if "--cold-spec" in sys.argv:
         return cold_spec_child()
@@ -549,10 +584,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--ntransitions", type=int, default=NT_HEADLINE,
                     help="the setting the headline value is quoted on")
-    ap.add_argument("--min-seconds", type=float, default=1.0,
-                    help="repeat the K-step block until this much has been timed (per setting)")
-    ap.add_argument("--headline-seconds", type=float, default=7.0,
-                    help="timed device work of the headline setting (one uninterrupted stretch)")
+    ap.add_argument("--min-seconds", type=float, default=0.0,
+                    help="repeat the K-step block until this much has been timed (per setting); "
+                         "0: exactly K timed steps")
+    ap.add_argument("--headline-seconds", type=float, default=0.0,
+                    help="the same for the headline setting (one uninterrupted stretch); 0: exactly K timed steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the headline ensemble's state after its last timed step as DIR/<name>.npy")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-alt", action="store_true",
@@ -634,6 +672,9 @@ def main():
             def stats(self):
                 return self.g.stats()
 
+            def state(self):
+                return self.g.state() + (None,)
+
             def set_timing(self, n, stride=1):
                 for sh in self.g.shards:
                     sh.set_timing(n, stride=stride)
@@ -658,6 +699,15 @@ def main():
     n_total = WALKERS_PER_GPU * world
     if not emulate:
         ens = k.AisEnsemble(model, n_total, seed=SEED, ctx=ctx, comm=comm).init()
+        # the chip's clocks come up under sustained load only: WARM_SECONDS of headline generations on
+        # a scratch ensemble of the same model, so that a small K is not timed cold.  Its own walkers
+        # and no collectives: the measured ensemble's trajectory depends on the arguments alone.
+        scratch = k.AisEnsemble(model, WALKERS_PER_GPU, seed=SEED + 1, ctx=ctx).init()
+        t0 = time.perf_counter()
+        while time.perf_counter() - t0 < WARM_SECONDS:
+            scratch.advance(8, nt_head)
+            ctx.synchronize()
+        scratch.close()
 
     def sync():
         ctx.synchronize()
@@ -672,15 +722,17 @@ def main():
             v = comm.allreduce_sum(v)
         return dict(zip(("proposals", "cost_evals", "accepted"), v))
 
-    def timed_region(nt_r, steps, warm):
+    def timed_region(nt_r, steps, warm, min_s):
         ens.advance(warm, nt_r)
         sync()
-        t0 = time.perf_counter()   # calibration block (not reported): how long K steps take
-        ens.advance(steps, nt_r)
-        sync()
-        blocks = max(1, int(math.ceil(args.min_seconds / max(time.perf_counter() - t0, 1e-9))))
-        if comm:   # every rank must run the same number of blocks
-            blocks = int(comm.allreduce_max([float(blocks)])[0])
+        blocks = 1
+        if min_s > 0:
+            t0 = time.perf_counter()   # calibration block (not reported): how long K steps take
+            ens.advance(steps, nt_r)
+            sync()
+            blocks = max(1, int(math.ceil(min_s / max(time.perf_counter() - t0, 1e-9))))
+            if comm:   # every rank must run the same number of blocks
+                blocks = int(comm.allreduce_max([float(blocks)])[0])
         s0 = global_stats()
         # hipEvent pairs on the kernel's stream, one pair per 8 consecutive half-generation
         # launches (a pair per launch adds ~3 us of marker overhead to every figure); with
@@ -717,15 +769,15 @@ def main():
 
     settings = [nt_head] if args.no_alt else sorted(set(NT_SET) | {nt_head})
     regions = {}
-    base_min = args.min_seconds
     for nt_r in settings:
-        # the same K everywhere would make the nt = 1 block 100x shorter; the block count
-        # (min-seconds) evens the timed duration out instead.  The headline setting runs
-        # --headline-seconds without a gap, so that an external sampler with a period of several
-        # seconds sees the GPU busy at least once.
-        args.min_seconds = max(base_min, args.headline_seconds) if nt_r == nt_head else base_min
-        regions[nt_r] = timed_region(nt_r, args.steps, args.warmup if nt_r == nt_head else 5)
-    args.min_seconds = base_min
+        # by default every setting times exactly K steps.  With --min-seconds the block count evens
+        # the timed duration out instead (the same K would make the nt = 1 block 100x shorter), and
+        # the headline setting runs --headline-seconds without a gap, so that an external sampler
+        # with a period of several seconds sees the GPU busy at least once.
+        min_s = max(args.min_seconds, args.headline_seconds) if nt_r == nt_head else args.min_seconds
+        regions[nt_r] = timed_region(nt_r, args.steps, args.warmup if nt_r == nt_head else 5, min_s)
+        if nt_r == nt_head and args.dump_outputs:
+            dump_outputs(args.dump_outputs, ens, global_stats(), rank, world, comm is not None)
 
     def kernel_leg(model, N, Dm, nts=(NT_HEADLINE,)):
         """half-generation kernel time and evals/s of another single-GPU workload"""
