@@ -25,12 +25,15 @@ KABC_HD kabc_u128_t kabc_slot(const kabc_slotwin_t* w, uint32_t j) {
     return kabc_stream_block(w->seed, w->walker, w->t, w->base + j, w->domain);
 }
 
-/* Gamma(shape a, scale 1) using slots [off, off+64) of the window */
-KABC_HD double kabc_sample_gamma1(const kabc_slotwin_t* w, uint32_t off, double a) {
-    double boost = 1.0;
+/* Gamma(shape a, scale 1) using slots [off, off+64) of the window, in two factors: returns the
+ * Marsaglia-Tsang draw G of shape a (a + 1 when a < 1) and sets *logboost = log(U) / a for a < 1
+ * (the boost U^(1/a) of the small shape; 0 otherwise), so that the draw is G exp(*logboost).
+ * kabc_sample_gamma1 multiplies them out; a caller whose draw underflows there keeps the log. */
+KABC_HD double kabc_sample_gamma1_split(const kabc_slotwin_t* w, uint32_t off, double a, double* logboost) {
+    *logboost = 0.0;
     if (a < 1.0) {
         double ub = kabc_u01(kabc_lo64(kabc_slot(w, off + 63u)));
-        boost = kabc_exp(kabc_log(ub) / a);
+        *logboost = kabc_log(ub) / a;
         a += 1.0;
     }
     double d = a - 1.0 / 3.0;
@@ -44,9 +47,16 @@ KABC_HD double kabc_sample_gamma1(const kabc_slotwin_t* w, uint32_t off, double 
         double v = 1.0 + c * z0;
         if (v <= 0.0) continue;
         v = v * v * v;
-        if (kabc_log(u) < 0.5 * z0 * z0 + d - d * v + d * kabc_log(v)) return d * v * boost;
+        if (kabc_log(u) < 0.5 * z0 * z0 + d - d * v + d * kabc_log(v)) return d * v;
     }
-    return d * boost;
+    return d;
+}
+
+/* Gamma(shape a, scale 1) using slots [off, off+64) of the window */
+KABC_HD double kabc_sample_gamma1(const kabc_slotwin_t* w, uint32_t off, double a) {
+    double logboost;
+    const double g = kabc_sample_gamma1_split(w, off, a, &logboost);
+    return (a < 1.0) ? g * kabc_exp(logboost) : g;
 }
 
 /* Poisson(lam) using slots [off, off+64) */

@@ -22,7 +22,46 @@ void set_error(const char* fmt, ...) {
 }
 const char* get_error() { return g_err; }
 
-static double std_normal_cdf(double z) { return 0.5 * std::erfc(-z * M_SQRT1_2); }
+// log Q(z) = log P(Z > z), z >= 0: erfc while it is far from underflow, beyond that Laplace's
+// continued fraction of the Mills ratio, Q(z) = phi(z) / (z + 1/(z + 2/(z + 3/(z + ...))))
+static double std_normal_logq(double z) {
+    if (z == HUGE_VAL) return -HUGE_VAL;
+    if (z < 30.0) return std::log(0.5 * std::erfc(z * M_SQRT1_2));
+    double t = z;
+    for (int n = 64; n >= 1; --n) t = z + n / t;
+    return -0.5 * z * z - 0.5 * KABC_LOG_2PI - std::log(t);
+}
+
+// log(Phi(b) - Phi(a)), a < b: the truncated Normal's log-mass, without cancellation or underflow.
+// Mirrored so that b > 0; a window across 0 is a sum of two erf values of either sign; a narrow
+// window, (b - a)(b + a) <= 2, is phi(a) times the integral of exp(-(z - a)(z + a) / 2) over it
+// (16-point Gauss-Legendre: the integrand is within [e^-1, 1]); a wider one is Q(a) (1 - Q(b) / Q(a))
+// with Q(b) / Q(a) <= e^-1, in logs.
+static double std_normal_logmass(double a, double b) {
+    static const double X[8] = {0x1.852bd6676a9f9p-4, 0x1.205cae642337cp-2, 0x1.d50259a43a772p-2,
+                                0x1.3c5a466d5e8b8p-1, 0x1.82c45dda4726bp-1, 0x1.bb3403514e483p-1,
+                                0x1.e39f56616f9b0p-1, 0x1.fa92c264d787ep-1};
+    static const double W[8] = {0x1.83feae80e4dfcp-3, 0x1.75f8c77e0c00fp-3, 0x1.5a6ebbb5a75fcp-3,
+                                0x1.325f61bca3cbfp-3, 0x1.fe7af2bad386ap-4, 0x1.85c4ee79cc258p-4,
+                                0x1.fdfb1a2c1265dp-5, 0x1.bcddab4b7c211p-6};
+    if (b <= 0.0) {
+        const double t = a;
+        a = -b;
+        b = -t;
+    }
+    if (a < 0.0) return std::log(0.5 * (std::erf(b * M_SQRT1_2) - std::erf(a * M_SQRT1_2)));
+    if ((b - a) * (b + a) <= 2.0) {
+        const double h = 0.5 * (b - a);
+        double s = 0.0;
+        for (int i = 0; i < 8; ++i) {
+            const double t0 = h * (1.0 - X[i]), t1 = h * (1.0 + X[i]);  // z - a at the two nodes
+            s += W[i] * (std::exp(-0.5 * t0 * (2.0 * a + t0)) + std::exp(-0.5 * t1 * (2.0 * a + t1)));
+        }
+        return -0.5 * a * a - 0.5 * KABC_LOG_2PI + std::log(h * s);
+    }
+    const double qa = std_normal_logq(a), qb = std_normal_logq(b);
+    return qa + std::log1p(-std::exp(qb - qa));
+}
 
 // ---- MvNormal(mu, Sigma) priors (include/kabc_mvnormal.h) ---------------------------
 // Registered once per process; the prepared block is copied to a device at first use there.
@@ -122,10 +161,7 @@ bool prepare_prior(const kabc_prior_t& pr, PriorDev& q) {
         case KABC_PRIOR_TRUNCNORMAL: {
             if (!(b > 0) || !(pr.p[3] > pr.p[2])) return false;
             q.c0 = kabc_log(b);
-            const double zl = (pr.p[2] - a) / b, zh = (pr.p[3] - a) / b;
-            const double tp = (zl > 0) ? std_normal_cdf(-zl) - std_normal_cdf(-zh)
-                                       : std_normal_cdf(zh) - std_normal_cdf(zl);
-            q.c1 = std::log(tp);
+            q.c1 = std_normal_logmass((pr.p[2] - a) / b, (pr.p[3] - a) / b);
             return true;
         }
         case KABC_PRIOR_BETA:

@@ -607,8 +607,8 @@ class UserMvPrior(Factored):
 
 class Dirichlet(UserMvPrior):
     """Dirichlet(alpha) of Distributions.jl as a prior: logpdf = sum (alpha_k - 1) log x_k - log B(alpha) on
-    the probability simplex (all x_k >= 0 and |sum x - 1| <= D * 2^-52 * 4, the tolerance of isprobvec's
-    isapprox at this scale), -Inf elsewhere; rand: independent Gamma(alpha_k, 1) draws, normalised.
+    the probability simplex (all x_k >= 0 and |sum x - 1| <= 2^-26 max(sum x, 1): isprobvec's
+    isapprox(sum(x), 1), rtol = sqrt(eps)), -Inf elsewhere; rand: independent Gamma(alpha_k, 1) draws, normalised.
     p_k = (alpha_k, -, log B(alpha))."""
     SOURCE = """
 KABC_HD double kabc_user_mvprior_logpdf(const double* x, int D, const double* p, int pstride, const double* tab) {
@@ -617,7 +617,7 @@ KABC_HD double kabc_user_mvprior_logpdf(const double* x, int D, const double* p,
         if (!(x[k] >= 0.0)) return -KABC_INF;
         sx += x[k];
     }
-    if (!(kabc_fabs(sx - 1.0) <= (double)D * 0x1p-50)) return -KABC_INF;
+    if (!(kabc_fabs(sx - 1.0) <= 0x1p-26 * (sx > 1.0 ? sx : 1.0))) return -KABC_INF;
     for (int k = 0; k < D; ++k) {
         const double a = p[k * pstride];
         if (a != 1.0) s += (a - 1.0) * kabc_log_t(x[k], tab);

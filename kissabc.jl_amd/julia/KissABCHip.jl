@@ -387,7 +387,7 @@ KABC_HD double kabc_user_mvprior_logpdf(const double* x, int D, const double* p,
         if (!(x[k] >= 0.0)) return -KABC_INF;
         sx += x[k];
     }
-    if (!(kabc_fabs(sx - 1.0) <= (double)D * 0x1p-50)) return -KABC_INF;
+    if (!(kabc_fabs(sx - 1.0) <= 0x1p-26 * (sx > 1.0 ? sx : 1.0))) return -KABC_INF;
     for (int k = 0; k < D; ++k) {
         const double a = p[k * pstride];
         if (a != 1.0) s += (a - 1.0) * kabc_log_t(x[k], tab);

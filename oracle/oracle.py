@@ -106,6 +106,23 @@ def _dp(a):
 
 
 _user_prior_done = set()
+_include_digest_v = None
+
+
+def _include_digest():
+    """the bytes of include/*.h: a snippet's cached .so is keyed by its text AND the headers it was
+    compiled against, so that a changed sampler header is never served from an old build"""
+    global _include_digest_v
+    if _include_digest_v is None:
+        import hashlib
+        inc = os.path.join(os.path.dirname(_HERE), "include")
+        h = hashlib.sha1()
+        for name in sorted(os.listdir(inc)):
+            if name.endswith(".h"):
+                with open(os.path.join(inc, name), "rb") as f:
+                    h.update(name.encode() + b"\0" + f.read())
+        _include_digest_v = h.digest()
+    return _include_digest_v
 
 
 def register_user_prior(dist):
@@ -119,7 +136,7 @@ def register_user_prior(dist):
             "    return kabc_user_prior_logpdf(x, p, tab);\n}\n"
             "double orc_user_prior_rand_entry(const double* p, const kabc_slotwin_t* w) {\n"
             "    return kabc_user_prior_rand(p, w);\n}\n")
-    tag = hashlib.sha1(text.encode()).hexdigest()[:16]
+    tag = hashlib.sha1(text.encode() + _include_digest()).hexdigest()[:16]
     bdir = os.path.join(_HERE, "_build")
     os.makedirs(bdir, exist_ok=True)
     so = os.path.join(bdir, f"libuserprior_{tag}.so")
@@ -149,7 +166,7 @@ def register_user_mvprior(fac):
             "    return kabc_user_mvprior_logpdf(x, D, p, st, tab);\n}\n"
             "void orc_user_mvprior_rand_entry(double* out, int D, const double* p, int st, const kabc_slotwin_t* w) {\n"
             "    kabc_user_mvprior_rand(out, D, p, st, w);\n}\n")
-    tag = hashlib.sha1(text.encode()).hexdigest()[:16]
+    tag = hashlib.sha1(text.encode() + _include_digest()).hexdigest()[:16]
     bdir = os.path.join(_HERE, "_build")
     os.makedirs(bdir, exist_ok=True)
     so = os.path.join(bdir, f"libusermvprior_{tag}.so")
@@ -301,7 +318,7 @@ def register_user_cost(cost):
             "void orc_user_init_entry(double* x, int D, const double* params, const double* data, "
             "int64_t ndata, kabc_cost_rng_t* rng) {\n"
             "    kabc_user_sample_init(x, D, params, data, ndata, rng);\n}\n#endif\n")
-    tag = hashlib.sha1(text.encode()).hexdigest()[:16]
+    tag = hashlib.sha1(text.encode() + _include_digest()).hexdigest()[:16]
     bdir = os.path.join(_HERE, "_build")
     os.makedirs(bdir, exist_ok=True)
     so = os.path.join(bdir, f"libuser_{tag}.so")

@@ -1,5 +1,6 @@
 """Shared helpers for the test-suite (model builders, golden loaders)."""
 import json
+import math
 import os
 
 import numpy as np
@@ -37,3 +38,194 @@ def ulp_diff(a, b):
     with np.errstate(invalid="ignore"):
         d = np.abs(a - b) / sp
     return np.where(same, 0.0, d)
+
+
+# ---- the law of a prior's draws against an independent reference (test_prior_laws.py, test_gpu_prior_laws.py)
+class Law:
+    """The reference law of one prior component as check_law needs it.
+
+    cdf(t): P(X <= t) for a real t given as an mpmath number (exact midpoints between doubles);
+    ppf(q): approximate quantiles (numpy; only used to place the chi^2 bin edges, whose probabilities
+    come from cdf); lo, hi: the support; mean, sd, kurt (excess): None where they do not exist or are
+    not checked; discrete: integer support (cdf at integers, no rounding of draws)."""
+
+    def __init__(self, cdf, ppf, lo, hi, mean=None, sd=None, kurt=None, discrete=False, sf=None):
+        self.cdf, self.ppf, self.lo, self.hi = cdf, ppf, float(lo), float(hi)
+        self.sf = sf or (lambda t: 1 - cdf(t))
+        self.mean, self.sd, self.kurt, self.discrete = mean, sd, kurt, discrete
+
+
+def _mid(a, b):
+    import mpmath as mp
+    return (mp.mpf(float(a)) + mp.mpf(float(b))) / 2
+
+
+def _rounding_mass(law, v):
+    """P(the real draw rounds to the double v) under round-to-nearest (integers for a discrete law)"""
+    if law.discrete:
+        return float(law.cdf(v) - law.cdf(v - 1))
+    up, down = np.nextafter(v, np.inf), np.nextafter(v, -np.inf)
+    hi_p = law.sf(_mid(v, up)) if v < law.hi else 0
+    lo_p = law.cdf(_mid(down, v)) if v > law.lo else 0
+    return float(1 - hi_p - lo_p)
+
+
+def _count_ok(c, n, p, what):
+    """a count of draws against its binomial expectation: 6 standard errors, and a slack of 3
+    for the counts of a few that a vanishing p (a birthday collision of doubles) still allows"""
+    sd = np.sqrt(n * p * (1 - p))
+    assert abs(c - n * p) <= 6 * sd + 3, f"{what}: {c} of {n} draws, expected {n * p:.6g} (sd {sd:.3g})"
+
+
+def check_law(x, law, label="", nbins=64, p_min=1e-6):
+    """The protocol of tests/test_prior_laws.py, correct for doubles, not only for reals:
+      * no NaN, nothing outside the support, no infinity (no family here has mass beyond the
+        largest double at the parameters tested);
+      * point masses: the most frequent value and each finite end of the support appear as often
+        as the reference law puts mass on the reals that round to them (6 standard errors) -- a
+        plain KS test fails faithful samplers at tiny shapes, where whole percents of the mass round
+        to 0 or 1;
+      * chi^2 over `nbins` bins with edges at the reference quantiles rounded to doubles, merged
+        where they coincide (or hold less than 5 expected draws), probabilities from the reference
+        cdf: p > p_min;
+      * mean and variance within 6 standard errors where the law gives them."""
+    from scipy import stats
+    x = np.asarray(x, dtype=np.float64).ravel()
+    n = x.size
+    assert not np.isnan(x).any(), f"{label}: {np.isnan(x).sum()} NaN draws"
+    assert np.isfinite(x).all(), f"{label}: infinite draws"
+    assert x.min() >= law.lo and x.max() <= law.hi, f"{label}: draws outside [{law.lo}, {law.hi}]: {x.min()}, {x.max()}"
+    if law.discrete:
+        assert np.array_equal(x, np.rint(x)), f"{label}: non-integer draws"
+    # point masses
+    vals, cnt = np.unique(x, return_counts=True)
+    i = int(np.argmax(cnt))
+    if cnt[i] >= 2 or law.discrete:
+        _count_ok(int(cnt[i]), n, _rounding_mass(law, vals[i]), f"{label}: most frequent value {vals[i]!r}")
+    for end in (law.lo, law.hi):
+        if np.isfinite(end):
+            _count_ok(int(np.sum(x == end)), n, _rounding_mass(law, end), f"{label}: draws at the end {end!r}")
+    # chi^2 on (merged) quantile bins; a draw equal to an edge counts in the bin above it
+    with np.errstate(all="ignore"):
+        e = np.asarray(law.ppf(np.arange(1, nbins) / nbins), dtype=np.float64)
+    if law.discrete:
+        e = np.floor(e) + 1.0                        # bins [e_i, e_{i+1}) of integers
+    e = np.unique(e[np.isfinite(e) & (e > law.lo) & (e <= law.hi if law.discrete else e < law.hi)])
+    if law.discrete:
+        cdf_at = [law.cdf(v - 1) for v in e]
+    else:
+        cdf_at = [law.cdf(_mid(np.nextafter(v, -np.inf), v)) for v in e]
+    probs = np.diff(np.array([0.0] + [float(c) for c in cdf_at] + [1.0]))
+    obs = np.bincount(np.searchsorted(e, x, side="right"), minlength=len(probs)).astype(float)
+    # merge bins with fewer than 5 expected draws into their neighbour
+    P, O = [], []
+    for p, o in zip(probs, obs):
+        if P and (P[-1] * n < 5 or p * n < 5):
+            P[-1] += p
+            O[-1] += o
+        else:
+            P.append(p)
+            O.append(o)
+    if len(P) > 1 and P[-1] * n < 5:
+        P[-2] += P.pop()
+        O[-2] += O.pop()
+    P, O = np.array(P), np.array(O)
+    if len(P) > 1:
+        chi2 = float(np.sum((O - n * P) ** 2 / (n * P)))
+        pv = stats.chi2(len(P) - 1).sf(chi2)
+        assert pv > p_min, f"{label}: chi^2 {chi2:.1f} on {len(P) - 1} dof, p = {pv:.3g}"
+    # moments, standardised (scales such as 1e-300 would underflow the squares)
+    if law.mean is not None and law.sd is not None and law.sd > 0:
+        z = (x - law.mean) / law.sd
+        assert abs(z.mean()) <= 6 / np.sqrt(n), f"{label}: mean off by {z.mean() * np.sqrt(n):.2f} SE"
+        if law.kurt is not None and np.isfinite(law.kurt):
+            se = np.sqrt((law.kurt + 2) / n)
+            assert abs(np.mean(z * z) - 1) <= 6 * se, f"{label}: variance off by {(np.mean(z * z) - 1) / se:.2f} SE"
+
+
+def prior_law(kind, params):
+    """Law of make_dist(k, kind, params): mpmath cdfs (40 digits) where scipy's lose the rounding masses
+    of tiny shapes and far tails, scipy's where mpmath's series do not converge (shapes >= 100)"""
+    import mpmath as mp
+    from scipy import special, stats
+    mp.mp.dps = 40
+    mpf, inf = mp.mpf, float("inf")
+    reg = dict(regularized=True)
+    if kind == "TruncNormal":
+        mu, s, lo, hi = map(float, params)
+        za, zb = (mpf(lo) - mu) / s, (mpf(hi) - mu) / s
+        right = za >= 0           # in the right tail P(Z > z) keeps the digits, elsewhere P(Z < z)
+        F = (lambda z: -mp.ncdf(-z)) if right else mp.ncdf
+        Z = F(zb) - F(za)
+
+        def cdf(t):
+            z = min(max((mpf(t) - mu) / s, za), zb)
+            return (F(z) - F(za)) / Z
+
+        def sf(t):
+            z = min(max((mpf(t) - mu) / s, za), zb)
+            return (F(zb) - F(z)) / Z
+        phi = lambda z: mp.npdf(z) / Z                                        # noqa: E731
+        m1 = mp.quad(lambda z: z * phi(z), [za, zb])
+        m2 = mp.quad(lambda z: (z - m1) ** 2 * phi(z), [za, zb])
+        m4 = mp.quad(lambda z: (z - m1) ** 4 * phi(z), [za, zb])
+        ref = stats.truncnorm((lo - mu) / s, (hi - mu) / s, loc=mu, scale=s)
+        return Law(cdf, ref.ppf, lo, hi, mean=float(mu + s * m1), sd=float(s * mp.sqrt(m2)),
+                   kurt=float(m4 / m2 ** 2 - 3), sf=sf)
+    if kind == "Gamma":
+        a, th = map(float, params)
+        ref = stats.gamma(a, scale=th)
+        if a < 100:
+            cdf = lambda t: mp.gammainc(a, 0, max(mpf(t), 0) / th, **reg)            # noqa: E731
+            sf = lambda t: mp.gammainc(a, max(mpf(t), 0) / th, mp.inf, **reg)        # noqa: E731
+        else:
+            cdf = lambda t: mpf(special.gammainc(a, max(float(t), 0) / th))          # noqa: E731
+            sf = lambda t: mpf(special.gammaincc(a, max(float(t), 0) / th))          # noqa: E731
+        return Law(cdf, ref.ppf, 0.0, inf, mean=a * th, sd=math.sqrt(a) * th, kurt=6 / a, sf=sf)
+    if kind == "Beta":
+        a, b = map(float, params)
+        ref = stats.beta(a, b)
+        m, v, _, kt = (float(u) for u in ref.stats(moments="mvsk"))
+        clip = lambda t: min(max(mpf(t), 0), 1)                                      # noqa: E731
+        if max(a, b) < 100:
+            cdf = lambda t: mp.betainc(a, b, 0, clip(t), **reg)                      # noqa: E731
+            sf = lambda t: mp.betainc(a, b, clip(t), 1, **reg)                       # noqa: E731
+        else:
+            cdf = lambda t: mpf(special.betainc(a, b, float(clip(t))))               # noqa: E731
+            sf = lambda t: mpf(special.betaincc(a, b, float(clip(t))))               # noqa: E731
+        return Law(cdf, ref.ppf, 0.0, 1.0, mean=m, sd=math.sqrt(v), kurt=kt, sf=sf)
+    if kind == "Exponential":
+        th = float(params[0])
+        return Law(lambda t: -mp.expm1(-max(mpf(t), 0) / th), stats.expon(scale=th).ppf, 0.0, inf,
+                   mean=th, sd=th, kurt=6.0, sf=lambda t: mp.exp(-max(mpf(t), 0) / th))
+    if kind == "LogNormal":
+        mu, s = map(float, params)
+        ref = stats.lognorm(s, scale=np.exp(mu))
+        m, v, _, kt = (float(u) for u in ref.stats(moments="mvsk"))
+        z = lambda t: (mp.log(mpf(t)) - mu) / s if t > 0 else -mp.inf                # noqa: E731
+        return Law(lambda t: mp.ncdf(z(t)), ref.ppf, 0.0, inf, mean=m, sd=math.sqrt(v),
+                   kurt=kt if s < 0.5 else None, sf=lambda t: mp.ncdf(-z(t)))
+    if kind == "Laplace":
+        mu, th = map(float, params)
+        cdf = lambda t: (mp.exp((mpf(t) - mu) / th) / 2 if t < mu else 1 - mp.exp(-(mpf(t) - mu) / th) / 2)  # noqa: E731
+        return Law(cdf, stats.laplace(mu, th).ppf, -inf, inf, mean=mu, sd=math.sqrt(2) * th, kurt=3.0)
+    if kind == "TruncatedGamma":
+        a, th, lo, hi = map(float, params)
+        G = lambda t: mp.gammainc(a, 0, min(max(mpf(t), lo, 0), hi) / th, **reg)  # noqa: E731
+        Z = G(hi) - G(lo)
+        g = stats.gamma(a, scale=th)
+        ppf = lambda q: g.ppf(g.cdf(lo) + q * (g.cdf(hi) - g.cdf(lo)))              # noqa: E731
+        return Law(lambda t: (G(t) - G(lo)) / Z, ppf, max(lo, 0.0), hi, sf=lambda t: (G(hi) - G(t)) / Z)
+    # discrete families: cdf at integers (floats are fine: no rounding of the draws)
+    if kind == "DiscreteUniform":
+        a, b = map(float, params)
+        nn = b - a + 1
+        cdf = lambda t: mpf(min(max(np.floor(float(t)) - a + 1, 0), nn)) / nn       # noqa: E731
+        ppf = lambda q: a + np.floor(q * nn)                                          # noqa: E731
+        return Law(cdf, ppf, a, b, mean=(a + b) / 2, sd=math.sqrt((nn * nn - 1) / 12), kurt=-6 * (nn * nn + 1) / (5 * (nn * nn - 1)) if nn > 1 else None, discrete=True)
+    if kind in ("Poisson", "NegativeBinomial"):
+        ref = stats.poisson(float(params[0])) if kind == "Poisson" else stats.nbinom(*map(float, params))
+        m, v, _, kt = (float(u) for u in ref.stats(moments="mvsk"))
+        return Law(lambda t: mpf(ref.cdf(float(t))), ref.ppf, 0.0, inf, mean=m, sd=math.sqrt(v), kurt=kt, discrete=True,
+                   sf=lambda t: mpf(ref.sf(float(t))))
+    raise KeyError(kind)
