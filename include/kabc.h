@@ -49,7 +49,8 @@ typedef enum kabc_status {
     KABC_ERR_INVALID_STATE = 3,   /* src/types.jl:70 "starting sample invalid."         */
     KABC_ERR_DEVICE = 4,          /* HIP runtime error / no gfx950 device / no kernels   */
     KABC_ERR_UNSUPPORTED = 5,     /* model outside the DeviceCost / prior surface        */
-    KABC_ERR_NAN_COST = 6         /* Statistics.quantile: "undefined in presence of NaNs" */
+    KABC_ERR_NAN_COST = 6,        /* Statistics.quantile: "undefined in presence of NaNs" */
+    KABC_ERR_CANCELLED = 7        /* kabc_ctx_cancel: stopped at a generation / iteration boundary */
 } kabc_status_t;
 
 /* ---- Factored prior surface (src/priors.jl:10-49) ------------------------ */
@@ -147,6 +148,45 @@ int32_t kabc_device_count(void);
 kabc_status_t kabc_ctx_create(int32_t device_id, void* stream, kabc_ctx_t** out);
 kabc_status_t kabc_ctx_destroy(kabc_ctx_t* ctx);
 kabc_status_t kabc_ctx_synchronize(kabc_ctx_t* ctx);
+
+/* Cancellation.  kabc_ctx_cancel REQUESTS that the call running on ctx stop: one store to a word
+ * the context owns (pinned host memory the device reads), no HIP call, no lock -- safe from any
+ * thread and from a signal handler.  The request is sticky: the first call on ctx that observes it
+ * returns KABC_ERR_CANCELLED ("cancelled") and clears it; a request made while ctx is idle cancels
+ * the next call before it launches anything.  kabc_ctx_clear_cancel drops a pending request.
+ * Calls that observe it:
+ *   kabc_ais_advance  stops at a generation boundary.  With k generations completed, the handle's
+ *                     state, counters and stats are those of kabc_ais_advance(h, k, nt, ...) from
+ *                     the same start, kabc_ais_get_state reports t0 + k * nt, the first k
+ *                     generations of out_samples are filled (rows after k are unspecified), and
+ *                     the handle stays usable: advancing it further gives the bits of a run that
+ *                     was never interrupted.
+ *   kabc_smc_run      stops at an iteration boundary: result holds the population after the k
+ *                     completed iterations (theta, cost, alive, eps, iterations = k, the first k
+ *                     log records), bit-identical to the same call with max_iterations = k.
+ * A call that is never cancelled is unchanged.  Sharded and distributed calls (kabc_ais_create_dist
+ * handles, kabc_ais_advance_multi, kabc_smc_run_dist*) do not poll -- a cancel seen on one rank
+ * would leave the others in a collective -- and neither do kabc_ais_init, kabc_abcde_run and
+ * kabc_pfilter_run. */
+/* Response time: the device paths look at the word at bounded intervals of WORK, not of time: the one-
+ * workgroup AIS kernel once per ~1 ms of modelled work (0.6 us per batch of 64 walkers and sub-step),
+ * batch handles between launch blocks of ~25 ms of modelled work, the half-generation path before every
+ * generation with ~25 ms of queued work at most, the smc loop kernel every 32nd pass and the one-workgroup
+ * smc kernel every 16th iteration (a read of host memory stalls the wave that waits for it:
+ * tools/host_word_latency_probe.hip).  With the built-in costs that is well within 0.1 s; an expensive
+ * cost (a simulator, a user cost) at small ensembles stretches it by the same factor as a generation
+ * or an iteration. */
+kabc_status_t kabc_ctx_cancel(kabc_ctx_t* ctx);
+kabc_status_t kabc_ctx_clear_cancel(kabc_ctx_t* ctx);
+/* Ctrl-C for a blocking call: on = 1 arms ctx, on = 0 disarms it.  While at least one context is
+ * armed, a SIGINT stores the cancel request of every armed context and is NOT passed on; otherwise
+ * it goes to the handler that was installed before (the hook re-installs itself in front of a
+ * handler installed later, at the next arming).  Disarming returns KABC_ERR_CANCELLED if a SIGINT
+ * arrived while ctx was armed, and then also drops ctx's request: the caller re-raises the signal
+ * for its own handler (Python: KeyboardInterrupt).  KABC_OK otherwise.  A process that ignores SIGINT
+ * (SIG_IGN: started under nohup, in the background, or by its own choice) is not armed: arming returns
+ * KABC_OK and the signal stays ignored.  More than 64 contexts armed at once: KABC_ERR_UNSUPPORTED. */
+kabc_status_t kabc_ctx_cancel_on_sigint(kabc_ctx_t* ctx, int32_t on);
 
 /* Page-locked host memory for the buffers the caller hands to kabc_ais_advance
  * (out_samples): the sample trace is then DMA'd over PCIe while the next
@@ -620,8 +660,9 @@ kabc_status_t kabc_smc_run_dist_mode(kabc_comm_t* comm, const kabc_prior_t* prio
 
 /* How the calling thread's last kabc_smc_run / kabc_smc_run_dist[_mode] was driven: out[0] epsilon-
  * iterations, [1] collectives issued (grouped all-gathers; those of batches enqueued past the end of the
- * loop or behind a stalled selection included), [2] host looks at the control block (the batched course
- * and the sharded courses count them), [3] selections decided by the one exchange, [4] selections made
+ * loop or behind a stalled selection included), [2] host looks at the control block (the batched courses
+ * -- single GPU too -- and the sharded courses; the persistent loop kernel and the one-workgroup kernel
+ * make none), [3] selections decided by the one exchange, [4] selections made
  * phase by phase / by the select kernel inside the batched course (the first two, and every stalled one),
  * [5] propose / accept passes, [6] 1 when batches of iterations with the one-exchange selection were
  * enqueued between looks -- sharded runs with mcmc_retrys = 0, and single-GPU runs of 2^20 particles and

@@ -6,7 +6,7 @@ module kissabc_jl_amd.py registers this package under that name).
 """
 from . import costs
 from ._cdefs import KABC_MAX_DIM
-from ._lib import Context, KabcError, LIB_PATH, default_context
+from ._lib import Cancelled, Context, KabcError, LIB_PATH, default_context
 from .api import (ABCDE, AIS, AisEnsemble, ApproxKernelizedPosterior, ApproxPosterior, CommonLogDensity,
                   MCMCThreads, compile_model, pfilter, set_specialize,
                   Particles, sample, smc)
@@ -23,7 +23,7 @@ __all__ = [
     "MCMCThreads", "pfilter",
     "Particles", "sample", "smc", "DeviceCost", "costs", "Factored", "Uniform", "Normal",
     "Truncated", "truncated", "TruncatedNormal", "Beta", "DiscreteUniform", "NegativeBinomial",
-    "Exponential", "Gamma", "LogNormal", "Product", "MvNormal", "MultivariateNormal", "Context", "KabcError", "default_context", "LIB_PATH",
+    "Exponential", "Gamma", "LogNormal", "Product", "MvNormal", "MultivariateNormal", "Context", "KabcError", "Cancelled", "default_context", "LIB_PATH",
     "KABC_MAX_DIM", "comm", "Comm", "EnsembleGroup", "UserInit", "InitFromSnippet",
     "UserPrior", "UserMvPrior", "Dirichlet", "Ar1Normal", "Poisson", "Laplace", "TruncatedGamma", "compile_model", "set_specialize",
 ]

@@ -15,7 +15,7 @@ COMM_RCCL, COMM_P2P = 1, 2
 
 # kabc_status_t
 KABC_OK, KABC_ERR_INVALID_ARG, KABC_ERR_RETRY_EXHAUSTED, KABC_ERR_INVALID_STATE, \
-    KABC_ERR_DEVICE, KABC_ERR_UNSUPPORTED, KABC_ERR_NAN_COST = range(7)
+    KABC_ERR_DEVICE, KABC_ERR_UNSUPPORTED, KABC_ERR_NAN_COST, KABC_ERR_CANCELLED = range(8)
 
 # kabc_prior_kind_t
 PRIOR_UNIFORM, PRIOR_NORMAL, PRIOR_TRUNCNORMAL, PRIOR_BETA, PRIOR_DISCRETE_UNIFORM, \
@@ -113,6 +113,9 @@ PROTOTYPES = {
     "kabc_ctx_create": (C.c_int, [C.c_int32, VP, C.POINTER(VP)]),
     "kabc_ctx_destroy": (C.c_int, [VP]),
     "kabc_ctx_synchronize": (C.c_int, [VP]),
+    "kabc_ctx_cancel": (C.c_int, [VP]),
+    "kabc_ctx_clear_cancel": (C.c_int, [VP]),
+    "kabc_ctx_cancel_on_sigint": (C.c_int, [VP, C.c_int32]),
     "kabc_math_probe": (C.c_int, [VP, C.c_int32, C.c_int64, c_double_p, c_double_p]),
     "kabc_host_alloc": (C.c_int, [C.c_size_t, C.POINTER(VP)]),
     "kabc_host_free": (C.c_int, [VP]),

@@ -5,7 +5,9 @@ visible, the product path raises.  (The CPU oracle lives under oracle/ and is
 only ever used by tests/, smoke() and bench.py's cpu_baseline leg.)
 """
 import ctypes as C
+import contextlib
 import os
+import signal
 import threading
 
 from . import _cdefs
@@ -27,6 +29,11 @@ class KabcError(RuntimeError):
     def __init__(self, status, message):
         super().__init__(message)
         self.status = status
+
+
+class Cancelled(KabcError):
+    """KABC_ERR_CANCELLED: the call stopped at a generation / iteration boundary because
+    Context.cancel() was called (include/kabc.h: what the handle or result then holds)."""
 
 
 def _preload_torch_hip():
@@ -72,7 +79,8 @@ def load():
 def check(status):
     if status != 0:
         msg = load().kabc_last_error()
-        raise KabcError(status, msg.decode("utf-8", "replace") if msg else f"kabc status {status}")
+        cls = Cancelled if status == _cdefs.KABC_ERR_CANCELLED else KabcError
+        raise cls(status, msg.decode("utf-8", "replace") if msg else f"kabc status {status}")
 
 
 class Context:
@@ -95,6 +103,33 @@ class Context:
 
     def synchronize(self):
         check(load().kabc_ctx_synchronize(self._h))
+
+    def cancel(self):
+        """Request that the call running on this context stop at its next generation / iteration
+        boundary; it then raises Cancelled.  Safe from any thread (e.g. a threading.Timer).  The
+        request is sticky: made while the context is idle, it cancels the next call."""
+        check(load().kabc_ctx_cancel(self._h))
+
+    def clear_cancel(self):
+        """Drop a pending cancel request."""
+        check(load().kabc_ctx_clear_cancel(self._h))
+
+    @contextlib.contextmanager
+    def interruptible(self):
+        """Around a blocking library call: Ctrl-C cancels the call (it stops at its next boundary)
+        and then raises KeyboardInterrupt as usual.  Arming is one sigaction look and a store."""
+        lib = load()
+        arm = threading.current_thread() is threading.main_thread()
+        if arm:
+            check(lib.kabc_ctx_cancel_on_sigint(self._h, 1))
+        try:
+            yield
+        finally:
+            if arm and lib.kabc_ctx_cancel_on_sigint(self._h, 0) == _cdefs.KABC_ERR_CANCELLED:
+                # the signal was held back from Python's handler while the call ran: deliver it now
+                # (KeyboardInterrupt, or whatever handler the program installed); it replaces the
+                # Cancelled the call raised
+                signal.raise_signal(signal.SIGINT)
 
     def close(self):
         if self._h and self._owned:

@@ -12,6 +12,7 @@ ABI of include/kabc.h.  This file only marshals arguments and shapes results
 (bundle_samples / chainsstack, src/KissABC.jl:82-104).
 """
 import collections
+import contextlib
 import concurrent.futures
 import ctypes as C
 import math
@@ -213,10 +214,14 @@ class AisEnsemble:
                 raise ValueError(f"out must be a C-contiguous float64 array of shape {shape}")
             ptr = out.ctypes.data_as(cd.c_double_p)
         st = cd.Stats()
-        _lib.check(lib.kabc_ais_advance(self._h, int(ngenerations), int(ntransitions), ptr,
-                                        C.byref(st)))
-        self.last_stats = {"proposals": st.proposals, "cost_evals": st.cost_evals,
-                           "accepted": st.accepted}
+        # Ctrl-C / Context.cancel(): the call stops at a generation boundary and raises (the handle
+        # then holds the state after the generations it completed; include/kabc.h)
+        with (self.ctx.interruptible() if self.comm is None else contextlib.nullcontext()):
+            status = lib.kabc_ais_advance(self._h, int(ngenerations), int(ntransitions), ptr,
+                                          C.byref(st))
+            self.last_stats = {"proposals": st.proposals, "cost_evals": st.cost_evals,
+                               "accepted": st.accepted}
+            _lib.check(status)
         return out
 
     def half_generation(self, half, ntransitions, trace_ptr=None):
@@ -410,7 +415,7 @@ class SmcResult(collections.namedtuple("SmcResult", ["P", "C", "eps", "info"])):
 
 def smc(prior, cost, *, nparticles=100, alpha=0.95, mcmc_retrys=0, mcmc_tol=0.015, epstol=0.0,
         r_epstol=None, min_r_ess=None, max_stretch=2.0, verbose=False, parallel=False, seed=0,
-        ctx=None, return_array=False, comm=None, shard=None):
+        ctx=None, return_array=False, comm=None, shard=None, max_iterations=None):
     """smc(prior, cost; ...) -- src/smc.jl:92-206, same keywords and defaults.
     `parallel` is accepted and ignored (every particle is a GPU lane).
     `comm` (a comm.Comm): the cost loop is sharded over the communicator's ranks
@@ -419,6 +424,9 @@ def smc(prior, cost, *, nparticles=100, alpha=0.95, mcmc_retrys=0, mcmc_tol=0.01
     `shard` = "particles": the ranks own their particles and the epsilon-selection is sharded too
     (kabc_smc_run_dist_mode, KABC_SMC_DIST_PARTICLES); "cost_loop": the pass only; None:
     kabc_smc_run_dist's default (KABC_SMC_DIST).
+    `max_iterations` bounds the outer loop (default 100 000).  Context.cancel() or Ctrl-C stops a
+    single-GPU run at an iteration boundary: Cancelled (its `.result` holds the population after the
+    iterations that completed) or KeyboardInterrupt.
     Returns (P, C, ϵ) as the reference does (+ an `info` dict)."""
     fac = as_factored(prior)
     scalar = isinstance(prior, UnivariateDistribution)
@@ -438,6 +446,8 @@ def smc(prior, cost, *, nparticles=100, alpha=0.95, mcmc_retrys=0, mcmc_tol=0.01
     o.min_r_ess = math.nan if min_r_ess is None else float(min_r_ess)
     o.max_stretch = float(max_stretch)
     o.seed = int(seed)
+    if max_iterations is not None:   # (kabc_smc_opts_t.max_iterations: the loop's safety bound, 100 000)
+        o.max_iterations = int(max_iterations)
     N, D = int(nparticles), len(fac)
     n_alloc = max(N, 1)
     t_host0 = time.perf_counter()
@@ -460,8 +470,22 @@ def smc(prior, cost, *, nparticles=100, alpha=0.95, mcmc_retrys=0, mcmc_tol=0.01
     elif comm is not None:
         _lib.check(lib.kabc_smc_run_dist(comm.handle, fac.to_c(), D, C.byref(cc), C.byref(o), C.byref(r)))
     else:
-        _lib.check(lib.kabc_smc_run(ctx.handle, fac.to_c(), D, C.byref(cc), C.byref(o), C.byref(r)))
-    t_host1 = time.perf_counter()
+        with ctx.interruptible():
+            status = lib.kabc_smc_run(ctx.handle, fac.to_c(), D, C.byref(cc), C.byref(o), C.byref(r))
+            if status == cd.KABC_ERR_CANCELLED:
+                # the population after the iterations that completed travels with the exception
+                try:
+                    _lib.check(status)
+                except _lib.Cancelled as e:
+                    e.result = _smc_result(lib, r, theta, Cst, alive, log, n_alloc, N, return_array,
+                                           scalar, t_host0, time.perf_counter())
+                    raise
+            _lib.check(status)
+    return _smc_result(lib, r, theta, Cst, alive, log, n_alloc, N, return_array, scalar, t_host0,
+                       time.perf_counter())
+
+
+def _smc_result(lib, r, theta, Cst, alive, log, n_alloc, N, return_array, scalar, t_host0, t_host1):
     mask = alive.view(np.bool_)          # (the library writes 0 / 1)
     # every particle alive (the usual end of a run): the result IS the array, not a gathered copy
     kept = theta if (r.n_alive == n_alloc and N > 0) else theta[mask]

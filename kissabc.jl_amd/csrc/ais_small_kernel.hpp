@@ -67,6 +67,11 @@ struct AisSmallArgs {
     // launch, per half [chain][ngen * nt][W][rows[h]]; NULL = the producers compute them
     const double* aux[2];
     int64_t stride_aux[2];   // doubles per chain
+    // cancellation (single-chain launches): the context's cancel word in host-coherent memory, read by
+    // consumer 0 every `poll_every` generations, NULL = no poll.  Enters no draw.  The generations
+    // the launch completed go to counters->small_done.
+    const uint32_t* cancel;
+    int32_t poll_every;
 };
 
 // one ring slot = the record of ONE (batch, sub-step) unit
@@ -128,6 +133,7 @@ __global__ void __launch_bounds__(kAisSmallBlock) ais_small_kernel(const AisSmal
     __shared__ uint32_t s_full[T];                      // unit number + 1 of the record a slot holds
     __shared__ uint32_t s_done[kAisSmallMaxConsumers];  // units consumer c has taken
     __shared__ uint32_t s_arrive;                       // consumers' arrivals at half-step ends
+    __shared__ uint32_t s_stop;                         // first generation that does not run (cancel)
     __shared__ PriorDev sprior[D];
     __shared__ double sbox_lo[D], sbox_hi[D];
     constexpr bool kGaussBox = PC == kPriorSimple || PC == kPriorNormal;
@@ -174,7 +180,10 @@ __global__ void __launch_bounds__(kAisSmallBlock) ais_small_kernel(const AisSmal
     }
     if (tid < T) s_full[tid] = 0u;
     if (tid < kAisSmallMaxConsumers) s_done[tid] = 0u;
-    if (tid == 0) s_arrive = 0u;
+    if (tid == 0) {
+        s_arrive = 0u;
+        s_stop = (uint32_t)A.ngen;
+    }
     if constexpr (kNbTabs > 0) {
         int slot = 0;
         bool has_nb = false;
@@ -207,6 +216,7 @@ __global__ void __launch_bounds__(kAisSmallBlock) ais_small_kernel(const AisSmal
     const int nC = nb0 < kAisSmallMaxConsumers ? nb0 : kAisSmallMaxConsumers;  // (rows0 >= rows1, rows0 >= 1)
     const int S = T / nC;  // slots per consumer: consumer c's ring is ring[c * S .. c * S + S)
     const int nt = A.nt;
+    const bool poll = A.cancel != nullptr;
 
     if (wave >= nC) {
         // ================= PRODUCER q of consumer c
@@ -226,7 +236,18 @@ __global__ void __launch_bounds__(kAisSmallBlock) ais_small_kernel(const AisSmal
                 const uint32_t slot = u % (uint32_t)S;
                 if (u >= (uint32_t)S) {  // the slot's previous record (unit u - S) must have been taken
                     const uint32_t need = u - (uint32_t)S + 1u;
-                    while (lds_word_peek(&s_done[c]) < need) __builtin_amdgcn_s_sleep(1);
+                    bool stop = false;
+                    while (lds_word_peek(&s_done[c]) < need) {
+                        // a cancel: the consumers stop before generation s_stop and never take its units --
+                        // a producer waiting for their slots would wait for ever (a unit whose slot is free
+                        // is produced and never read: at most S of them)
+                        if (poll && u / per_gen >= (uint32_t)__builtin_amdgcn_readfirstlane((int)lds_word_peek(&s_stop))) {
+                            stop = true;
+                            break;
+                        }
+                        __builtin_amdgcn_s_sleep(1);
+                    }
+                    if (stop) break;
                     lds_acquire();
                 }
                 const uint32_t g = u / per_gen;
@@ -313,6 +334,12 @@ __global__ void __launch_bounds__(kAisSmallBlock) ais_small_kernel(const AisSmal
         uint32_t u = 0;  // this consumer's unit counter
         int slot = 0;
         uint32_t halfsteps = 0;
+        // cancellation: every poll_every generations consumer 0 reads the word and publishes the stop
+        // generation before the generation's last arrival; after that arrival every consumer reads the
+        // same s_stop.  (The read is waited for at once -- ~1.2 us once per ~1 ms of work: a register
+        // kept across the loop for a deferred test spilled these kernels, which are at 256 VGPRs.)
+        int poll_in = A.poll_every;  // (both consumers count it down: s_stop can only change where it hits 0)
+        int gdone = A.ngen;
 #pragma unroll 1
         for (int g = 0; g < A.ngen; ++g) {
 #pragma unroll 1
@@ -529,6 +556,11 @@ __global__ void __launch_bounds__(kAisSmallBlock) ais_small_kernel(const AisSmal
                         }
                     }
                 }
+                const bool look = poll && h == 1 && --poll_in == 0;
+                if (look && c == 0 && g + 1 < A.ngen &&
+                    __builtin_amdgcn_readfirstlane((int)__hip_atomic_load(A.cancel, __ATOMIC_RELAXED,
+                                                                          __HIP_MEMORY_SCOPE_SYSTEM)) != 0)
+                    lds_word_publish(&s_stop, (uint32_t)(g + 1), lane);
                 // the half-step ends: every consumer's rows of half h are in LDS before anybody draws
                 // partners from them, and nobody still reads the other half's rows that come next
                 ++halfsteps;
@@ -541,14 +573,23 @@ __global__ void __launch_bounds__(kAisSmallBlock) ais_small_kernel(const AisSmal
                 } else {
                     wave_lds_fence();
                 }
+                if (look) {
+                    poll_in = A.poll_every;
+                    if ((uint32_t)(g + 1) >= (uint32_t)__builtin_amdgcn_readfirstlane((int)lds_word_peek(&s_stop))) {
+                        gdone = g + 1;
+                        break;
+                    }
+                }
             }
+            if (gdone == g + 1) break;  // (the consumers stop here; the producers abandon what follows)
         }
         // counters: one atomic per consumer and counter
         const unsigned long long se = wave_total_u32(n_eval);
         const unsigned long long sa = wave_total_u32(n_acc);
         if (lane == 0) {
             unsigned long long* sl = A.slots + (size_t)((unsigned)blockIdx.x & (kCounterSlots - 1)) * 8;
-            if (c == 0) atomicAdd(&sl[0], (unsigned long long)N * (unsigned long long)nt * (unsigned long long)A.ngen);
+            if (c == 0) atomicAdd(&sl[0], (unsigned long long)N * (unsigned long long)nt * (unsigned long long)gdone);
+            if (c == 0 && chain == 0) A.counters->small_done = gdone;
             atomicAdd(&sl[1], se);
             atomicAdd(&sl[2], sa);
         }

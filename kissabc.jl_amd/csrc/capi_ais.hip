@@ -210,6 +210,8 @@ struct kabc_ais {
     // prepared-cost words of the launch in flight (ais_aux_kernels.hpp)
     double* d_aux;
     size_t aux_cap;  // bytes
+    // cancellation: the two block / interval events of a bounded queue (created at first need)
+    hipEvent_t ev_blk[2];
     // debug records (tests)
     int32_t* d_dbg;
     int64_t dbg_cap;  // in int32 units
@@ -1068,11 +1070,35 @@ static int64_t ais_small_units_per_gen(const kabc_ais_t* h, int32_t ntransitions
 // (ais_small_kernel.hpp) per block of generations -- a block ends where the device trace buffer
 // (64 MiB) or the kernel's 32-bit unit counters would.  Enqueued on the handle's stream; the trace
 // block is copied to out_samples behind its launch.
-static kabc_status_t ais_small_run(kabc_ais_t* h, int64_t ngenerations, int32_t ntransitions, double* out_samples) {
+//
+// Cancellation.  A single chain polls the context's word on the device (ais_small_kernel.hpp, every
+// poll_every generations, ~kCancelPollUs of modelled work apart); *last_gc receives the generations of
+// the last launch, which the caller checks against counters.small_done.  The chains of a batch are
+// independent workgroups that could not agree on a stop generation without waiting on each other: they
+// do not poll, their blocks are capped to ~kCancelInflightMs of modelled work instead, and the host
+// looks at the word between blocks with at most two in flight (*cancelled).
+static kabc_status_t ensure_blk_events(kabc_ais_t* h) {
+    for (hipEvent_t& e : h->ev_blk)
+        if (!e) KABC_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    return KABC_OK;
+}
+
+static kabc_status_t ais_small_run(kabc_ais_t* h, int64_t ngenerations, int32_t ntransitions, double* out_samples,
+                                   int64_t* last_gc, bool* cancelled) {
     hipStream_t s = h->ctx->stream;
     const int64_t gen_elems = h->N * h->D * h->nchains;  // [chain][N][D] per generation
     const size_t gen_bytes = sizeof(double) * (size_t)gen_elems;
-    int64_t block = (1ll << 30) / ais_small_units_per_gen(h, ntransitions);
+    const int64_t upg = ais_small_units_per_gen(h, ntransitions);
+    int64_t block = (1ll << 30) / upg;
+    const bool dev_poll = h->nchains == 1;
+    if (!dev_poll) {
+        const int64_t cap = (int64_t)(kCancelInflightMs * 1000.0 / (kCancelUnitUs * (double)upg));
+        if (cap < block) block = cap;
+    }
+    int64_t poll_every = (int64_t)std::ceil(kCancelPollUs / (kCancelUnitUs * (double)upg));
+    if (poll_every < 1) poll_every = 1;
+    if (poll_every > (1 << 30)) poll_every = 1 << 30;
+    *last_gc = 0;
     if (out_samples) {
         size_t target = (size_t)64 << 20;
         if (const char* e = std::getenv("KABC_TRACE_CHUNK_MIB")) {  // tuning / tests: force several blocks
@@ -1117,8 +1143,25 @@ static kabc_status_t ais_small_run(kabc_ais_t* h, int64_t ngenerations, int32_t 
         KABC_HIP_CHECK(dev_malloc(&h->d_strace, gen_bytes * (size_t)block));
         h->strace_cap = gen_bytes * (size_t)block;
     }
-    for (int64_t g0 = 0; g0 < ngenerations; g0 += block) {
+    const bool blocks = ngenerations > block;
+    if (blocks && !dev_poll)
+        if (kabc_status_t st = ensure_blk_events(h)) return st;
+    int64_t nblk = 0;
+    for (int64_t g0 = 0; g0 < ngenerations; g0 += block, ++nblk) {
         const int64_t gc = ngenerations - g0 < block ? ngenerations - g0 : block;
+        if (nblk > 0 && dev_poll) {
+            // (a block of 2^30 units or a full trace buffer: the look costs nothing beside it)
+            int64_t done = 0;
+            KABC_HIP_CHECK(hipMemcpyAsync(&done, &h->d_counters->small_done, sizeof done, hipMemcpyDeviceToHost, s));
+            KABC_HIP_CHECK(hipStreamSynchronize(s));
+            if (done < *last_gc) return KABC_OK;  // the caller finds it in the counters
+        } else if (nblk > 0) {
+            if (nblk >= 2) KABC_HIP_CHECK(hipEventSynchronize(h->ev_blk[nblk & 1]));  // block nblk - 2
+            if (cancel_pending(h->ctx)) {
+                *cancelled = true;
+                return KABC_OK;
+            }
+        }
         if (h->spec_state == KABC_SPEC_PENDING) ais_poll_spec(h);
         h->launches++;
         AisSmallArgs a;
@@ -1149,6 +1192,8 @@ static kabc_status_t ais_small_run(kabc_ais_t* h, int64_t ngenerations, int32_t 
         a.box_lp = h->box_lp;
         a.prior = h->d_prior;
         a.seeds = h->d_seeds;
+        a.cancel = dev_poll ? h->ctx->cancel_d : nullptr;
+        a.poll_every = (int32_t)poll_every;
         const bool t_on = h->timing && (h->ev_used + 2 <= h->ev.size());
         if (t_on && h->open_count == 0) KABC_HIP_CHECK(hipEventRecord(h->ev[h->ev_used], s));
         if (auxW) {  // (inside the timed region, like the half-generation path's pre-pass)
@@ -1181,10 +1226,50 @@ static kabc_status_t ais_small_run(kabc_ais_t* h, int64_t ngenerations, int32_t 
         if (out_samples)
             KABC_HIP_CHECK(hipMemcpyAsync(out_samples + g0 * gen_elems, h->d_strace, gen_bytes * (size_t)gc,
                                           hipMemcpyDeviceToHost, s));
+        if (blocks && !dev_poll) KABC_HIP_CHECK(hipEventRecord(h->ev_blk[nblk & 1], s));
         h->t += (uint64_t)gc * (uint64_t)ntransitions;
+        *last_gc = dev_poll ? gc : 0;
     }
     return KABC_OK;
 }
+
+// The half-generation path's bound on what a cancel may find queued: an event every interval of ~
+// kCancelInflightMs, and before one is recorded the host waits for the one before it -- at most two
+// intervals in flight, one host wait per interval (not per generation).  The interval, in generations,
+// follows the measured duration of the last one.
+// The first interval comes from a model of a generation's time (the launch pair's floor, or the units
+// spread over the 256 CUs), so that a short call records no event at all.
+struct InflightBound {
+    kabc_ais_t* h;
+    int64_t iv, n = 0;  // generations per interval; enqueued since the last event
+    int64_t recorded = 0;
+    std::chrono::steady_clock::time_point t_prev;
+    InflightBound(kabc_ais_t* h_, int32_t nt) : h(h_) {
+        const double units = (double)(h->rows_owned[0] + h->rows_owned[1]) * h->nchains / 64.0 * nt;
+        const double gen_us = std::max(kCancelLaunchUs, units * kCancelUnitUs / 256.0);
+        iv = std::min<int64_t>(64, std::max<int64_t>(1, (int64_t)(kCancelInflightMs * 1000.0 / gen_us)));
+        t_prev = std::chrono::steady_clock::now();
+    }
+    kabc_status_t generation_enqueued(hipStream_t s) {
+        if (++n < iv) return KABC_OK;
+        n = 0;
+        if (recorded == 0) {
+            if (kabc_status_t st = ensure_blk_events(h)) return st;
+        } else {
+            KABC_HIP_CHECK(hipEventSynchronize(h->ev_blk[(recorded - 1) & 1]));
+            // (the time between two waits ~ one interval on the device; the first from the call's start)
+            const auto now = std::chrono::steady_clock::now();
+            const double ms = std::chrono::duration<double, std::milli>(now - t_prev).count();
+            const double r = ms > 0.0 ? kCancelInflightMs / ms : 8.0;
+            const double f = r < 0.25 ? 0.25 : (r > 8.0 ? 8.0 : r);
+            iv = std::min<int64_t>(1ll << 24, std::max<int64_t>(1, (int64_t)((double)iv * f)));
+            t_prev = now;
+        }
+        KABC_HIP_CHECK(hipEventRecord(h->ev_blk[recorded & 1], s));
+        ++recorded;
+        return KABC_OK;
+    }
+};
 
 extern "C" {
 
@@ -1213,10 +1298,17 @@ kabc_status_t kabc_ais_advance(kabc_ais_t* h, int64_t ngenerations, int32_t ntra
         set_error("kabc_ais_init / kabc_ais_set_state has not been called");
         return KABC_ERR_INVALID_STATE;
     }
+    // kabc_ctx_cancel (single-process handles; a sharded handle does not poll: kabc.h): a pending request
+    // ends the call before it launches anything
+    const bool polls = !h->comm;
+    if (polls && cancel_take(h->ctx)) return KABC_ERR_CANCELLED;
+    bool cancelled = false;
+    int64_t small_gc = 0;  // generations of the one-workgroup driver's last launch (it may stop early)
     KABC_HIP_CHECK(hipSetDevice(h->ctx->device));
     hipStream_t s = h->ctx->stream;
     const int64_t gen_elems = h->N * h->D * h->nchains;  // [chain][N][D] per generation
     const size_t gen_bytes = sizeof(double) * (size_t)gen_elems;
+    InflightBound ib(h, ntransitions);
     // A rank-local failure (a launch that did not go out) must not leave the other ranks
     // blocked in a collective this rank never joins: the kernels stop, the exchanges of the
     // remaining half-generations are still issued, and the ranks agree on the outcome below.
@@ -1229,9 +1321,14 @@ kabc_status_t kabc_ais_advance(kabc_ais_t* h, int64_t ngenerations, int32_t ntra
         }
     };
     if (h->small_ok && ngenerations > 0 && ais_small_units_per_gen(h, ntransitions) <= (1ll << 30)) {
-        if (kabc_status_t st = ais_small_run(h, ngenerations, ntransitions, out_samples)) return st;
+        if (kabc_status_t st = ais_small_run(h, ngenerations, ntransitions, out_samples, &small_gc, &cancelled))
+            return st;
     } else if (!out_samples || ngenerations == 0) {
         for (int64_t g = 0; g < ngenerations; ++g) {
+            if (polls && cancel_pending(h->ctx)) {  // (h->t counts the generations enqueued)
+                cancelled = true;
+                break;
+            }
             for (int hf = 0; hf < 2; ++hf) {
                 // exchange diagnostics: this half-generation is timed while entries are left
                 kabc_ais::XT* xt = (h->comm && h->timing && h->xt_used < h->xt.size()) ? &h->xt[h->xt_used] : nullptr;
@@ -1281,6 +1378,8 @@ kabc_status_t kabc_ais_advance(kabc_ais_t* h, int64_t ngenerations, int32_t ntra
                 if (local_err && !h->comm) return local_err;
             }
             if (local_err == KABC_OK) h->t += (uint64_t)ntransitions;
+            if (polls)
+                if (kabc_status_t st = ib.generation_enqueued(s)) return st;
         }
         if (h->comm && h->xk > 1) keep(comm_exchange_fence(h->comm));
         if (h->xt_open >= 0) {
@@ -1339,6 +1438,7 @@ kabc_status_t kabc_ais_advance(kabc_ais_t* h, int64_t ngenerations, int32_t ntra
         std::mutex mu;
         std::condition_variable cv;
         int64_t filled = 0, drained = 0;  // chunks submitted / chunks copied out
+        int64_t stop_at = nchunks, part_gc = 0;  // a cancel: chunks to drain, generations of the last one
         bool abort_drain = false;
         hipError_t drain_err = hipSuccess;
         std::thread drainer([&] {
@@ -1346,11 +1446,15 @@ kabc_status_t kabc_ais_advance(kabc_ais_t* h, int64_t ngenerations, int32_t ntra
             for (int64_t c = 0; c < nchunks && e == hipSuccess; ++c) {
                 {
                     std::unique_lock<std::mutex> lk(mu);
-                    cv.wait(lk, [&] { return filled > c || abort_drain; });
-                    if (abort_drain) break;
+                    cv.wait(lk, [&] { return filled > c || abort_drain || stop_at <= c; });
+                    if (abort_drain || stop_at <= c) break;
                 }
                 const int b = (int)(c % kTraceBufs);
-                const int64_t gc = (c + 1 < nchunks) ? chunk : ngenerations - c * chunk;
+                int64_t gc = (c + 1 < nchunks) ? chunk : ngenerations - c * chunk;
+                {
+                    std::lock_guard<std::mutex> lk(mu);
+                    if (c + 1 == stop_at && part_gc > 0) gc = part_gc;
+                }
                 e = hipEventSynchronize(h->ev_filled[b]);
                 if (e == hipSuccess)
                     e = hipMemcpyAsync(out_samples + c * chunk * gen_elems, h->d_trace[b],
@@ -1375,19 +1479,36 @@ kabc_status_t kabc_ais_advance(kabc_ais_t* h, int64_t ngenerations, int32_t ntra
                 cv.wait(lk, [&] { return drained > c - kTraceBufs; });
                 if (drain_err != hipSuccess) break;
             }
-            for (int64_t g = 0; g < gc && st == KABC_OK; ++g) {
+            int64_t g = 0;
+            for (; g < gc && st == KABC_OK; ++g) {
+                if (cancel_pending(h->ctx)) {
+                    cancelled = true;
+                    break;
+                }
                 double* tr0 = h->d_trace[b] + g * gen_elems;
                 st = kabc_ais_half_generation(h, 0, ntransitions, tr0);
                 if (st == KABC_OK)
                     st = kabc_ais_half_generation(h, 1, ntransitions, tr0 + h->rows[0] * h->D);
                 if (st == KABC_OK) h->t += (uint64_t)ntransitions;
+                if (st == KABC_OK) st = ib.generation_enqueued(s);
             }
             if (st != KABC_OK) break;
+            if (cancelled && g == 0) {  // nothing of this chunk ran: the drain ends with the one before
+                std::lock_guard<std::mutex> lk(mu);
+                stop_at = c;
+                cv.notify_all();
+                break;
+            }
             sub_err = hipEventRecord(h->ev_filled[b], s);
             if (sub_err != hipSuccess) break;
             std::lock_guard<std::mutex> lk(mu);
             filled = c + 1;
+            if (cancelled) {  // the generations of this chunk that ran are drained, then the drain ends
+                stop_at = c + 1;
+                part_gc = g;
+            }
             cv.notify_all();
+            if (cancelled) break;
         }
         {
             std::lock_guard<std::mutex> lk(mu);
@@ -1404,6 +1525,10 @@ kabc_status_t kabc_ais_advance(kabc_ais_t* h, int64_t ngenerations, int32_t ntra
     if (read_counters(h, &c)) return KABC_ERR_DEVICE;
     kabc_status_t st = check_device_error(h, c);
     if (st) return st;
+    if (small_gc > 0 && c.small_done < small_gc) {  // the one-workgroup kernel saw the request
+        h->t -= (uint64_t)(small_gc - c.small_done) * (uint64_t)ntransitions;
+        cancelled = true;
+    }
     if (stats) {
         stats->proposals += c.proposals - h->last.proposals;
         stats->cost_evals += c.cost_evals - h->last.cost_evals;
@@ -1412,6 +1537,10 @@ kabc_status_t kabc_ais_advance(kabc_ais_t* h, int64_t ngenerations, int32_t ntra
     h->last.proposals = c.proposals;
     h->last.cost_evals = c.cost_evals;
     h->last.accepted = c.accepted;
+    if (cancelled) {  // (the state, t, the trace and the stats are those of the generations that ran)
+        if (!cancel_take(h->ctx)) set_error("cancelled");
+        return KABC_ERR_CANCELLED;
+    }
     return KABC_OK;
 }
 
@@ -1784,6 +1913,8 @@ kabc_status_t kabc_ais_destroy(kabc_ais_t* h) {
         if (h->ev_filled[b]) (void)hipEventDestroy(h->ev_filled[b]);
     }
     if (h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
+    for (hipEvent_t e : h->ev_blk)
+        if (e) (void)hipEventDestroy(e);
     if (h->d_dbg) (void)hipFree(h->d_dbg);
     if (h->d_aux) (void)hipFree(h->d_aux);
     if (h->d_strace) (void)hipFree(h->d_strace);

@@ -1,5 +1,6 @@
 // capi_common.hip -- context, error plumbing, prior preparation and the small
 // Factored utility kernels (logpdf / rand) of the C ABI (include/kabc.h).
+#include <csignal>
 #include <cstddef>
 #include <map>
 #include <mutex>
@@ -333,6 +334,18 @@ kabc_status_t kabc_ctx_create(int32_t device_id, void* stream, kabc_ctx_t** out)
             return KABC_ERR_DEVICE;
         }
     }
+    void* w = nullptr;
+    hipError_t e = hipHostMalloc(&w, 64, hipHostMallocCoherent | hipHostMallocMapped);
+    if (e == hipSuccess) e = hipHostGetDevicePointer((void**)&c->cancel_d, w, 0);
+    if (e != hipSuccess) {
+        if (w) (void)hipHostFree(w);
+        if (c->own_stream) (void)hipStreamDestroy(c->stream);
+        delete c;
+        set_error("kabc_ctx_create: the cancel word: %s", hipGetErrorString(e));
+        return KABC_ERR_DEVICE;
+    }
+    c->cancel_h = (uint32_t*)w;
+    *c->cancel_h = 0u;
     *out = c;
     return KABC_OK;
 }
@@ -343,7 +356,106 @@ kabc_status_t kabc_ctx_destroy(kabc_ctx_t* ctx) {
     (void)hipStreamSynchronize(ctx->stream);
     for (auto& e : ctx->pool) (void)hipFree(e.second);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->stream);
+    (void)kabc_ctx_cancel_on_sigint(ctx, 0);
+    if (ctx->cancel_h) (void)hipHostFree(ctx->cancel_h);
     delete ctx;
+    return KABC_OK;
+}
+
+kabc_status_t kabc_ctx_cancel(kabc_ctx_t* ctx) {
+    if (!ctx) return KABC_ERR_INVALID_ARG;  // (no message: this may run in a signal handler)
+    __atomic_store_n(ctx->cancel_h, 1u, __ATOMIC_RELEASE);
+    return KABC_OK;
+}
+
+kabc_status_t kabc_ctx_clear_cancel(kabc_ctx_t* ctx) {
+    if (!ctx) {
+        set_error("ctx is NULL");
+        return KABC_ERR_INVALID_ARG;
+    }
+    __atomic_store_n(ctx->cancel_h, 0u, __ATOMIC_RELEASE);
+    return KABC_OK;
+}
+
+// ---- Ctrl-C: a SIGINT handler in front of the program's own.  The armed contexts are a fixed table
+// of words the handler stores to (async-signal-safe: atomic stores only, no allocation, no lock).
+static constexpr int kSigSlots = 64;
+static uint32_t* volatile g_sig_word[kSigSlots];   // an armed context's cancel word, or NULL
+static volatile int g_sig_hit[kSigSlots];          // a SIGINT arrived while the slot was armed
+static kabc_ctx_t* g_sig_ctx[kSigSlots];           // (owner of a slot; under g_sig_mu)
+static struct sigaction g_sig_prev;                // the handler in front of which ours sits
+static std::mutex g_sig_mu;
+
+static void sigint_hook(int sig, siginfo_t* info, void* uc) {
+    bool armed = false;
+    for (int i = 0; i < kSigSlots; ++i) {
+        uint32_t* w = __atomic_load_n(&g_sig_word[i], __ATOMIC_ACQUIRE);
+        if (w) {
+            __atomic_store_n(w, 1u, __ATOMIC_RELEASE);
+            __atomic_store_n(&g_sig_hit[i], 1, __ATOMIC_RELEASE);
+            armed = true;
+        }
+    }
+    if (armed) return;  // (disarming reports it: the caller re-raises for its own handler)
+    if (g_sig_prev.sa_flags & SA_SIGINFO) {
+        if (g_sig_prev.sa_sigaction) g_sig_prev.sa_sigaction(sig, info, uc);
+    } else if (g_sig_prev.sa_handler == SIG_DFL) {
+        signal(sig, SIG_DFL);
+        raise(sig);
+    } else if (g_sig_prev.sa_handler != SIG_IGN) {
+        g_sig_prev.sa_handler(sig);
+    }
+}
+
+kabc_status_t kabc_ctx_cancel_on_sigint(kabc_ctx_t* ctx, int32_t on) {
+    if (!ctx) {
+        set_error("ctx is NULL");
+        return KABC_ERR_INVALID_ARG;
+    }
+    std::lock_guard<std::mutex> lk(g_sig_mu);
+    int slot = -1;
+    for (int i = 0; i < kSigSlots && slot < 0; ++i)
+        if (g_sig_ctx[i] == ctx) slot = i;
+    if (!on) {
+        if (slot < 0) return KABC_OK;
+        __atomic_store_n(&g_sig_word[slot], (uint32_t*)nullptr, __ATOMIC_RELEASE);
+        g_sig_ctx[slot] = nullptr;
+        if (!__atomic_exchange_n(&g_sig_hit[slot], 0, __ATOMIC_ACQ_REL)) return KABC_OK;
+        __atomic_store_n(ctx->cancel_h, 0u, __ATOMIC_RELEASE);  // (the caller raises instead)
+        set_error("interrupted (SIGINT)");
+        return KABC_ERR_CANCELLED;
+    }
+    // (re-)install the hook in front of whatever handler is there now, unless it is the hook
+    struct sigaction cur;
+    if (sigaction(SIGINT, nullptr, &cur) != 0) {
+        set_error("kabc_ctx_cancel_on_sigint: sigaction failed");
+        return KABC_ERR_DEVICE;
+    }
+    const bool hooked = (cur.sa_flags & SA_SIGINFO) && cur.sa_sigaction == sigint_hook;
+    if (!hooked && !(cur.sa_flags & SA_SIGINFO) && cur.sa_handler == SIG_IGN)
+        return KABC_OK;  // the process ignores SIGINT: so does the call (not armed)
+    if (!hooked) {
+        struct sigaction sa;
+        std::memset(&sa, 0, sizeof sa);
+        sa.sa_sigaction = sigint_hook;
+        sa.sa_flags = SA_SIGINFO | (cur.sa_flags & (SA_ONSTACK | SA_RESTART));  // (the program's restart policy)
+        sigemptyset(&sa.sa_mask);
+        g_sig_prev = cur;
+        if (sigaction(SIGINT, &sa, nullptr) != 0) {
+            set_error("kabc_ctx_cancel_on_sigint: sigaction failed");
+            return KABC_ERR_DEVICE;
+        }
+    }
+    if (slot >= 0) return KABC_OK;
+    for (int i = 0; i < kSigSlots && slot < 0; ++i)
+        if (!g_sig_ctx[i]) slot = i;
+    if (slot < 0) {
+        set_error("kabc_ctx_cancel_on_sigint: more than %d contexts armed", kSigSlots);
+        return KABC_ERR_UNSUPPORTED;
+    }
+    g_sig_ctx[slot] = ctx;
+    __atomic_store_n(&g_sig_hit[slot], 0, __ATOMIC_RELEASE);
+    __atomic_store_n(&g_sig_word[slot], ctx->cancel_h, __ATOMIC_RELEASE);
     return KABC_OK;
 }
 

@@ -377,6 +377,9 @@ static kabc_status_t smc_run_impl(kabc_ctx_t* ctx, kabc_comm_t* comm, const kabc
     const double alpha = o->alpha;
     const double r_epstol = std::isnan(o->r_epstol) ? std::pow(1.0 - alpha, 1.5) / 50.0 : o->r_epstol;
     const double min_r_ess = std::isnan(o->min_r_ess) ? alpha * alpha : o->min_r_ess;
+    // kabc_ctx_cancel (single-rank runs; a sharded run does not poll: kabc.h): a pending request ends
+    // the call before it launches anything
+    if (!comm && cancel_take(ctx)) return KABC_ERR_CANCELLED;
     // src/smc.jl:107-118, same messages
 #define KABC_REQ(cond, msg)          \
     if (!(cond)) {                   \
@@ -927,6 +930,7 @@ static kabc_status_t smc_run_impl(kabc_ctx_t* ctx, kabc_comm_t* comm, const kabc
             sm.max_passes = auxW ? aux_ring : 0;
             sm.aux = auxW ? d_aux : nullptr;
             sm.aux_ring = aux_ring;
+            sm.cancel = ctx->cancel_d;
             PriorDev* d_prior;
             KABC_HIP_CHECK(bufs.alloc(&d_prior, (size_t)KABC_MAX_DIM));
             KABC_HIP_CHECK(hipMemcpyAsync(d_prior, &P, sizeof(PriorSet), hipMemcpyHostToDevice, s));
@@ -990,6 +994,7 @@ static kabc_status_t smc_run_impl(kabc_ctx_t* ctx, kabc_comm_t* comm, const kabc
             la.min_r_ess = min_r_ess;
             la.loop = lpz;
             la.retry_n = R;
+            la.cancel = ctx->cancel_d;
             PriorDev* d_prior;
             KABC_HIP_CHECK(bufs.alloc(&d_prior, (size_t)KABC_MAX_DIM));
             KABC_HIP_CHECK(hipMemcpyAsync(d_prior, &P, sizeof(PriorSet), hipMemcpyHostToDevice, s));
@@ -1108,6 +1113,11 @@ static kabc_status_t smc_run_impl(kabc_ctx_t* ctx, kabc_comm_t* comm, const kabc
                     stop = true;
                     return KABC_OK;
                 }
+                if (!comm && cancel_pending(ctx)) {  // (the pass before has ended: an iteration boundary)
+                    hc.cancelled = 1;
+                    stop = true;
+                    return KABC_OK;
+                }
             }
             if (dist_particles) {
                 if (kabc_status_t st = dist_select()) return st;
@@ -1172,6 +1182,13 @@ static kabc_status_t smc_run_impl(kabc_ctx_t* ctx, kabc_comm_t* comm, const kabc
             pending = false;
             if (kabc_status_t st = look()) return st;
             if (hc.done) break;
+            // kabc_ctx_cancel: an iteration boundary -- every pass of the batch has ended, or a selection
+            // stalled, and then every kernel behind it was a no-op: the last completed iteration's pass
+            // end was folded before it (dsel2_begin_kernel)
+            if (!comm && cancel_pending(ctx)) {
+                hc.cancelled = 1;
+                break;
+            }
             cur_host = hc.cur;
             kb = std::min(2 * kb, kDistBatch);
             if (sel2 && hz.stalled) {
@@ -1259,6 +1276,7 @@ static kabc_status_t smc_run_impl(kabc_ctx_t* ctx, kabc_comm_t* comm, const kabc
                 if (r1 < R) {  // many retries allowed: look before enqueueing more
                     KABC_HIP_CHECK(hipMemcpyAsync(&hc, ctrl, sizeof hc, hipMemcpyDeviceToHost, s));
                     KABC_HIP_CHECK(hipStreamSynchronize(s));
+                    ++n_looks;
                     if (hc.done || !hc.pass_open) break;
                 }
             }
@@ -1269,6 +1287,7 @@ static kabc_status_t smc_run_impl(kabc_ctx_t* ctx, kabc_comm_t* comm, const kabc
         KABC_HIP_CHECK(hipGetLastError());
         KABC_HIP_CHECK(hipMemcpyAsync(&hc, ctrl, sizeof hc, hipMemcpyDeviceToHost, s));
         KABC_HIP_CHECK(hipStreamSynchronize(s));
+        ++n_looks;
         float ms = 0.f;
         if ((first || !hc.done) && hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) {
             mcmc_ms += ms;
@@ -1276,6 +1295,10 @@ static kabc_status_t smc_run_impl(kabc_ctx_t* ctx, kabc_comm_t* comm, const kabc
         }
         first = false;
         if (hc.done) break;
+        if (cancel_pending(ctx)) {  // (the look falls on an iteration boundary: the batch's last one)
+            hc.cancelled = 1;
+            break;
+        }
     }
     if (hc.error) {
         if (hc.error == 1) {
@@ -1362,6 +1385,10 @@ static kabc_status_t smc_run_impl(kabc_ctx_t* ctx, kabc_comm_t* comm, const kabc
         const kabc_status_t st2 = kabc_smc_run(ctx, prior, D, cost, o, res);
         tl_smc_no_loop = false;
         return st2;
+    }
+    if (rc == KABC_OK && hc.cancelled) {  // the result holds the population after hc.iteration iterations
+        if (!cancel_take(ctx)) set_error("cancelled");
+        rc = KABC_ERR_CANCELLED;
     }
     {
         tl_dist_stats[0] = hc.iteration;

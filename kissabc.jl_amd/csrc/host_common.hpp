@@ -75,7 +75,35 @@ struct kabc_ctx {
     std::mutex pool_mu;
     std::vector<std::pair<size_t, void*>> pool;
     size_t pool_bytes = 0;
+    // kabc_ctx_cancel's request word: pinned, host-coherent, mapped -- the host stores to
+    // cancel_h, the polling kernels read it through cancel_d
+    uint32_t* cancel_h = nullptr;
+    uint32_t* cancel_d = nullptr;
 };
+
+namespace kabc {
+// a cancel request is pending on ctx (a plain look: the request stays)
+inline bool cancel_pending(const kabc_ctx_t* ctx) {
+    return __atomic_load_n(ctx->cancel_h, __ATOMIC_ACQUIRE) != 0u;
+}
+// the call observes the request: it is consumed, the message set; the caller returns
+// KABC_ERR_CANCELLED
+inline bool cancel_take(kabc_ctx_t* ctx) {
+    if (__atomic_exchange_n(ctx->cancel_h, 0u, __ATOMIC_ACQ_REL) == 0u) return false;
+    set_error("cancelled");
+    return true;
+}
+// modelled cost of one (batch of 64 walkers, sub-step) unit of the one-workgroup AIS kernel and how
+// much work a cancel may find queued or running between two looks (kabc_ctx_cancel's response time).
+// A device read of the host word takes ~1.2 us, twelve times a read of device memory (MI355X, one wave,
+// s_memrealtime stamps: tools/host_word_latency_probe.hip, profiles/host_word_latency_probe.txt), and the
+// compiler waits for it at the next memory wait of the wave; so the one-workgroup kernel looks once per
+// ~1 ms of modelled work.
+constexpr double kCancelUnitUs = 0.6;
+constexpr double kCancelPollUs = 1000.0;      // device polls of the one-workgroup kernel
+constexpr double kCancelInflightMs = 25.0;    // host looks between launch blocks
+constexpr double kCancelLaunchUs = 10.0;      // floor of one half-generation launch pair
+}  // namespace kabc
 
 // ---- communicators (capi_comm.hip) ------------------------------------------------
 namespace kabc {

@@ -581,6 +581,7 @@ struct DevCounters {
     unsigned long long retries;   // init: total re-draws (src/KissABC.jl:57)
     int32_t error;                // 0 ok, 1 correction invalid, 2 starting sample invalid
     int32_t init_failed;          // retry budget exhausted
+    int64_t small_done;           // generations the last one-workgroup AIS launch completed (cancellation)
 };
 
 }  // namespace kabc

@@ -38,6 +38,8 @@ struct SmcCtrl {
     int32_t use_ridx;               // next MCMC pass gathers through ridx (first of an iteration)
     int32_t pass_open;              // retry passes of this iteration may still run (:192)
     int32_t passes;                 // passes executed in this iteration
+    int32_t cancelled;              // the loop stopped at an iteration boundary on kabc_ctx_cancel
+    int32_t pad_;
     unsigned long long pass;        // global pass counter = transition counter of the streams
     unsigned long long accepted;    // accumulated in this iteration
     unsigned long long cost_evals;  // cumulative

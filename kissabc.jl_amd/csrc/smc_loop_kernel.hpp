@@ -109,7 +109,13 @@ struct SmcLoopArgs {
     int32_t retry_n;          // 1 + mcmc_retrys
     unsigned long long* stamps;  // diagnostic (KABC_SMC_STAMPS): s_memrealtime sums per phase [16]
     const PriorDev* prior;    // [D] prepared components, device memory
+    // kabc_ctx_cancel's word (host-coherent memory), or NULL: read by workgroup 0 / thread 0 only and
+    // published with the pass's records, so that every workgroup takes the same decision
+    const uint32_t* cancel;
 };
+
+// passes between two reads of the cancel word by workgroup 0 (a power of two; ~1 ms at C4's 28 us)
+constexpr unsigned long long kLoopCancelEvery = 32;
 
 // keys of this kernel: -0.0 is folded onto +0.0 so that key order and `<` on the values agree
 __device__ __forceinline__ uint64_t loop_key(double x) { return key_of(x + 0.0); }
@@ -498,6 +504,8 @@ __global__ void __launch_bounds__(kLoopBlock) smc_loop_kernel(const SmcLoopArgs 
     unsigned long long pass = 0, acc_iter = 0, tot_evals = (unsigned long long)N, tot_props = 0;
     int passes_iter = 0;
     int error = prologue_ok ? 0 : 3;
+    int cancelled = 0;
+    uint32_t cw = 0u;  // (workgroup 0, thread 0: the cancel word as last read)
     // own particle
     double Xi = in ? A.X[0][i] : 0.0;
     bool alive_i = in;
@@ -579,7 +587,8 @@ __global__ void __launch_bounds__(kLoopBlock) smc_loop_kernel(const SmcLoopArgs 
             const unsigned bl = (unsigned)((b >> 42) & 0x7ffull), ab = (unsigned)(b >> 53);
             unsigned long long* P = g->part[q & 1][bid];
             P[0] = a;
-            P[1] = b & ((1ull << 42) - 1ull);
+            // (bit 63 of workgroup 0's second word: the cancel request it read, summed with zeros by the fold)
+            P[1] = (b & ((1ull << 42) - 1ull)) | ((unsigned long long)(cw != 0u) << 63);
             P[2] = s_acc[2];
             P[3] = s_acc[3];
             if (bl) atomicAdd(&g->hist[slot][kLoopBins], bl);
@@ -630,6 +639,11 @@ __global__ void __launch_bounds__(kLoopBlock) smc_loop_kernel(const SmcLoopArgs 
             break;
         }
         KABC_LSTAMP(1)
+        // the cancel word for the next pass's records.  The wait for the records below also waits for this
+        // read of host memory (vector loads retire in order), and workgroup 0 is on every barrier's critical
+        // path: so it is read once per kLoopCancelEvery passes only (tools/host_word_latency_probe.hip)
+        if (bid == 0 && tid == 0 && A.cancel && (pass & (kLoopCancelEvery - 1u)) == 0u)
+            cw = __hip_atomic_load(A.cancel, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         // ================= B1 passed.  Everything the selection may need from global memory is
         // requested at once (a dependent round trip through the fabric costs 1-2 us): the
         // records, this thread's four bins of the window histogram and its two side counters.
@@ -686,6 +700,10 @@ __global__ void __launch_bounds__(kLoopBlock) smc_loop_kernel(const SmcLoopArgs 
                 eps <= A.loop.epstol || acc < A.loop.mcmc_tol * (double)N ||
                 iteration >= A.loop.max_iterations)
                 break;
+            if (F.b >> 63) {  // a cancel: the same records, the same decision in every workgroup
+                cancelled = 1;
+                break;
+            }
         }
         if (n == 0 || nn > 0) {
             error = (nn > 0) ? 1 : 2;
@@ -1117,6 +1135,7 @@ __global__ void __launch_bounds__(kLoopBlock) smc_loop_kernel(const SmcLoopArgs 
         c.resampled = resampled;
         c.error = error;
         c.done = 1;
+        c.cancelled = cancelled;
         c.cur = cur;
         c.passes = passes_iter;
         c.pass = pass;

@@ -51,6 +51,7 @@ struct SmcSmallArgs {
     const double* aux;   // prepared cost words [aux_ring][W][N] (pass t in slot t mod aux_ring), or NULL
     int32_t aux_ring;
     const PriorDev* prior;  // [D] prepared components, device memory
+    const uint32_t* cancel;  // kabc_ctx_cancel's word (host-coherent memory), or NULL
 };
 
 // sums of up to three 0/1 flags over the workgroup (every thread gets them), packed 10 bits each: wave
@@ -106,12 +107,19 @@ __global__ void __launch_bounds__(kSmallBlock) smc_small_kernel(const SmcSmallAr
     int passes_left = (A.max_passes > 0 && R == 1) ? A.max_passes : 0x7fffffff;
     const double sqrtD = kabc_sqrt((double)D);
     const unsigned long long below = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+    uint32_t cw = 0u;  // (thread 0: the cancel word, requested at the previous iteration's MCMC step)
 
     while (passes_left >= R) {
         // ================= Step 1 (:134-143): ε = quantile(Xs[alive], α), alive mask, ESS
         const double Xi = in ? s_X[tid] : 0.0;
-        const unsigned nc = small_count3(alive_i, alive_i && Xi != Xi, false, s_cntA, wid, lane);
+        // (the third count carries thread 0's cancel request through the step's barrier: one decision)
+        const unsigned nc = small_count3(alive_i, alive_i && Xi != Xi, tid == 0 && cw != 0u, s_cntA, wid, lane);
         const unsigned n = nc & 1023u, nn = (nc >> 10) & 1023u;
+        if ((nc >> 20) != 0u && c.iteration > 0) {  // stop at this iteration boundary (kabc_ctx_cancel)
+            c.cancelled = 1;
+            c.done = 1;
+            break;
+        }
         if (n == 0u || nn > 0u) {
             c.error = nn > 0u ? 1 : 2;
             c.done = 1;
@@ -196,6 +204,9 @@ __global__ void __launch_bounds__(kSmallBlock) smc_small_kernel(const SmcSmallAr
         c.resampled = resampled;
         c.accepted = 0;
         c.passes = 0;
+        // (every 16th iteration: a read of host memory, ~1.2 us, stalls the wave where it is waited for)
+        if (tid == 0 && A.cancel && (c.iteration & 15) == 0)
+            cw = __hip_atomic_load(A.cancel, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         // ================= Step 3 (:156-193): propose from the frozen ensemble, then accept
         for (int r = 0; r < R; ++r) {
             const uint64_t pass = c.pass + 1u;

@@ -132,7 +132,9 @@ mutable struct KabcPfilterResult
     cost_evals::UInt64
 end
 
-check(st) = st == 0 ? nothing :
+const KABC_ERR_CANCELLED = Cint(7)
+# a cancelled call (cancel!) ends like an interrupted Julia loop would: InterruptException
+check(st) = st == 0 ? nothing : st == KABC_ERR_CANCELLED ? throw(InterruptException()) :
     error(unsafe_string(ccall((:kabc_last_error, libkabc), Cstring, ())))   # reference's text
 
 # ---- DeviceCost: the `cost` argument on the device path ----------------------
@@ -456,6 +458,13 @@ function context(device::Integer = 0)
     end
 end
 
+"""cancel!(device = 0): request that the sample / smc call running on that device's context stop at
+its next generation / iteration boundary (it then throws InterruptException).  One store: callable from
+any task or thread.  Sticky: made while the context is idle, it cancels the next call."""
+cancel!(device::Integer = 0) = check(ccall((:kabc_ctx_cancel, libkabc), Cint, (Ptr{Cvoid},), context(device)))
+"clear_cancel!(device = 0): drop a pending cancel request"
+clear_cancel!(device::Integer = 0) = check(ccall((:kabc_ctx_clear_cancel, libkabc), Cint, (Ptr{Cvoid},), context(device)))
+
 "with_model(f, model): lowers the model to a kabc_model_t that stays valid while `f` runs"
 function with_model(f, model)
     pri = lower_prior(prior_of(model))
@@ -778,7 +787,7 @@ function spec_counters()
     (started = out[1], loaded = out[2], failed = out[3], cache_hits = out[4])
 end
 
-export DeviceCost, UserCost, UserPrior, compile_model, release_model, prefetch_model, spec_counters, set_specialize, rtc_cache_dir, UserMvPrior, InitFrom, InitFromSnippet, GaussDist, Rosenbrock, HierGaussSim, NormalMeanStdSim, DiracSq,
+export cancel!, clear_cancel!, DeviceCost, UserCost, UserPrior, compile_model, release_model, prefetch_model, spec_counters, set_specialize, rtc_cache_dir, UserMvPrior, InitFrom, InitFromSnippet, GaussDist, Rosenbrock, HierGaussSim, NormalMeanStdSim, DiracSq,
        AbsDiff, NormShell, NoisyQuadDU, Mixture, NoisyBanana, WienerRms, sample_sharded, unique_id,
        comm_init_rank
 end # module
