@@ -82,6 +82,72 @@ struct kabc_ctx {
 };
 
 namespace kabc {
+// device buffers of one run-to-completion call (kabc_smc_run, kabc_pfilter_run), released on every
+// return path
+struct DevBufs {
+    kabc_ctx_t* ctx = nullptr;                         // set: buffers come from / go back to its cache
+    std::vector<std::pair<size_t, void*>> held;
+    // bytes kept per context: 4 GiB of the 288 (the working set of smc at 2 M particles x 16 is
+    // 0.9 GB: with the former 512 MiB every call allocated and freed two 268 MB buffers);
+    // KABC_POOL_MB overrides
+    static size_t pool_cap() {
+        static const size_t cap = [] {
+            const char* e = std::getenv("KABC_POOL_MB");
+            const double mb = e ? std::atof(e) : 4096.0;
+            return (size_t)((mb > 0.0 ? mb : 0.0) * (double)(1 << 20));
+        }();
+        return cap;
+    }
+    ~DevBufs() { release(); }
+    // hands every buffer back (to the context's cache, else to the driver); the owner's pointers dangle
+    void release() {
+        for (auto& e : held) {
+            if (!e.second) continue;
+            if (ctx) {
+                std::lock_guard<std::mutex> lk(ctx->pool_mu);
+                if (ctx->pool_bytes + e.first <= pool_cap()) {
+                    ctx->pool.push_back(e);
+                    ctx->pool_bytes += e.first;
+                    continue;
+                }
+            }
+            (void)hipFree(e.second);
+        }
+        held.clear();
+    }
+    template <class T>
+    hipError_t alloc(T** p, size_t n) {
+        const size_t bytes = sizeof(T) * (n ? n : 1);
+        if (ctx) {  // smallest cached buffer that fits and is not more than twice too large
+            std::lock_guard<std::mutex> lk(ctx->pool_mu);
+            int best = -1;
+            for (int i = 0; i < (int)ctx->pool.size(); ++i)
+                if (ctx->pool[i].first >= bytes && ctx->pool[i].first <= 2 * bytes + 4096 &&
+                    (best < 0 || ctx->pool[i].first < ctx->pool[best].first))
+                    best = i;
+            if (best >= 0) {
+                held.push_back(ctx->pool[best]);
+                *p = (T*)ctx->pool[best].second;
+                ctx->pool_bytes -= ctx->pool[best].first;
+                ctx->pool.erase(ctx->pool.begin() + best);
+                // (a recycled buffer carries the last run's bytes: the same poison as a fresh one)
+                return poison_alloc() ? poison_fill((void*)*p, held.back().first) : hipSuccess;
+            }
+        }
+        hipError_t e = dev_malloc(p, bytes);
+        if (e == hipSuccess) held.push_back({bytes, (void*)*p});
+        return e;
+    }
+};
+
+// the select kernel (smc_kernels.hpp) of smc and pfilter: its grid for N particles, whether it is launched
+// cooperatively (KABC_SMC_COOPERATIVE=1, or `force_coop`: a run repeated after an ordinary launch timed
+// out), and its launch (capi_smc.hip)
+struct SmcSelectArgs;
+unsigned select_blocks(int64_t N);
+bool select_cooperative(bool force_coop);
+hipError_t launch_select(const SmcSelectArgs& sa, unsigned G, hipStream_t s, bool force_coop);
+
 // a cancel request is pending on ctx (a plain look: the request stays)
 inline bool cancel_pending(const kabc_ctx_t* ctx) {
     return __atomic_load_n(ctx->cancel_h, __ATOMIC_ACQUIRE) != 0u;

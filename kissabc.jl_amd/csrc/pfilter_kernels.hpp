@@ -53,7 +53,7 @@ struct PfArgs {
 
 constexpr int kPfBlock = 64;
 
-#ifdef KABC_SMC_SINGLE_UNIT  // non-template kernel: defined once, in capi_smc.hip
+#ifdef KABC_PFILTER_UNIT  // non-template kernels: defined once, in capi_pfilter.hip
 // pending[i] = !ok[i]; remaining = N - n_ok   (idxbad, :301)
 __global__ void __launch_bounds__(256) pf_mark_kernel(uint8_t* pending, const uint8_t* ok,
                                                       PfCtrl* ctrl, const SmcCtrl* sel, int64_t N) {
@@ -96,7 +96,7 @@ __global__ void pf_iter_end_kernel(PfCtrl* ctrl, SmcCtrl* sel, int64_t N, double
     }
 }
 
-#endif  // KABC_SMC_SINGLE_UNIT
+#endif  // KABC_PFILTER_UNIT
 
 // the rejection loop of ONE bad particle i (:306-325), attempts [a0, a_end): its proposals are built
 // from survivors only (idxok[0 .. nok)), which nobody writes during the iteration, so the loop needs
