@@ -52,6 +52,11 @@ typedef enum kabc_status {
     KABC_ERR_NAN_COST = 6,        /* Statistics.quantile: "undefined in presence of NaNs" */
     KABC_ERR_CANCELLED = 7        /* kabc_ctx_cancel: stopped at a generation / iteration boundary */
 } kabc_status_t;
+/* KABC_ERR_INVALID_STATE from kabc_smc_run*: "no alive particle to resample from" when an
+ * iteration's alive mask is empty and a resample is due (ESS = 0; the reference's
+ * ceil(Int, N/0) throws there).  ε = quantile(Xs[alive], α) is NaN when the interpolation meets
+ * 0·Inf or -Inf + Inf, and then no particle passes the alive test.  The oracle and every device
+ * course report the same status and message; the call's result is not written. */
 
 /* ---- Factored prior surface (src/priors.jl:10-49) ------------------------ */
 typedef enum kabc_prior_kind {

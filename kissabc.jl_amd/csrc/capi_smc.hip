@@ -1020,6 +1020,7 @@ kabc_status_t run_one_exchange(SmcRun& r) {
                 return KABC_OK;
             }
         }
+        ++r.n_stalls;  // (counted here: a run that ends at the previous pass makes no selection)
         if (r.dist_particles) {
             if (kabc_status_t st = r.dist_select()) return st;
         } else {
@@ -1042,7 +1043,6 @@ kabc_status_t run_one_exchange(SmcRun& r) {
     // ensemble fits a slot: then every alive key is a candidate from the start)
     if (sel2 && !(r.N <= dz.spec_cap && r.N <= (int64_t)kDselStage))
         for (int i = 0; i < 2 && !stop; ++i) {
-            ++r.n_stalls;
             if (kabc_status_t st = looked_iteration()) return st;
         }
     int kb = kDistBatch;
@@ -1091,7 +1091,6 @@ kabc_status_t run_one_exchange(SmcRun& r) {
         if (sel2 && r.hz.stalled) {
             // every kernel behind the stalled selection was a no-op (the collectives re-gathered what
             // was there): that selection phase by phase, its pass, and on with shorter batches
-            ++r.n_stalls;
             r.n_spec -= 1;
             if (std::getenv("KABC_SMC_STAMPS") && r.rank == 0)
                 fprintf(stderr, "[kabc smc] the one-exchange selection of iteration %lld stalled (reason %d)\n",
@@ -1258,6 +1257,11 @@ kabc_status_t finish(SmcRun& r) {
         // repeated below on the kernel-per-phase path -- every draw is counter-based, so the
         // repetition is the same run.
         rc = KABC_ERR_UNSUPPORTED;
+    } else if (hc.error == 5) {
+        // ESS = 0 with a resample due: ε came out NaN (0·Inf or -Inf + Inf in the quantile's
+        // interpolation), so no particle passed the alive test (include/kabc.h)
+        set_error("no alive particle to resample from");
+        rc = KABC_ERR_INVALID_STATE;
     } else if (hc.error) {
         set_error("collection must be non-empty");
         rc = KABC_ERR_INVALID_STATE;

@@ -562,7 +562,7 @@ __global__ void __launch_bounds__(kSelBlock) dsel_compact_kernel(const DselArgs 
     if (blockIdx.x == 0 && tid == 0) {
         A.st->ESS = ESS;
         A.st->resample = resample;
-        if (fail) dsel_fail(A, 2);
+        if (fail) dsel_fail(A, 5);
     }
 }
 
@@ -1176,7 +1176,7 @@ __global__ void __launch_bounds__(kSelBlock) dsel2_decide_kernel(const DselArgs 
         S.state = 3;
         *A.st = S;
         if (resample && ESS == 0) {
-            dsel_fail(A, 2);
+            dsel_fail(A, 5);
             return;
         }
         A.ctrl->iteration = iteration0 + 1;

@@ -32,7 +32,7 @@ struct SmcCtrl {
     long long iteration;
     int32_t flag;
     int32_t resampled;
-    int32_t error;                  // 1 NaN cost among alive, 2 no alive particle
+    int32_t error;                  // 1 NaN cost among alive, 2 no alive particle, 5 ESS = 0 at a resample
     int32_t done;                   // outer loop has terminated (:194-198) or failed
     int32_t cur;                    // buffer set holding the current ensemble
     int32_t use_ridx;               // next MCMC pass gathers through ridx (first of an iteration)
@@ -768,8 +768,8 @@ __global__ void __launch_bounds__(kSelBlock) smc_select_kernel(const SmcSelectAr
         if (tid == 0) g->ncand = 0;
     }
     if (tid == 0) {
-        if (fail) {
-            A.ctrl->error = 2;
+        if (fail) {  // (ε = NaN: nothing to resample from)
+            A.ctrl->error = 5;
             A.ctrl->done = 1;
             return;
         }

@@ -954,6 +954,10 @@ __global__ void __launch_bounds__(kLoopBlock) smc_loop_kernel(const SmcLoopArgs 
                         for (int u = 0; u < 4; ++u) mw[u] |= mi[u];
                     }
                 }
+                if (eps != eps) {  // ε = NaN (0·Inf, -Inf + Inf): no cost is below it, not even below the bin
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) mw[u] = 0ull;
+                }
                 // The words go to LDS; the candidates that join the alive set OR their bit in (one
                 // LDS atomic per candidate, issued by the lanes that hold them); every thread reads
                 // its words back.  (Each thread scanning the whole candidate list for bits that
@@ -1012,8 +1016,8 @@ __global__ void __launch_bounds__(kLoopBlock) smc_loop_kernel(const SmcLoopArgs 
             KABC_LOOP_RECYCLE()
             // Step 2 decision: α*ESS <= nparticles*min_r_ess  (:145)
             resampled = (A.alpha * (double)ess <= (double)N * A.min_r_ess) ? 1 : 0;
-            if (resampled && ess == 0) {
-                error = 2;
+            if (resampled && ess == 0) {  // (ε = NaN: nothing to resample from)
+                error = 5;
                 break;
             }
             alive_i = in && (resampled ? true : ((s_words[i >> 6] >> (i & 63)) & 1ull) != 0ull);

@@ -170,8 +170,8 @@ __global__ void __launch_bounds__(kSmallBlock) smc_small_kernel(const SmcSmallAr
         __syncthreads();
         // ================= Step 2 (:145-153): cyclic resample
         const int resampled = (A.alpha * (double)ESS <= (double)N * A.min_r_ess) ? 1 : 0;
-        if (resampled && ESS == 0u) {
-            c.error = 2;
+        if (resampled && ESS == 0u) {  // (ε = NaN: nothing to resample from)
+            c.error = 5;
             c.done = 1;
             break;
         }

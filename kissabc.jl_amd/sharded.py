@@ -237,8 +237,8 @@ def sharded_select(X_own, alive_own, lo, N, alpha, min_r_ess, all_gather, cand_c
     resample = alpha * ESS <= N * min_r_ess
     idx = None
     if resample:
-        if ESS == 0:
-            raise ValueError("collection must be non-empty")
+        if ESS == 0:   # (ε = NaN; include/kabc.h)
+            raise ValueError("no alive particle to resample from")
         idx = np.concatenate([np.asarray(s, dtype=np.int64)
                               for s in all_gather(lo + np.flatnonzero(new_alive))])
         new_alive = np.ones_like(new_alive)
@@ -317,8 +317,8 @@ def sharded_select_one_exchange(X_own, alive_own, lo, N, alpha, min_r_ess, all_g
     new_alive = (X_own <= eps) if flag else (X_own < eps)
     idx = None
     if resample:
-        if ESS == 0:
-            raise ValueError("collection must be non-empty")
+        if ESS == 0:   # (ε = NaN; include/kabc.h)
+            raise ValueError("no alive particle to resample from")
         X_all = np.asarray(X_all, dtype=np.float64)
         idx = np.flatnonzero((X_all <= eps) if flag else (X_all < eps))   # no exchange
         new_alive = np.ones_like(new_alive)

@@ -415,15 +415,16 @@ class OracleAIS:
 
 
 def smc(prior, cost, *, nparticles=100, alpha=0.95, mcmc_retrys=0, mcmc_tol=0.015, epstol=0.0,
-        r_epstol=None, min_r_ess=None, max_stretch=2.0, verbose=False, seed=0):
-    """CPU restatement of smc() (src/smc.jl:92-206); returns dict."""
+        r_epstol=None, min_r_ess=None, max_stretch=2.0, verbose=False, seed=0, max_iterations=None):
+    """CPU restatement of smc() (src/smc.jl:92-206); returns dict.  `max_iterations` bounds the
+    outer loop as kissabc_jl_amd.smc's does (None: the 100 000 of kabc_smc_opts_t)."""
     fac = as_factored(prior)
     o = cd.SmcOpts()
     o.nparticles, o.alpha, o.mcmc_retrys, o.verbose = int(nparticles), alpha, mcmc_retrys, int(verbose)
     o.mcmc_tol, o.epstol, o.max_stretch, o.seed = mcmc_tol, epstol, max_stretch, seed
     o.r_epstol = math.nan if r_epstol is None else r_epstol
     o.min_r_ess = math.nan if min_r_ess is None else min_r_ess
-    o.max_iterations = 0
+    o.max_iterations = 0 if max_iterations is None else int(max_iterations)
     N, D = int(nparticles), len(fac)
     theta = np.empty((max(N, 1), D))
     Cst = np.empty(max(N, 1))

@@ -229,3 +229,198 @@ def prior_law(kind, params):
         return Law(lambda t: mpf(ref.cdf(float(t))), ref.ppf, 0.0, inf, mean=m, sd=math.sqrt(v), kurt=kt, discrete=True,
                    sf=lambda t: mpf(ref.sf(float(t))))
     raise KeyError(kind)
+
+
+# ---- one ε-selection of smc (src/smc.jl:131-153), independent of the oracle and the kernels
+# (tests/smc_scenarios.py, test_smc_selection_edges.py, test_gpu_smc_selection_edges.py)
+def quantile7(v, p):
+    """Statistics.quantile(v, p) with its defaults (alpha = beta = 1, "type 7"), from the documented
+    definition: aleph = n p + (1 - p), j = trunc(aleph) in [1, n - 1], γ = aleph - j in [0, 1], the
+    order statistics a = v(j), b = v(j+1); a + γ(b - a) when both are finite, else (1 - γ)a + γb."""
+    s = np.sort(np.asarray(v, dtype=np.float64))
+    n = s.size
+    if n == 0:
+        raise ValueError("collection must be non-empty")
+    if np.isnan(s).any():
+        raise ValueError("quantiles are undefined in presence of NaNs")
+    aleph = float(n) * p + (1.0 - p)
+    j = 1 if n == 1 else min(max(int(aleph), 1), n - 1)
+    g = min(max(aleph - float(j), 0.0), 1.0)
+    a = float(s[j - 1])
+    b = float(s[0] if n == 1 else s[j])
+    with np.errstate(invalid="ignore"):
+        if math.isfinite(a) and math.isfinite(b):
+            return float(np.float64(a) + np.float64(g) * (np.float64(b) - np.float64(a)))
+        return float((1.0 - np.float64(g)) * np.float64(a) + np.float64(g) * np.float64(b))
+
+
+NO_ALIVE = "no alive particle to resample from"
+
+
+def select_step(C, alive, alpha, min_r_ess, N):
+    """Step 1 and the decision of step 2 of one smc iteration (src/smc.jl:134-147), by value
+    comparisons only: returns (ε, flag, new alive mask, ESS, resample, error).  `error` is
+    NO_ALIVE when ESS = 0 and a resample is due (the reference's ceil(Int, N/0) throws)."""
+    C = np.asarray(C, dtype=np.float64)
+    alive = np.asarray(alive, dtype=bool)
+    Xa = C[alive]
+    eps = quantile7(Xa, alpha)
+    mn = float(Xa.min())
+    with np.errstate(invalid="ignore"):
+        flag = 0 if eps > mn else 1
+        new = (C <= eps) if flag else (C < eps)
+    ess = int(new.sum())
+    resample = int(alpha * float(ess) <= float(N) * min_r_ess)
+    err = NO_ALIVE if (resample and ess == 0) else None
+    return eps, flag, new, ess, resample, err
+
+
+def key_of(x):
+    """the kernels' order-preserving key of a double (csrc/smc_kernels.hpp key_of): -0.0 < +0.0"""
+    u = np.atleast_1d(np.asarray(x, dtype=np.float64)).view(np.uint64)
+    top = np.uint64(1 << 63)
+    return np.where(u & top, ~u, u | top)
+
+
+def _bits(span):
+    return int(span).bit_length()
+
+
+def _narrow(keys, lo, hi, kt):
+    """one 1024-bin histogram round of the kernels over the sorted key array `keys` restricted to
+    [lo, hi]: the bin of rank kt.  Returns (lo, hi, kt, count, shift)."""
+    shift = max(_bits(hi - lo) - 10, 0)
+    sel = keys[(keys >= np.uint64(lo)) & (keys <= np.uint64(hi))]
+    bins = ((sel - np.uint64(lo)) >> np.uint64(shift)).astype(np.int64)
+    cnt = np.bincount(bins, minlength=1024)
+    cum = np.cumsum(cnt)
+    b = int(np.searchsorted(cum, kt, side="right"))
+    before = int(cum[b - 1]) if b else 0
+    nlo = lo + (b << shift)
+    nhi = min(nlo + (1 << shift) - 1, hi)
+    return nlo, nhi, kt - before, int(cnt[b]), shift
+
+
+def _target(n, alpha):
+    aleph = float(n) * alpha + (1.0 - alpha)
+    return 1 if n == 1 else min(max(int(aleph), 1), n - 1)
+
+
+def witness_select(Xa, alpha):
+    """the select kernel's narrowing (csrc/smc_kernels.hpp, smc_select_kernel (c)) on the alive costs
+    Xa: global 1024-bin rounds until the range holds <= kSelCand = 4096 keys, list rounds until
+    <= 64, state 2 (every key of the range equal), needmin (rank j is above the final range) and
+    above_scan (needmin, and no listed key lies above the range: X is scanned again).  The phase-by-phase
+    course (csrc/smc_dsel_kernels.hpp dsel_*) narrows with the same states: its narrowing rounds are the
+    global rounds here, and above_scan is its dsel_above pass."""
+    keys = np.sort(key_of(Xa))
+    n = keys.size
+    j = _target(n, alpha)
+    lo, hi, kt, cnt = int(keys[0]), int(keys[-1]), j - 1, n
+    out = dict(global_rounds=0, list_rounds=0, state2=False, needmin=False)
+    state = 2 if lo == hi else (1 if n <= 4096 else 0)
+    while state == 0:
+        lo, hi, kt, cnt, shift = _narrow(keys, lo, hi, kt)
+        out["global_rounds"] += 1
+        state = 2 if shift == 0 else (1 if cnt <= 4096 else 0)
+    listed = None
+    if state == 1:
+        listed = (lo, hi)
+        state = 3 if cnt <= 64 else 0
+        while state == 0:
+            if hi == lo:
+                state = 2
+                break
+            lo, hi, kt, cnt, shift = _narrow(keys, lo, hi, kt)
+            out["list_rounds"] += 1
+            state = 2 if shift == 0 else (3 if cnt <= 64 else 0)
+    out["state2"] = state == 2
+    out["needmin"] = n > 1 and kt + 1 >= cnt
+    # the key above the final range is looked up among the listed keys; without a list, or with none of
+    # them above the range, the costs are scanned again (the phase-by-phase course's dsel_above pass)
+    out["above_scan"] = out["needmin"] and (listed is None or not bool(
+        ((keys > np.uint64(hi)) & (keys <= np.uint64(listed[1]))).any()))
+    return out
+
+
+def loop_key(x):
+    """the loop and one-workgroup kernels' key: -0.0 folded onto +0.0 (key_of(x + 0.0))"""
+    return key_of(np.asarray(x, dtype=np.float64) + 0.0)
+
+
+def witness_loop(C, alive, alpha, eps_1, eps_2):
+    """the persistent loop kernel's selection (csrc/smc_loop_kernel.hpp) of an iteration whose two
+    previous ε are eps_1 (last) and eps_2 (None: fewer than two): whether the predicted window
+    [key(ε) - max(8 d, 4096), key(ε)] held the target rank ("hit") or missed, the histogram rounds,
+    whether a round's bin held more than kLoopCand = 512 alive keys, and the candidate count of the
+    final bin (alive and dead particles: over kLoopCandCap = 1024 it is error 4)."""
+    C = np.asarray(C, dtype=np.float64)
+    alive = np.asarray(alive, dtype=bool)
+    kall = loop_key(C)
+    keys = np.sort(kall[alive])
+    n = keys.size
+    kt = _target(n, alpha) - 1
+    out = dict(pred=False, hit=False, rounds=0, over512=False, ncand=0, state2=False)
+    lo, hi = int(keys[0]), int(keys[-1])
+    have = None
+    if eps_2 is not None and math.isfinite(eps_1) and math.isfinite(eps_2):
+        out["pred"] = True
+        whi = int(loop_key(eps_1)[0])
+        kp = int(loop_key(eps_2)[0])
+        d = min(kp - whi if kp > whi else 1, 1 << 56)
+        span = max(d * 8, 4096)
+        wlo = whi - span if whi > span else 0
+        below, above = int((keys < np.uint64(wlo)).sum()), int((keys > np.uint64(whi)).sum())
+        if above == 0 and kt >= below:
+            out["hit"] = True
+            lo, hi, kt, have = wlo, whi, kt - below, True
+    state = 0
+    while state == 0:
+        if lo == hi:
+            state = 2
+            break
+        lo, hi, kt, cnt, shift = _narrow(keys, lo, hi, kt)
+        out["rounds"] += 1
+        if shift == 0:
+            state = 2
+        elif cnt <= 512:
+            state = 1
+        else:
+            out["over512"] = True
+    out["state2"] = state == 2
+    if state == 1:
+        out["ncand"] = int(((kall >= np.uint64(lo)) & (kall <= np.uint64(hi))).sum())
+    return out
+
+
+def witness_dsel2(Xa, alpha, eps_1, eps_2, eps_now, N):
+    """the one-exchange course's stall reason (csrc/smc_dsel_kernels.hpp dsel2_*) for an iteration of a
+    single-rank run of N > kDselStage = 4096 particles whose two previous ε are eps_1 (last) and eps_2:
+    1 no window (d = eps_2 - eps_1 not > 0 or not finite), 2 the window holds more alive keys than the
+    payload slot (max(4096, N / 8)), 3 the target rank outside the window [key(eps_1 - 1.4 d),
+    key(eps_1 - 0.65 d)], 5 the target's bin holds more than kSelCand = 4096 keys, 7 the selected ε is 0.
+    0: the course decided.  (7 is also raised when needmin finds no key above the final range: not
+    modelled.)"""
+    keys = np.sort(key_of(Xa))
+    n = keys.size
+    e1, e0 = float(eps_1), float(eps_2)
+    with np.errstate(invalid="ignore", over="ignore"):
+        d = e0 - e1
+    if not (math.isfinite(e1) and math.isfinite(d) and d > 0.0):
+        return 1
+    wlo, whi = int(key_of(e1 - 1.4 * d)[0]), int(key_of(e1 - 0.65 * d)[0])
+    if wlo > whi:
+        return 1
+    below = int((keys < np.uint64(wlo)).sum())
+    inside = int(((keys >= np.uint64(wlo)) & (keys <= np.uint64(whi))).sum())
+    if inside > max(4096, (N // 8 + 1) & ~1):      # the payload slot's capacity (capi_smc.hip spec_cap)
+        return 2
+    kt = _target(n, alpha) - 1 - below
+    if kt < 0 or kt >= inside:
+        return 3
+    _, _, _, cnt, _ = _narrow(keys, wlo, whi, kt)
+    if cnt > 4096:
+        return 5
+    if eps_now == 0.0:
+        return 7
+    return 0
