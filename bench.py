@@ -11,9 +11,17 @@ script needs neither torch nor torch.distributed).  Weak scaling: per-GPU walker
 are fixed, N_total = 65 536 * gpus.
 
 `ntransitions`: SURVEY §8d prescribes {1, 16}; the reference's own examples sample
-with 100 (README.md:57, BASELINE.json configs[0]).  All three are timed in every
-run and reported under `by_ntransitions`; the headline (`value`, `roofline`) is the
-one --ntransitions selects (default 100) and says so in `config`.
+with 100 (README.md:57, BASELINE.json configs[0]).  The headline (`value`, `roofline`)
+is the one --ntransitions selects (default 100) and says so in `config`; with --full
+all three are timed and reported under `by_ntransitions`.
+
+A plain run does what the headline needs and nothing else: set-up, warm-up, the timed
+steps, --dump-outputs, the result line.  Its ensemble still takes the steps the other
+settings take before the headline in a --full run (5 + K of each, untimed; none with
+--no-alt), so the headline's inputs, its figure and its dumped state do not depend on
+--full.  --full adds everything else: the other settings' figures, `smc_c4`, the
+README / C2 / reference-shape / prior-class legs, the cold-cache child, the latency-floor
+probes and `cpu_baseline`.
 
 Timed region: after WARM_SECONDS of the same work on a scratch ensemble (the clocks come
 up), W warm-up steps, then EXACTLY K timed steps (--steps K), bracketed by a
@@ -30,10 +38,11 @@ algorithmic bytes per launch = rows * ntransitions * 8(3D+4) over 
 kernel's average duration measured with hipEvents on its stream over the timed
 region; `roofline.valu` is the second, binding resource: VALU wave-instructions per
 launch (committed PMC summary, profiles/) x the kernel's mix-weighted issue cycles
-(profiles/r*_valu_mix.json) / (1024 SIMDs x 2.4 GHz x kernel time).  `smc_c4` times BASELINE.json configs[3] (smc, 32 768 particles, D = 16) the
-same way.  `next_rows` are wall-clock legs of SURVEY 8's f3 / f4 rows (ABCDE, pfilter) beside the
-oracle on the same runs.  `cpu_baseline` times the CPU oracle's faithful serial restatement of the
-reference on a bounded sample of the same workloads.
+(profiles/r*_valu_mix.json) / (1024 SIMDs x 2.4 GHz x kernel time).  With --full, `smc_c4` times
+BASELINE.json configs[3] (smc, 32 768 particles, D = 16) the same way, `next_rows` are wall-clock
+legs of SURVEY 8's f3 / f4 rows (ABCDE, pfilter) beside the oracle on the same runs, and
+`cpu_baseline` times the CPU oracle's faithful serial restatement of the reference on a bounded
+sample of the same workloads.
 """
 import argparse
 import glob
@@ -487,8 +496,8 @@ def stub_rank(mode, rank, world, args):
     if rank == 0:
         print("stub: a line that is not the result")
         print(json.dumps({"metric": "stub", "value": 1.0, "n_gpus": world, "steps": args.steps,
-                          "warmup": args.warmup, "ranks_env": [os.environ.get(v) for v in
-                                                               ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR")]}),
+                          "warmup": args.warmup, "full": args.full,
+                          "ranks_env": [os.environ.get(v) for v in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR")]}),
               flush=True)
     raise SystemExit(0)
 
@@ -591,10 +600,15 @@ def main():
                     help="the same for the headline setting (one uninterrupted stretch); 0: exactly K timed steps")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write the headline ensemble's state after its last timed step as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: the other ntransitions settings, the smc, "
+                         "README, C2, reference-shape and prior-class legs, the cold-cache child, the "
+                         "latency-floor probes and the CPU baseline (the --no-* options below trim it)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-alt", action="store_true",
-                    help="time the headline ntransitions only (clean rocprof summaries)")
+                    help="run the headline ntransitions only, without the other settings' steps before it "
+                         "(clean rocprof summaries)")
     ap.add_argument("--no-smc", action="store_true", help="skip the C4 smc leg")
     ap.add_argument("--no-cold-spec", action="store_true",
                     help="skip the cold-cache measurement of the default specialisation path (a child process)")
@@ -620,13 +634,13 @@ def main():
     # leg spawns worker processes, and a process that has initialised HIP must not
     # fork+exec on this pool.
     cpu = None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         import kissabc_jl_amd as k0
         cpu = cpu_baseline(k0, args.cpu_seconds, with_smc=not args.no_smc)
 
     floor_in = None
     sharded1 = None
-    if world == 1 and not emulate and not args.no_smc:
+    if args.full and world == 1 and not emulate and not args.no_smc:
         floor_in = latency_floor_inputs()
         if not args.no_alt:
             sharded1 = smc_sharded_world1()
@@ -634,7 +648,7 @@ def main():
     # ... and so does the cold-cache leg of the default specialisation path (its own process: the
     # code-object cache must be empty and no unit loaded)
     cold_spec = None
-    if world == 1 and not emulate and not args.no_alt and not args.no_cold_spec:
+    if args.full and world == 1 and not emulate and not args.no_alt and not args.no_cold_spec:
         import subprocess
         try:
             cp = subprocess.run([sys.executable, os.path.abspath(__file__), "--cold-spec"],
@@ -770,6 +784,13 @@ def main():
     settings = [nt_head] if args.no_alt else sorted(set(NT_SET) | {nt_head})
     regions = {}
     for nt_r in settings:
+        if not args.full and nt_r != nt_head:
+            # a plain run times the headline alone; a setting ahead of it still takes the steps it
+            # takes in a --full run (untimed), so the headline starts from the same ensemble
+            if nt_r < nt_head:
+                ens.advance(5, nt_r)
+                ens.advance(args.steps, nt_r)
+            continue
         # by default every setting times exactly K steps.  With --min-seconds the block count evens
         # the timed duration out instead (the same K would make the nt = 1 block 100x shorter), and
         # the headline setting runs --headline-seconds without a gap, so that an external sampler
@@ -805,7 +826,7 @@ def main():
         return res
 
     extra = {}
-    if world == 1 and not args.no_alt and isinstance(ctx, k.Context):
+    if args.full and world == 1 and not args.no_alt and isinstance(ctx, k.Context):
         # BASELINE.json configs[0]: the README example end to end through sample()
         rm = readme_problem(k)
         k.sample(rm, k.AIS(10), 1000, ntransitions=NT_HEADLINE, seed=1, ctx=ctx, return_array=True)
@@ -980,7 +1001,7 @@ def main():
         extra["by_prior_class"] = bpc
 
     smc = None
-    if world == 1 and not args.no_smc and isinstance(ctx, k.Context):
+    if args.full and world == 1 and not args.no_smc and isinstance(ctx, k.Context):
         prior, cost, kw = c4_problem(k)
         # warm-up: module load, allocations, and a one-off ~25 ms hiccup on the fourth call that
         # returns the 4 MiB particle array (host-side; steady state afterwards)
@@ -1079,8 +1100,9 @@ def main():
         # What a smaller ntransitions could reach at best with this kernel: every half-generation
         # must see the rows the previous one wrote, and the cheapest way to pay for that on this
         # chip is the kernel boundary itself (profiles/r03_halfgen_floor.json: 3.6 us per half at
-        # 512 workgroups, against 18-31 us for a device-wide barrier inside one launch).
-        if str(100) in by_nt and by_nt["100"]["kernel_avg_us"] > 0:
+        # 512 workgroups, against 18-31 us for a device-wide barrier inside one launch).  (--full: the
+        # slope below wants the 16 setting's own run.)
+        if args.full and str(100) in by_nt and by_nt["100"]["kernel_avg_us"] > 0:
             try:
                 fl = json.load(open(os.path.join(ROOT, "profiles", "r03_halfgen_floor.json")))
                 launch_us = float(fl.get("launch_512", 3.6))
@@ -1121,7 +1143,8 @@ def main():
                        "ntransitions": nt_head,
                        "ntransitions_note": "headline = the reference's own setting (README.md:57, "
                                             "BASELINE.json configs[0]); SURVEY 8d's {1, 16} are "
-                                            "under by_ntransitions",
+                                            "under by_ntransitions with --full",
+                       "full": args.full,
                        "evals_per_step": n_total * nt_head, "seed": SEED,
                        "timed_blocks": h["blocks"], "timed_seconds": h["timed_s"],
                        "parallelism": (f"REHEARSAL: {emulate} emulated ranks on ONE GPU, P2P exchange "

@@ -1,6 +1,6 @@
 """bench.py --steps / --dump-outputs: the timed steps are exactly --steps, and the outputs of the timed
 path are written as float64 .npy files within a byte budget.  CPU: the writer on a stand-in ensemble.
-GPU: two runs with the same arguments dump the same bits."""
+GPU: two runs with the same arguments dump the same bits, and so do a plain and a --full run."""
 import json
 import os
 import subprocess
@@ -80,5 +80,32 @@ def test_bench_times_exactly_steps_and_dumps_the_same_outputs_twice(tmp_path, gp
     assert set(a) == {"walkers", "logprior", "loglik", "counters"}
     assert a["walkers"].shape == (65536, 8) and np.all(np.isfinite(a["walkers"]))
     assert a["counters"][0] == 65536 * 100 * (warmup + steps)
+    for name in a:
+        assert np.array_equal(a[name].view(np.uint64), b[name].view(np.uint64)), name
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_headline_alone_from_the_state_a_full_run_times(tmp_path, gpu_ctx):
+    """A plain run reports the headline only; --full adds the other settings and legs.  Both time the
+    headline on the same ensemble (a plain run takes the other settings' steps untimed), so they dump
+    the same bits."""
+    steps, warmup = 7, 2
+    lines = {}
+    for name, extra in (("plain", []), ("full", ["--full", "--no-cpu-baseline", "--no-smc", "--no-cold-spec"])):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps),
+                            "--warmup", str(warmup), "--dump-outputs", str(tmp_path / name), *extra],
+                           capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines[name] = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    plain, full = lines["plain"], lines["full"]
+    assert set(plain["by_ntransitions"]) == {"100"} and set(full["by_ntransitions"]) == {"1", "16", "100"}
+    assert plain["config"]["full"] is False and full["config"]["full"] is True
+    assert not {"cpu_baseline", "smc_c4", "readme_c1", "c2", "by_prior_class", "value_survey_8d"} & set(plain)
+    assert {"readme_c1", "c2", "by_prior_class", "value_survey_8d"} <= set(full)
+    for line in (plain, full):
+        assert line["steps"] == steps and line["value"] > 0 and line["ms_per_step"] > 0
+        assert line["roofline"]["frac"] > 0
+    a, b = _load(tmp_path / "plain"), _load(tmp_path / "full")
+    assert a["counters"][0] == 65536 * ((1 + 16) * (5 + steps) + 100 * (warmup + steps))
     for name in a:
         assert np.array_equal(a[name].view(np.uint64), b[name].view(np.uint64)), name

@@ -28,6 +28,13 @@ def test_spawned_ranks_get_launcher_variables_and_rank0_line_is_last():
     assert d["ranks_env"] == ["0", "0", "4", "127.0.0.1"]
 
 
+def test_full_reaches_the_ranks_and_is_off_by_default():
+    for extra, want in (((), False), (("--full",), True)):
+        p, _ = _run(2, "ok", extra)
+        assert p.returncode == 0, p.stderr
+        assert json.loads(p.stdout.strip().splitlines()[-1])["full"] is want
+
+
 def test_a_failing_rank_fails_the_launch_and_ends_the_others():
     p, el = _run(3, "fail2")
     assert p.returncode == 7

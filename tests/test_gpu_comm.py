@@ -247,10 +247,11 @@ def test_smc_dist_modes_on_an_rccl_communicator_world1():
     assert d["cost_loop"] is True and d["particles"] is True and d["iterations"] > 20
 
 
-def _bench(extra_env, launcher):
+def _bench(extra_env, launcher, full=False):
     env = dict(os.environ, KABC_FORCE_COLLECTIVE="1", **extra_env)
     cmd = launcher + [os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "1",
-                      "--no-cpu-baseline", "--min-seconds", "0.05", "--headline-seconds", "0.05"]
+                      "--no-cpu-baseline", "--min-seconds", "0.05", "--headline-seconds", "0.05",
+                      *(["--full"] if full else [])]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")]
@@ -260,7 +261,7 @@ def _bench(extra_env, launcher):
 
 def test_bench_with_communicator_env_launch():
     d = _bench(dict(MASTER_ADDR="127.0.0.1", MASTER_PORT="29534", RANK="0", LOCAL_RANK="0",
-                    WORLD_SIZE="1"), [sys.executable])
+                    WORLD_SIZE="1"), [sys.executable], full=True)
     assert d["n_gpus"] == 1 and d["value"] > 0 and d["roofline"]["frac"] > 0
     assert set(d["by_ntransitions"]) == {"1", "16", "100"} and d["config"]["ntransitions"] == 100
     assert d["smc_c4"]["iterations"] > 100 and d["smc_c4"]["wall_ms"] > 0

@@ -6,7 +6,7 @@
 # prints (kernel us, G evals/s) of the AIS half-generation kernel at ntransitions = 1, 16, 100,
 # twice per build, alternating.  tools/_base.so matches *.so in .gitignore and is not committed.
 run() {
-  python bench.py --no-cpu-baseline --no-smc --min-seconds 0.5 2>/dev/null | python -c "
+  python bench.py --full --no-cpu-baseline --no-smc --min-seconds 0.5 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print({nt:(round(v['kernel_avg_us'],2), round(v['value']/1e9,2)) for nt,v in d['by_ntransitions'].items()})"

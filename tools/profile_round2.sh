@@ -4,7 +4,7 @@
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 O=${1:-gpurun_out/r02p}; mkdir -p $O
 (rocm-smi --showclocks --showpower 2>/dev/null || true) > $O/rocm_smi_before.txt
-python3 bench.py > $O/bench.json 2> $O/bench.err
+python3 bench.py --full > $O/bench.json 2> $O/bench.err
 for NT in 1 16 100; do
   B="python3 bench.py --ntransitions $NT --no-alt --no-smc --no-cpu-baseline --steps 50 --warmup 5 --min-seconds 0.2"
   rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_nt$NT -- $B > $O/bench_under_rocprof_nt$NT.json 2> $O/stats_nt$NT.err

@@ -5,8 +5,8 @@
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 O=${1:-gpurun_out/r06p}; mkdir -p $O
 (rocm-smi --showclocks --showpower 2>/dev/null || true) > $O/rocm_smi_before.txt
-python3 bench.py > $O/bench.json 2> $O/bench.err
-KABC_BENCH_EMULATE_RANKS=8 python3 bench.py --gpus 8 --no-cpu-baseline --steps 50 --warmup 5 > $O/bench_emulated8.json 2> $O/bench_emulated8.err
+python3 bench.py --full > $O/bench.json 2> $O/bench.err
+KABC_BENCH_EMULATE_RANKS=8 python3 bench.py --full --gpus 8 --no-cpu-baseline --steps 50 --warmup 5 > $O/bench_emulated8.json 2> $O/bench_emulated8.err
 for NT in 1 16 100; do
   B="python3 bench.py --ntransitions $NT --no-alt --no-smc --no-cpu-baseline --steps 50 --warmup 5 --min-seconds 0.2 --headline-seconds 0.2"
   rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_nt$NT -- $B > $O/bench_under_rocprof_nt$NT.json 2> $O/stats_nt$NT.err
