@@ -7,6 +7,7 @@
 #include <cstdlib>
 #include <mutex>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "ais_aux_kernels.hpp"
@@ -142,17 +143,17 @@ using namespace kabc;
 static constexpr int kTraceBufs = 3;
 
 struct kabc_ais {
-    kabc_ctx_t* ctx;
-    int32_t D, posterior, cost_id;
-    double eps;
-    kabc_prior_t raw[KABC_MAX_DIM];
-    PriorSet prior;
-    double* d_cost_params;
-    double* d_cost_data;
-    int64_t cost_ndata;
-    int64_t N;             // total walkers (all ranks)
-    int64_t rows[2];       // global rows per half
-    int64_t rows_owned[2]; // owned rows per half (all segments)
+    kabc_ctx_t* ctx = nullptr;
+    int32_t D = 0, posterior = 0, cost_id = 0;
+    double eps = 0.0;
+    kabc_prior_t raw[KABC_MAX_DIM] = {};
+    PriorSet prior = {};
+    double* d_cost_params = nullptr;
+    double* d_cost_data = nullptr;
+    int64_t cost_ndata = 0;
+    int64_t N = 0;                  // total walkers (all ranks)
+    int64_t rows[2] = {};           // global rows per half
+    int64_t rows_owned[2] = {};     // owned rows per half (all segments)
     // Ownership is block-cyclic over `xk` EXCHANGE CHUNKS: chunk k of a half is the row range
     // [k * world * cper, (k + 1) * world * cper), split into `world` rank segments of cper rows
     // -- so that the all-gather of chunk k is in place and contiguous (count = cper * D) and
@@ -161,68 +162,68 @@ struct kabc_ais {
     // depend on xk or world.
     struct Seg { int64_t first, count, off; };  // global first row, rows, offset in lp / ll
     std::vector<Seg> seg[2];
-    int32_t xk;
-    int64_t cper[2];       // rows per rank and chunk (all-gather count / D)
-    kabc_comm_t* comm;     // library-owned exchange (kabc_ais_create_dist), else NULL
+    int32_t xk = 1;
+    int64_t cper[2] = {};           // rows per rank and chunk (all-gather count / D)
+    kabc_comm_t* comm = nullptr;    // library-owned exchange (kabc_ais_create_dist), else NULL
     // length(prior) > KABC_MAX_DIM: run-time-dimension kernels (ais_dyn_kernels.hpp)
     AisDynLaunch dyn;
     std::vector<kabc_prior_t> raw_dyn;
     std::vector<PriorDev> prior_dyn;
-    kabc_prior_t* d_raw;   // [D] raw components (dyn)
-    double* d_scratch;     // [max rows_owned][2][D] (dyn)
-    int32_t nchains;       // independent ensembles in this handle (kabc_ais_create_batch), else 1
-    uint64_t* d_seeds;     // [nchains] (batch handles)
-    unsigned long long* d_chain_retries;  // [nchains]
-    uint32_t id_base[2];   // global walker id of row 0 of each half
-    double* d_half[2];     // global halves [rows[h]][D]
-    bool own_halves;
-    double* d_lp[2];
-    double* d_ll[2];
-    DevCounters* d_counters;
-    unsigned long long* d_slots;  // [kCounterSlots][8]
-    PriorDev* d_prior;            // [KABC_MAX_DIM] prepared components
-    uint64_t seed, t;
-    int32_t rank, world;
+    kabc_prior_t* d_raw = nullptr;  // [D] raw components (dyn)
+    double* d_scratch = nullptr;    // [max rows_owned][2][D] (dyn)
+    int32_t nchains = 1;            // independent ensembles in this handle (kabc_ais_create_batch), else 1
+    uint64_t* d_seeds = nullptr;    // [nchains] (batch handles)
+    unsigned long long* d_chain_retries = nullptr;  // [nchains]
+    uint32_t id_base[2] = {};       // global walker id of row 0 of each half
+    double* d_half[2] = {};         // global halves [rows[h]][D]
+    bool own_halves = false;
+    double* d_lp[2] = {};
+    double* d_ll[2] = {};
+    DevCounters* d_counters = nullptr;
+    unsigned long long* d_slots = nullptr;  // [kCounterSlots][8]
+    PriorDev* d_prior = nullptr;            // [KABC_MAX_DIM] prepared components
+    uint64_t seed = 0, t = 0;
+    int32_t rank = 0, world = 1;
     AisLaunch launch;      // half-generation kernel (a small-ensemble handle resolves it at first need)
-    int32_t pc;            // its prior class
+    int32_t pc = 0;        // its prior class
     // the one-workgroup driver of small ensembles (ais_small_kernel.hpp): kabc_ais_advance runs every
     // generation of a call in ONE launch; spec_state / spec_variant then describe THIS kernel
-    bool small_ok;
+    bool small_ok = false;
     AisSmallLaunch small;
-    int32_t small_pcx;     // the prebuilt table's variant (prior class BOX / NORMAL / GENERAL + posterior kind)
-    double* d_strace;      // its device trace buffer
-    size_t strace_cap;     // bytes
-    ModelUnit* unit;       // run-time compiled unit (user prior families / specialised model), else NULL
+    int32_t small_pcx = 0;          // the prebuilt table's variant (prior class BOX / NORMAL / GENERAL + posterior kind)
+    double* d_strace = nullptr;     // its device trace buffer
+    size_t strace_cap = 0;          // bytes
+    ModelUnit* unit = nullptr;      // run-time compiled unit (user prior families / specialised model), else NULL
     // the model's own kernels (the default, non-blocking specialisation: plugin_registry.hpp)
-    int32_t spec_state;    // KABC_SPEC_*
-    int32_t spec_variant;  // the AIS variant asked of the unit while KABC_SPEC_PENDING
-    int64_t launches;      // half-generation launches so far
-    int64_t spec_switch_at;  // launches that ran before the switch, -1
+    int32_t spec_state = KABC_SPEC_NONE;
+    int32_t spec_variant = 0;       // the AIS variant asked of the unit while KABC_SPEC_PENDING
+    int64_t launches = 0;           // half-generation launches so far
+    int64_t spec_switch_at = -1;    // launches that ran before the switch, -1
     std::chrono::steady_clock::time_point spec_next_poll;
-    double box_lp;
-    bool initialised;
+    double box_lp = 0.0;
+    bool initialised = false;
     // sample-trace streaming: device chunks filled in rotation by the kernels and
     // drained to the caller's buffer on a copy stream while the next chunks compute
-    double* d_trace[kTraceBufs];
-    int64_t trace_cap_gens;
-    hipStream_t copy_stream;
-    hipEvent_t ev_filled[kTraceBufs];
+    double* d_trace[kTraceBufs] = {};
+    size_t trace_cap[kTraceBufs] = {};  // bytes
+    hipStream_t copy_stream = nullptr;
+    hipEvent_t ev_filled[kTraceBufs] = {};
     // prepared-cost words of the launch in flight (ais_aux_kernels.hpp)
-    double* d_aux;
-    size_t aux_cap;  // bytes
+    double* d_aux = nullptr;
+    size_t aux_cap = 0;  // bytes
     // cancellation: the two block / interval events of a bounded queue (created at first need)
-    hipEvent_t ev_blk[2];
+    hipEvent_t ev_blk[2] = {};
     // debug records (tests)
-    int32_t* d_dbg;
-    int64_t dbg_cap;  // in int32 units
+    int32_t* d_dbg = nullptr;
+    int64_t dbg_cap = 0;  // in int32 units
     // timing
-    bool timing;
-    int32_t timing_stride;   // launches per event pair
-    int32_t open_count;      // launches inside the pair that is open (0 = none open)
+    bool timing = false;
+    int32_t timing_stride = 1;  // launches per event pair
+    int32_t open_count = 0;     // launches inside the pair that is open (0 = none open)
     std::vector<hipEvent_t> ev;
     std::vector<int32_t> ev_n;  // launches bracketed by pair i
-    size_t ev_used;
-    kabc_stats_t last;  // counters at the last kabc_ais_advance return
+    size_t ev_used = 0;
+    kabc_stats_t last = {};     // counters at the last kabc_ais_advance return
     // exchange diagnostics of a sharded handle (kabc_ais_exchange_us): per timed half-generation
     // three events on the context stream -- e0 the half's kernels start, e1 they have ended, e2 the
     // gathered half is available to the stream -- and a pair per exchange chunk on the stream the
@@ -233,8 +234,8 @@ struct kabc_ais {
         bool closed;
     };
     std::vector<XT> xt;
-    size_t xt_used;
-    int xt_open;  // entry whose e2 is still to be recorded (pipelined exchange), else -1
+    size_t xt_used = 0;
+    int xt_open = -1;  // entry whose e2 is still to be recorded (pipelined exchange), else -1
 };
 
 static constexpr size_t kXtHalves = 128;
@@ -337,10 +338,11 @@ static kabc_status_t ais_resolve_half(kabc_ais_t* h) {
     return KABC_OK;
 }
 
-static kabc_status_t ais_create_common(kabc_ctx_t* ctx, const kabc_model_t* m, int64_t n_total,
-                                       int32_t rank, int32_t world, uint64_t seed, void* ext0,
-                                       void* ext1, kabc_comm_t* comm, kabc_ais_t** out,
-                                       int32_t nchains = 1, const uint64_t* seeds = nullptr) {
+// the checks of every creation, in this order; `mres` receives the model with its priors resolved (into
+// `resolved`)
+static kabc_status_t ais_validate(kabc_ctx_t* ctx, const kabc_model_t* m, kabc_ais_t** out, int64_t n_total,
+                                  int32_t rank, int32_t world, const kabc_comm_t* comm, int32_t nchains,
+                                  std::vector<kabc_prior_t>& resolved, kabc_model_t& mres) {
     if (!ctx || !m || !out || !m->prior) {
         set_error("kabc_ais_create: NULL argument");
         return KABC_ERR_INVALID_ARG;
@@ -352,9 +354,9 @@ static kabc_status_t ais_create_common(kabc_ctx_t* ctx, const kabc_model_t* m, i
     }
     // the library-side fields of MvNormal components (device block, D): everything below works
     // on the resolved copy
-    std::vector<kabc_prior_t> resolved((size_t)m->D);
+    resolved.resize((size_t)m->D);
     if (kabc_status_t st = resolve_priors(ctx, m->prior, m->D, resolved.data())) return st;
-    kabc_model_t mres = *m;
+    mres = *m;
     mres.prior = resolved.data();
     m = &mres;
     const bool dyn = m->D > KABC_MAX_DIM;
@@ -408,61 +410,13 @@ static kabc_status_t ais_create_common(kabc_ctx_t* ctx, const kabc_model_t* m, i
             }
         }
     }
-    // prior class of the half-generation kernel (ais_kernels.hpp)
-    bool isbox = true, gaussbox = true, allnormal = true;
-    for (int k = 0; k < m->D; ++k) {
-        const int kd = m->prior[k].kind;
-        const bool box = kd == KABC_PRIOR_UNIFORM || kd == KABC_PRIOR_DISCRETE_UNIFORM;
-        const bool gauss = kd == KABC_PRIOR_NORMAL || kd == KABC_PRIOR_TRUNCNORMAL;
-        isbox = isbox && box;
-        gaussbox = gaussbox && (box || gauss);
-        allnormal = allnormal && kd == KABC_PRIOR_NORMAL;
-    }
-    const int pc = isbox ? kPriorBox : allnormal ? kPriorNormal : gaussbox ? kPriorSimple : kPriorGeneral;
-    static_assert(kPriorClasses == 4, "capi_plugin.hip decodes pcx with 4 prior classes");
-    // (run-time compiled kernels are loaded on the CURRENT device)
-    KABC_HIP_CHECK(hipSetDevice(ctx->device));
-    // user prior families among the components, or a specialisation of exactly this model
-    // (kabc_compile_model): the kernels of that unit, GENERAL class (plugin_registry.hpp)
-    ModelUnit* unit = nullptr;
-    if (kabc_status_t st = model_unit_for(m->prior, m->D, m->cost.id, &unit)) return st;
-    // length(prior) > KABC_MAX_DIM: the run-time-dimension kernels -- of the unit (user prior families:
-    // compiled with their snippets), of the user cost (hipRTC form, or its plugin .so), or the built-in ones
-    AisDynLaunch dyn_fn;
-    if (dyn) {
-        if (unit) {
-            const PluginKernel kh = unit_kernel(unit, kPfAisDyn, m->D, 0), ki = unit_kernel(unit, kPfAisDyn, m->D, 1);
-            dyn_fn = AisDynLaunch(kh.mod, unit_kernel(unit, kPfAisDyn, m->D, 2).mod, unit_kernel(unit, kPfAisDyn, m->D, 3).mod, ki.mod);
-            if (!dyn_fn) return KABC_ERR_DEVICE;  // (message set by the compilation / load)
-        } else if (m->cost.id >= KABC_COST_USER) {
-            const CostPlugin* pl = find_plugin(m->cost.id);
-            if (pl && pl->rtc) {
-                const PluginKernel kh = plugin_kernel(pl, kPfAisDyn, m->D, 0), ki = plugin_kernel(pl, kPfAisDyn, m->D, 1);
-                dyn_fn = AisDynLaunch(kh.mod, plugin_kernel(pl, kPfAisDyn, m->D, 2).mod, plugin_kernel(pl, kPfAisDyn, m->D, 3).mod, ki.mod);
-            } else if (pl && pl->ais_dyn) {
-                dyn_fn = AisDynLaunch((AisDynLaunchFn)pl->ais_dyn());
-            }
-        } else {
-            dyn_fn = AisDynLaunch(find_ais_dyn_kernel(m->cost.id));
-        }
-        if (!dyn_fn) {
-            if (!get_error()[0])
-                set_error("length(prior) = %d > %d: no run-time-dimension kernels for cost id %d (a plugin .so "
-                          "built from older headers?)", m->D, KABC_MAX_DIM, m->cost.id);
-            return KABC_ERR_UNSUPPORTED;
-        }
-    }
-    const int spec_variant = kPriorGeneral + kPriorClasses * (m->posterior - 1);
-    kabc_ais_t* h = new kabc_ais_t();
-    h->ctx = ctx;
-    h->D = m->D;
-    h->posterior = m->posterior;
-    h->cost_id = m->cost.id;
-    h->eps = m->eps;
-    std::memset(h->raw, 0, sizeof h->raw);
-    std::memset(&h->prior, 0, sizeof h->prior);
-    h->d_raw = nullptr;
-    h->d_scratch = nullptr;
+    return KABC_OK;
+}
+
+// the prepared components, their class for the half-generation kernel (ais_kernels.hpp) and the BOX
+// class's in-support log-density
+static kabc_status_t ais_prepare_prior(kabc_ais_t* h, const kabc_model_t* m) {
+    const bool dyn = h->D > KABC_MAX_DIM;
     bool prior_ok = true;
     if (dyn) {
         h->raw_dyn.assign(m->prior, m->prior + m->D);
@@ -474,81 +428,113 @@ static kabc_status_t ais_create_common(kabc_ctx_t* ctx, const kabc_model_t* m, i
         prior_ok = prepare_priors(h->raw, h->D, h->prior);
     }
     if (!prior_ok) {
-        delete h;
         set_error("invalid prior parameters");
         return KABC_ERR_INVALID_ARG;
     }
-    h->unit = unit;
-    h->pc = pc;
-    h->spec_state = KABC_SPEC_NONE;
-    h->spec_variant = spec_variant;
-    h->launches = 0;
-    h->small_ok = false;
-    h->d_strace = nullptr;
-    h->strace_cap = 0;
+    bool isbox = true, gaussbox = true, allnormal = true;
+    for (int k = 0; k < m->D; ++k) {
+        const int kd = m->prior[k].kind;
+        const bool box = kd == KABC_PRIOR_UNIFORM || kd == KABC_PRIOR_DISCRETE_UNIFORM;
+        const bool gauss = kd == KABC_PRIOR_NORMAL || kd == KABC_PRIOR_TRUNCNORMAL;
+        isbox = isbox && box;
+        gaussbox = gaussbox && (box || gauss);
+        allnormal = allnormal && kd == KABC_PRIOR_NORMAL;
+    }
+    h->pc = isbox ? kPriorBox : allnormal ? kPriorNormal : gaussbox ? kPriorSimple : kPriorGeneral;
+    static_assert(kPriorClasses == 4, "capi_plugin.hip decodes pcx with 4 prior classes");
+    // BOX class: logpdf inside the box = c0_1 + ... + c0_D, summed left to right
+    // exactly as logpdf(d::Factored, x) does (src/priors.jl:30-36)
+    h->box_lp = h->prior.c[0].c0;
+    for (int k = 1; k < h->D && !dyn; ++k) h->box_lp += h->prior.c[k].c0;
+    return KABC_OK;
+}
+
+// the handle's kernels: the run-time-dimension ones, the one-workgroup driver where it applies and the
+// half-generation kernel
+static kabc_status_t ais_resolve_kernels(kabc_ais_t* h, const kabc_model_t* m) {
+    const bool dyn = h->D > KABC_MAX_DIM;
+    // (run-time compiled kernels are loaded on the CURRENT device)
+    KABC_HIP_CHECK(hipSetDevice(h->ctx->device));
+    // user prior families among the components, or a specialisation of exactly this model
+    // (kabc_compile_model): the kernels of that unit, GENERAL class (plugin_registry.hpp)
+    if (kabc_status_t st = model_unit_for(m->prior, m->D, m->cost.id, &h->unit)) return st;
+    ModelUnit* unit = h->unit;
+    // length(prior) > KABC_MAX_DIM: the run-time-dimension kernels -- of the unit (user prior families:
+    // compiled with their snippets), of the user cost (hipRTC form, or its plugin .so), or the built-in ones
+    if (dyn) {
+        if (unit) {
+            const PluginKernel kh = unit_kernel(unit, kPfAisDyn, m->D, 0), ki = unit_kernel(unit, kPfAisDyn, m->D, 1);
+            h->dyn = AisDynLaunch(kh.mod, unit_kernel(unit, kPfAisDyn, m->D, 2).mod, unit_kernel(unit, kPfAisDyn, m->D, 3).mod, ki.mod);
+            if (!h->dyn) return KABC_ERR_DEVICE;  // (message set by the compilation / load)
+        } else if (m->cost.id >= KABC_COST_USER) {
+            const CostPlugin* pl = find_plugin(m->cost.id);
+            if (pl && pl->rtc) {
+                const PluginKernel kh = plugin_kernel(pl, kPfAisDyn, m->D, 0), ki = plugin_kernel(pl, kPfAisDyn, m->D, 1);
+                h->dyn = AisDynLaunch(kh.mod, plugin_kernel(pl, kPfAisDyn, m->D, 2).mod, plugin_kernel(pl, kPfAisDyn, m->D, 3).mod, ki.mod);
+            } else if (pl && pl->ais_dyn) {
+                h->dyn = AisDynLaunch((AisDynLaunchFn)pl->ais_dyn());
+            }
+        } else {
+            h->dyn = AisDynLaunch(find_ais_dyn_kernel(m->cost.id));
+        }
+        if (!h->dyn) {
+            if (!get_error()[0])
+                set_error("length(prior) = %d > %d: no run-time-dimension kernels for cost id %d (a plugin .so "
+                          "built from older headers?)", m->D, KABC_MAX_DIM, m->cost.id);
+            return KABC_ERR_UNSUPPORTED;
+        }
+    }
     // Small ensembles (both halves fit one workgroup's LDS, ais_small_kernel.hpp): one workgroup per
     // chain runs every generation of a kabc_ais_advance call in one launch (a cost with a grid-wide
     // pre-pass, ais_aux_kernels.hpp: one pre-pass launch per half for all of the call's sub-steps first).
     // Not for sharded handles, caller-lent halves, the run-time-dimension kernels; KABC_AIS_SMALL=0 keeps
     // the launch per half-generation.
-    {
-        const char* e = std::getenv("KABC_AIS_SMALL");
-        const bool off = e && e[0] == '0';
-        if (!off && !dyn && !comm && world == 1 && ext0 == nullptr &&
-            (n_total + 1) / 2 <= (int64_t)ais_small_rmax(m->D)) {
-            const int pk_off = kPriorClasses * (m->posterior - 1);
-            // prebuilt classes of the small kernel: BOX, NORMAL up to kAisInstSplit parameters (the two
-            // the default path never specialises), GENERAL for everything else -- same bits
-            const bool plug = m->cost.id >= KABC_COST_USER;
-            const int spc = isbox ? kPriorBox : (allnormal && m->D <= kAisInstSplit && !plug) ? kPriorNormal : kPriorGeneral;
-            h->small_pcx = spc + pk_off;
-            AisSmallLaunch sfn;
-            int st = KABC_SPEC_NONE;
-            if (unit) {
-                const PluginKernel uk = unit_kernel(unit, kPfAisSmall, m->D, spec_variant, &st);
-                if (uk.mod) sfn = AisSmallLaunch(uk.mod, &ais_small_geom, (unsigned)kAisSmallBlock);
-            }
-            if (!sfn && !(unit && unit_required(unit))) sfn = find_ais_small_kernel(m->cost.id, m->D, h->small_pcx);
-            if (sfn) {
-                h->small = sfn;
-                h->small_ok = true;
-                h->spec_state = st;
-            } else {
-                set_error("%s", "");  // (no small kernel for this model: the launch per half-generation serves)
-            }
+    const char* e = std::getenv("KABC_AIS_SMALL");
+    const bool off = e && e[0] == '0';
+    if (!off && !dyn && !h->comm && h->world == 1 && h->own_halves &&
+        (h->N + 1) / 2 <= (int64_t)ais_small_rmax(m->D)) {
+        const int pk_off = kPriorClasses * (m->posterior - 1);
+        // prebuilt classes of the small kernel: BOX, NORMAL up to kAisInstSplit parameters (the two
+        // the default path never specialises), GENERAL for everything else -- same bits
+        const bool plug = m->cost.id >= KABC_COST_USER;
+        const int spc = h->pc == kPriorBox ? kPriorBox
+                        : (h->pc == kPriorNormal && m->D <= kAisInstSplit && !plug) ? kPriorNormal : kPriorGeneral;
+        h->small_pcx = spc + pk_off;
+        AisSmallLaunch sfn;
+        int st = KABC_SPEC_NONE;
+        if (unit) {
+            const PluginKernel uk = unit_kernel(unit, kPfAisSmall, m->D, h->spec_variant, &st);
+            if (uk.mod) sfn = AisSmallLaunch(uk.mod, &ais_small_geom, (unsigned)kAisSmallBlock);
+        }
+        if (!sfn && !(unit && unit_required(unit))) sfn = find_ais_small_kernel(m->cost.id, m->D, h->small_pcx);
+        if (sfn) {
+            h->small = sfn;
+            h->small_ok = true;
+            h->spec_state = st;
+        } else {
+            set_error("%s", "");  // (no small kernel for this model: the launch per half-generation serves)
         }
     }
-    h->dyn = dyn_fn;
     if (!h->small_ok || (m->cost.id < KABC_COST_USER && !(unit && unit_required(unit)))) {
         // (a small-ensemble handle of a user cost / user prior families compiles its half-generation
         // kernel only when somebody asks for one: kabc_ais_half_generation)
-        if (kabc_status_t st = ais_resolve_half(h)) {
-            delete h;
-            return st;
-        }
+        if (kabc_status_t st = ais_resolve_half(h)) return st;
     }
     h->spec_switch_at = h->spec_state == KABC_SPEC_ACTIVE ? 0 : -1;
-    // BOX class: logpdf inside the box = c0_1 + ... + c0_D, summed left to right
-    // exactly as logpdf(d::Factored, x) does (src/priors.jl:30-36)
-    h->box_lp = h->prior.c[0].c0;
-    for (int k = 1; k < h->D && !dyn; ++k) h->box_lp += h->prior.c[k].c0;
-    h->N = n_total;
-    h->rows[0] = (n_total + 1) / 2;
-    h->rows[1] = n_total / 2;
-    h->id_base[0] = 0;
+    return KABC_OK;
+}
+
+// the rows of each half, the exchange chunks and this rank's segments of them
+static void ais_geometry(kabc_ais_t* h) {
+    const int64_t world = h->world;
+    h->rows[0] = (h->N + 1) / 2;
+    h->rows[1] = h->N / 2;
     h->id_base[1] = (uint32_t)h->rows[0];
-    h->rank = rank;
-    h->world = world;
-    h->comm = comm;
-    h->nchains = nchains;
-    h->d_seeds = nullptr;
-    h->d_chain_retries = nullptr;
     // exchange chunks: KABC_EXCHANGE_CHUNKS, else one chunk per residency wave of the half-
     // generation kernel (512 workgroups of 64 walkers fill the 256 CUs; a launch below that
     // takes as long as a full one -- tools/occupancy_probe.py -- so finer chunks would only
     // serialise the compute they are meant to overlap)
-    h->xk = 1;
-    if (comm) {
+    if (h->comm) {
         const int64_t per_rank = (h->rows[0] + world - 1) / world;
         int64_t k = world > 1 ? per_rank / (512 * (int64_t)kBatch) : 1;
         if (const char* e = std::getenv("KABC_EXCHANGE_CHUNKS")) k = std::atol(e);
@@ -557,44 +543,50 @@ static kabc_status_t ais_create_common(kabc_ctx_t* ctx, const kabc_model_t* m, i
     for (int hf = 0; hf < 2; ++hf) {
         // caller-lent buffers: equal shards (n_total % (2 world) == 0 was checked); library-
         // owned exchange: ceil shards, the last segments may hold fewer rows or none
-        const int64_t parts = (int64_t)world * h->xk;
-        const int64_t cper = comm ? (h->rows[hf] + parts - 1) / parts : h->rows[hf] / world;
+        const int64_t parts = world * h->xk;
+        const int64_t cper = h->comm ? (h->rows[hf] + parts - 1) / parts : h->rows[hf] / world;
         h->cper[hf] = cper;
-        h->rows_owned[hf] = 0;
         for (int k = 0; k < h->xk; ++k) {
-            int64_t lo = cper * ((int64_t)k * world + rank), hi = lo + cper;
+            int64_t lo = cper * (k * world + h->rank), hi = lo + cper;
             lo = lo < h->rows[hf] ? lo : h->rows[hf];
             hi = hi < h->rows[hf] ? hi : h->rows[hf];
             h->seg[hf].push_back({lo, hi - lo, h->rows_owned[hf]});
             h->rows_owned[hf] += hi - lo;
         }
     }
-    h->seed = seed;
-    h->t = 0;
-    h->initialised = false;
-    h->trace_cap_gens = 0;
-    h->copy_stream = nullptr;
-    for (int b = 0; b < kTraceBufs; ++b) {
-        h->d_trace[b] = nullptr;
-        h->ev_filled[b] = nullptr;
-    }
-    h->d_dbg = nullptr;
-    h->dbg_cap = 0;
-    h->d_aux = nullptr;
-    h->aux_cap = 0;
-    h->timing = false;
-    h->timing_stride = 1;
-    h->open_count = 0;
-    h->ev_used = 0;
-    h->last = kabc_stats_t{0, 0, 0};
-    h->xt_used = 0;
-    h->xt_open = -1;
-    h->d_cost_params = h->d_cost_data = nullptr;
-    h->cost_ndata = m->cost.ndata;
-    h->own_halves = (ext0 == nullptr);
+}
 
-    // every early return below releases what was allocated so far
-    if (kabc_status_t st = ais_alloc(h, m, ext0, ext1, seeds)) {
+static kabc_status_t ais_create_common(kabc_ctx_t* ctx, const kabc_model_t* m, int64_t n_total,
+                                       int32_t rank, int32_t world, uint64_t seed, void* ext0,
+                                       void* ext1, kabc_comm_t* comm, kabc_ais_t** out,
+                                       int32_t nchains = 1, const uint64_t* seeds = nullptr) {
+    std::vector<kabc_prior_t> resolved;
+    kabc_model_t mres;
+    if (kabc_status_t st = ais_validate(ctx, m, out, n_total, rank, world, comm, nchains, resolved, mres))
+        return st;
+    kabc_ais_t* h = new kabc_ais_t();
+    h->ctx = ctx;
+    h->D = mres.D;
+    h->posterior = mres.posterior;
+    h->cost_id = mres.cost.id;
+    h->eps = mres.eps;
+    h->cost_ndata = mres.cost.ndata;
+    h->N = n_total;
+    h->rank = rank;
+    h->world = world;
+    h->comm = comm;
+    h->nchains = nchains;
+    h->seed = seed;
+    h->own_halves = ext0 == nullptr;
+    h->spec_variant = kPriorGeneral + kPriorClasses * (mres.posterior - 1);
+    // every failure below releases what was set up so far (kabc_ais_destroy: what was not reached is null)
+    kabc_status_t st = ais_prepare_prior(h, &mres);
+    if (st == KABC_OK) st = ais_resolve_kernels(h, &mres);
+    if (st == KABC_OK) {
+        ais_geometry(h);
+        st = ais_alloc(h, &mres, ext0, ext1, seeds);
+    }
+    if (st) {
         (void)kabc_ais_destroy(h);
         return st;
     }
@@ -629,6 +621,76 @@ static kabc_status_t check_device_error(kabc_ais_t* h, const DevCounters& c) {
         return KABC_ERR_INVALID_STATE;
     }
     return KABC_OK;
+}
+
+// The members the AIS argument structs share, from the handle (after a memset: the rest is the caller's).
+// The aux pre-pass takes only the cost and the draws; InitArgs holds the prepared prior by value.
+template <class A>
+static void fill_args(A& a, const kabc_ais_t* h) {
+    constexpr bool aux = std::is_same_v<A, AuxArgs>, init = std::is_same_v<A, InitArgs>;
+    constexpr bool dyn = std::is_same_v<A, AisDynArgs>, small = std::is_same_v<A, AisSmallArgs>;
+    std::memset(&a, 0, sizeof a);
+    a.cost_params = h->d_cost_params;
+    a.cost_data = h->d_cost_data;
+    a.cost_ndata = h->cost_ndata;
+    a.seed = h->seed;
+    if constexpr (!dyn) a.seeds = h->d_seeds;  // (a run-time-dimension handle holds one chain)
+    if constexpr (!aux) {
+        a.counters = h->d_counters;
+        a.eps = h->eps;
+    }
+    if constexpr (init) a.prior = h->prior;
+    if constexpr (!aux && !init) {
+        a.slots = h->d_slots;
+        a.reps = (h->posterior == KABC_POSTERIOR_COMMON) ? 1.0 : 1.0 / h->eps;
+        a.prior = h->d_prior;
+    }
+    if constexpr (!aux && !dyn && !init) a.box_lp = h->box_lp;
+    if constexpr (!aux && !small) a.posterior = h->posterior;
+    if constexpr (dyn || init) a.cost_id = h->cost_id;
+}
+
+// a size knob of the environment (tests, tuning) in `unit` bytes, else `dflt`; read at every call, as
+// the tests change it between handles
+static size_t env_bytes(const char* name, size_t unit, size_t dflt) {
+    if (const char* e = std::getenv(name)) {
+        const long v = std::atol(e);
+        if (v > 0) return (size_t)v * unit;
+    }
+    return dflt;
+}
+
+// grows a device buffer to `bytes` (it never shrinks); the old one may still be read by work queued on
+// the handle's stream, which is waited for first
+template <class T>
+static kabc_status_t grow(kabc_ais_t* h, T** p, size_t* cap, size_t bytes) {
+    if (bytes <= *cap) return KABC_OK;
+    if (*p) {
+        KABC_HIP_CHECK(hipStreamSynchronize(h->ctx->stream));
+        KABC_HIP_CHECK(hipFree(*p));
+        *p = nullptr;
+        *cap = 0;
+    }
+    KABC_HIP_CHECK(dev_malloc(p, bytes));
+    *cap = bytes;
+    return KABC_OK;
+}
+
+// enqueues the grid-wide pre-pass of a prepared cost (ais_aux_kernels.hpp): its words for sub-steps
+// [t0, t0 + nt) of `rows` rows of `half` from row_first, into `base`; returns the doubles per chain
+static int64_t enqueue_aux(kabc_ais_t* h, int half, int64_t row_first, int64_t rows, uint64_t t0, int32_t nt,
+                           double* base) {
+    AuxArgs x;
+    fill_args(x, h);
+    x.aux = base;
+    x.row_first = row_first;
+    x.rows = rows;
+    x.t0 = t0;
+    x.id_base = h->id_base[half];
+    x.nt = nt;
+    x.stride_aux = (int64_t)nt * aux_prepass_words(h->cost_id) * rows;
+    launch_aux_prepass(h->cost_id, x, h->ctx->stream, (unsigned)h->nchains);
+    return x.stride_aux;
 }
 
 extern "C" {
@@ -676,28 +738,17 @@ static double* chunk_base(kabc_ais_t* h, int half, int k) {
 
 static AisDynArgs dyn_args(kabc_ais_t* h, int half, const kabc_ais::Seg& sg) {
     AisDynArgs a;
-    std::memset(&a, 0, sizeof a);
+    fill_args(a, h);
     a.x_act = h->d_half[half];
     a.x_comp = h->d_half[1 - half];
     a.lp = h->d_lp[half] + sg.off;
     a.ll = h->d_ll[half] + sg.off;
     a.scratch = h->d_scratch + sg.off * 2 * h->D;
-    a.counters = h->d_counters;
-    a.slots = h->d_slots;
-    a.cost_params = h->d_cost_params;
-    a.cost_data = h->d_cost_data;
-    a.cost_ndata = h->cost_ndata;
     a.row_first = sg.first;
     a.rows_owned = sg.count;
     a.n_comp = h->rows[1 - half];
-    a.seed = h->seed;
     a.id_base = h->id_base[half];
-    a.posterior = h->posterior;
-    a.cost_id = h->cost_id;
     a.D = h->D;
-    a.eps = h->eps;
-    a.reps = (h->posterior == KABC_POSTERIOR_COMMON) ? 1.0 : 1.0 / h->eps;
-    a.prior = h->d_prior;
     a.raw = h->d_raw;
     return a;
 }
@@ -729,25 +780,15 @@ static kabc_status_t ais_init_enqueue(kabc_ais_t* h, int32_t retry_sampling) {
                 continue;
             }
             InitArgs a;
-            std::memset(&a, 0, sizeof a);
+            fill_args(a, h);
             a.x_act = h->d_half[hf];
             a.lp = h->d_lp[hf] + sg.off;
             a.ll = h->d_ll[hf] + sg.off;
-            a.counters = h->d_counters;
-            a.cost_params = h->d_cost_params;
-            a.cost_data = h->d_cost_data;
-            a.cost_ndata = h->cost_ndata;
             a.row_first = sg.first;
             a.rows_owned = sg.count;
-            a.seed = h->seed;
             a.id_base = h->id_base[hf];
-            a.posterior = h->posterior;
-            a.cost_id = h->cost_id;
-            a.eps = h->eps;
             a.retry_budget = budget;
-            a.prior = h->prior;
             std::memcpy(a.raw, h->raw, sizeof a.raw);
-            a.seeds = h->d_seeds;
             a.chain_retries = h->d_chain_retries;
             a.stride_act = h->rows[hf] * h->D;
             a.stride_own = h->rows_owned[hf];
@@ -889,6 +930,38 @@ static kabc_status_t timing_close_pair(kabc_ais_t* h) {
     return KABC_OK;
 }
 
+// the events of one exchange-diagnostics entry (those not created are null)
+static void xt_release(const kabc_ais::XT& x, int xk) {
+    for (hipEvent_t e : {x.e0, x.e1, x.e2})
+        if (e) (void)hipEventDestroy(e);
+    for (int k = 0; k < xk; ++k) {
+        if (x.x0[k]) (void)hipEventDestroy(x.x0[k]);
+        if (x.x1[k]) (void)hipEventDestroy(x.x1[k]);
+    }
+}
+
+// creates all of them, or none: a failure releases those created before it
+static hipError_t xt_create(kabc_ais::XT& x, int xk) {
+    x = kabc_ais::XT{};
+    hipError_t e = hipEventCreate(&x.e0);
+    if (e == hipSuccess) e = hipEventCreate(&x.e1);
+    if (e == hipSuccess) e = hipEventCreate(&x.e2);
+    for (int k = 0; k < xk && e == hipSuccess; ++k) {
+        e = hipEventCreate(&x.x0[k]);
+        if (e == hipSuccess) e = hipEventCreate(&x.x1[k]);
+    }
+    if (e != hipSuccess) xt_release(x, xk);
+    return e;
+}
+
+// the timing events and the exchange diagnostics' entries
+static void timing_release(kabc_ais_t* h) {
+    for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
+    h->ev.clear();
+    for (const kabc_ais::XT& x : h->xt) xt_release(x, h->xk);
+    h->xt.clear();
+}
+
 // A handle that started on the prebuilt kernels while the worker compiles the model's own: look
 // for them (a map lookup; a stat() at most every 2 ms) and switch.  Same bits either way.
 static void ais_poll_spec(kabc_ais_t* h) {
@@ -936,29 +1009,17 @@ static kabc_status_t launch_half_seg(kabc_ais_t* h, int32_t half, const kabc_ais
         h->dyn(a, s, 0);
     } else {
         AisArgs a;
-        std::memset(&a, 0, sizeof a);
+        fill_args(a, h);
         a.x_act = h->d_half[half];
         a.x_comp = h->d_half[1 - half];
         a.lp = h->d_lp[half] + sg.off;
         a.ll = h->d_ll[half] + sg.off;
         a.dbg = dbg;
         a.dbg_nt = ntransitions;
-        a.counters = h->d_counters;
-        a.slots = h->d_slots;
-        a.cost_params = h->d_cost_params;
-        a.cost_data = h->d_cost_data;
-        a.cost_ndata = h->cost_ndata;
         a.row_first = sg.first;
         a.rows_owned = sg.count;
         a.n_comp = h->rows[1 - half];
-        a.seed = h->seed;
         a.id_base = h->id_base[half];
-        a.posterior = h->posterior;
-        a.eps = h->eps;
-        a.reps = (h->posterior == KABC_POSTERIOR_COMMON) ? 1.0 : 1.0 / h->eps;
-        a.box_lp = h->box_lp;
-        a.prior = h->d_prior;
-        a.seeds = h->d_seeds;
         a.stride_act = h->rows[half] * h->D;
         a.stride_comp = h->rows[1 - half] * h->D;
         a.stride_own = h->rows_owned[half];
@@ -983,23 +1044,10 @@ static kabc_status_t launch_half_seg(kabc_ais_t* h, int32_t half, const kabc_ais
         int32_t blk = ntransitions;
         if (W) {
             const size_t per_step = sizeof(double) * (size_t)W * (size_t)sg.count * (size_t)h->nchains;
-            size_t cap = (size_t)256 << 20;
-            if (const char* e = std::getenv("KABC_AUX_KIB")) {  // tests: force the block path
-                const long kib = std::atol(e);
-                if (kib > 0) cap = (size_t)kib << 10;
-            }
+            const size_t cap = env_bytes("KABC_AUX_KIB", 1 << 10, (size_t)256 << 20);  // tests: force the block path
             const size_t fit = cap / per_step;
             blk = (int32_t)(fit < 1 ? 1 : (fit > (size_t)ntransitions ? (size_t)ntransitions : fit));
-            if (per_step * (size_t)blk > h->aux_cap) {
-                if (h->d_aux) {
-                    KABC_HIP_CHECK(hipStreamSynchronize(s));
-                    KABC_HIP_CHECK(hipFree(h->d_aux));
-                    h->d_aux = nullptr;
-                    h->aux_cap = 0;
-                }
-                KABC_HIP_CHECK(dev_malloc(&h->d_aux, per_step * (size_t)blk));
-                h->aux_cap = per_step * (size_t)blk;
-            }
+            if (kabc_status_t st = grow(h, &h->d_aux, &h->aux_cap, per_step * (size_t)blk)) return st;
         }
         for (int32_t s0 = 0; s0 < ntransitions; s0 += blk) {
             const int32_t nb = ntransitions - s0 < blk ? ntransitions - s0 : blk;
@@ -1009,23 +1057,8 @@ static kabc_status_t launch_half_seg(kabc_ais_t* h, int32_t half, const kabc_ais
             // push_p(x) after the LAST transition is the sample step() returns (src/KissABC.jl:78)
             a.trace = (dev_trace_rows && s0 + nb == ntransitions) ? dev_trace_rows + sg.off * h->D : nullptr;
             if (W) {
-                AuxArgs x;
-                std::memset(&x, 0, sizeof x);
-                x.aux = h->d_aux;
-                x.cost_params = h->d_cost_params;
-                x.cost_data = h->d_cost_data;
-                x.cost_ndata = h->cost_ndata;
-                x.row_first = sg.first;
-                x.rows = sg.count;
-                x.seed = h->seed;
-                x.t0 = a.t0;
-                x.id_base = h->id_base[half];
-                x.nt = nb;
-                x.seeds = h->d_seeds;
-                x.stride_aux = (int64_t)nb * W * sg.count;
-                launch_aux_prepass(h->cost_id, x, s, (unsigned)h->nchains);
                 a.aux = h->d_aux;
-                a.stride_aux = x.stride_aux;
+                a.stride_aux = enqueue_aux(h, half, sg.first, sg.count, a.t0, nb, h->d_aux);
             }
             h->launch(a, s, (unsigned)h->nchains);
         }
@@ -1099,12 +1132,8 @@ static kabc_status_t ais_small_run(kabc_ais_t* h, int64_t ngenerations, int32_t 
     if (poll_every < 1) poll_every = 1;
     if (poll_every > (1 << 30)) poll_every = 1 << 30;
     *last_gc = 0;
-    if (out_samples) {
-        size_t target = (size_t)64 << 20;
-        if (const char* e = std::getenv("KABC_TRACE_CHUNK_MIB")) {  // tuning / tests: force several blocks
-            const long mib = std::atol(e);
-            if (mib > 0) target = (size_t)mib << 20;
-        }
+    if (out_samples) {  // (KABC_TRACE_CHUNK_MIB: tuning / tests, force several blocks)
+        const size_t target = env_bytes("KABC_TRACE_CHUNK_MIB", 1 << 20, (size_t)64 << 20);
         const int64_t fit = (int64_t)(target / gen_bytes);
         if (fit < block) block = fit;
     }
@@ -1112,37 +1141,17 @@ static kabc_status_t ais_small_run(kabc_ais_t* h, int64_t ngenerations, int32_t 
     // sub-step), bounded like the half-generation path's buffer (KABC_AUX_KIB)
     const int auxW = aux_prepass_words(h->cost_id);
     const size_t aux_gen_bytes = sizeof(double) * (size_t)auxW * (size_t)h->N * (size_t)h->nchains * (size_t)ntransitions;
-    if (auxW) {
-        size_t cap = (size_t)256 << 20;
-        if (const char* e = std::getenv("KABC_AUX_KIB")) {  // tests: force several blocks
-            const long kib = std::atol(e);
-            if (kib > 0) cap = (size_t)kib << 10;
-        }
+    if (auxW) {  // (KABC_AUX_KIB: tests, force several blocks)
+        const size_t cap = env_bytes("KABC_AUX_KIB", 1 << 10, (size_t)256 << 20);
         const int64_t fit = (int64_t)(cap / aux_gen_bytes);
         if (fit < block) block = fit;
     }
     if (block < 1) block = 1;
     if (block > ngenerations) block = ngenerations;
-    if (auxW && aux_gen_bytes * (size_t)block > h->aux_cap) {
-        if (h->d_aux) {
-            KABC_HIP_CHECK(hipStreamSynchronize(s));
-            KABC_HIP_CHECK(hipFree(h->d_aux));
-            h->d_aux = nullptr;
-            h->aux_cap = 0;
-        }
-        KABC_HIP_CHECK(dev_malloc(&h->d_aux, aux_gen_bytes * (size_t)block));
-        h->aux_cap = aux_gen_bytes * (size_t)block;
-    }
-    if (out_samples && gen_bytes * (size_t)block > h->strace_cap) {
-        if (h->d_strace) {
-            KABC_HIP_CHECK(hipStreamSynchronize(s));
-            KABC_HIP_CHECK(hipFree(h->d_strace));
-            h->d_strace = nullptr;
-            h->strace_cap = 0;
-        }
-        KABC_HIP_CHECK(dev_malloc(&h->d_strace, gen_bytes * (size_t)block));
-        h->strace_cap = gen_bytes * (size_t)block;
-    }
+    if (auxW)
+        if (kabc_status_t st = grow(h, &h->d_aux, &h->aux_cap, aux_gen_bytes * (size_t)block)) return st;
+    if (out_samples)
+        if (kabc_status_t st = grow(h, &h->d_strace, &h->strace_cap, gen_bytes * (size_t)block)) return st;
     const bool blocks = ngenerations > block;
     if (blocks && !dev_poll)
         if (kabc_status_t st = ensure_blk_events(h)) return st;
@@ -1165,7 +1174,7 @@ static kabc_status_t ais_small_run(kabc_ais_t* h, int64_t ngenerations, int32_t 
         if (h->spec_state == KABC_SPEC_PENDING) ais_poll_spec(h);
         h->launches++;
         AisSmallArgs a;
-        std::memset(&a, 0, sizeof a);
+        fill_args(a, h);
         for (int hf = 0; hf < 2; ++hf) {
             a.x[hf] = h->d_half[hf];
             a.lp[hf] = h->d_lp[hf];
@@ -1176,47 +1185,21 @@ static kabc_status_t ais_small_run(kabc_ais_t* h, int64_t ngenerations, int32_t 
         a.trace = out_samples ? h->d_strace : nullptr;
         // debug records: [N][nt][6] in walker order (those of the block's last generation remain)
         a.dbg = (h->d_dbg && h->N * (int64_t)ntransitions * 6 <= h->dbg_cap) ? h->d_dbg : nullptr;
-        a.counters = h->d_counters;
-        a.slots = h->d_slots;
-        a.cost_params = h->d_cost_params;
-        a.cost_data = h->d_cost_data;
-        a.cost_ndata = h->cost_ndata;
-        a.seed = h->seed;
         a.t0 = h->t;
         a.nt = ntransitions;
         a.ngen = (int32_t)gc;
         a.trace_from = 0;
         a.nchains = h->nchains;
-        a.eps = h->eps;
-        a.reps = (h->posterior == KABC_POSTERIOR_COMMON) ? 1.0 : 1.0 / h->eps;
-        a.box_lp = h->box_lp;
-        a.prior = h->d_prior;
-        a.seeds = h->d_seeds;
         a.cancel = dev_poll ? h->ctx->cancel_d : nullptr;
         a.poll_every = (int32_t)poll_every;
         const bool t_on = h->timing && (h->ev_used + 2 <= h->ev.size());
         if (t_on && h->open_count == 0) KABC_HIP_CHECK(hipEventRecord(h->ev[h->ev_used], s));
         if (auxW) {  // (inside the timed region, like the half-generation path's pre-pass)
-            double* base = reinterpret_cast<double*>(h->d_aux);
+            double* base = h->d_aux;
             for (int hf = 0; hf < 2; ++hf) {
-                AuxArgs x;
-                std::memset(&x, 0, sizeof x);
-                x.aux = base;
-                x.cost_params = h->d_cost_params;
-                x.cost_data = h->d_cost_data;
-                x.cost_ndata = h->cost_ndata;
-                x.row_first = 0;
-                x.rows = h->rows[hf];
-                x.seed = h->seed;
-                x.t0 = h->t;
-                x.id_base = h->id_base[hf];
-                x.nt = (int32_t)(gc * (int64_t)ntransitions);
-                x.seeds = h->d_seeds;
-                x.stride_aux = (int64_t)x.nt * auxW * h->rows[hf];
-                launch_aux_prepass(h->cost_id, x, s, (unsigned)h->nchains);
                 a.aux[hf] = base;
-                a.stride_aux[hf] = x.stride_aux;
-                base += (size_t)x.stride_aux * (size_t)h->nchains;
+                a.stride_aux[hf] = enqueue_aux(h, hf, 0, h->rows[hf], h->t, (int32_t)(gc * (int64_t)ntransitions), base);
+                base += (size_t)a.stride_aux[hf] * (size_t)h->nchains;
             }
         }
         h->small(a, s);
@@ -1271,6 +1254,263 @@ struct InflightBound {
     }
 };
 
+// Exchange diagnostics of an xk = 1 half-generation (kabc_ais_exchange_us), as both advance entry points
+// record them on the handle's stream: the entry it fills while timed entries are left (e0 goes before its
+// kernels), xt_kernels_done after them (their event pair ends before the collective), xt_gathered after the
+// all-gather is enqueued.
+static kabc_ais::XT* xt_next(kabc_ais_t* h) {
+    return (h->comm && h->timing && h->xt_used < h->xt.size()) ? &h->xt[h->xt_used] : nullptr;
+}
+
+static kabc_status_t xt_kernels_done(kabc_ais_t* h, kabc_ais::XT* x) {
+    const kabc_status_t st = timing_close_pair(h);
+    KABC_HIP_CHECK(hipEventRecord(x->e1, h->ctx->stream));
+    KABC_HIP_CHECK(hipEventRecord(x->x0[0], h->ctx->stream));
+    return st;
+}
+
+static kabc_status_t xt_gathered(kabc_ais_t* h, kabc_ais::XT* x) {
+    x->closed = true;
+    ++h->xt_used;
+    KABC_HIP_CHECK(hipEventRecord(x->x1[0], h->ctx->stream));
+    KABC_HIP_CHECK(hipEventRecord(x->e2, h->ctx->stream));
+    return KABC_OK;
+}
+
+// the pipelined exchange's open entry, if any: the previous half's gathers have landed for the stream
+static void xt_close_open(kabc_ais_t* h) {
+    if (h->xt_open < 0) return;
+    (void)hipEventRecord(h->xt[(size_t)h->xt_open].e2, h->ctx->stream);
+    h->xt[(size_t)h->xt_open].closed = true;
+    h->xt_open = -1;
+}
+
+// The half-generation course of kabc_ais_advance: per generation the launches of each half (one per
+// exchange chunk of a pipelined sharded handle), on a sharded handle each followed by its all-gather.
+// A rank-local failure (a launch that did not go out) must not leave the other ranks blocked in a
+// collective this rank never joins: the kernels stop, the exchanges of the remaining half-generations
+// are still issued, and the ranks agree on the outcome at the end.
+static kabc_status_t ais_half_run(kabc_ais_t* h, int64_t ngenerations, int32_t ntransitions, bool* cancelled) {
+    hipStream_t s = h->ctx->stream;
+    const bool polls = !h->comm;
+    InflightBound ib(h, ntransitions);
+    kabc_status_t local_err = KABC_OK;
+    char local_msg[512] = "";
+    auto keep = [&](kabc_status_t st) {
+        if (st != KABC_OK && local_err == KABC_OK) {
+            local_err = st;
+            std::snprintf(local_msg, sizeof local_msg, "%s", get_error());
+        }
+    };
+    for (int64_t g = 0; g < ngenerations; ++g) {
+        if (polls && cancel_pending(h->ctx)) {  // (h->t counts the generations enqueued)
+            *cancelled = true;
+            break;
+        }
+        for (int hf = 0; hf < 2; ++hf) {
+            // exchange diagnostics: this half-generation is timed while entries are left
+            kabc_ais::XT* xt = xt_next(h);
+            if (!h->comm || h->xk == 1) {
+                if (xt) keep(hipEventRecord(xt->e0, s) == hipSuccess ? KABC_OK : KABC_ERR_DEVICE);
+                if (local_err == KABC_OK) keep(kabc_ais_half_generation(h, hf, ntransitions, nullptr));
+                if (xt) (void)xt_kernels_done(h, xt);
+                // the one collective of the design: rebuild half hf on every rank
+                if (h->comm)
+                    keep(comm_allgather_inplace(h->comm, h->d_half[hf], (size_t)h->cper[hf] * h->D));
+                if (xt) (void)xt_gathered(h, xt);
+            } else {
+                // pipelined: the kernels read the half gathered last (fence), then chunk k
+                // is gathered on the exchange stream while the kernels of chunk k + 1 run
+                keep(comm_exchange_fence(h->comm));
+                xt_close_open(h);
+                if (xt) (void)hipEventRecord(xt->e0, s);
+                for (int k = 0; k < h->xk; ++k) {
+                    if (local_err == KABC_OK)
+                        keep(launch_half_seg(h, hf, h->seg[hf][k], ntransitions, nullptr));
+                    if (xt && k == h->xk - 1) {
+                        (void)timing_close_pair(h);
+                        (void)hipEventRecord(xt->e1, s);
+                    }
+                    keep(comm_exchange_chunk(h->comm, chunk_base(h, hf, k),
+                                             (size_t)h->cper[hf] * h->D, k, xt ? xt->x0[k] : nullptr,
+                                             xt ? xt->x1[k] : nullptr));
+                }
+                if (xt) {
+                    h->xt_open = (int)h->xt_used;
+                    ++h->xt_used;
+                }
+            }
+            if (local_err && !h->comm) return local_err;
+        }
+        if (local_err == KABC_OK) h->t += (uint64_t)ntransitions;
+        if (polls)
+            if (kabc_status_t st = ib.generation_enqueued(s)) return st;
+    }
+    if (h->comm && h->xk > 1) keep(comm_exchange_fence(h->comm));
+    xt_close_open(h);
+    if (h->comm) {
+        uint64_t bad = local_err != KABC_OK;
+        const kabc_status_t st = kabc_comm_allreduce_sum_u64(h->comm, &bad, 1);
+        if (local_err) {
+            set_error("%s", local_msg);
+            return local_err;
+        }
+        if (st) return st;
+        if (bad) {
+            set_error("kabc_ais_advance failed on %llu other rank(s) of the communicator",
+                      (unsigned long long)bad);
+            return KABC_ERR_DEVICE;
+        }
+    }
+    return KABC_OK;
+}
+
+// The streamed-trace course of kabc_ais_advance (a single-process handle on the half-generation kernel
+// asked for its samples).
+static kabc_status_t ais_stream_run(kabc_ais_t* h, int64_t ngenerations, int32_t ntransitions, double* out_samples,
+                                    bool* cancelled) {
+    hipStream_t s = h->ctx->stream;
+    const int64_t gen_elems = h->N * h->D * h->nchains;  // [chain][N][D] per generation
+    const size_t gen_bytes = sizeof(double) * (size_t)gen_elems;
+    InflightBound ib(h, ntransitions);
+    // The kernels write the trace into kTraceBufs device chunks in rotation; a drain
+    // thread copies each finished chunk to the caller's buffer while this thread keeps
+    // the device fed with the next chunks.  The copies are issued from their own
+    // thread because hipMemcpyAsync to host memory holds its calling thread until the
+    // chunk's kernels have finished (measured: the whole run time, pinned or not); on
+    // this thread that would stop kernel submission and idle the device.
+    // 4..32 MiB chunks (1/16 of the trace): long enough to amortise a copy's set-up,
+    // short enough that the last copy -- the only one no kernel hides -- is a short tail.
+    size_t target = gen_bytes * (size_t)ngenerations / 16;
+    if (target < (4ull << 20)) target = 4ull << 20;
+    if (target > (32ull << 20)) target = 32ull << 20;
+    target = env_bytes("KABC_TRACE_CHUNK_MIB", 1 << 20, target);  // tuning/probing only
+    int64_t chunk = (int64_t)(target / gen_bytes);
+    if (chunk < 1) chunk = 1;
+    if (chunk > ngenerations) chunk = ngenerations;
+    for (int b = 0; b < kTraceBufs; ++b)
+        if (kabc_status_t st = grow(h, &h->d_trace[b], &h->trace_cap[b], gen_bytes * chunk)) return st;
+    if (!h->copy_stream) {
+        KABC_HIP_CHECK(hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
+        for (int b = 0; b < kTraceBufs; ++b)
+            KABC_HIP_CHECK(hipEventCreateWithFlags(&h->ev_filled[b], hipEventDisableTiming));
+    }
+    const int64_t nchunks = (ngenerations + chunk - 1) / chunk;
+    std::mutex mu;
+    std::condition_variable cv;
+    int64_t filled = 0, drained = 0;  // chunks submitted / chunks copied out
+    int64_t stop_at = nchunks, part_gc = 0;  // a cancel: chunks to drain, generations of the last one
+    bool abort_drain = false;
+    hipError_t drain_err = hipSuccess;
+    std::thread drainer([&] {
+        hipError_t e = hipSetDevice(h->ctx->device);
+        for (int64_t c = 0; c < nchunks && e == hipSuccess; ++c) {
+            {
+                std::unique_lock<std::mutex> lk(mu);
+                cv.wait(lk, [&] { return filled > c || abort_drain || stop_at <= c; });
+                if (abort_drain || stop_at <= c) break;
+            }
+            const int b = (int)(c % kTraceBufs);
+            int64_t gc = (c + 1 < nchunks) ? chunk : ngenerations - c * chunk;
+            {
+                std::lock_guard<std::mutex> lk(mu);
+                if (c + 1 == stop_at && part_gc > 0) gc = part_gc;
+            }
+            e = hipEventSynchronize(h->ev_filled[b]);
+            if (e == hipSuccess)
+                e = hipMemcpyAsync(out_samples + c * chunk * gen_elems, h->d_trace[b],
+                                   gen_bytes * gc, hipMemcpyDeviceToHost, h->copy_stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(h->copy_stream);
+            std::lock_guard<std::mutex> lk(mu);
+            drained = c + 1;
+            cv.notify_all();
+        }
+        std::lock_guard<std::mutex> lk(mu);
+        drain_err = e;
+        drained = nchunks;  // releases the submitter on error
+        cv.notify_all();
+    });
+    kabc_status_t st = KABC_OK;
+    hipError_t sub_err = hipSuccess;
+    for (int64_t c = 0; c < nchunks && st == KABC_OK && sub_err == hipSuccess; ++c) {
+        const int b = (int)(c % kTraceBufs);
+        const int64_t gc = (c + 1 < nchunks) ? chunk : ngenerations - c * chunk;
+        if (c >= kTraceBufs) {  // the chunk that used this buffer last must be out
+            std::unique_lock<std::mutex> lk(mu);
+            cv.wait(lk, [&] { return drained > c - kTraceBufs; });
+            if (drain_err != hipSuccess) break;
+        }
+        int64_t g = 0;
+        for (; g < gc && st == KABC_OK; ++g) {
+            if (cancel_pending(h->ctx)) {
+                *cancelled = true;
+                break;
+            }
+            double* tr0 = h->d_trace[b] + g * gen_elems;
+            st = kabc_ais_half_generation(h, 0, ntransitions, tr0);
+            if (st == KABC_OK)
+                st = kabc_ais_half_generation(h, 1, ntransitions, tr0 + h->rows[0] * h->D);
+            if (st == KABC_OK) h->t += (uint64_t)ntransitions;
+            if (st == KABC_OK) st = ib.generation_enqueued(s);
+        }
+        if (st != KABC_OK) break;
+        if (*cancelled && g == 0) {  // nothing of this chunk ran: the drain ends with the one before
+            std::lock_guard<std::mutex> lk(mu);
+            stop_at = c;
+            cv.notify_all();
+            break;
+        }
+        sub_err = hipEventRecord(h->ev_filled[b], s);
+        if (sub_err != hipSuccess) break;
+        std::lock_guard<std::mutex> lk(mu);
+        filled = c + 1;
+        if (*cancelled) {  // the generations of this chunk that ran are drained, then the drain ends
+            stop_at = c + 1;
+            part_gc = g;
+        }
+        cv.notify_all();
+        if (*cancelled) break;
+    }
+    {
+        std::lock_guard<std::mutex> lk(mu);
+        if (st != KABC_OK || sub_err != hipSuccess) abort_drain = true;
+        cv.notify_all();
+    }
+    drainer.join();
+    if (st != KABC_OK) return st;
+    KABC_HIP_CHECK(sub_err);
+    KABC_HIP_CHECK(drain_err);
+    return KABC_OK;
+}
+
+// What every course of kabc_ais_advance ends with, and kabc_ais_advance_multi for each of its handles: the
+// counters read back and checked, the generations the one-workgroup kernel did not run (it saw a cancel:
+// small_gc > small_done) taken back, the stats of the call, the cancel verdict.
+static kabc_status_t ais_advance_end(kabc_ais_t* h, int32_t ntransitions, int64_t small_gc, bool cancelled,
+                                     kabc_stats_t* stats) {
+    if (kabc_status_t st = timing_close_pair(h)) return st;
+    DevCounters c;
+    if (read_counters(h, &c)) return KABC_ERR_DEVICE;
+    if (kabc_status_t st = check_device_error(h, c)) return st;
+    if (small_gc > 0 && c.small_done < small_gc) {  // the one-workgroup kernel saw the request
+        h->t -= (uint64_t)(small_gc - c.small_done) * (uint64_t)ntransitions;
+        cancelled = true;
+    }
+    if (stats) {
+        stats->proposals += c.proposals - h->last.proposals;
+        stats->cost_evals += c.cost_evals - h->last.cost_evals;
+        stats->accepted += c.accepted - h->last.accepted;
+    }
+    h->last.proposals = c.proposals;
+    h->last.cost_evals = c.cost_evals;
+    h->last.accepted = c.accepted;
+    if (cancelled) {  // (the state, t, the trace and the stats are those of the generations that ran)
+        if (!cancel_take(h->ctx)) set_error("cancelled");
+        return KABC_ERR_CANCELLED;
+    }
+    return KABC_OK;
+}
+
 extern "C" {
 
 kabc_status_t kabc_ais_advance(kabc_ais_t* h, int64_t ngenerations, int32_t ntransitions,
@@ -1300,248 +1540,21 @@ kabc_status_t kabc_ais_advance(kabc_ais_t* h, int64_t ngenerations, int32_t ntra
     }
     // kabc_ctx_cancel (single-process handles; a sharded handle does not poll: kabc.h): a pending request
     // ends the call before it launches anything
-    const bool polls = !h->comm;
-    if (polls && cancel_take(h->ctx)) return KABC_ERR_CANCELLED;
+    if (!h->comm && cancel_take(h->ctx)) return KABC_ERR_CANCELLED;
+    KABC_HIP_CHECK(hipSetDevice(h->ctx->device));
+    // one course per call: the one-workgroup driver where the handle has one, else a launch per
+    // half-generation -- with the trace streamed out when the caller asks for samples
     bool cancelled = false;
     int64_t small_gc = 0;  // generations of the one-workgroup driver's last launch (it may stop early)
-    KABC_HIP_CHECK(hipSetDevice(h->ctx->device));
-    hipStream_t s = h->ctx->stream;
-    const int64_t gen_elems = h->N * h->D * h->nchains;  // [chain][N][D] per generation
-    const size_t gen_bytes = sizeof(double) * (size_t)gen_elems;
-    InflightBound ib(h, ntransitions);
-    // A rank-local failure (a launch that did not go out) must not leave the other ranks
-    // blocked in a collective this rank never joins: the kernels stop, the exchanges of the
-    // remaining half-generations are still issued, and the ranks agree on the outcome below.
-    kabc_status_t local_err = KABC_OK;
-    char local_msg[512] = "";
-    auto keep = [&](kabc_status_t st) {
-        if (st != KABC_OK && local_err == KABC_OK) {
-            local_err = st;
-            std::snprintf(local_msg, sizeof local_msg, "%s", get_error());
-        }
-    };
-    if (h->small_ok && ngenerations > 0 && ais_small_units_per_gen(h, ntransitions) <= (1ll << 30)) {
-        if (kabc_status_t st = ais_small_run(h, ngenerations, ntransitions, out_samples, &small_gc, &cancelled))
-            return st;
-    } else if (!out_samples || ngenerations == 0) {
-        for (int64_t g = 0; g < ngenerations; ++g) {
-            if (polls && cancel_pending(h->ctx)) {  // (h->t counts the generations enqueued)
-                cancelled = true;
-                break;
-            }
-            for (int hf = 0; hf < 2; ++hf) {
-                // exchange diagnostics: this half-generation is timed while entries are left
-                kabc_ais::XT* xt = (h->comm && h->timing && h->xt_used < h->xt.size()) ? &h->xt[h->xt_used] : nullptr;
-                if (!h->comm || h->xk == 1) {
-                    if (xt) keep(hipEventRecord(xt->e0, s) == hipSuccess ? KABC_OK : KABC_ERR_DEVICE);
-                    if (local_err == KABC_OK) keep(kabc_ais_half_generation(h, hf, ntransitions, nullptr));
-                    if (xt) {
-                        (void)timing_close_pair(h);  // (the kernel pair ends before the collective)
-                        (void)hipEventRecord(xt->e1, s);
-                        (void)hipEventRecord(xt->x0[0], s);
-                    }
-                    // the one collective of the design: rebuild half hf on every rank
-                    if (h->comm)
-                        keep(comm_allgather_inplace(h->comm, h->d_half[hf], (size_t)h->cper[hf] * h->D));
-                    if (xt) {
-                        (void)hipEventRecord(xt->x1[0], s);
-                        (void)hipEventRecord(xt->e2, s);
-                        xt->closed = true;
-                        ++h->xt_used;
-                    }
-                } else {
-                    // pipelined: the kernels read the half gathered last (fence), then chunk k
-                    // is gathered on the exchange stream while the kernels of chunk k + 1 run
-                    keep(comm_exchange_fence(h->comm));
-                    if (h->xt_open >= 0) {  // the previous half's gathers have landed for this stream
-                        (void)hipEventRecord(h->xt[(size_t)h->xt_open].e2, s);
-                        h->xt[(size_t)h->xt_open].closed = true;
-                        h->xt_open = -1;
-                    }
-                    if (xt) (void)hipEventRecord(xt->e0, s);
-                    for (int k = 0; k < h->xk; ++k) {
-                        if (local_err == KABC_OK)
-                            keep(launch_half_seg(h, hf, h->seg[hf][k], ntransitions, nullptr));
-                        if (xt && k == h->xk - 1) {
-                            (void)timing_close_pair(h);
-                            (void)hipEventRecord(xt->e1, s);
-                        }
-                        keep(comm_exchange_chunk(h->comm, chunk_base(h, hf, k),
-                                                 (size_t)h->cper[hf] * h->D, k, xt ? xt->x0[k] : nullptr,
-                                                 xt ? xt->x1[k] : nullptr));
-                    }
-                    if (xt) {
-                        h->xt_open = (int)h->xt_used;
-                        ++h->xt_used;
-                    }
-                }
-                if (local_err && !h->comm) return local_err;
-            }
-            if (local_err == KABC_OK) h->t += (uint64_t)ntransitions;
-            if (polls)
-                if (kabc_status_t st = ib.generation_enqueued(s)) return st;
-        }
-        if (h->comm && h->xk > 1) keep(comm_exchange_fence(h->comm));
-        if (h->xt_open >= 0) {
-            (void)hipEventRecord(h->xt[(size_t)h->xt_open].e2, s);
-            h->xt[(size_t)h->xt_open].closed = true;
-            h->xt_open = -1;
-        }
-        if (h->comm) {
-            uint64_t bad = local_err != KABC_OK;
-            const kabc_status_t st = kabc_comm_allreduce_sum_u64(h->comm, &bad, 1);
-            if (local_err) {
-                set_error("%s", local_msg);
-                return local_err;
-            }
-            if (st) return st;
-            if (bad) {
-                set_error("kabc_ais_advance failed on %llu other rank(s) of the communicator",
-                          (unsigned long long)bad);
-                return KABC_ERR_DEVICE;
-            }
-        }
-    } else {
-        // ---- sample-trace streaming ------------------------------------------------
-        // The kernels write the trace into kTraceBufs device chunks in rotation; a drain
-        // thread copies each finished chunk to the caller's buffer while this thread keeps
-        // the device fed with the next chunks.  The copies are issued from their own
-        // thread because hipMemcpyAsync to host memory holds its calling thread until the
-        // chunk's kernels have finished (measured: the whole run time, pinned or not); on
-        // this thread that would stop kernel submission and idle the device.
-        // 4..32 MiB chunks (1/16 of the trace): long enough to amortise a copy's set-up,
-        // short enough that the last copy -- the only one no kernel hides -- is a short tail.
-        size_t target = gen_bytes * (size_t)ngenerations / 16;
-        if (target < (4ull << 20)) target = 4ull << 20;
-        if (target > (32ull << 20)) target = 32ull << 20;
-        if (const char* e = std::getenv("KABC_TRACE_CHUNK_MIB")) {  // tuning/probing only
-            const long mib = std::atol(e);
-            if (mib > 0) target = (size_t)mib << 20;
-        }
-        int64_t chunk = (int64_t)(target / gen_bytes);
-        if (chunk < 1) chunk = 1;
-        if (chunk > ngenerations) chunk = ngenerations;
-        if (chunk > h->trace_cap_gens) {
-            for (int b = 0; b < kTraceBufs; ++b) {
-                if (h->d_trace[b]) KABC_HIP_CHECK(hipFree(h->d_trace[b]));
-                h->d_trace[b] = nullptr;
-                KABC_HIP_CHECK(dev_malloc(&h->d_trace[b], gen_bytes * chunk));
-            }
-            h->trace_cap_gens = chunk;
-        }
-        if (!h->copy_stream) {
-            KABC_HIP_CHECK(hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
-            for (int b = 0; b < kTraceBufs; ++b)
-                KABC_HIP_CHECK(hipEventCreateWithFlags(&h->ev_filled[b], hipEventDisableTiming));
-        }
-        const int64_t nchunks = (ngenerations + chunk - 1) / chunk;
-        std::mutex mu;
-        std::condition_variable cv;
-        int64_t filled = 0, drained = 0;  // chunks submitted / chunks copied out
-        int64_t stop_at = nchunks, part_gc = 0;  // a cancel: chunks to drain, generations of the last one
-        bool abort_drain = false;
-        hipError_t drain_err = hipSuccess;
-        std::thread drainer([&] {
-            hipError_t e = hipSetDevice(h->ctx->device);
-            for (int64_t c = 0; c < nchunks && e == hipSuccess; ++c) {
-                {
-                    std::unique_lock<std::mutex> lk(mu);
-                    cv.wait(lk, [&] { return filled > c || abort_drain || stop_at <= c; });
-                    if (abort_drain || stop_at <= c) break;
-                }
-                const int b = (int)(c % kTraceBufs);
-                int64_t gc = (c + 1 < nchunks) ? chunk : ngenerations - c * chunk;
-                {
-                    std::lock_guard<std::mutex> lk(mu);
-                    if (c + 1 == stop_at && part_gc > 0) gc = part_gc;
-                }
-                e = hipEventSynchronize(h->ev_filled[b]);
-                if (e == hipSuccess)
-                    e = hipMemcpyAsync(out_samples + c * chunk * gen_elems, h->d_trace[b],
-                                       gen_bytes * gc, hipMemcpyDeviceToHost, h->copy_stream);
-                if (e == hipSuccess) e = hipStreamSynchronize(h->copy_stream);
-                std::lock_guard<std::mutex> lk(mu);
-                drained = c + 1;
-                cv.notify_all();
-            }
-            std::lock_guard<std::mutex> lk(mu);
-            drain_err = e;
-            drained = nchunks;  // releases the submitter on error
-            cv.notify_all();
-        });
-        kabc_status_t st = KABC_OK;
-        hipError_t sub_err = hipSuccess;
-        for (int64_t c = 0; c < nchunks && st == KABC_OK && sub_err == hipSuccess; ++c) {
-            const int b = (int)(c % kTraceBufs);
-            const int64_t gc = (c + 1 < nchunks) ? chunk : ngenerations - c * chunk;
-            if (c >= kTraceBufs) {  // the chunk that used this buffer last must be out
-                std::unique_lock<std::mutex> lk(mu);
-                cv.wait(lk, [&] { return drained > c - kTraceBufs; });
-                if (drain_err != hipSuccess) break;
-            }
-            int64_t g = 0;
-            for (; g < gc && st == KABC_OK; ++g) {
-                if (cancel_pending(h->ctx)) {
-                    cancelled = true;
-                    break;
-                }
-                double* tr0 = h->d_trace[b] + g * gen_elems;
-                st = kabc_ais_half_generation(h, 0, ntransitions, tr0);
-                if (st == KABC_OK)
-                    st = kabc_ais_half_generation(h, 1, ntransitions, tr0 + h->rows[0] * h->D);
-                if (st == KABC_OK) h->t += (uint64_t)ntransitions;
-                if (st == KABC_OK) st = ib.generation_enqueued(s);
-            }
-            if (st != KABC_OK) break;
-            if (cancelled && g == 0) {  // nothing of this chunk ran: the drain ends with the one before
-                std::lock_guard<std::mutex> lk(mu);
-                stop_at = c;
-                cv.notify_all();
-                break;
-            }
-            sub_err = hipEventRecord(h->ev_filled[b], s);
-            if (sub_err != hipSuccess) break;
-            std::lock_guard<std::mutex> lk(mu);
-            filled = c + 1;
-            if (cancelled) {  // the generations of this chunk that ran are drained, then the drain ends
-                stop_at = c + 1;
-                part_gc = g;
-            }
-            cv.notify_all();
-            if (cancelled) break;
-        }
-        {
-            std::lock_guard<std::mutex> lk(mu);
-            if (st != KABC_OK || sub_err != hipSuccess) abort_drain = true;
-            cv.notify_all();
-        }
-        drainer.join();
-        if (st != KABC_OK) return st;
-        KABC_HIP_CHECK(sub_err);
-        KABC_HIP_CHECK(drain_err);
-    }
-    if (kabc_status_t stc = timing_close_pair(h)) return stc;
-    DevCounters c;
-    if (read_counters(h, &c)) return KABC_ERR_DEVICE;
-    kabc_status_t st = check_device_error(h, c);
+    kabc_status_t st;
+    if (h->small_ok && ngenerations > 0 && ais_small_units_per_gen(h, ntransitions) <= (1ll << 30))
+        st = ais_small_run(h, ngenerations, ntransitions, out_samples, &small_gc, &cancelled);
+    else if (out_samples && ngenerations > 0)
+        st = ais_stream_run(h, ngenerations, ntransitions, out_samples, &cancelled);
+    else
+        st = ais_half_run(h, ngenerations, ntransitions, &cancelled);
     if (st) return st;
-    if (small_gc > 0 && c.small_done < small_gc) {  // the one-workgroup kernel saw the request
-        h->t -= (uint64_t)(small_gc - c.small_done) * (uint64_t)ntransitions;
-        cancelled = true;
-    }
-    if (stats) {
-        stats->proposals += c.proposals - h->last.proposals;
-        stats->cost_evals += c.cost_evals - h->last.cost_evals;
-        stats->accepted += c.accepted - h->last.accepted;
-    }
-    h->last.proposals = c.proposals;
-    h->last.cost_evals = c.cost_evals;
-    h->last.accepted = c.accepted;
-    if (cancelled) {  // (the state, t, the trace and the stats are those of the generations that ran)
-        if (!cancel_take(h->ctx)) set_error("cancelled");
-        return KABC_ERR_CANCELLED;
-    }
-    return KABC_OK;
+    return ais_advance_end(h, ntransitions, small_gc, cancelled, stats);
 }
 
 kabc_status_t kabc_ais_advance_multi(kabc_ais_t** hs, int32_t n, int64_t ngenerations,
@@ -1569,24 +1582,18 @@ kabc_status_t kabc_ais_advance_multi(kabc_ais_t** hs, int32_t n, int64_t ngenera
                 for (int i = 0; i < n; ++i) {
                     kabc_ais_t* h = hs[i];
                     KABC_HIP_CHECK(hipSetDevice(h->ctx->device));
-                    xts[i] = (h->timing && h->xt_used < h->xt.size()) ? &h->xt[h->xt_used] : nullptr;
+                    xts[i] = xt_next(h);
                     if (xts[i]) KABC_HIP_CHECK(hipEventRecord(xts[i]->e0, h->ctx->stream));
                     if (kabc_status_t st = kabc_ais_half_generation(h, hf, ntransitions, nullptr))
                         return st;
-                    if (xts[i]) {
-                        if (kabc_status_t stc = timing_close_pair(h)) return stc;
-                        KABC_HIP_CHECK(hipEventRecord(xts[i]->e1, h->ctx->stream));
-                        KABC_HIP_CHECK(hipEventRecord(xts[i]->x0[0], h->ctx->stream));
-                    }
+                    if (xts[i])
+                        if (kabc_status_t st = xt_kernels_done(h, xts[i])) return st;
                 }
                 if (kabc_status_t st = gather_multi(hs, n, hf, 0)) return st;
                 for (int i = 0; i < n; ++i) {
                     if (!xts[i]) continue;
                     KABC_HIP_CHECK(hipSetDevice(hs[i]->ctx->device));
-                    KABC_HIP_CHECK(hipEventRecord(xts[i]->x1[0], hs[i]->ctx->stream));
-                    KABC_HIP_CHECK(hipEventRecord(xts[i]->e2, hs[i]->ctx->stream));
-                    xts[i]->closed = true;
-                    ++hs[i]->xt_used;
+                    if (kabc_status_t st = xt_gathered(hs[i], xts[i])) return st;
                 }
                 continue;
             }
@@ -1609,20 +1616,8 @@ kabc_status_t kabc_ais_advance_multi(kabc_ais_t** hs, int32_t n, int64_t ngenera
     if (xk > 1)
         if (kabc_status_t st = comm_exchange_fence_multi(comms, n, true)) return st;
     for (int i = 0; i < n; ++i) {
-        kabc_ais_t* h = hs[i];
-        KABC_HIP_CHECK(hipSetDevice(h->ctx->device));
-        if (kabc_status_t stc = timing_close_pair(h)) return stc;
-        DevCounters c;
-        if (read_counters(h, &c)) return KABC_ERR_DEVICE;
-        if (kabc_status_t st = check_device_error(h, c)) return st;
-        if (stats) {
-            stats->proposals += c.proposals - h->last.proposals;
-            stats->cost_evals += c.cost_evals - h->last.cost_evals;
-            stats->accepted += c.accepted - h->last.accepted;
-        }
-        h->last.proposals = c.proposals;
-        h->last.cost_evals = c.cost_evals;
-        h->last.accepted = c.accepted;
+        KABC_HIP_CHECK(hipSetDevice(hs[i]->ctx->device));
+        if (kabc_status_t st = ais_advance_end(hs[i], ntransitions, 0, false, stats)) return st;
     }
     return KABC_OK;
 }
@@ -1759,8 +1754,7 @@ kabc_status_t kabc_ais_set_timing_stride(kabc_ais_t* h, int32_t stride) {
 kabc_status_t kabc_ais_set_timing(kabc_ais_t* h, int32_t max_launches) {
     if (check_handle(h)) return KABC_ERR_INVALID_ARG;
     KABC_HIP_CHECK(hipSetDevice(h->ctx->device));
-    for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
-    h->ev.clear();
+    timing_release(h);
     h->ev_used = 0;
     h->open_count = 0;
     h->timing = max_launches > 0;
@@ -1771,30 +1765,13 @@ kabc_status_t kabc_ais_set_timing(kabc_ais_t* h, int32_t max_launches) {
     }
     h->ev_n.assign((size_t)(max_launches > 0 ? max_launches : 0), 0);
     // exchange diagnostics of a sharded handle: up to kXtHalves half-generations
-    for (kabc_ais::XT& x : h->xt) {
-        (void)hipEventDestroy(x.e0);
-        (void)hipEventDestroy(x.e1);
-        (void)hipEventDestroy(x.e2);
-        for (int k = 0; k < h->xk; ++k) {
-            (void)hipEventDestroy(x.x0[k]);
-            (void)hipEventDestroy(x.x1[k]);
-        }
-    }
-    h->xt.clear();
     h->xt_used = 0;
     h->xt_open = -1;
     if (h->comm && max_launches > 0) {
         const size_t nh = (size_t)max_launches < kXtHalves ? (size_t)max_launches : kXtHalves;
         for (size_t i = 0; i < nh; ++i) {
             kabc_ais::XT x;
-            std::memset(&x, 0, sizeof x);
-            KABC_HIP_CHECK(hipEventCreate(&x.e0));
-            KABC_HIP_CHECK(hipEventCreate(&x.e1));
-            KABC_HIP_CHECK(hipEventCreate(&x.e2));
-            for (int k = 0; k < h->xk; ++k) {
-                KABC_HIP_CHECK(hipEventCreate(&x.x0[k]));
-                KABC_HIP_CHECK(hipEventCreate(&x.x1[k]));
-            }
+            KABC_HIP_CHECK(xt_create(x, h->xk));
             h->xt.push_back(x);
         }
     }
@@ -1918,16 +1895,7 @@ kabc_status_t kabc_ais_destroy(kabc_ais_t* h) {
     if (h->d_dbg) (void)hipFree(h->d_dbg);
     if (h->d_aux) (void)hipFree(h->d_aux);
     if (h->d_strace) (void)hipFree(h->d_strace);
-    for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
-    for (kabc_ais::XT& x : h->xt) {
-        (void)hipEventDestroy(x.e0);
-        (void)hipEventDestroy(x.e1);
-        (void)hipEventDestroy(x.e2);
-        for (int k = 0; k < h->xk; ++k) {
-            (void)hipEventDestroy(x.x0[k]);
-            (void)hipEventDestroy(x.x1[k]);
-        }
-    }
+    timing_release(h);
     delete h;
     return KABC_OK;
 }

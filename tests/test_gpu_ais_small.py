@@ -26,6 +26,12 @@ def _h16(k):
     return k.ApproxKernelizedPosterior(H16, k.costs.HierGaussSim(rng.normal(size=14)), 0.3)
 
 
+def _readme(k):
+    """README.md:31-57's simulator: a cost with a grid-wide pre-pass"""
+    return k.ApproxKernelizedPosterior(k.Factored(k.Uniform(1, 3), k.Truncated(k.Normal(0, 0.1), 0, 100)),
+                                       k.costs.NormalMeanStdSim(100, 2.0, 0.04), 0.005)
+
+
 def _mixed5(k):
     mixed = k.Factored(k.Gamma(2.5, 0.7), k.LogNormal(0.3, 0.6), k.Exponential(2.0),
                        k.DiscreteUniform(1, 10), k.TruncatedNormal(0, 1, -1, 2))
@@ -72,11 +78,38 @@ def test_small_driver_limits(k, gpu_ctx, monkeypatch):
     assert k.AisEnsemble(_h16(k), 257).driver == "halves"
     # a cost with a grid-wide pre-pass (README.md:31-57's simulator): one pre-pass launch per half for all of a
     # call's sub-steps, then the one workgroup
-    readme = k.ApproxKernelizedPosterior(k.Factored(k.Uniform(1, 3), k.Truncated(k.Normal(0, 0.1), 0, 100)),
-                                         k.costs.NormalMeanStdSim(100, 2.0, 0.04), 0.005)
-    assert k.AisEnsemble(readme, 10).driver == "small"
+    assert k.AisEnsemble(_readme(k), 10).driver == "small"
     monkeypatch.setenv("KABC_AIS_SMALL", "0")
     assert k.AisEnsemble(_u8(k), 100).driver == "halves"
+
+
+@pytest.mark.parametrize("kib", [0, 32])
+def test_launch_count_per_half_generation(k, gpu_ctx, monkeypatch, kib):
+    """The launches kabc_ais_kernel_ms counts, which bench.py's roofline divides by: one per half-generation
+    on the other driver, also when a bounded pre-pass buffer cuts a prepared cost's launch into blocks of
+    sub-steps (KABC_AUX_KIB = 32: 2 words x 2048 rows x 8 bytes fill it with one sub-step, so 4 blocks)."""
+    monkeypatch.setenv("KABC_AIS_SMALL", "0")
+    if kib:
+        monkeypatch.setenv("KABC_AUX_KIB", str(kib))
+    ens = k.AisEnsemble(_readme(k) if kib else _u8(k), 4096, seed=1).init()
+    assert ens.driver == "halves"
+    ens.set_timing(64, stride=1)
+    ens.advance(5, 4)
+    ms, n = ens.kernel_ms()
+    assert n == 10 and ms > 0
+
+
+def test_launch_count_one_workgroup_driver(k, gpu_ctx, monkeypatch):
+    """... and one per call on the one-workgroup driver, its pre-pass launches included"""
+    monkeypatch.delenv("KABC_AIS_SMALL", raising=False)
+    for model, N in ((_u8(k), 512), (_readme(k), 10)):
+        ens = k.AisEnsemble(model, N, seed=1).init()
+        assert ens.driver == "small"
+        ens.set_timing(64, stride=1)
+        for gens, nt in ((5, 4), (3, 1)):
+            ens.advance(gens, nt)
+            ms, n = ens.kernel_ms()
+            assert n == 1 and ms > 0
 
 
 @pytest.mark.parametrize("N,nt,n_draws,kib", [(10, 100, 1000, 0), (10, 7, 999, 0), (12, 5, 37, 0), (130, 3, 64, 0),
