@@ -169,6 +169,12 @@ kabc_status_t kabc_ctx_synchronize(kabc_ctx_t* ctx);
  *   kabc_smc_run      stops at an iteration boundary: result holds the population after the k
  *                     completed iterations (theta, cost, alive, eps, iterations = k, the first k
  *                     log records), bit-identical to the same call with max_iterations = k.
+ *   kabc_smc_run_batch, kabc_abcde_run_batch
+ *                     every run of the launch grid stops at an iteration / generation boundary with
+ *                     its population after the k it completed (an ABCDE run: bit-identical to the
+ *                     same run with generations = k; a run that starts after the request still
+ *                     completes its initial draw, k = 0); one after another, the runs after the
+ *                     current one are not started (see each entry point).
  * A call that is never cancelled is unchanged.  Sharded and distributed calls (kabc_ais_create_dist
  * handles, kabc_ais_advance_multi, kabc_smc_run_dist*) do not poll -- a cancel seen on one rank
  * would leave the others in a collective -- and neither do kabc_ais_init, kabc_abcde_run and
@@ -176,8 +182,10 @@ kabc_status_t kabc_ctx_synchronize(kabc_ctx_t* ctx);
 /* Response time: the device paths look at the word at bounded intervals of WORK, not of time: the one-
  * workgroup AIS kernel once per ~1 ms of modelled work (0.6 us per batch of 64 walkers and sub-step),
  * batch handles between launch blocks of ~25 ms of modelled work, the half-generation path before every
- * generation with ~25 ms of queued work at most, the smc loop kernel every 32nd pass and the one-workgroup
- * smc kernel every 16th iteration (a read of host memory stalls the wave that waits for it:
+ * generation with ~25 ms of queued work at most, the smc loop kernel every 32nd pass, the one-workgroup
+ * smc kernel every 16th iteration and the ABCDE launch grid at every generation boundary (the read is
+ * issued one generation ahead and decided on at the next boundary; a read of host memory stalls the
+ * wave that waits for it:
  * tools/host_word_latency_probe.hip).  With the built-in costs that is well within 0.1 s; an expensive
  * cost (a simulator, a user cost) at small ensembles stretches it by the same factor as a generation
  * or an iteration. */
@@ -254,7 +262,8 @@ kabc_status_t kabc_compile_cost_plugin(const char* src, const int32_t* dims, int
  * (variant = 1 for priors without Beta / Gamma / LogNormal / NegativeBinomial components, else
  * 0), 3 smc init, 4 smc persistent loop, 5 / 6 ABCDE init / generation, 7 pfilter attempt,
  * 10 the one-workgroup smc driver, 13 the one-workgroup AIS driver of small ensembles (variant as
- * family 0; prior classes 0 and 2). */
+ * family 0; prior classes 0 and 2), 14 the one-workgroup ABCDE driver of kabc_abcde_run_batch
+ * (variant 0). */
 kabc_status_t kabc_plugin_precompile(int32_t cost_id, int32_t family, int32_t D, int32_t variant);
 
 /* ---- user prior families ------------------------------------------------------
@@ -733,6 +742,34 @@ void kabc_abcde_default_opts(kabc_abcde_opts_t* o);
 kabc_status_t kabc_abcde_run(kabc_ctx_t* ctx, const kabc_prior_t* prior, int32_t D,
                              const kabc_cost_t* cost, const kabc_abcde_opts_t* opts,
                              kabc_abcde_result_t* result);
+
+/* nruns INDEPENDENT ABCDE runs -- one per seed, or one per dataset -- in one call: run r is
+ * kabc_abcde_run(prior, costs[r]) with opts->seed replaced by seeds[r] (every other option is shared),
+ * and results[r] is filled as that call fills it, bit for bit.  A failed run's theta / cost arrays may
+ * be overwritten (its other fields are not set).  costs[r] all have the same id, nparams and ndata
+ * (their params / data may differ); 1 <= nruns <= 65535; the options are checked as kabc_abcde_run
+ * checks them.  Shapes the one-workgroup kernel takes (3 <= nparticles <= 256, D <= KABC_MAX_DIM, a
+ * built-in DeviceCost or a hipRTC user cost, verbose = 0, KABC_ABCDE_SMALL not 0) run as ONE launch:
+ * workgroup r runs run r from its initial draw to its last generation.  Other shapes (nparticles > 256,
+ * D > KABC_MAX_DIM, cost plugins built by hipcc) run one after another through kabc_abcde_run.
+ * status[r] is run r's own verdict: KABC_OK, KABC_ERR_RETRY_EXHAUSTED (its initial draw never produced
+ * a finite (cost, logpdf) pair; the other runs are left alone) or KABC_ERR_CANCELLED.  The return value
+ * is KABC_OK when every run is, else the status of the lowest failing run, whose index
+ * kabc_last_error() names ("run 3: ABCDE: the prior never produced ...").
+ * kabc_ctx_cancel: KABC_ERR_CANCELLED; in the launch grid every run stops at a generation boundary and
+ * its result holds its population after the k generations it completed (bit-identical to the same run
+ * with generations = k); one after another, the look falls between two runs: the runs after it are not
+ * started (status KABC_ERR_CANCELLED, result untouched).
+ * Results are copied with one copy per array when results[r + 1]'s arrays follow results[r]'s (theta
+ * by N*D doubles, cost by N), else through one page-locked block. */
+kabc_status_t kabc_abcde_run_batch(kabc_ctx_t* ctx, const kabc_prior_t* prior, int32_t D, const kabc_cost_t* costs,
+                                   int64_t nruns, const uint64_t* seeds, const kabc_abcde_opts_t* opts,
+                                   kabc_abcde_result_t* results, kabc_status_t* status);
+
+/* How the calling thread's last kabc_abcde_run_batch was driven: out[0] the course (1 one launch grid,
+ * 0 one run after another), [1] kernel launches (of the one-workgroup kernel; one after another: the
+ * runs started), [2] runs per launch, [3] 0 (reserved). */
+void kabc_abcde_batch_stats(int64_t out[4]);
 
 /* ---- pfilter(prior, cost, N; kwargs...) -- src/smc.jl:275-340 -----------------
  * Rejection-refresh particle filter (exported, undocumented and untested in the

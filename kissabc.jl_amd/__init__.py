@@ -7,7 +7,7 @@ module kissabc_jl_amd.py registers this package under that name).
 from . import costs
 from ._cdefs import KABC_MAX_DIM
 from ._lib import Cancelled, Context, KabcError, LIB_PATH, default_context
-from .api import (ABCDE, AIS, AisEnsemble, ApproxKernelizedPosterior, ApproxPosterior, CommonLogDensity,
+from .api import (ABCDE, ABCDE_batch, AIS, AisEnsemble, ApproxKernelizedPosterior, ApproxPosterior, CommonLogDensity,
                   MCMCThreads, compile_model, pfilter, set_specialize,
                   Particles, sample, smc, smc_batch)
 from . import comm
@@ -19,7 +19,7 @@ from .distributions import (Ar1Normal, Beta, Dirichlet, DiscreteUniform, Exponen
                             UserMvPrior, UserPrior, truncated)
 
 __all__ = [
-    "ABCDE", "AIS", "AisEnsemble", "ApproxKernelizedPosterior", "ApproxPosterior", "CommonLogDensity",
+    "ABCDE", "ABCDE_batch", "AIS", "AisEnsemble", "ApproxKernelizedPosterior", "ApproxPosterior", "CommonLogDensity",
     "MCMCThreads", "pfilter",
     "Particles", "sample", "smc", "smc_batch", "DeviceCost", "costs", "Factored", "Uniform", "Normal",
     "Truncated", "truncated", "TruncatedNormal", "Beta", "DiscreteUniform", "NegativeBinomial",

@@ -707,6 +707,116 @@ def ABCDE(prior, cost, eps_target, *, nparticles=50, generations=20, α=0.0, alp
                        bool(r.reached_eps), info)
 
 
+class AbcdeBatchResult(list):
+    """ABCDE_batch's result: one AbcdeResult per run (a list), and `.info` about the whole call."""
+
+    info = None
+
+
+def ABCDE_batch(prior, cost, eps_target, nruns=None, *, seeds=None, seed=0, nparticles=50, generations=20,
+                α=0.0, alpha=None, earlystop=False, proposal_width=1.0, parallel=False, verbose=False, ctx=None,
+                return_array=False):
+    """Many independent ABCDE runs in one call (kabc_abcde_run_batch): run r is
+    ABCDE(prior, cost_r, eps_target, seed=seeds[r], <the same keywords>), bit for bit.
+
+    `cost` is one DeviceCost (the runs differ by their seeds only; `nruns` is required) or a sequence
+    of DeviceCosts, one per dataset, with the same cost id and the same params and data lengths
+    (`nruns` defaults to its length).  `seeds` defaults to chain_seeds(seed, nruns).  With
+    3 <= nparticles <= 256 and length(prior) <= KABC_MAX_DIM the runs are the workgroups of ONE launch
+    (info["course"] == "grid"); other shapes run one after another ("sequential").  `verbose` is
+    refused; `parallel` is accepted and ignored, as ABCDE does.
+
+    Returns a list of AbcdeResult, entry r as ABCDE returns it (its P / C are views into one
+    [nruns][N][D] / [nruns][N] block); the list's `.info` holds the course, the kernel launches, the
+    runs per launch, the wall time and the runs' statuses.  A failed run raises KabcError("run r: ...")
+    whose `.results` is the list with None at the failed runs; Context.cancel() / Ctrl-C raise Cancelled
+    whose `.result` is the list of the runs' populations after the generations they completed (None for
+    runs never started)."""
+    fac = as_factored(prior)
+    scalar = isinstance(prior, UnivariateDistribution)
+    if isinstance(cost, DeviceCost):
+        if nruns is None:
+            raise ValueError("ABCDE_batch: nruns is required with a single DeviceCost")
+        nruns = int(nruns)
+        cost_list = [cost] * max(nruns, 0)
+    else:
+        cost_list = list(cost)
+        if not all(isinstance(c, DeviceCost) for c in cost_list):
+            raise TypeError("`cost` must be a DeviceCost or a sequence of DeviceCosts on the MI355X path")
+        nruns = len(cost_list) if nruns is None else int(nruns)
+        if len(cost_list) != nruns:
+            raise ValueError(f"ABCDE_batch: {len(cost_list)} costs for nruns = {nruns}")
+    if nruns < 1:
+        raise ValueError("ABCDE_batch: nruns must be >= 1")
+    c0 = cost_list[0]
+    for i, c in enumerate(cost_list):
+        if c.id != c0.id or c.params.size != c0.params.size or c.data.size != c0.data.size:
+            raise ValueError(f"ABCDE_batch: cost {i} differs from cost 0 in its id or its params / data lengths")
+    seeds = chain_seeds(seed, nruns) if seeds is None else [int(x) for x in seeds]
+    if len(seeds) != nruns:
+        raise ValueError(f"ABCDE_batch: len(seeds) = {len(seeds)} != nruns = {nruns}")
+    if verbose:
+        raise ValueError("ABCDE_batch: verbose=True is not supported")
+    a = float(α if alpha is None else alpha)
+    if not (0.0 <= a < 1.0):   # @assert 0<=α<1 (src/smc.jl:348), before the library runs anything
+        raise ValueError("α must be in 0 <= α < 1.")
+    lib = _lib.load()
+    ctx = ctx or _lib.default_context()
+    o = cd.AbcdeOpts()
+    lib.kabc_abcde_default_opts(C.byref(o))
+    o.nparticles, o.generations, o.eps_target = int(nparticles), int(generations), float(eps_target)
+    o.alpha = a
+    o.proposal_width, o.earlystop, o.verbose = float(proposal_width), int(bool(earlystop)), 0
+    R, N, D = nruns, max(int(nparticles), 1), len(fac)
+    t_host0 = time.perf_counter()
+    theta = _lib.result_empty((R, N, D))
+    Cst = _lib.result_empty((R, N))
+    # the R result records, written through a uint64 view (every field is 8 bytes wide, reached_eps and
+    # reserved share one): run r's arrays follow run r - 1's, so that the library copies each array once
+    res = (cd.AbcdeResult * R)()
+    w = np.frombuffer(res, dtype=np.uint64).reshape(R, C.sizeof(cd.AbcdeResult) // 8)
+    rr = np.arange(R, dtype=np.uint64)
+    col = lambda f: getattr(cd.AbcdeResult, f).offset // 8   # noqa: E731
+    w[:, col("theta")] = np.uint64(theta.ctypes.data) + rr * np.uint64(N * D * 8)
+    w[:, col("cost")] = np.uint64(Cst.ctypes.data) + rr * np.uint64(N * 8)
+    w[:, col("generations_run")] = np.uint64(2**64 - 1)   # (-1: a run that never started)
+    cc_of = {}   # (one record per distinct DeviceCost: a repeated one points at the same params)
+    for c in cost_list:
+        if id(c) not in cc_of:
+            cc_of[id(c)] = c.to_c()
+    ccs = (cd.Cost * R)(*[cc_of[id(c)] for c in cost_list])
+    sd = (C.c_uint64 * R)(*seeds)
+    st = (C.c_int * R)()
+    with ctx.interruptible():   # (a Cancelled raised inside becomes KeyboardInterrupt after Ctrl-C)
+        status = lib.kabc_abcde_run_batch(ctx.handle, fac.to_c(), D, ccs, R, sd, C.byref(o), res, st)
+        t_host1 = time.perf_counter()
+        bs = (C.c_int64 * 4)()
+        lib.kabc_abcde_batch_stats(bs)
+
+        def entry(r):
+            q = res[r]
+            if q.generations_run < 0:
+                return None
+            info = {"generations_run": q.generations_run, "nsims": q.nsims}
+            return AbcdeResult(theta[r] if return_array else _bundle(theta[r], scalar), Cst[r],
+                               bool(q.reached_eps), info)
+
+        out = AbcdeBatchResult(entry(r) if st[r] in (0, cd.KABC_ERR_CANCELLED) else None for r in range(R))
+        out.info = {"course": "grid" if bs[0] == 1 else "sequential", "launches": int(bs[1]),
+                    "runs_per_launch": int(bs[2]), "nruns": R, "wall_ms": (t_host1 - t_host0) * 1e3,
+                    "status": [int(x) for x in st]}
+        if status != 0:
+            try:
+                _lib.check(status)
+            except _lib.Cancelled as e:
+                e.result = out
+                raise
+            except _lib.KabcError as e:
+                e.results = out
+                raise
+        return out
+
+
 PfilterResult = collections.namedtuple("PfilterResult", ["P", "C", "info"])
 
 

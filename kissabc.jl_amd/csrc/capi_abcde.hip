@@ -1,11 +1,16 @@
 // capi_abcde.hip -- kabc_abcde_run: ABCDE(prior, cost, ϵ_target; ...) of
 // src/smc.jl:347-430.  All generations are enqueued without a host round trip; the
 // earlystop break is taken on the device (kernels after it are no-ops).
+// kabc_abcde_run_batch: many independent runs, one workgroup each, as one launch grid
+// (abcde_small_kernel.hpp), or one after another through kabc_abcde_run.
 #include <cmath>
+#include <cstdlib>
+#include <string>
 #include <vector>
 
 #define KABC_ABCDE_SINGLE_UNIT 1
 #include "abcde_kernels.hpp"
+#include "abcde_small_kernel.hpp"
 #include "host_common.hpp"
 #include "plugin_registry.hpp"
 
@@ -29,6 +34,16 @@ static AbcdeLaunchFn pick_init(int D, std::integer_sequence<int, Ds...>) {
 template <int... Ds>
 static AbcdeLaunchFn pick_gen(int D, std::integer_sequence<int, Ds...>) {
     static const AbcdeLaunchFn f[] = {&l_gen<Ds + 1>...};
+    return f[D - 1];
+}
+
+template <int D>
+static void l_small(const AbcdeSmallArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL((abcde_small_kernel<D>), abcde_small_geom(a), dim3(abcde_small_block(a.N)), 0, s, a);
+}
+template <int... Ds>
+static AbcdeSmallLaunchFn pick_small(int D, std::integer_sequence<int, Ds...>) {
+    static const AbcdeSmallLaunchFn f[] = {&l_small<Ds + 1>...};
     return f[D - 1];
 }
 
@@ -641,6 +656,285 @@ kabc_status_t kabc_abcde_run(kabc_ctx_t* ctx, const kabc_prior_t* prior, int32_t
         fprintf(stderr, "ABCDE End: converged = %d nsim = %llu range_eps = (%g, %g)\n",
                 res->reached_eps, (unsigned long long)hc.nsims, hc.eps_l, hc.eps_h);
     return KABC_OK;
+}
+
+}  // extern "C"
+
+// ---- kabc_abcde_run_batch -----------------------------------------------------------------------
+namespace kabc {
+namespace {
+
+// how the calling thread's last kabc_abcde_run_batch was driven (kabc_abcde_batch_stats)
+thread_local int64_t tl_abcde_batch_stats[4] = {0, 0, 0, 0};
+
+const char* const kAbcdeExhausted = "ABCDE: the prior never produced a finite (cost, logpdf) pair for some particle";
+
+// the one-workgroup kernel of (cost, D): prebuilt for the built-in costs, compiled into the model unit
+// or the hipRTC user cost's unit otherwise; none for a cost plugin built by hipcc
+AbcdeSmallLaunch find_abcde_small_kernel(int cost_id, int D, int64_t N, ModelUnit* unit) {
+    const unsigned block = abcde_small_block(N);
+    if (unit) {  // user prior families / a specialised model (plugin_registry.hpp)
+        const PluginKernel k = unit_kernel(unit, kPfAbcdeSmall, D, 0);
+        if (k.mod) return AbcdeSmallLaunch(k.mod, &abcde_small_geom, block);
+        if (unit_required(unit)) return AbcdeSmallLaunch();
+        // (a specialisation that is not there (yet): the kernels below, same bits)
+    }
+    if (cost_id < KABC_COST_USER) return AbcdeSmallLaunch(pick_small(D, std::make_integer_sequence<int, KABC_MAX_DIM>{}));
+    const PluginKernel k = plugin_kernel(find_plugin(cost_id), kPfAbcdeSmall, D, 0);
+    return k.mod ? AbcdeSmallLaunch(k.mod, &abcde_small_geom, block) : AbcdeSmallLaunch();
+}
+
+// can the one-workgroup kernel take this shape at all (before anything is resolved)?
+// (KABC_ABCDE_SMALL=0: one run after another; verbose: kabc_abcde_run prints each run's summary)
+bool abcde_batch_shape_small(const kabc_abcde_opts_t* o, int D) {
+    const char* env = std::getenv("KABC_ABCDE_SMALL");
+    return !(env && env[0] == '0') && !o->verbose && o->nparticles >= 3 && o->nparticles <= kAbcdeSmallBlock &&
+           D >= 1 && D <= KABC_MAX_DIM;
+}
+
+// The launch grid: workgroup r runs run r from its initial draw to its last generation.  *grid = false
+// (and KABC_OK) when there is no kernel for the pair: the caller runs the batch one run after another.
+// A non-OK return: the batch as a whole failed (message set).
+kabc_status_t abcde_run_grid(kabc_ctx_t* ctx, const kabc_prior_t* prior, int32_t D, const kabc_cost_t* costs,
+                             int64_t nruns, const uint64_t* seeds, const kabc_abcde_opts_t* o,
+                             kabc_abcde_result_t* results, kabc_status_t* status, bool* grid) {
+    *grid = false;
+    const kabc_cost_t* cost = &costs[0];
+    const int64_t N = o->nparticles, NR = nruns;
+    // the checks of kabc_abcde_run that need the prior and the cost
+    std::vector<kabc_prior_t> resolved((size_t)D);  // MvNormal components: device block, D
+    if (kabc_status_t st = resolve_priors(ctx, prior, D, resolved.data())) return st;
+    prior = resolved.data();
+    AbcdeSmallArgs A;
+    std::memset(&A, 0, sizeof A);
+    if (!prepare_priors(prior, D, A.prior)) {
+        set_error("invalid prior parameters");
+        return KABC_ERR_INVALID_ARG;
+    }
+    if (!cost_dim_ok_rt(cost->id, D)) {
+        set_error("DeviceCost id %d does not accept D = %d", cost->id, D);
+        return KABC_ERR_UNSUPPORTED;
+    }
+    // (run-time compiled kernels are loaded on the CURRENT device)
+    KABC_HIP_CHECK(hipSetDevice(ctx->device));
+    ModelUnit* unit = nullptr;
+    if (kabc_status_t st = model_unit_for(prior, D, cost->id, &unit)) return st;
+    const AbcdeSmallLaunch f = find_abcde_small_kernel(cost->id, D, N, unit);
+    if (!f) return KABC_OK;
+    *grid = true;
+    tl_abcde_batch_stats[0] = 1;
+    tl_abcde_batch_stats[2] = NR;
+    std::memcpy(A.raw, prior, sizeof(kabc_prior_t) * D);
+    hipStream_t s = ctx->stream;
+    DevBufs bufs;
+    bufs.ctx = ctx;
+    double *d_out = nullptr, *d_dout = nullptr, *d_params = nullptr, *d_data = nullptr;
+    AbcdeSmallRec* d_rec = nullptr;
+    uint64_t* d_seeds = nullptr;
+    KABC_HIP_CHECK(bufs.alloc(&d_out, (size_t)(NR * N * D)));
+    KABC_HIP_CHECK(bufs.alloc(&d_dout, (size_t)(NR * N)));
+    KABC_HIP_CHECK(bufs.alloc(&d_rec, (size_t)NR));
+    KABC_HIP_CHECK(bufs.alloc(&d_seeds, (size_t)NR));
+    KABC_HIP_CHECK(hipMemcpyAsync(d_seeds, seeds, sizeof(uint64_t) * NR, hipMemcpyHostToDevice, s));
+    // the runs' params / data side by side, unless every run points at the same ones
+    bool same_p = true, same_d = true;
+    for (int64_t q = 1; q < NR; ++q) {
+        same_p = same_p && costs[q].params == cost->params;
+        same_d = same_d && costs[q].data == cost->data;
+    }
+    std::vector<double> h_params, h_data;  // (staging; alive until the copies ran)
+    if (cost->nparams > 0) {
+        const int64_t n = same_p ? cost->nparams : cost->nparams * NR;
+        if (!same_p) {
+            h_params.resize((size_t)n);
+            for (int64_t q = 0; q < NR; ++q)
+                std::memcpy(h_params.data() + q * cost->nparams, costs[q].params, sizeof(double) * cost->nparams);
+        }
+        KABC_HIP_CHECK(bufs.alloc(&d_params, (size_t)n));
+        KABC_HIP_CHECK(hipMemcpyAsync(d_params, same_p ? cost->params : h_params.data(), sizeof(double) * n,
+                                      hipMemcpyHostToDevice, s));
+        A.params_stride = same_p ? 0 : cost->nparams;
+    }
+    if (cost->ndata > 0) {
+        const int64_t n = same_d ? cost->ndata : cost->ndata * NR;
+        if (!same_d) {
+            h_data.resize((size_t)n);
+            for (int64_t q = 0; q < NR; ++q)
+                std::memcpy(h_data.data() + q * cost->ndata, costs[q].data, sizeof(double) * cost->ndata);
+        }
+        KABC_HIP_CHECK(bufs.alloc(&d_data, (size_t)n));
+        KABC_HIP_CHECK(hipMemcpyAsync(d_data, same_d ? cost->data : h_data.data(), sizeof(double) * n,
+                                      hipMemcpyHostToDevice, s));
+        A.data_stride = same_d ? 0 : cost->ndata;
+    }
+    A.out = d_out;
+    A.dout = d_dout;
+    A.rec = d_rec;
+    A.seeds = d_seeds;
+    A.cost_params = d_params;
+    A.cost_data = d_data;
+    A.cost_ndata = cost->ndata;
+    A.generations = o->generations;
+    A.cancel = ctx->cancel_d;
+    A.N = (int32_t)N;
+    A.nruns = (int32_t)NR;
+    A.cost_id = cost->id;
+    A.earlystop = o->earlystop;
+    A.eps_target = o->eps_target;
+    A.alpha = o->alpha;
+    A.gamma = o->proposal_width * 2.38 / std::sqrt((double)(2 * D));
+    f(A, s);
+    KABC_HIP_CHECK(hipGetLastError());
+    tl_abcde_batch_stats[1] = 1;
+    // ONE copy per array: straight into the caller's arrays when they follow each other run after run,
+    // else into one page-locked block and scattered from there
+    std::vector<AbcdeSmallRec> hrec((size_t)NR);
+    KABC_HIP_CHECK(hipMemcpyAsync(hrec.data(), d_rec, sizeof(AbcdeSmallRec) * NR, hipMemcpyDeviceToHost, s));
+    struct Arr {
+        const double* dev;
+        size_t run;  // doubles of one run
+        bool present, direct;
+        size_t off;  // in the page-locked block (doubles)
+    } arr[2] = {{d_out, (size_t)(N * D), false, true, 0}, {d_dout, (size_t)N, false, true, 0}};
+    auto host_of = [&](int j, int64_t q) -> double* { return j == 0 ? results[q].theta : results[q].cost; };
+    size_t staged = 0;
+    for (int j = 0; j < 2; ++j) {
+        Arr& a = arr[j];
+        for (int64_t q = 0; q < NR; ++q) {
+            a.present = a.present || host_of(j, q) != nullptr;
+            a.direct = a.direct && host_of(j, q) && host_of(j, q) == host_of(j, 0) + q * a.run;
+        }
+        if (a.present && !a.direct) {
+            a.off = staged;
+            staged += a.run * NR;
+        }
+    }
+    double* pin = nullptr;
+    if (staged) KABC_HIP_CHECK(hipHostMalloc((void**)&pin, sizeof(double) * staged, hipHostMallocDefault));
+    struct PinFree {
+        double* p;
+        ~PinFree() {
+            if (p) (void)hipHostFree(p);
+        }
+    } pin_free{pin};
+    for (int j = 0; j < 2; ++j) {
+        const Arr& a = arr[j];
+        if (!a.present) continue;
+        double* dst = a.direct ? host_of(j, 0) : pin + a.off;
+        KABC_HIP_CHECK(hipMemcpyAsync(dst, a.dev, sizeof(double) * a.run * NR, hipMemcpyDeviceToHost, s));
+    }
+    KABC_HIP_CHECK(hipStreamSynchronize(s));
+    bool cancelled = false;
+    for (int64_t q = 0; q < NR; ++q) {
+        const AbcdeSmallRec& h = hrec[(size_t)q];
+        status[q] = h.error ? KABC_ERR_RETRY_EXHAUSTED : h.cancelled ? KABC_ERR_CANCELLED : KABC_OK;
+        cancelled = cancelled || status[q] == KABC_ERR_CANCELLED;
+        if (status[q] == KABC_ERR_RETRY_EXHAUSTED) continue;
+        for (int j = 0; j < 2; ++j) {
+            const Arr& a = arr[j];
+            if (a.present && !a.direct && host_of(j, q))
+                std::memcpy(host_of(j, q), pin + a.off + (size_t)q * a.run, sizeof(double) * a.run);
+        }
+        kabc_abcde_result_t& rq = results[q];
+        rq.reached_eps = h.reached;
+        rq.reserved = 0;
+        rq.generations_run = h.iters;
+        rq.nsims = h.nsims;
+    }
+    if (cancelled) (void)cancel_take(ctx);
+    return KABC_OK;
+}
+
+// the course of shapes the one-workgroup kernel cannot take: the runs one after another, with a look
+// at the cancel word between two runs (kabc_abcde_run itself does not poll)
+void abcde_batch_sequential(kabc_ctx_t* ctx, const kabc_prior_t* prior, int32_t D, const kabc_cost_t* costs,
+                            int64_t nruns, const uint64_t* seeds, const kabc_abcde_opts_t* o,
+                            kabc_abcde_result_t* results, kabc_status_t* status, std::string* first_msg) {
+    for (int64_t q = 0; q < nruns; ++q) status[q] = KABC_ERR_CANCELLED;  // (runs a cancel leaves unstarted)
+    for (int64_t q = 0; q < nruns; ++q) {
+        if (cancel_take(ctx)) {
+            if (first_msg->empty()) *first_msg = "cancelled";
+            break;
+        }
+        kabc_abcde_opts_t oq = *o;
+        oq.seed = seeds[q];
+        status[q] = kabc_abcde_run(ctx, prior, D, &costs[q], &oq, &results[q]);
+        tl_abcde_batch_stats[1] = q + 1;
+        if (status[q] != KABC_OK && first_msg->empty()) {
+            const char* m = get_error();
+            *first_msg = m && *m ? m : "failed";
+        }
+    }
+}
+
+kabc_status_t abcde_batch_impl(kabc_ctx_t* ctx, const kabc_prior_t* prior, int32_t D, const kabc_cost_t* costs,
+                               int64_t nruns, const uint64_t* seeds, const kabc_abcde_opts_t* o,
+                               kabc_abcde_result_t* results, kabc_status_t* status) {
+    std::memset(tl_abcde_batch_stats, 0, sizeof tl_abcde_batch_stats);
+    if (!ctx || !prior || !costs || !seeds || !o || !results || !status) {
+        set_error("kabc_abcde_run_batch: NULL argument");
+        return KABC_ERR_INVALID_ARG;
+    }
+    if (nruns < 1 || nruns > 65535) {
+        set_error("kabc_abcde_run_batch: nruns = %lld is outside 1..65535", (long long)nruns);
+        return KABC_ERR_INVALID_ARG;
+    }
+    for (int64_t q = 1; q < nruns; ++q)
+        if (costs[q].id != costs[0].id || costs[q].nparams != costs[0].nparams || costs[q].ndata != costs[0].ndata) {
+            set_error("kabc_abcde_run_batch: costs[%lld] differs from costs[0] in its id or its params / data lengths",
+                      (long long)q);
+            return KABC_ERR_INVALID_ARG;
+        }
+    // kabc_abcde_run's own checks of the options, before anything runs
+    if (!(o->alpha >= 0 && o->alpha < 1)) {  // @assert 0<=α<1 (:348)
+        set_error("α must be in 0 <= α < 1.");
+        return KABC_ERR_INVALID_ARG;
+    }
+    if (D < 1 || D > KABC_MAX_DIM_DYN) {
+        set_error("length(prior) = %d is outside the device path's range 1..%d", D, KABC_MAX_DIM_DYN);
+        return KABC_ERR_UNSUPPORTED;
+    }
+    if (o->nparticles < 3 || o->nparticles >= (1ll << 31)) {
+        set_error("nparticles must be >= 3 (and < 2^31)");
+        return KABC_ERR_INVALID_ARG;
+    }
+    bool grid = false;
+    std::string first_msg;  // (one after another: the first failing run's own message)
+    if (abcde_batch_shape_small(o, D)) {
+        const kabc_status_t st = abcde_run_grid(ctx, prior, D, costs, nruns, seeds, o, results, status, &grid);
+        if (st) {  // (the batch as a whole failed: every run shares the verdict)
+            for (int64_t q = 0; q < nruns; ++q) status[q] = st;
+            return st;
+        }
+    }
+    if (!grid) {
+        tl_abcde_batch_stats[0] = 0;
+        tl_abcde_batch_stats[2] = 1;
+        abcde_batch_sequential(ctx, prior, D, costs, nruns, seeds, o, results, status, &first_msg);
+    }
+    // the lowest failing run names the verdict ("run 3: <its message>")
+    for (int64_t q = 0; q < nruns; ++q) {
+        if (status[q] == KABC_OK) continue;
+        if (grid) first_msg = status[q] == KABC_ERR_CANCELLED ? "cancelled" : kAbcdeExhausted;
+        set_error("run %lld: %s", (long long)q, first_msg.c_str());
+        return status[q];
+    }
+    return KABC_OK;
+}
+
+}  // namespace
+}  // namespace kabc
+
+extern "C" {
+
+kabc_status_t kabc_abcde_run_batch(kabc_ctx_t* ctx, const kabc_prior_t* prior, int32_t D, const kabc_cost_t* costs,
+                                   int64_t nruns, const uint64_t* seeds, const kabc_abcde_opts_t* opts,
+                                   kabc_abcde_result_t* results, kabc_status_t* status) {
+    return abcde_batch_impl(ctx, prior, D, costs, nruns, seeds, opts, results, status);
+}
+
+void kabc_abcde_batch_stats(int64_t out[4]) {
+    if (out) std::memcpy(out, tl_abcde_batch_stats, sizeof tl_abcde_batch_stats);
 }
 
 }  // extern "C"

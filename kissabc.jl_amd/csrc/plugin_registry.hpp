@@ -39,7 +39,9 @@ enum PluginFamily {
     // ABCDE / pfilter beyond KABC_MAX_DIM: their own families, instantiated with D = 0
     kPfAisDyn, kPfSmcDyn,
     // (hipRTC units) the one-workgroup AIS driver of small ensembles (ais_small_kernel.hpp); variant = AIS pcx
-    kPfAisSmall
+    kPfAisSmall,
+    // (hipRTC units) the one-workgroup ABCDE driver of kabc_abcde_run_batch (abcde_small_kernel.hpp)
+    kPfAbcdeSmall
 };
 struct PluginKernel {
     void* host = nullptr;
