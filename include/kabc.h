@@ -405,6 +405,24 @@ kabc_status_t kabc_ais_create(kabc_ctx_t* ctx, const kabc_model_t* model, int64_
 kabc_status_t kabc_ais_create_batch(kabc_ctx_t* ctx, const kabc_model_t* model, int64_t nparticles,
                                     int32_t nchains, const uint64_t* seeds, kabc_ais_t** out);
 
+/* One model fitted to nchains DATASETS in one handle: kabc_ais_create_batch with model->cost replaced
+ * by costs[c] for chain c.  Chain c is bit-identical to a kabc_ais_create handle on `model` with
+ * cost costs[c] and seed seeds[c] (trace, state, ensemble, counters).  Every costs[c] has
+ * model->cost's id, nparams and ndata; its params / data values may differ.  The handle keeps one
+ * device block [nchains][nparams] and one [nchains][ndata]; an array that is byte-equal to chain 0's
+ * in every chain is kept once, and a batch whose costs are all equal runs exactly as
+ * kabc_ais_create_batch on costs[0].  costs == NULL is kabc_ais_create_batch.  Limits and layouts are
+ * kabc_ais_create_batch's (1 <= nchains <= 65535, D <= KABC_MAX_DIM; host arrays gain a leading chain
+ * axis), and every entry point below works on such a handle.  No launch shape or buffer size depends
+ * on a cost's values: NormalMeanStdSim's draw count params[0] may differ per chain (each chain's
+ * pre-pass and producers read their own).  A cost plugin .so built by hipcc
+ * (kabc_register_cost_plugin) is refused with KABC_ERR_UNSUPPORTED when the values differ: its
+ * kernels may predate the per-chain fields; its hipRTC form serves.  A failed kabc_ais_init of any
+ * batch handle names the lowest failing chain: "chain 3: Prior leads to ∞ costs too often, ...". */
+kabc_status_t kabc_ais_create_batch_costs(kabc_ctx_t* ctx, const kabc_model_t* model, int64_t nparticles,
+                                          int32_t nchains, const uint64_t* seeds, const kabc_cost_t* costs,
+                                          kabc_ais_t** out);
+
 /* Sharded variant: this process owns rows [rank*rows_h/world, (rank+1)*rows_h/world)
  * of each half of an ensemble of n_total walkers (n_total divisible by 2*world).
  * dev_half0 / dev_half1 are caller-provided DEVICE buffers of n_total/2 * D

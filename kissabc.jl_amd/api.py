@@ -161,10 +161,20 @@ class MCMCThreads:
 class AisEnsemble:
     """kabc_ais_t: the device-resident AISState (src/KissABC.jl:25-33)."""
 
-    def __init__(self, model, nparticles, seed=0, ctx=None, sharded=None, comm=None, seeds=None):
+    def __init__(self, model, nparticles, seed=0, ctx=None, sharded=None, comm=None, seeds=None, costs=None):
         """`seeds` (a sequence) makes a BATCH handle: len(seeds) independent ensembles of
         `nparticles` walkers, chain = a grid dimension of every launch (kabc_ais_create_batch);
-        state / trace arrays gain a leading chain axis."""
+        state / trace arrays gain a leading chain axis.  `costs` (a sequence of DeviceCosts, one per
+        chain, with model.cost's id and params / data lengths) fits the model to one dataset per
+        chain: chain c runs on model with its cost replaced by costs[c] (kabc_ais_create_batch_costs)."""
+        if costs is not None:
+            if seeds is None:
+                raise ValueError("AisEnsemble: costs needs seeds (one per chain)")
+            costs = list(costs)
+            if not all(isinstance(c, DeviceCost) for c in costs):
+                raise TypeError("AisEnsemble: costs must be DeviceCosts")
+            if len(costs) != len(seeds):
+                raise ValueError(f"AisEnsemble: {len(costs)} costs for {len(seeds)} seeds")
         self.model = model
         self.comm = comm
         self.nchains = 1 if seeds is None else len(seeds)
@@ -175,7 +185,12 @@ class AisEnsemble:
         self._cmodel = model.to_c()
         self._h = C.c_void_p()
         lib = _lib.load()
-        if seeds is not None:
+        if seeds is not None and costs is not None:
+            arr = (C.c_uint64 * len(seeds))(*[int(v) & (2 ** 64 - 1) for v in seeds])
+            ccs = (cd.Cost * len(costs))(*[c.to_c() for c in costs])   # (copied by the library)
+            _lib.check(lib.kabc_ais_create_batch_costs(self.ctx.handle, C.byref(self._cmodel), self.N,
+                                                       len(seeds), arr, ccs, C.byref(self._h)))
+        elif seeds is not None:
             arr = (C.c_uint64 * len(seeds))(*[int(v) & (2 ** 64 - 1) for v in seeds])
             _lib.check(lib.kabc_ais_create_batch(self.ctx.handle, C.byref(self._cmodel), self.N,
                                                  len(seeds), arr, C.byref(self._h)))
@@ -340,6 +355,31 @@ def _bundle(samples, scalar):
     return P[0] if (len(P) == 1 or scalar) else P
 
 
+def _sample_chains(model, N, Ns, seeds, costs, ntransitions, discard_initial, retry_sampling, ctx):
+    """len(seeds) independent chains of AIS(N) in ONE batch handle (costs: one DeviceCost per chain, or
+    None): the first Ns samples of each, [Nc][Ns][D], and the handle's driver"""
+    Nc, D = len(seeds), len(model)
+    ens = AisEnsemble(model, N, ctx=ctx, seeds=seeds, costs=costs)
+    gk = max(1, -(-Ns // N))
+    big = gk * Nc * N * D * 8 > (1 << 20)   # (a small trace is not worth a helper thread: see sample)
+    pool = concurrent.futures.ThreadPoolExecutor(1) if big else None
+    buf = pool.submit(_lib.pinned_empty, (gk, Nc, N, D)) if big else None
+    try:
+        driver = ens.driver
+        ens.init(retry_sampling)
+        gd = -(-int(discard_initial) // N)
+        if gd:
+            ens.advance(gd, ntransitions)
+        tr = ens.advance(gk, ntransitions,
+                         out=buf.result() if big else _lib.pinned_empty((gk, Nc, N, D)))   # [gk][Nc][N][D]
+        chains = np.ascontiguousarray(tr.transpose(1, 0, 2, 3)).reshape(Nc, gk * N, D)[:, :Ns]
+    finally:
+        if pool is not None:
+            pool.shutdown(wait=True)
+        ens.close()
+    return chains, driver
+
+
 def sample(model, spl, *args, ntransitions=1, discard_initial=0, retry_sampling=100, seed=0,
            progress=False, ctx=None, return_array=False, **kwargs):
     """sample(model, AIS(N), Ns; ...) and sample(model, AIS(N), MCMCThreads(), Ns, Nc; ...).
@@ -356,25 +396,9 @@ def sample(model, spl, *args, ntransitions=1, discard_initial=0, retry_sampling=
         # ensembles (kabc_ais_create_batch); chain c is bit-identical to a single-chain run
         # with its seed
         _, Ns, Nc = args
-        Ns, Nc, N, D = int(Ns), int(Nc), spl.nparticles, len(model)
-        seeds = chain_seeds(seed, Nc)
-        ens = AisEnsemble(model, N, ctx=ctx, seeds=seeds)
-        gk = max(1, -(-Ns // N))
-        big = gk * Nc * N * D * 8 > (1 << 20)   # (a small trace is not worth a helper thread: see below)
-        pool = concurrent.futures.ThreadPoolExecutor(1) if big else None
-        buf = pool.submit(_lib.pinned_empty, (gk, Nc, N, D)) if big else None
-        try:
-            ens.init(retry_sampling)
-            gd = -(-int(discard_initial) // N)
-            if gd:
-                ens.advance(gd, ntransitions)
-            tr = ens.advance(gk, ntransitions,
-                             out=buf.result() if big else _lib.pinned_empty((gk, Nc, N, D)))   # [gk][Nc][N][D]
-            chains = np.ascontiguousarray(tr.transpose(1, 0, 2, 3)).reshape(Nc, gk * N, D)[:, :Ns]
-        finally:
-            if pool is not None:
-                pool.shutdown(wait=True)
-            ens.close()
+        Ns, Nc, D = int(Ns), int(Nc), len(model)
+        chains, _ = _sample_chains(model, spl.nparticles, Ns, chain_seeds(seed, Nc), None, ntransitions,
+                                   discard_initial, retry_sampling, ctx)
         stacked = chains.reshape(Nc * Ns, D)  # chainsstack, src/KissABC.jl:96-104
         return stacked if return_array else _bundle(stacked, model.scalar)
     (Ns,) = args
@@ -401,6 +425,100 @@ def sample(model, spl, *args, ntransitions=1, discard_initial=0, retry_sampling=
             pool.shutdown(wait=True)
         ens.close()
     return out if return_array else _bundle(out, model.scalar)
+
+
+class AisBatchResult(list):
+    """sample_batch's result: one entry per run, shaped as sample() returns it, and `.info` about the call."""
+
+    info = None
+
+
+def _model_difference(m, m0):
+    """what sets model m apart from model 0 beyond its cost's params / data, else None"""
+    if type(m) is not type(m0):
+        return "its class"
+    if len(m) != len(m0) or m.scalar != m0.scalar or bytes(m.prior.to_c()) != bytes(m0.prior.to_c()):
+        return "its prior"
+    if not (m.eps == m0.eps or (math.isnan(m.eps) and math.isnan(m0.eps))):
+        return "its eps"
+    if m.cost.id != m0.cost.id:
+        return "its cost id"
+    if m.cost.params.size != m0.cost.params.size or m.cost.data.size != m0.cost.data.size:
+        return "its cost's params / data lengths"
+    return None
+
+
+def sample_batch(model, spl, Ns, nruns=None, *, seeds=None, seed=0, ntransitions=1, discard_initial=0,
+                 retry_sampling=100, ctx=None, return_array=False):
+    """One model fitted to many datasets, or one dataset under many seeds, in one call: run r is
+    sample(model_r, spl, Ns, seed=seeds[r], <the same keywords>), bit for bit.
+
+    `model` is one model (the runs differ by their seeds only; `nruns` is required) or a sequence of
+    models, one per dataset, of one class with the same prior, eps, cost id and cost params / data lengths
+    (`nruns` defaults to its length).  `seeds` defaults to chain_seeds(seed, nruns).  With
+    length(prior) <= KABC_MAX_DIM the runs are the chains of ONE batch handle (kabc_ais_create_batch_costs:
+    info["course"] == "grid", info["driver"] "small" or "halves"); other shapes, and a cost plugin built
+    by hipcc whose runs differ in their cost values, run as sample() calls one after another
+    ("sequential").  Returns a list with one entry per run; its `.info` holds the course, the driver,
+    nruns and the wall time.  A failed initial draw raises KabcError("run r: <the reference's message>");
+    Context.cancel() / Ctrl-C behave as they do for sample()."""
+    if not isinstance(spl, AIS):
+        raise TypeError("sampler must be AIS(nparticles)")
+    if isinstance(model, _ApproxModel):
+        if nruns is None:
+            raise ValueError("sample_batch: nruns is required with a single model")
+        nruns = int(nruns)
+        models = [model] * max(nruns, 0)
+    else:
+        models = list(model)
+        if not all(isinstance(m, _ApproxModel) for m in models):
+            raise TypeError("sample_batch: `model` must be a model or a sequence of models")
+        nruns = len(models) if nruns is None else int(nruns)
+        if len(models) != nruns:
+            raise ValueError(f"sample_batch: {len(models)} models for nruns = {nruns}")
+    if nruns < 1:
+        raise ValueError("sample_batch: nruns must be >= 1")
+    m0 = models[0]
+    for r, m in enumerate(models):
+        if m is not m0:
+            what = _model_difference(m, m0)
+            if what:
+                raise ValueError(f"sample_batch: model {r} differs from model 0 in {what}")
+    seeds = chain_seeds(seed, nruns) if seeds is None else [int(x) for x in seeds]
+    if len(seeds) != nruns:
+        raise ValueError(f"sample_batch: len(seeds) = {len(seeds)} != nruns = {nruns}")
+    Ns, N, D = int(Ns), spl.nparticles, len(m0)
+    kw = dict(ntransitions=ntransitions, discard_initial=discard_initial, retry_sampling=retry_sampling)
+    t0 = time.perf_counter()
+    chains, driver = None, None
+    if D <= cd.KABC_MAX_DIM:
+        try:
+            chains, driver = _sample_chains(m0, N, Ns, seeds, [m.cost for m in models], ctx=ctx, **kw)
+        except _lib.Cancelled:
+            raise
+        except _lib.KabcError as e:
+            msg = str(e)
+            if msg.startswith("chain "):   # (a failed initial draw: "chain r: ...")
+                raise _lib.KabcError(e.status, "run " + msg[len("chain "):]) from None
+            if e.status != cd.KABC_ERR_UNSUPPORTED:
+                raise
+            # (a shape the batch handle refuses: the runs one after another, each with sample()'s own checks)
+    if chains is not None:
+        out = AisBatchResult(c if return_array else _bundle(c, m0.scalar) for c in chains)
+        course = "grid"
+    else:
+        out = AisBatchResult()
+        for r, m in enumerate(models):
+            try:
+                out.append(sample(m, spl, Ns, seed=seeds[r], ctx=ctx, return_array=return_array, **kw))
+            except _lib.Cancelled:
+                raise
+            except _lib.KabcError as e:
+                raise _lib.KabcError(e.status, f"run {r}: {e}") from None
+        course, driver = "sequential", "halves"   # (the run-time-dimension kernels, a hipcc plugin's kernels)
+    out.info = {"course": course, "driver": driver, "nruns": nruns,
+                "wall_ms": (time.perf_counter() - t0) * 1e3}
+    return out
 
 
 class SmcResult(collections.namedtuple("SmcResult", ["P", "C", "eps", "info"])):

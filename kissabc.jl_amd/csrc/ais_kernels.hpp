@@ -54,6 +54,11 @@ struct AisArgs {
     int64_t stride_aux;
     // debug records of a launch that covers sub-steps [dbg_s0, dbg_s0 + nt) of dbg_nt
     int32_t dbg_nt, dbg_s0;
+    // per-chain costs (kabc_ais_create_batch_costs): chain c reads its cost's params / data at
+    // cost_params + c * params_stride, cost_data + c * data_stride (doubles; 0 = every chain shares
+    // one copy).  Read only where seeds != NULL.  Last, so that the fields before them keep their
+    // offsets for cost plugins built by hipcc against the same KABC_VERSION.
+    int64_t params_stride, data_stride;
 };
 
 // leading normal-pair blocks of the cost's stream that the AIS producers expand (0: none).  Bounded
@@ -88,6 +93,7 @@ struct InitArgs {
     const uint64_t* seeds;
     unsigned long long* chain_retries;  // [nchains]
     int64_t stride_act, stride_own;
+    int64_t params_stride, data_stride;  // per-chain costs, see AisArgs (read only where seeds != NULL)
 };
 
 constexpr int kInitBlock = 64;
@@ -593,6 +599,8 @@ ais_half_kernel(const AisArgs A0) {
         A.ll += c * A0.stride_own;
         if (A0.trace) A.trace += c * A0.stride_trace;
         if (A0.aux) A.aux += c * A0.stride_aux;
+        A.cost_params += c * A0.params_stride;
+        A.cost_data += c * A0.data_stride;
     }
     __shared__ ChunkRec<D> rec[2];
     __shared__ uint8_t listB[kChunk][kBatch];
@@ -1070,6 +1078,8 @@ __global__ void __launch_bounds__(kInitBlock) ais_init_kernel(const InitArgs A) 
     double* x_act = A.x_act + (A.seeds ? chain * A.stride_act : 0);
     double* lp_out = A.lp + (A.seeds ? chain * A.stride_own : 0);
     double* ll_out = A.ll + (A.seeds ? chain * A.stride_own : 0);
+    const double* cparams = A.cost_params + (A.seeds ? chain * A.params_stride : 0);
+    const double* cdata = A.cost_data + (A.seeds ? chain * A.data_stride : 0);
     double x[D], xp[D];
     double lp = 0.0, ll = 0.0;
     uint64_t attempt = 0;
@@ -1079,7 +1089,7 @@ __global__ void __launch_bounds__(kInitBlock) ais_init_kernel(const InitArgs A) 
         // src/KissABC.jl: unconditional_sample): drawn by the plugin's function
         if (A.raw[0].kind == KABC_PRIOR_USER_INIT) {
             kabc_cost_rng_t irng = {seed, attempt, w, KABC_DOM_AIS_INIT, 0u};
-            kabc_user_sample_init(x, D, A.cost_params, A.cost_data, A.cost_ndata, &irng);
+            kabc_user_sample_init(x, D, cparams, cdata, A.cost_ndata, &irng);
         } else
 #endif
         {
@@ -1093,20 +1103,18 @@ __global__ void __launch_bounds__(kInitBlock) ais_init_kernel(const InitArgs A) 
         kabc_cost_rng_t rng = {seed, attempt, w, KABC_DOM_AIS_INIT_COST, 0u};
         if (A.posterior == KABC_POSTERIOR_COMMON) {
             lp = 0.0;
-            ll = kabc_cost_eval(A.cost_id, x, D, A.cost_params, A.cost_data, A.cost_ndata, &rng);
+            ll = kabc_cost_eval(A.cost_id, x, D, cparams, cdata, A.cost_ndata, &rng);
         } else if (A.posterior == KABC_POSTERIOR_KERNELIZED) {
             ll = lp;
             if (kabc_isfinite(lp)) {
-                const double c = kabc_cost_eval(A.cost_id, xp, D, A.cost_params, A.cost_data,
-                                                A.cost_ndata, &rng);
+                const double c = kabc_cost_eval(A.cost_id, xp, D, cparams, cdata, A.cost_ndata, &rng);
                 const double q = kabc_div_rc(c, A.eps, 1.0 / A.eps);
                 ll = -0.5 * (q * q);
             }
         } else {
             ll = -lp;
             if (kabc_isfinite(lp))
-                ll = kabc_cost_eval(A.cost_id, xp, D, A.cost_params, A.cost_data, A.cost_ndata,
-                                    &rng);
+                ll = kabc_cost_eval(A.cost_id, xp, D, cparams, cdata, A.cost_ndata, &rng);
         }
         if (ld_valid(A.posterior, lp, ll)) break;
         const unsigned long long used = atomicAdd(retries, 1ull) + 1ull;

@@ -72,6 +72,9 @@ struct AisSmallArgs {
     // the launch completed go to counters->small_done.
     const uint32_t* cancel;
     int32_t poll_every;
+    // per-chain costs (kabc_ais_create_batch_costs): chain c's params / data at cost_params + c *
+    // params_stride, cost_data + c * data_stride (doubles; 0 = shared); read only where seeds != NULL
+    int64_t params_stride, data_stride;
 };
 
 // one ring slot = the record of ONE (batch, sub-step) unit
@@ -151,6 +154,9 @@ __global__ void __launch_bounds__(kAisSmallBlock) ais_small_kernel(const AisSmal
     double* const gx[2] = {A.x[0] + chain * rows0 * D, A.x[1] + chain * rows1 * D};
     double* const glp[2] = {A.lp[0] + chain * rows0, A.lp[1] + chain * rows1};
     double* const gll[2] = {A.ll[0] + chain * rows0, A.ll[1] + chain * rows1};
+    // this chain's cost (per-chain costs: kabc_ais_create_batch_costs; strides 0 otherwise)
+    const double* const gparams = A.cost_params + (A.seeds ? chain * A.params_stride : 0);
+    const double* const gdata = A.cost_data + (A.seeds ? chain * A.data_stride : 0);
 
     // ---- stage: tables, prior, the ensemble, the hand-over words
     for (int i = tid; i < KABC_MATH_TAB_WORDS; i += kAisSmallBlock) slogtab[i] = kabc_log_tab[i];
@@ -282,7 +288,7 @@ __global__ void __launch_bounds__(kAisSmallBlock) ais_small_kernel(const AisSmal
                         // kabc_cost_eval would do in place -- include/kabc_costs.h)
                         kabc_cost_rng_t rng = {seed, t, w_base + (uint32_t)lane, KABC_DOM_AIS_COST, 0u, 0u, nullptr, slogtab};
                         double a[kAuxW];
-                        kabc_cost_prepare(COST, A.cost_params, A.cost_data, A.cost_ndata, &rng, a);
+                        kabc_cost_prepare(COST, gparams, gdata, A.cost_ndata, &rng, a);
 #pragma unroll
                         for (int jw = 0; jw < kAuxW; ++jw) SL.aux[jw][lane] = a[jw];
                     }
@@ -308,10 +314,10 @@ __global__ void __launch_bounds__(kAisSmallBlock) ais_small_kernel(const AisSmal
         double cpar[kRP > 0 ? kRP : 1];
 #pragma unroll
         for (int k = 0; k < kRP; ++k) {
-            cpar[k] = A.cost_params[k];
+            cpar[k] = gparams[k];
             asm volatile("" : "+v"(cpar[k]));
         }
-        const double* const cparams = kRP > 0 ? cpar : A.cost_params;
+        const double* const cparams = kRP > 0 ? cpar : gparams;
         const bool dbg_on = __builtin_amdgcn_readfirstlane(A.dbg != nullptr ? 1 : 0) != 0;
         const bool trace_on = __builtin_amdgcn_readfirstlane(A.trace != nullptr ? 1 : 0) != 0;
         // a stochastic cost reads its slot's variates while it is evaluated: the slot goes back late
@@ -495,7 +501,7 @@ __global__ void __launch_bounds__(kAisSmallBlock) ais_small_kernel(const AisSmal
                             rng.pre_stride = (uint32_t)kBatch;
                         }
                         double nlp, nll;
-                        loglike<D, COST, PC>(sprior, box, gbox, PK, A.eps, A.reps, y, cparams, A.cost_data, A.cost_ndata,
+                        loglike<D, COST, PC>(sprior, box, gbox, PK, A.eps, A.reps, y, cparams, gdata, A.cost_ndata,
                                              &rng, nlp, nll, ev, slogtab, kNbTabs > 0 ? snb : nullptr);
                         __builtin_amdgcn_sched_barrier(0);
                         n_eval += ev ? 1u : 0u;

@@ -148,9 +148,12 @@ struct kabc_ais {
     double eps = 0.0;
     kabc_prior_t raw[KABC_MAX_DIM] = {};
     PriorSet prior = {};
-    double* d_cost_params = nullptr;
-    double* d_cost_data = nullptr;
+    double* d_cost_params = nullptr;  // [nchains][nparams] with per-chain costs, else [nparams]
+    double* d_cost_data = nullptr;    // [nchains][ndata] with per-chain costs, else [ndata]
     int64_t cost_ndata = 0;
+    // per-chain costs (kabc_ais_create_batch_costs): doubles between two chains' params / data, 0 when
+    // every chain's array is byte-equal to chain 0's (one copy, the handle runs as a plain batch)
+    int64_t params_stride = 0, data_stride = 0;
     int64_t N = 0;                  // total walkers (all ranks)
     int64_t rows[2] = {};           // global rows per half
     int64_t rows_owned[2] = {};     // owned rows per half (all segments)
@@ -248,23 +251,39 @@ static kabc_status_t check_handle(const kabc_ais_t* h) {
     return KABC_OK;
 }
 
+// one device block of a cost array: chain c's `n` doubles at c * stride (stride 0: one copy of src(0))
+template <class Src>
+static kabc_status_t upload_chain_block(kabc_ais_t* h, double** dst, int64_t n, int64_t stride, Src src) {
+    if (n <= 0) return KABC_OK;
+    hipStream_t s = h->ctx->stream;
+    if (stride == 0) {  // (ais_alloc ends with a synchronisation)
+        KABC_HIP_CHECK(dev_malloc(dst, sizeof(double) * n));
+        KABC_HIP_CHECK(hipMemcpyAsync(*dst, src(0), sizeof(double) * n, hipMemcpyHostToDevice, s));
+        return KABC_OK;
+    }
+    const size_t nch = (size_t)h->nchains;
+    std::vector<double> blk((size_t)n * nch);
+    for (size_t c = 0; c < nch; ++c) std::memcpy(blk.data() + c * (size_t)n, src((int32_t)c), sizeof(double) * n);
+    KABC_HIP_CHECK(dev_malloc(dst, blk.size() * sizeof(double)));
+    KABC_HIP_CHECK(hipMemcpyAsync(*dst, blk.data(), blk.size() * sizeof(double), hipMemcpyHostToDevice, s));
+    KABC_HIP_CHECK(hipStreamSynchronize(s));  // (`blk` goes out of scope)
+    return KABC_OK;
+}
+
+// `costs`: the per-chain costs of kabc_ais_create_batch_costs (h->params_stride / data_stride set), else NULL
 static kabc_status_t ais_alloc(kabc_ais_t* h, const kabc_model_t* m, void* ext0, void* ext1,
-                               const uint64_t* seeds) {
+                               const uint64_t* seeds, const kabc_cost_t* costs) {
     kabc_ctx_t* ctx = h->ctx;
     const int world = h->world;
     const size_t nch = (size_t)h->nchains;
     KABC_HIP_CHECK(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    if (m->cost.nparams > 0) {
-        KABC_HIP_CHECK(dev_malloc(&h->d_cost_params, sizeof(double) * m->cost.nparams));
-        KABC_HIP_CHECK(hipMemcpyAsync(h->d_cost_params, m->cost.params,
-                                      sizeof(double) * m->cost.nparams, hipMemcpyHostToDevice, s));
-    }
-    if (m->cost.ndata > 0) {
-        KABC_HIP_CHECK(dev_malloc(&h->d_cost_data, sizeof(double) * m->cost.ndata));
-        KABC_HIP_CHECK(hipMemcpyAsync(h->d_cost_data, m->cost.data, sizeof(double) * m->cost.ndata,
-                                      hipMemcpyHostToDevice, s));
-    }
+    auto params_of = [&](int32_t c) { return (h->params_stride ? costs[c] : m->cost).params; };
+    auto data_of = [&](int32_t c) { return (h->data_stride ? costs[c] : m->cost).data; };
+    if (kabc_status_t st = upload_chain_block(h, &h->d_cost_params, m->cost.nparams, h->params_stride, params_of))
+        return st;
+    if (kabc_status_t st = upload_chain_block(h, &h->d_cost_data, m->cost.ndata, h->data_stride, data_of))
+        return st;
     for (int hf = 0; hf < 2; ++hf) {
         if (h->own_halves) {
             // padded to world equal segments so that the in-place all-gather has one count
@@ -559,7 +578,9 @@ static void ais_geometry(kabc_ais_t* h) {
 static kabc_status_t ais_create_common(kabc_ctx_t* ctx, const kabc_model_t* m, int64_t n_total,
                                        int32_t rank, int32_t world, uint64_t seed, void* ext0,
                                        void* ext1, kabc_comm_t* comm, kabc_ais_t** out,
-                                       int32_t nchains = 1, const uint64_t* seeds = nullptr) {
+                                       int32_t nchains = 1, const uint64_t* seeds = nullptr,
+                                       const kabc_cost_t* costs = nullptr, int64_t params_stride = 0,
+                                       int64_t data_stride = 0) {
     std::vector<kabc_prior_t> resolved;
     kabc_model_t mres;
     if (kabc_status_t st = ais_validate(ctx, m, out, n_total, rank, world, comm, nchains, resolved, mres))
@@ -571,6 +592,8 @@ static kabc_status_t ais_create_common(kabc_ctx_t* ctx, const kabc_model_t* m, i
     h->cost_id = mres.cost.id;
     h->eps = mres.eps;
     h->cost_ndata = mres.cost.ndata;
+    h->params_stride = params_stride;
+    h->data_stride = data_stride;
     h->N = n_total;
     h->rank = rank;
     h->world = world;
@@ -584,7 +607,7 @@ static kabc_status_t ais_create_common(kabc_ctx_t* ctx, const kabc_model_t* m, i
     if (st == KABC_OK) st = ais_resolve_kernels(h, &mres);
     if (st == KABC_OK) {
         ais_geometry(h);
-        st = ais_alloc(h, &mres, ext0, ext1, seeds);
+        st = ais_alloc(h, &mres, ext0, ext1, seeds, costs);
     }
     if (st) {
         (void)kabc_ais_destroy(h);
@@ -648,6 +671,9 @@ static void fill_args(A& a, const kabc_ais_t* h) {
     if constexpr (!aux && !dyn && !init) a.box_lp = h->box_lp;
     if constexpr (!aux && !small) a.posterior = h->posterior;
     if constexpr (dyn || init) a.cost_id = h->cost_id;
+    // per-chain costs (a run-time-dimension handle holds one chain; the pre-pass reads params only)
+    if constexpr (!dyn) a.params_stride = h->params_stride;
+    if constexpr (!dyn && !aux) a.data_stride = h->data_stride;
 }
 
 // a size knob of the environment (tests, tuning) in `unit` bytes, else `dflt`; read at every call, as
@@ -708,6 +734,66 @@ kabc_status_t kabc_ais_create_batch(kabc_ctx_t* ctx, const kabc_model_t* model, 
     }
     return ais_create_common(ctx, model, nparticles, 0, 1, seeds[0], nullptr, nullptr, nullptr, out,
                              nchains, seeds);
+}
+
+kabc_status_t kabc_ais_create_batch_costs(kabc_ctx_t* ctx, const kabc_model_t* model, int64_t nparticles,
+                                          int32_t nchains, const uint64_t* seeds, const kabc_cost_t* costs,
+                                          kabc_ais_t** out) {
+    if (!costs) return kabc_ais_create_batch(ctx, model, nparticles, nchains, seeds, out);
+    // (the checks that need no device come first)
+    if (!model || !out || !seeds) {
+        set_error("kabc_ais_create_batch_costs: NULL argument");
+        return KABC_ERR_INVALID_ARG;
+    }
+    if (nchains < 1 || nchains > 65535) {
+        set_error("kabc_ais_create_batch_costs: nchains must be 1..65535");
+        return KABC_ERR_INVALID_ARG;
+    }
+    const kabc_cost_t& c0 = model->cost;
+    if (c0.nparams < 0 || c0.ndata < 0 || (c0.nparams > 0 && !c0.params) || (c0.ndata > 0 && !c0.data)) {
+        set_error("kabc_ais_create_batch_costs: model->cost has a NULL params / data array or a negative length");
+        return KABC_ERR_INVALID_ARG;
+    }
+    // The strides: 0 when every chain's array is byte-equal to chain 0's (one copy, a plain batch)
+    bool same_p = true, same_d = true;
+    for (int32_t c = 0; c < nchains; ++c) {
+        const kabc_cost_t& q = costs[c];
+        if (q.id != c0.id || q.nparams != c0.nparams || q.ndata != c0.ndata) {
+            set_error("kabc_ais_create_batch_costs: costs[%d] differs from model->cost in its id or its params / "
+                      "data lengths (id %d, %lld params, %lld data; model->cost: id %d, %lld, %lld)",
+                      c, q.id, (long long)q.nparams, (long long)q.ndata, c0.id, (long long)c0.nparams,
+                      (long long)c0.ndata);
+            return KABC_ERR_INVALID_ARG;
+        }
+        if ((q.nparams > 0 && !q.params) || (q.ndata > 0 && !q.data)) {
+            set_error("kabc_ais_create_batch_costs: costs[%d] has a NULL params / data array", c);
+            return KABC_ERR_INVALID_ARG;
+        }
+        same_p = same_p && (q.nparams == 0 || std::memcmp(q.params, costs[0].params, sizeof(double) * q.nparams) == 0);
+        same_d = same_d && (q.ndata == 0 || std::memcmp(q.data, costs[0].data, sizeof(double) * q.ndata) == 0);
+    }
+    if (!ctx) {
+        set_error("kabc_ais_create_batch_costs: NULL argument");
+        return KABC_ERR_INVALID_ARG;
+    }
+    // Chain 0's own arrays stand in for model->cost's: a batch whose costs are all equal runs as
+    // kabc_ais_create_batch on costs[0]
+    kabc_model_t m = *model;
+    m.cost = costs[0];
+    const int64_t ps = same_p ? 0 : c0.nparams, ds = same_d ? 0 : c0.ndata;
+    // A cost plugin built by hipcc may predate the stride fields of the kernel arguments (they are the
+    // last ones, and its KABC_VERSION is the same): it does not get chains with different values.
+    if ((ps || ds) && c0.id >= KABC_COST_USER) {
+        const CostPlugin* pl = find_plugin(c0.id);
+        if (pl && !pl->rtc) {
+            set_error("kabc_ais_create_batch_costs: cost id %d is a plugin .so built by hipcc, whose kernels "
+                      "read one cost for every chain; chains with different params / data need its hipRTC "
+                      "form (kabc_compile_cost_plugin), or one handle per cost", c0.id);
+            return KABC_ERR_UNSUPPORTED;
+        }
+    }
+    return ais_create_common(ctx, &m, nparticles, 0, 1, seeds[0], nullptr, nullptr, nullptr, out, nchains, seeds,
+                             costs, ps, ds);
 }
 
 kabc_status_t kabc_ais_create_sharded(kabc_ctx_t* ctx, const kabc_model_t* model, int64_t n_total,
@@ -802,9 +888,26 @@ static kabc_status_t ais_init_enqueue(kabc_ais_t* h, int32_t retry_sampling) {
     return KABC_OK;
 }
 
-static kabc_status_t ais_init_failed() {
+// `h`: a handle whose init failed; a batch handle's message names the lowest chain that went past its
+// budget ("chain 3: Prior leads ...")
+static kabc_status_t ais_init_failed(kabc_ais_t* h = nullptr, int32_t retry_sampling = 0) {
     // src/KissABC.jl:58-59
-    set_error("Prior leads to ∞ costs too often, tune the prior or increase `retry_sampling`.");
+    static const char* const msg = "Prior leads to ∞ costs too often, tune the prior or increase `retry_sampling`.";
+    if (h && h->d_chain_retries) {
+        const unsigned long long budget = (unsigned long long)retry_sampling *
+                                          (unsigned long long)(h->rows_owned[0] + h->rows_owned[1]);
+        std::vector<unsigned long long> used((size_t)h->nchains);
+        KABC_HIP_CHECK(hipMemcpyAsync(used.data(), h->d_chain_retries, sizeof(unsigned long long) * used.size(),
+                                      hipMemcpyDeviceToHost, h->ctx->stream));
+        KABC_HIP_CHECK(hipStreamSynchronize(h->ctx->stream));
+        for (int32_t c = 0; c < h->nchains; ++c) {
+            if (used[(size_t)c] > budget) {
+                set_error("chain %d: %s", c, msg);
+                return KABC_ERR_RETRY_EXHAUSTED;
+            }
+        }
+    }
+    set_error("%s", msg);
     return KABC_ERR_RETRY_EXHAUSTED;
 }
 
@@ -858,7 +961,7 @@ kabc_status_t kabc_ais_init(kabc_ais_t* h, int32_t retry_sampling) {
         }
         failed = v[0];
     }
-    if (failed) return ais_init_failed();
+    if (failed) return ais_init_failed(h, retry_sampling);
     ais_mark_initialised(h);
     return KABC_OK;
 }
