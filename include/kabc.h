@@ -175,6 +175,11 @@ kabc_status_t kabc_ctx_synchronize(kabc_ctx_t* ctx);
  *                     same run with generations = k; a run that starts after the request still
  *                     completes its initial draw, k = 0); one after another, the runs after the
  *                     current one are not started (see each entry point).
+ *   kabc_pfilter_run_batch
+ *                     a run of the launch grid that has started stops at an iteration boundary after
+ *                     k >= 1 iterations, bit-identical to the same run with max_iters = k - 1; a run
+ *                     whose workgroup starts after the request is never started (result untouched);
+ *                     one after another, the runs after the current one are not started.
  * A call that is never cancelled is unchanged.  Sharded and distributed calls (kabc_ais_create_dist
  * handles, kabc_ais_advance_multi, kabc_smc_run_dist*) do not poll -- a cancel seen on one rank
  * would leave the others in a collective -- and neither do kabc_ais_init, kabc_abcde_run and
@@ -186,7 +191,10 @@ kabc_status_t kabc_ctx_synchronize(kabc_ctx_t* ctx);
  * smc kernel every 16th iteration and the ABCDE launch grid at every generation boundary (the read is
  * issued one generation ahead and decided on at the next boundary; a read of host memory stalls the
  * wave that waits for it:
- * tools/host_word_latency_probe.hip).  With the built-in costs that is well within 0.1 s; an expensive
+ * tools/host_word_latency_probe.hip).  The pfilter launch grid looks at every iteration boundary, never
+ * inside the rejection phase: a pfilter iteration lengthens as the run converges (about 1 / eff proposals
+ * per replaced particle, down to eff_tol), so its response time is one iteration of the slowest resident
+ * run; workgroups not yet started end at once.  With the built-in costs that is well within 0.1 s; an expensive
  * cost (a simulator, a user cost) at small ensembles stretches it by the same factor as a generation
  * or an iteration. */
 kabc_status_t kabc_ctx_cancel(kabc_ctx_t* ctx);
@@ -263,7 +271,7 @@ kabc_status_t kabc_compile_cost_plugin(const char* src, const int32_t* dims, int
  * 0), 3 smc init, 4 smc persistent loop, 5 / 6 ABCDE init / generation, 7 pfilter attempt,
  * 10 the one-workgroup smc driver, 13 the one-workgroup AIS driver of small ensembles (variant as
  * family 0; prior classes 0 and 2), 14 the one-workgroup ABCDE driver of kabc_abcde_run_batch
- * (variant 0). */
+ * (variant 0), 15 the one-workgroup pfilter driver of kabc_pfilter_run_batch (variant 0). */
 kabc_status_t kabc_plugin_precompile(int32_t cost_id, int32_t family, int32_t D, int32_t variant);
 
 /* ---- user prior families ------------------------------------------------------
@@ -824,6 +832,38 @@ int64_t kabc_pfilter_nparticles(int64_t N, double q, int32_t D);
 kabc_status_t kabc_pfilter_run(kabc_ctx_t* ctx, const kabc_prior_t* prior, int32_t D,
                                const kabc_cost_t* cost, const kabc_pfilter_opts_t* opts,
                                kabc_pfilter_result_t* result);
+
+/* nruns INDEPENDENT pfilter runs -- one per seed, or one per dataset -- in one call: run r is
+ * kabc_pfilter_run(prior, costs[r]) with opts->seed replaced by seeds[r] (every other option is shared),
+ * and results[r] is filled as that call fills it, bit for bit.  A failed run's theta / cost arrays may
+ * be overwritten (its other fields are not set).  costs[r] all have the same id, nparams and ndata
+ * (their params / data may differ); 1 <= nruns <= 65535; the options are checked as kabc_pfilter_run
+ * checks them.  Shapes the one-workgroup kernel takes (kabc_pfilter_nparticles(N, q, D) <= 256,
+ * D <= KABC_MAX_DIM, a built-in DeviceCost or a hipRTC user cost, no user prior family, verbose = 0,
+ * KABC_PF_BATCH not 0) run as ONE launch: workgroup r runs run r from its initial draw to its push_p'ed
+ * output, the rejection loops parallel over attempts (KABC_PF_BATCH_SPREAD=0: one lane per particle; the
+ * same bits).  Other shapes (more than 256 particles, D > KABC_MAX_DIM, cost plugins built by hipcc,
+ * verbose) run one after another through kabc_pfilter_run.
+ * status[r] is run r's own verdict: KABC_OK, KABC_ERR_RETRY_EXHAUSTED (its initial draw never produced
+ * a finite (cost, logpdf) pair, or a particle was not replaced after 2^24 proposals), KABC_ERR_NAN_COST
+ * or KABC_ERR_CANCELLED; the other runs are left alone.  The return value is KABC_OK when every run is,
+ * else the status of the lowest failing run, whose index kabc_last_error() names ("run 3: pfilter: the
+ * prior never produced ...").
+ * kabc_ctx_cancel: KABC_ERR_CANCELLED; in the launch grid each run is finished (KABC_OK), stopped at an
+ * iteration boundary after k >= 1 iterations (KABC_ERR_CANCELLED, result filled: that of the same run
+ * with max_iters = k - 1) or never started (KABC_ERR_CANCELLED, result untouched); one after another,
+ * the look falls between two runs: the runs after it are not started (KABC_ERR_CANCELLED, result untouched).
+ * Results are copied with one copy per array when results[r + 1]'s arrays follow results[r]'s (theta
+ * by N_eff*D doubles, cost by N_eff), else through one page-locked block. */
+kabc_status_t kabc_pfilter_run_batch(kabc_ctx_t* ctx, const kabc_prior_t* prior, int32_t D,
+                                     const kabc_cost_t* costs, int64_t nruns, const uint64_t* seeds,
+                                     const kabc_pfilter_opts_t* opts, kabc_pfilter_result_t* results,
+                                     kabc_status_t* status);
+
+/* How the calling thread's last kabc_pfilter_run_batch was driven: out[0] the course (1 one launch grid,
+ * 0 one run after another), [1] kernel launches (of the one-workgroup kernel; one after another: the
+ * runs started), [2] runs per launch, [3] 0 (reserved). */
+void kabc_pfilter_batch_stats(int64_t out[4]);
 
 #ifdef __cplusplus
 }

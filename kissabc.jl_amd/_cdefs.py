@@ -206,6 +206,10 @@ PROTOTYPES = {
                                        C.POINTER(C.c_uint64), C.POINTER(AbcdeOpts), C.POINTER(AbcdeResult),
                                        C.POINTER(C.c_int)]),
     "kabc_abcde_batch_stats": (None, [C.POINTER(C.c_int64)]),
+    "kabc_pfilter_run_batch": (C.c_int, [VP, C.POINTER(Prior), C.c_int32, C.POINTER(Cost), C.c_int64,
+                                         C.POINTER(C.c_uint64), C.POINTER(PfilterOpts), C.POINTER(PfilterResult),
+                                         C.POINTER(C.c_int)]),
+    "kabc_pfilter_batch_stats": (None, [C.POINTER(C.c_int64)]),
 }
 
 

@@ -967,3 +967,115 @@ def pfilter(prior, cost, N, *, q=0.7, eff_tol=0.1, epstol=-math.inf, max_iters=m
             "cost_evals": r.cost_evals, "nparticles": n_eff}
     return PfilterResult(theta if return_array else _bundle(theta, scalar),
                          Cst if return_array else Particles(Cst), info)
+
+
+class PfilterBatchResult(list):
+    """pfilter_batch's result: one PfilterResult per run (a list), and `.info` about the whole call."""
+
+    info = None
+
+
+def pfilter_batch(prior, cost, N, nruns=None, *, seeds=None, seed=0, q=0.7, eff_tol=0.1, epstol=-math.inf,
+                  max_iters=math.inf, proposal_width=0.75, parallel=False, verbose=False, ctx=None,
+                  return_array=False):
+    """Many independent pfilter runs in one call (kabc_pfilter_run_batch): run r is
+    pfilter(prior, cost_r, N, seed=seeds[r], <the same keywords>), bit for bit.
+
+    `cost` is one DeviceCost (the runs differ by their seeds only; `nruns` is required) or a sequence
+    of DeviceCosts, one per dataset, with the same cost id and the same params and data lengths
+    (`nruns` defaults to its length).  `seeds` defaults to chain_seeds(seed, nruns).  With at most 256
+    particles (after pfilter's own raising of N) and length(prior) <= KABC_MAX_DIM the runs are the
+    workgroups of ONE launch (info["course"] == "grid"); other shapes run one after another
+    ("sequential").  `verbose` is refused; `parallel` is accepted and ignored, as pfilter does.
+
+    Returns a list of PfilterResult, entry r as pfilter returns it (its P / C are views into one
+    [nruns][N_eff][D] / [nruns][N_eff] block); the list's `.info` holds the course, the kernel launches,
+    the runs per launch, the wall time, the runs' statuses and the particle count.  A failed run raises
+    KabcError("run r: ...") whose `.results` is the list with None at the failed runs; Context.cancel() /
+    Ctrl-C raise Cancelled whose `.result` is the list of the runs as they ended -- finished, stopped
+    after k >= 1 iterations (that of the same run with max_iters = k - 1), or None for runs never
+    started."""
+    fac = as_factored(prior)
+    scalar = isinstance(prior, UnivariateDistribution)
+    if isinstance(cost, DeviceCost):
+        if nruns is None:
+            raise ValueError("pfilter_batch: nruns is required with a single DeviceCost")
+        nruns = int(nruns)
+        cost_list = [cost] * max(nruns, 0)
+    else:
+        cost_list = list(cost)
+        if not all(isinstance(c, DeviceCost) for c in cost_list):
+            raise TypeError("`cost` must be a DeviceCost or a sequence of DeviceCosts on the MI355X path")
+        nruns = len(cost_list) if nruns is None else int(nruns)
+        if len(cost_list) != nruns:
+            raise ValueError(f"pfilter_batch: {len(cost_list)} costs for nruns = {nruns}")
+    if nruns < 1:
+        raise ValueError("pfilter_batch: nruns must be >= 1")
+    c0 = cost_list[0]
+    for i, c in enumerate(cost_list):
+        if c.id != c0.id or c.params.size != c0.params.size or c.data.size != c0.data.size:
+            raise ValueError(f"pfilter_batch: cost {i} differs from cost 0 in its id or its params / data lengths")
+    seeds = chain_seeds(seed, nruns) if seeds is None else [int(x) for x in seeds]
+    if len(seeds) != nruns:
+        raise ValueError(f"pfilter_batch: len(seeds) = {len(seeds)} != nruns = {nruns}")
+    if verbose:
+        raise ValueError("pfilter_batch: verbose=True is not supported")
+    if not (0.0 < float(q) <= 1.0) or int(N) < 1:   # (the library's own check, before it runs anything)
+        raise ValueError("pfilter needs 0 < q <= 1 and N >= 1")
+    lib = _lib.load()
+    ctx = ctx or _lib.default_context()
+    o = cd.PfilterOpts()
+    lib.kabc_pfilter_default_opts(C.byref(o))
+    o.nparticles, o.q, o.eff_tol, o.epstol = int(N), float(q), float(eff_tol), float(epstol)
+    o.proposal_width, o.verbose = float(proposal_width), 0
+    o.max_iters = -1 if math.isinf(max_iters) else int(math.floor(max_iters))
+    R, D = nruns, len(fac)
+    n_eff = lib.kabc_pfilter_nparticles(int(N), float(q), D)
+    t_host0 = time.perf_counter()
+    theta = _lib.result_empty((R, n_eff, D))
+    Cst = _lib.result_empty((R, n_eff))
+    # the R result records, written through a uint64 view (every field is 8 bytes wide): run r's arrays
+    # follow run r - 1's, so that the library copies each array once
+    res = (cd.PfilterResult * R)()
+    w = np.frombuffer(res, dtype=np.uint64).reshape(R, C.sizeof(cd.PfilterResult) // 8)
+    rr = np.arange(R, dtype=np.uint64)
+    col = lambda f: getattr(cd.PfilterResult, f).offset // 8   # noqa: E731
+    w[:, col("theta")] = np.uint64(theta.ctypes.data) + rr * np.uint64(n_eff * D * 8)
+    w[:, col("cost")] = np.uint64(Cst.ctypes.data) + rr * np.uint64(n_eff * 8)
+    w[:, col("iterations")] = np.uint64(2**64 - 1)   # (-1: a run that never started)
+    cc_of = {}   # (one record per distinct DeviceCost: a repeated one points at the same params)
+    for c in cost_list:
+        if id(c) not in cc_of:
+            cc_of[id(c)] = c.to_c()
+    ccs = (cd.Cost * R)(*[cc_of[id(c)] for c in cost_list])
+    sd = (C.c_uint64 * R)(*seeds)
+    st = (C.c_int * R)()
+    with ctx.interruptible():   # (a Cancelled raised inside becomes KeyboardInterrupt after Ctrl-C)
+        status = lib.kabc_pfilter_run_batch(ctx.handle, fac.to_c(), D, ccs, R, sd, C.byref(o), res, st)
+        t_host1 = time.perf_counter()
+        bs = (C.c_int64 * 4)()
+        lib.kabc_pfilter_batch_stats(bs)
+
+        def entry(r):
+            x = res[r]
+            if x.iterations < 0:
+                return None
+            info = {"eps": x.eps, "eff": x.eff, "iterations": x.iterations, "nreps": x.nreps,
+                    "cost_evals": x.cost_evals, "nparticles": n_eff}
+            return PfilterResult(theta[r] if return_array else _bundle(theta[r], scalar),
+                                 Cst[r] if return_array else Particles(Cst[r]), info)
+
+        out = PfilterBatchResult(entry(r) if st[r] in (0, cd.KABC_ERR_CANCELLED) else None for r in range(R))
+        out.info = {"course": "grid" if bs[0] == 1 else "sequential", "launches": int(bs[1]),
+                    "runs_per_launch": int(bs[2]), "nruns": R, "wall_ms": (t_host1 - t_host0) * 1e3,
+                    "status": [int(x) for x in st], "nparticles": n_eff}
+        if status != 0:
+            try:
+                _lib.check(status)
+            except _lib.Cancelled as e:
+                e.result = out
+                raise
+            except _lib.KabcError as e:
+                e.results = out
+                raise
+        return out

@@ -1,14 +1,18 @@
 // capi_pfilter.hip -- kabc_pfilter_run: pfilter(prior, cost, N; ...) of src/smc.jl:275-340, driven from
 // the host: one iteration = the select kernel (shared with smc, capi_smc.hip) + the replacement of every
 // bad particle by a rejection loop.
+// kabc_pfilter_run_batch: many independent runs, one workgroup each, as one launch grid
+// (pfilter_small_kernel.hpp), or one after another through kabc_pfilter_run.
 #include <cmath>
 #include <cstdlib>
+#include <string>
 #include <vector>
 
 #define KABC_PFILTER_UNIT 1
 #include "host_common.hpp"
 #include "plugin_registry.hpp"
 #include "pfilter_kernels.hpp"
+#include "pfilter_small_kernel.hpp"
 
 namespace kabc {
 __global__ void smc_finalize_kernel(const SmcFinalArgs A);  // (capi_smc.hip)
@@ -67,6 +71,15 @@ void pf_l_small(const PfSmallArgs& a, hipStream_t s) {
 template <int... Ds>
 PfSmallLaunchFn pf_pick_small(int D, std::integer_sequence<int, Ds...>) {
     static const PfSmallLaunchFn f[] = {&pf_l_small<Ds + 1>...};
+    return f[D - 1];
+}
+template <int D>
+void pf_l_batch(const PfBatchArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL((pf_batch_kernel<D>), pf_batch_geom(a), dim3(pf_batch_block(a.N)), 0, s, a);
+}
+template <int... Ds>
+PfBatchLaunchFn pf_pick_batch(int D, std::integer_sequence<int, Ds...>) {
+    static const PfBatchLaunchFn f[] = {&pf_l_batch<Ds + 1>...};
     return f[D - 1];
 }
 }  // namespace
@@ -443,3 +456,297 @@ extern "C" kabc_status_t kabc_pfilter_run(kabc_ctx_t* ctx, const kabc_prior_t* p
                                           kabc_pfilter_result_t* res) {
     return pfilter_run_impl(ctx, prior, D, cost, o, res, false);
 }
+
+// ---- kabc_pfilter_run_batch ---------------------------------------------------------------------
+namespace kabc {
+namespace {
+
+// how the calling thread's last kabc_pfilter_run_batch was driven (kabc_pfilter_batch_stats)
+thread_local int64_t tl_pf_batch_stats[4] = {0, 0, 0, 0};
+
+// kabc_pfilter_run's own messages
+const char* const kPfExhausted = "pfilter: the prior never produced a finite (cost, logpdf) pair for some particle";
+const char* const kPfUnreplaced = "pfilter: a particle was not replaced after 2^24 proposals";
+const char* const kPfNanCost = "pfilter: quantile of the costs is undefined (NaN or empty)";
+
+bool env_is_zero(const char* name) {
+    const char* e = std::getenv(name);
+    return e && e[0] == '0';
+}
+
+// The launch grid: workgroup r runs run r from its initial draw to its output.  *grid = false (and
+// KABC_OK) when there is no kernel for the pair: the caller runs the batch one run after another.
+// A non-OK return: the batch as a whole failed (message set).
+kabc_status_t pf_run_grid(kabc_ctx_t* ctx, const kabc_prior_t* prior, int32_t D, const kabc_cost_t* costs,
+                          int64_t nruns, const uint64_t* seeds, const kabc_pfilter_opts_t* o,
+                          kabc_pfilter_result_t* results, kabc_status_t* status, bool* grid) {
+    *grid = false;
+    const kabc_cost_t* cost = &costs[0];
+    const int64_t N = kabc_pfilter_nparticles(o->nparticles, o->q, D), NR = nruns;
+    // the checks of kabc_pfilter_run that need the prior and the cost
+    std::vector<kabc_prior_t> resolved((size_t)D);  // MvNormal components: device block, D
+    if (kabc_status_t st = resolve_priors(ctx, prior, D, resolved.data())) return st;
+    prior = resolved.data();
+    PfBatchArgs A;
+    std::memset(&A, 0, sizeof A);
+    if (!prepare_priors(prior, D, A.prior)) {
+        set_error("invalid prior parameters");
+        return KABC_ERR_INVALID_ARG;
+    }
+    if (!cost_dim_ok_rt(cost->id, D)) {
+        set_error("DeviceCost id %d does not accept D = %d", cost->id, D);
+        return KABC_ERR_UNSUPPORTED;
+    }
+    // (run-time compiled kernels are loaded on the CURRENT device)
+    KABC_HIP_CHECK(hipSetDevice(ctx->device));
+    // a user prior family is known to its model unit only: those runs go one after another
+    ModelUnit* unit = nullptr;
+    if (kabc_status_t st = model_unit_for(prior, D, cost->id, &unit, false)) return st;
+    if (unit) return KABC_OK;
+    // the one-workgroup kernel of (cost, D): prebuilt for the built-in costs, compiled into the hipRTC
+    // user cost's unit otherwise; none for a cost plugin built by hipcc
+    PfBatchLaunch f;
+    if (cost->id < KABC_COST_USER) {
+        f = PfBatchLaunch(pf_pick_batch(D, std::make_integer_sequence<int, KABC_MAX_DIM>{}));
+    } else {
+        const PluginKernel k = plugin_kernel(find_plugin(cost->id), kPfPfilterBatch, D, 0);
+        if (k.mod) f = PfBatchLaunch(k.mod, &pf_batch_geom, pf_batch_block(N));
+    }
+    if (!f) return KABC_OK;
+    *grid = true;
+    tl_pf_batch_stats[0] = 1;
+    tl_pf_batch_stats[2] = NR;
+    std::memcpy(A.raw, prior, sizeof(kabc_prior_t) * D);
+    hipStream_t s = ctx->stream;
+    DevBufs bufs;
+    bufs.ctx = ctx;
+    double *d_out = nullptr, *d_cout = nullptr, *d_params = nullptr, *d_data = nullptr;
+    PfBatchRec* d_rec = nullptr;
+    uint64_t* d_seeds = nullptr;
+    KABC_HIP_CHECK(bufs.alloc(&d_out, (size_t)(NR * N * D)));
+    KABC_HIP_CHECK(bufs.alloc(&d_cout, (size_t)(NR * N)));
+    KABC_HIP_CHECK(bufs.alloc(&d_rec, (size_t)NR));
+    KABC_HIP_CHECK(bufs.alloc(&d_seeds, (size_t)NR));
+    KABC_HIP_CHECK(hipMemcpyAsync(d_seeds, seeds, sizeof(uint64_t) * NR, hipMemcpyHostToDevice, s));
+    // the runs' params / data side by side, unless every run points at the same ones
+    bool same_p = true, same_d = true;
+    for (int64_t r = 1; r < NR; ++r) {
+        same_p = same_p && costs[r].params == cost->params;
+        same_d = same_d && costs[r].data == cost->data;
+    }
+    std::vector<double> h_params, h_data;  // (staging; alive until the copies ran)
+    if (cost->nparams > 0) {
+        const int64_t n = same_p ? cost->nparams : cost->nparams * NR;
+        if (!same_p) {
+            h_params.resize((size_t)n);
+            for (int64_t r = 0; r < NR; ++r)
+                std::memcpy(h_params.data() + r * cost->nparams, costs[r].params, sizeof(double) * cost->nparams);
+        }
+        KABC_HIP_CHECK(bufs.alloc(&d_params, (size_t)n));
+        KABC_HIP_CHECK(hipMemcpyAsync(d_params, same_p ? cost->params : h_params.data(), sizeof(double) * n,
+                                      hipMemcpyHostToDevice, s));
+        A.params_stride = same_p ? 0 : cost->nparams;
+    }
+    if (cost->ndata > 0) {
+        const int64_t n = same_d ? cost->ndata : cost->ndata * NR;
+        if (!same_d) {
+            h_data.resize((size_t)n);
+            for (int64_t r = 0; r < NR; ++r)
+                std::memcpy(h_data.data() + r * cost->ndata, costs[r].data, sizeof(double) * cost->ndata);
+        }
+        KABC_HIP_CHECK(bufs.alloc(&d_data, (size_t)n));
+        KABC_HIP_CHECK(hipMemcpyAsync(d_data, same_d ? cost->data : h_data.data(), sizeof(double) * n,
+                                      hipMemcpyHostToDevice, s));
+        A.data_stride = same_d ? 0 : cost->ndata;
+    }
+    A.out = d_out;
+    A.cout = d_cout;
+    A.rec = d_rec;
+    A.seeds = d_seeds;
+    A.cost_params = d_params;
+    A.cost_data = d_data;
+    A.cost_ndata = cost->ndata;
+    A.max_iters = o->max_iters;
+    A.cancel = ctx->cancel_d;
+    A.N = (int32_t)N;
+    A.nruns = (int32_t)NR;
+    A.cost_id = cost->id;
+    A.spread = env_is_zero("KABC_PF_BATCH_SPREAD") ? 0 : 1;
+    A.q = o->q;
+    A.eff_tol = o->eff_tol;
+    A.epstol = o->epstol;
+    A.proposal_width = o->proposal_width;
+    f(A, s);
+    KABC_HIP_CHECK(hipGetLastError());
+    tl_pf_batch_stats[1] = 1;
+    // ONE copy per array: straight into the caller's arrays when they follow each other run after run,
+    // else into one page-locked block and scattered from there
+    std::vector<PfBatchRec> hrec((size_t)NR);
+    KABC_HIP_CHECK(hipMemcpyAsync(hrec.data(), d_rec, sizeof(PfBatchRec) * NR, hipMemcpyDeviceToHost, s));
+    struct Arr {
+        const double* dev;
+        size_t run;  // doubles of one run
+        bool present, direct;
+        size_t off;  // in the page-locked block (doubles)
+    } arr[2] = {{d_out, (size_t)(N * D), false, true, 0}, {d_cout, (size_t)N, false, true, 0}};
+    auto host_of = [&](int j, int64_t r) -> double* { return j == 0 ? results[r].theta : results[r].cost; };
+    size_t staged = 0;
+    for (int j = 0; j < 2; ++j) {
+        Arr& a = arr[j];
+        for (int64_t r = 0; r < NR; ++r) {
+            a.present = a.present || host_of(j, r) != nullptr;
+            a.direct = a.direct && host_of(j, r) && host_of(j, r) == host_of(j, 0) + r * a.run;
+        }
+    }
+    // a run that was never started leaves its result untouched: with a cancel in sight the arrays go
+    // through the page-locked block, whatever their layout (decided after the records are in)
+    KABC_HIP_CHECK(hipStreamSynchronize(s));
+    bool unstarted = false;
+    for (int64_t r = 0; r < NR; ++r) unstarted = unstarted || (hrec[(size_t)r].cancelled && hrec[(size_t)r].iters == 0);
+    for (int j = 0; j < 2; ++j) {
+        Arr& a = arr[j];
+        if (unstarted) a.direct = false;
+        if (a.present && !a.direct) {
+            a.off = staged;
+            staged += a.run * NR;
+        }
+    }
+    double* pin = nullptr;
+    if (staged) KABC_HIP_CHECK(hipHostMalloc((void**)&pin, sizeof(double) * staged, hipHostMallocDefault));
+    struct PinFree {
+        double* p;
+        ~PinFree() {
+            if (p) (void)hipHostFree(p);
+        }
+    } pin_free{pin};
+    for (int j = 0; j < 2; ++j) {
+        const Arr& a = arr[j];
+        if (!a.present) continue;
+        double* dst = a.direct ? host_of(j, 0) : pin + a.off;
+        KABC_HIP_CHECK(hipMemcpyAsync(dst, a.dev, sizeof(double) * a.run * NR, hipMemcpyDeviceToHost, s));
+    }
+    KABC_HIP_CHECK(hipStreamSynchronize(s));
+    bool cancelled = false;
+    for (int64_t r = 0; r < NR; ++r) {
+        const PfBatchRec& h = hrec[(size_t)r];
+        status[r] = h.error == 2 ? KABC_ERR_NAN_COST
+                    : h.error    ? KABC_ERR_RETRY_EXHAUSTED
+                    : h.cancelled ? KABC_ERR_CANCELLED
+                                  : KABC_OK;
+        cancelled = cancelled || status[r] == KABC_ERR_CANCELLED;
+        if (h.error || (h.cancelled && h.iters == 0)) continue;
+        for (int j = 0; j < 2; ++j) {
+            const Arr& a = arr[j];
+            if (a.present && !a.direct && host_of(j, r))
+                std::memcpy(host_of(j, r), pin + a.off + (size_t)r * a.run, sizeof(double) * a.run);
+        }
+        kabc_pfilter_result_t& rr = results[r];
+        rr.eps = h.eps;
+        rr.eff = h.eff;
+        rr.iterations = h.iters;
+        rr.nreps = h.total_reps;
+        rr.cost_evals = h.cost_evals;
+    }
+    if (cancelled) (void)cancel_take(ctx);
+    // (the message of a failing run: by its record)
+    for (int64_t r = 0; r < NR; ++r) {
+        if (status[r] == KABC_OK) continue;
+        const int e = hrec[(size_t)r].error;
+        set_error("run %lld: %s", (long long)r, e == 1 ? kPfExhausted : e == 9 ? kPfUnreplaced : e == 2 ? kPfNanCost : "cancelled");
+        break;
+    }
+    return KABC_OK;
+}
+
+// the course of shapes the one-workgroup kernel cannot take: the runs one after another, with a look
+// at the cancel word between two runs (kabc_pfilter_run itself does not poll)
+void pf_batch_sequential(kabc_ctx_t* ctx, const kabc_prior_t* prior, int32_t D, const kabc_cost_t* costs,
+                         int64_t nruns, const uint64_t* seeds, const kabc_pfilter_opts_t* o,
+                         kabc_pfilter_result_t* results, kabc_status_t* status, std::string* first_msg) {
+    for (int64_t r = 0; r < nruns; ++r) status[r] = KABC_ERR_CANCELLED;  // (runs a cancel leaves unstarted)
+    for (int64_t r = 0; r < nruns; ++r) {
+        if (cancel_take(ctx)) {
+            if (first_msg->empty()) *first_msg = "cancelled";
+            break;
+        }
+        kabc_pfilter_opts_t oq = *o;
+        oq.seed = seeds[r];
+        status[r] = kabc_pfilter_run(ctx, prior, D, &costs[r], &oq, &results[r]);
+        tl_pf_batch_stats[1] = r + 1;
+        if (status[r] != KABC_OK && first_msg->empty()) {
+            const char* m = get_error();
+            *first_msg = m && *m ? m : "failed";
+        }
+    }
+}
+
+kabc_status_t pf_batch_impl(kabc_ctx_t* ctx, const kabc_prior_t* prior, int32_t D, const kabc_cost_t* costs,
+                            int64_t nruns, const uint64_t* seeds, const kabc_pfilter_opts_t* o,
+                            kabc_pfilter_result_t* results, kabc_status_t* status) {
+    std::memset(tl_pf_batch_stats, 0, sizeof tl_pf_batch_stats);
+    if (!ctx || !prior || !costs || !seeds || !o || !results || !status) {
+        set_error("kabc_pfilter_run_batch: NULL argument");
+        return KABC_ERR_INVALID_ARG;
+    }
+    if (nruns < 1 || nruns > 65535) {
+        set_error("kabc_pfilter_run_batch: nruns = %lld is outside 1..65535", (long long)nruns);
+        return KABC_ERR_INVALID_ARG;
+    }
+    for (int64_t r = 1; r < nruns; ++r)
+        if (costs[r].id != costs[0].id || costs[r].nparams != costs[0].nparams || costs[r].ndata != costs[0].ndata) {
+            set_error("kabc_pfilter_run_batch: costs[%lld] differs from costs[0] in its id or its params / data lengths",
+                      (long long)r);
+            return KABC_ERR_INVALID_ARG;
+        }
+    // kabc_pfilter_run's own checks of the options, before anything runs
+    if (D < 1 || D > KABC_MAX_DIM_DYN) {
+        set_error("length(prior) = %d is outside the device path's range 1..%d", D, KABC_MAX_DIM_DYN);
+        return KABC_ERR_UNSUPPORTED;
+    }
+    if (!(o->q > 0 && o->q <= 1) || o->nparticles < 1) {
+        set_error("pfilter needs 0 < q <= 1 and N >= 1");
+        return KABC_ERR_INVALID_ARG;
+    }
+    bool grid = false;
+    if (!o->verbose && !env_is_zero("KABC_PF_BATCH") && D <= KABC_MAX_DIM &&
+        kabc_pfilter_nparticles(o->nparticles, o->q, D) <= (int64_t)kPfBatchBlock) {
+        const kabc_status_t st = pf_run_grid(ctx, prior, D, costs, nruns, seeds, o, results, status, &grid);
+        if (st) {  // (the batch as a whole failed: every run shares the verdict)
+            for (int64_t r = 0; r < nruns; ++r) status[r] = st;
+            return st;
+        }
+    }
+    if (!grid) {
+        std::string first_msg;  // (the first failing run's own message)
+        tl_pf_batch_stats[0] = 0;
+        tl_pf_batch_stats[2] = 1;
+        pf_batch_sequential(ctx, prior, D, costs, nruns, seeds, o, results, status, &first_msg);
+        for (int64_t r = 0; r < nruns; ++r) {
+            if (status[r] == KABC_OK) continue;
+            set_error("run %lld: %s", (long long)r, first_msg.c_str());
+            break;
+        }
+    }
+    // the lowest failing run names the verdict ("run 3: <its message>")
+    for (int64_t r = 0; r < nruns; ++r)
+        if (status[r] != KABC_OK) return status[r];
+    return KABC_OK;
+}
+
+}  // namespace
+}  // namespace kabc
+
+extern "C" {
+
+kabc_status_t kabc_pfilter_run_batch(kabc_ctx_t* ctx, const kabc_prior_t* prior, int32_t D,
+                                     const kabc_cost_t* costs, int64_t nruns, const uint64_t* seeds,
+                                     const kabc_pfilter_opts_t* opts, kabc_pfilter_result_t* results,
+                                     kabc_status_t* status) {
+    return pf_batch_impl(ctx, prior, D, costs, nruns, seeds, opts, results, status);
+}
+
+void kabc_pfilter_batch_stats(int64_t out[4]) {
+    if (out) std::memcpy(out, tl_pf_batch_stats, sizeof tl_pf_batch_stats);
+}
+
+}  // extern "C"

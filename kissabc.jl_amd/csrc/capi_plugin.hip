@@ -992,6 +992,11 @@ static PluginKernel rtc_family_kernel(RtcCache* R, const std::string& head, int 
             k.mod = rtc_kernel(R, head, "abcde_small_kernel.hpp", false, {n}, n);
             break;
         }
+        case kPfPfilterBatch: {
+            const std::string n = "kabc::pf_batch_kernel<" + d + ">";
+            k.mod = rtc_kernel(R, head, "pfilter_small_kernel.hpp", false, {n}, n);
+            break;
+        }
         case kPfAisDyn: {
             // variants: 0 / 2 / 3 the half-generation kernel with teams of 16 / 8 / 64 lanes per walker, 1 init
             const std::vector<std::string> n = {"kabc::ais_dyn_half_kernel<" + udyn + ", 16>",
@@ -1361,7 +1366,7 @@ extern "C" kabc_status_t kabc_plugin_precompile(int32_t cost_id, int32_t family,
         return KABC_ERR_INVALID_ARG;
     }
     if (family < kPfAis || (family > kPfAttempt && family != kPfSmcSmall && family != kPfAisDyn && family != kPfSmcDyn &&
-                            family != kPfAisSmall && family != kPfAbcdeSmall)) {
+                            family != kPfAisSmall && family != kPfAbcdeSmall && family != kPfPfilterBatch)) {
         set_error("kabc_plugin_precompile: unknown kernel family %d", family);
         return KABC_ERR_INVALID_ARG;
     }

@@ -41,7 +41,9 @@ enum PluginFamily {
     // (hipRTC units) the one-workgroup AIS driver of small ensembles (ais_small_kernel.hpp); variant = AIS pcx
     kPfAisSmall,
     // (hipRTC units) the one-workgroup ABCDE driver of kabc_abcde_run_batch (abcde_small_kernel.hpp)
-    kPfAbcdeSmall
+    kPfAbcdeSmall,
+    // (hipRTC user costs) the one-workgroup pfilter driver of kabc_pfilter_run_batch (pfilter_small_kernel.hpp)
+    kPfPfilterBatch
 };
 struct PluginKernel {
     void* host = nullptr;
