@@ -180,6 +180,9 @@ kabc_status_t kabc_ctx_synchronize(kabc_ctx_t* ctx);
  *                     k >= 1 iterations, bit-identical to the same run with max_iters = k - 1; a run
  *                     whose workgroup starts after the request is never started (result untouched);
  *                     one after another, the runs after the current one are not started.
+ *   kabc_cost_eval, kabc_prior_predictive
+ *                     a request pending at entry: nothing is launched; during the call: seen between
+ *                     two launches of KABC_EVAL_ROWS rows, the output arrays are then unspecified.
  * A call that is never cancelled is unchanged.  Sharded and distributed calls (kabc_ais_create_dist
  * handles, kabc_ais_advance_multi, kabc_smc_run_dist*) do not poll -- a cancel seen on one rank
  * would leave the others in a collective -- and neither do kabc_ais_init, kabc_abcde_run and
@@ -238,6 +241,49 @@ kabc_status_t kabc_factored_rand(kabc_ctx_t* ctx, const kabc_prior_t* prior, int
                                  uint64_t seed, uint32_t domain, int64_t first_walker, int64_t n,
                                  uint64_t attempt, double* out);
 
+/* ---- a DeviceCost evaluated OUTSIDE a sampler (host in, host out) -------------------
+ * In the reference a cost is a closure anybody can call: cost(θ), cost.(res.P) for a posterior
+ * predictive check, quantile(cost.(rand(prior) for _ in 1:n), 0.01) to choose the ϵ its samplers ask
+ * for (src/types.jl:42,55; src/smc.jl:94).  kabc_cost_eval is that call for n rows at once, nrep
+ * replicates each: out[i][j] = cost(theta[i]) under replicate stream j.  The rows go to the cost AS
+ * GIVEN: no prior, no push_p, no look at their values (NaN and Inf rows like any other).
+ * Streams (include/kabc_philox.h): replicate j of row i draws from kabc_cost_rng_t{seed, t = j, walker =
+ * first_row + i, KABC_DOM_EVAL_COST}, so out[i][j] depends on (seed, first_row + i, j, theta[i], cost) and
+ * on nothing else -- not on n, nrep, the launch geometry or how a caller cuts its rows into calls
+ * (first_row is what makes the pieces agree).  first_row >= 0, first_row + n <= 2^32 (the walker word has
+ * 32 bits), 1 <= D <= KABC_MAX_DIM_DYN, nrep >= 1: else KABC_ERR_INVALID_ARG; these are checked before
+ * ctx is used.  A D the cost does not accept: KABC_ERR_UNSUPPORTED.  n == 0: KABC_OK, nothing touched.
+ * Costs: every built-in DeviceCost and user costs in the hipRTC form (kabc_compile_cost_plugin; kernel
+ * family 16 of kabc_plugin_precompile, compiled at first use), also beyond KABC_MAX_DIM.  A cost plugin
+ * .so built by hipcc (kabc_register_cost_plugin) is REFUSED with KABC_ERR_UNSUPPORTED: it carries no
+ * evaluation kernel; the message names the hipRTC form.  A prepared cost needs no pre-pass here: a
+ * snippet with KABC_USER_AUX_WORDS is evaluated with rng.aux = NULL (it prepares in place), and
+ * NormalMeanStdSim's prepared words are computed by the evaluating thread itself (the same bits).
+ * Large calls are cut into launches of KABC_EVAL_ROWS rows (default 2^20; never more than 2^24
+ * evaluations or 2^25 words of rows per launch) through device buffers of the context's pool; every
+ * copy and kernel is queued on the context stream and the call waits once.  kabc_ctx_cancel: a request
+ * pending at entry returns KABC_ERR_CANCELLED before anything is launched; a request made during the
+ * call is seen between launches -- what is queued completes, out is then unspecified. */
+kabc_status_t kabc_cost_eval(kabc_ctx_t* ctx, const kabc_cost_t* cost, int32_t D, int64_t n,
+                             const double* theta /* [n][D], host */, int32_t nrep, uint64_t seed,
+                             int64_t first_row, double* out /* [n][nrep], host */);
+/* The pilot simulation cost.(rand(prior) for _ in 1:n) without θ visiting the host in between: row i
+ * is push_p(prior, rand(prior)) drawn exactly as kabc_factored_rand(seed, KABC_DOM_EVAL_DRAW,
+ * first_walker = first_row + i, attempt = 0) draws it and kabc_factored_push_p projects it;
+ * logprior_out[i] (optional) is what kabc_factored_logpdf returns for that row; out[i][j] is what
+ * kabc_cost_eval returns for it with the same seed and first_row.  The call equals those calls
+ * composed, bit for bit.  Priors: everything the Factored utilities take (user families, joint
+ * priors, MvNormal, D up to KABC_MAX_DIM_DYN).  Checks, costs, chunking and cancellation as above. */
+kabc_status_t kabc_prior_predictive(kabc_ctx_t* ctx, const kabc_prior_t* prior, int32_t D,
+                                    const kabc_cost_t* cost, int64_t n, int32_t nrep, uint64_t seed,
+                                    int64_t first_row, double* theta_out /* [n][D] */,
+                                    double* logprior_out /* [n] or NULL */, double* out /* [n][nrep] */);
+/* How the calling thread's last kabc_cost_eval / kabc_prior_predictive ran: out[0] device milliseconds of
+ * its evaluation kernels (event pairs around them; -1 unless KABC_EVAL_TIMING=1 was in the environment),
+ * [1] evaluation launches, [2] device milliseconds of the prior kernels (draw, push_p, logpdf; 0 without
+ * KABC_EVAL_TIMING=1), [3] rows per launch. */
+void kabc_eval_stats(double out[4]);
+
 /* ---- arithmetic-contract probe (verification only) ---------------------------
  * Evaluates one function of include/kabc_math.h on the device for n host inputs, so
  * that tests can compare the gfx950 code with the host build of the same header bit
@@ -271,7 +317,8 @@ kabc_status_t kabc_compile_cost_plugin(const char* src, const int32_t* dims, int
  * 0), 3 smc init, 4 smc persistent loop, 5 / 6 ABCDE init / generation, 7 pfilter attempt,
  * 10 the one-workgroup smc driver, 13 the one-workgroup AIS driver of small ensembles (variant as
  * family 0; prior classes 0 and 2), 14 the one-workgroup ABCDE driver of kabc_abcde_run_batch
- * (variant 0), 15 the one-workgroup pfilter driver of kabc_pfilter_run_batch (variant 0). */
+ * (variant 0), 15 the one-workgroup pfilter driver of kabc_pfilter_run_batch (variant 0), 16 the
+ * evaluation kernel of kabc_cost_eval / kabc_prior_predictive (variant 0; any D the cost lists). */
 kabc_status_t kabc_plugin_precompile(int32_t cost_id, int32_t family, int32_t D, int32_t variant);
 
 /* ---- user prior families ------------------------------------------------------

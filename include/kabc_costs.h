@@ -16,6 +16,7 @@
 #ifndef KABC_COSTS_H
 #define KABC_COSTS_H
 
+#include "kabc.h" /* (before kabc_cost_eval below: see there) */
 #include "kabc_philox.h"
 
 enum {
@@ -274,7 +275,14 @@ KABC_HD double kabc_cost_wiener_rms(const double* x, const double* data, int64_t
 }
 
 /* runtime dispatch (oracle, host checks).  The HIP kernels dispatch at compile
- * time on the id and call the functions above directly. */
+ * time on the id and call the functions above directly.
+ * include/kabc.h declares the ENTRY POINT of the same name (nine arguments: costs at n rows).  C++ tells
+ * the two apart by their arguments; C has no overloading, so there this dispatcher is kabc_cost_eval_id and
+ * the seven-argument call keeps its spelling through a function-like macro (kabc.h is included first, above,
+ * so that the macro never meets the entry point's prototype). */
+#ifndef __cplusplus
+#define kabc_cost_eval kabc_cost_eval_id
+#endif
 KABC_HD double kabc_cost_eval(int id, const double* x, int D, const double* params,
                               const double* data, int64_t ndata, kabc_cost_rng_t* rng) {
     switch (id) {
@@ -296,6 +304,11 @@ KABC_HD double kabc_cost_eval(int id, const double* x, int D, const double* para
             return KABC_NAN;
     }
 }
+
+#ifndef __cplusplus
+#undef kabc_cost_eval
+#define kabc_cost_eval(id, x, D, params, data, ndata, rng) kabc_cost_eval_id(id, x, D, params, data, ndata, rng)
+#endif
 
 /* minimum / exact dimension each cost accepts; 0 = any D >= 1 */
 KABC_HD int kabc_cost_dim_ok(int id, int D) {

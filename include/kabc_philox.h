@@ -55,6 +55,13 @@ typedef struct kabc_u128 {
 #define KABC_DOM_PF_INIT_COST 14u    /* src/smc.jl:287,292 */
 #define KABC_DOM_PF_MOVE 15u         /* src/smc.jl:309-319 */
 #define KABC_DOM_PF_COST 16u         /* src/smc.jl:321 */
+/* A cost evaluated outside a sampler (kabc_cost_eval / kabc_prior_predictive, include/kabc.h): replicate j
+ * of row i is the stream (seed, walker = first_row + i, t = j, KABC_DOM_EVAL_COST) -- the replicate takes the
+ * place of the transition counter, so a value depends on (seed, first_row + i, j, row, cost) and on nothing
+ * else (not on how many rows or replicates a call or a launch holds).  Row i of kabc_prior_predictive is drawn
+ * from (seed, walker = first_row + i, attempt 0, KABC_DOM_EVAL_DRAW), as kabc_factored_rand draws it. */
+#define KABC_DOM_EVAL_COST 17u       /* cost(θ): src/types.jl:42,55; src/smc.jl:94 */
+#define KABC_DOM_EVAL_DRAW 18u       /* rand(prior) of the pilot simulation */
 
 /* a ^ b ^ c: one v_bitop3_b32 on gfx950 instead of two v_xor_b32 */
 #if defined(__HIP_DEVICE_COMPILE__)

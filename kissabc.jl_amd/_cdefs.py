@@ -35,6 +35,7 @@ COST_GAUSS_DIST, COST_ROSENBROCK, COST_HIER_GAUSS_SIM, COST_NORMAL_MEANSTD_SIM, 
 # stream domains (include/kabc_philox.h)
 DOM_AIS_INIT, DOM_AIS_INIT_COST, DOM_AIS_MOVE, DOM_AIS_COST, DOM_SMC_INIT, DOM_SMC_INIT_COST, \
     DOM_SMC_MOVE, DOM_SMC_COST = range(1, 9)
+DOM_EVAL_COST, DOM_EVAL_DRAW = 17, 18   # cost.evaluate / prior_predictive: replicate = t, row = walker
 
 c_double_p = C.POINTER(C.c_double)
 
@@ -125,6 +126,12 @@ PROTOTYPES = {
                                        c_double_p]),
     "kabc_factored_rand": (C.c_int, [VP, C.POINTER(Prior), C.c_int32, C.c_uint64, C.c_uint32,
                                      C.c_int64, C.c_int64, C.c_uint64, c_double_p]),
+    "kabc_cost_eval": (C.c_int, [VP, C.POINTER(Cost), C.c_int32, C.c_int64, c_double_p, C.c_int32,
+                                 C.c_uint64, C.c_int64, c_double_p]),
+    "kabc_prior_predictive": (C.c_int, [VP, C.POINTER(Prior), C.c_int32, C.POINTER(Cost), C.c_int64,
+                                        C.c_int32, C.c_uint64, C.c_int64, c_double_p, c_double_p,
+                                        c_double_p]),
+    "kabc_eval_stats": (None, [c_double_p]),
     "kabc_register_cost_plugin": (C.c_int, [C.c_char_p, C.POINTER(C.c_int32)]),
     "kabc_plugin_precompile": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "kabc_compile_cost_plugin": (C.c_int, [C.c_char_p, C.POINTER(C.c_int32), C.c_int32, C.c_int32,

@@ -630,6 +630,47 @@ def _smc_result(lib, r, theta, Cst, alive, log, n_alloc, N, return_array, scalar
     return SmcResult(P, Cst, r.eps, info)
 
 
+PriorPredictiveResult = collections.namedtuple("PriorPredictiveResult", ["P", "C", "logprior", "info"])
+
+
+def prior_predictive(prior, cost, n, nrep=None, seed=0, first_row=0, ctx=None, return_array=False):
+    """The pilot simulation `cost.(rand(prior) for _ in 1:n)` in one call (kabc_prior_predictive,
+    include/kabc.h): n draws push_p(prior, rand(prior)), their log-prior and their costs, nrep
+    replicates each, without θ visiting the host in between -- where the reference picks the ϵ its
+    samplers ask for: `np.quantile(prior_predictive(prior, cost, 10_000).C, 0.01)`.
+
+    Returns (P, C, logprior, info): `P` bundled like smc's (one Particles per parameter, or the [n][D]
+    array with `return_array`), `C` [n] (`nrep=None`) or [n][nrep], `logprior` [n].  Row i is the draw
+    `kabc_factored_rand(seed, DOM_EVAL_DRAW, first_walker = first_row + i)`, and
+    `C == cost.evaluate(P, nrep, seed, first_row)` bit for bit."""
+    from .costs import check_eval_args
+    fac = as_factored(prior)
+    scalar = isinstance(prior, UnivariateDistribution)
+    n, D = int(n), len(fac)
+    if n < 0:
+        raise ValueError("n must be >= 0")
+    check_eval_args(cost, D, nrep, first_row, n)
+    R = 1 if nrep is None else int(nrep)
+    lib = _lib.load()
+    ctx = ctx or _lib.default_context()
+    t0 = time.perf_counter()
+    theta = _lib.result_empty((n, D))
+    lp = _lib.result_empty(n)
+    Cst = _lib.result_empty((n, R))
+    cc = cost.to_c()
+    with ctx.interruptible():
+        _lib.check(lib.kabc_prior_predictive(ctx.handle, fac.to_c(), D, C.byref(cc), n, R, int(seed), int(first_row),
+                                             theta.ctypes.data_as(cd.c_double_p), lp.ctypes.data_as(cd.c_double_p),
+                                             Cst.ctypes.data_as(cd.c_double_p)))
+    st = (C.c_double * 4)()
+    lib.kabc_eval_stats(st)
+    info = {"launches": int(st[1]), "rows_per_launch": int(st[3]), "kernel_ms": st[0], "prior_kernel_ms": st[2],
+            "wall_ms": (time.perf_counter() - t0) * 1e3}
+    if nrep is None:
+        Cst = Cst[:, 0]
+    return PriorPredictiveResult(theta if return_array else _bundle(theta, scalar), Cst, lp, info)
+
+
 class SmcBatchResult(list):
     """smc_batch's result: one SmcResult per run (a list), and `.info` about the whole call."""
 

@@ -20,7 +20,7 @@ class DeviceCost:
         self.params = np.ascontiguousarray(np.asarray(params, dtype=np.float64).ravel())
         self.data = np.ascontiguousarray(np.asarray(data, dtype=np.float64).ravel())
         self.name = name or f"cost{cost_id}"
-        self.dim = dim
+        self.dim = dim   # length(θ) when the cost takes exactly one (checked by evaluate / prior_predictive)
 
     def to_c(self):
         c = cd.Cost()
@@ -31,8 +31,56 @@ class DeviceCost:
         c.data = self.data.ctypes.data_as(cd.c_double_p) if self.data.size else None
         return c
 
+    def evaluate(self, theta, nrep=None, seed=0, first_row=0, ctx=None):
+        """The cost at given parameter rows, on the GPU (kabc_cost_eval, include/kabc.h): what the
+        reference writes `cost(θ)` / `cost.(res.P)` (its cost is a closure, src/types.jl:42,55).
+
+        `theta`: one row [D] or rows [n][D], evaluated as given (no prior, no push_p).  Returns [n]
+        (`nrep=None`: one replicate) or [n][nrep]; a single row drops the leading axis, so
+        `cost.evaluate(x)` of one point is a float.  Replicate j of row i draws from the stream
+        (seed, walker = first_row + i, t = j, DOM_EVAL_COST): the value depends on
+        (seed, first_row + i, j, row, cost) alone, so `evaluate(theta)[a:b]` equals
+        `evaluate(theta[a:b], first_row=a)`.  Context.cancel() / Ctrl-C: Cancelled /
+        KeyboardInterrupt."""
+        from . import _lib
+        a = np.asarray(theta, dtype=np.float64)
+        if a.ndim not in (1, 2) or a.shape[-1] < 1:
+            raise ValueError("theta is one row [D] or rows [n][D], D >= 1")
+        single = a.ndim == 1
+        rows = np.ascontiguousarray(a.reshape(-1, a.shape[-1]))
+        n, D = rows.shape
+        check_eval_args(self, D, nrep, first_row, n)
+        R = 1 if nrep is None else int(nrep)
+        out = _lib.result_empty((n, R))
+        ctx = ctx or _lib.default_context()
+        cc = self.to_c()
+        with ctx.interruptible():
+            _lib.check(_lib.load().kabc_cost_eval(ctx.handle, C.byref(cc), D, n, rows.ctypes.data_as(cd.c_double_p),
+                                                  R, int(seed), int(first_row), out.ctypes.data_as(cd.c_double_p)))
+        if nrep is None:
+            out = out[:, 0]
+        if single:
+            return float(out[0]) if nrep is None else out[0]
+        return out
+
+    __call__ = evaluate
+
     def __repr__(self):
         return f"DeviceCost({self.name})"
+
+
+def check_eval_args(cost, D, nrep, first_row, n):
+    """the refusals of DeviceCost.evaluate / prior_predictive that need no library"""
+    if not isinstance(cost, DeviceCost):
+        raise TypeError("`cost` must be a DeviceCost on the MI355X path")
+    if not 1 <= D <= cd.KABC_MAX_DIM_DYN:
+        raise ValueError(f"length(θ) = {D} outside 1..{cd.KABC_MAX_DIM_DYN}")
+    if cost.dim is not None and int(cost.dim) != D:
+        raise ValueError(f"{cost!r} takes rows of {int(cost.dim)} parameters, got {D}")
+    if nrep is not None and int(nrep) < 1:
+        raise ValueError("nrep must be >= 1")
+    if int(first_row) < 0 or int(first_row) + n > 1 << 32:
+        raise ValueError("first_row must be >= 0 and first_row + n <= 2^32")
 
 
 def GaussDist(center):
@@ -53,17 +101,17 @@ def HierGaussSim(ybar_obs):
 def NormalMeanStdSim(n, mean_obs, std_obs):
     """README.md:43-49: simulate n draws N(μ,σ); hypot(mean−mean_obs, 50(std−std_obs))"""
     return DeviceCost(cd.COST_NORMAL_MEANSTD_SIM, params=[n, mean_obs, std_obs],
-                      name="normal_meanstd_sim")
+                      name="normal_meanstd_sim", dim=2)
 
 
 def DiracSq(target=1.5):
     """test/runtests.jl:79-80: |μ²+1 − target|"""
-    return DeviceCost(cd.COST_DIRAC_SQ, params=[target], name="dirac_sq")
+    return DeviceCost(cd.COST_DIRAC_SQ, params=[target], name="dirac_sq", dim=1)
 
 
 def AbsDiff(target):
     """test/runtests.jl:178: |x − target|"""
-    return DeviceCost(cd.COST_ABS_DIFF, params=[target], name="abs_diff")
+    return DeviceCost(cd.COST_ABS_DIFF, params=[target], name="abs_diff", dim=1)
 
 
 def NormShell(target):
@@ -73,22 +121,22 @@ def NormShell(target):
 
 def NoisyQuadDU(target=5.5):
     """test/runtests.jl:108-109: |(n²+du)(n+0.01·randn) − target|"""
-    return DeviceCost(cd.COST_NOISY_QUAD_DU, params=[target], name="noisy_quad_du")
+    return DeviceCost(cd.COST_NOISY_QUAD_DU, params=[target], name="noisy_quad_du", dim=2)
 
 
 def Mixture(target=0.0):
     """test/runtests.jl:145-146: |μ + rand((0.1·randn, randn)) − target|"""
-    return DeviceCost(cd.COST_MIXTURE, params=[target], name="mixture")
+    return DeviceCost(cd.COST_MIXTURE, params=[target], name="mixture", dim=1)
 
 
 def NoisyBanana(p_inf=0.0):
     """test/runtests.jl:242,248: 50(x+0.01z₁−y²)² + (y−1+0.01z₂)², +Inf with prob p_inf"""
-    return DeviceCost(cd.COST_NOISY_BANANA, params=[p_inf], name="noisy_banana")
+    return DeviceCost(cd.COST_NOISY_BANANA, params=[p_inf], name="noisy_banana", dim=2)
 
 
 def WienerRms(tdata):
     """test/runtests.jl:116-126: mean |sqrt(μ²t²+σ²t)·(0.95+0.1·rand) − tdata_t|"""
-    return DeviceCost(cd.COST_WIENER_RMS, data=tdata, name="wiener_rms")
+    return DeviceCost(cd.COST_WIENER_RMS, data=tdata, name="wiener_rms", dim=2)
 
 
 # ---- user costs compiled at run time -------------------------------------------

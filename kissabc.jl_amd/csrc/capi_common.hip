@@ -205,6 +205,39 @@ bool prepare_priors(const kabc_prior_t* prior, int D, PriorSet& out) {
     return true;
 }
 
+kabc_status_t enqueue_prior_draw(hipStream_t s, void* m_rand, void* m_logpdf, const PriorDev* d_prep,
+                                 const kabc_prior_t* d_raw, int D, int64_t n, uint64_t seed, uint32_t first_walker,
+                                 uint32_t domain, double* d_theta, double* d_lp) {
+    PriorUtilArgs P;
+    std::memset(&P, 0, sizeof P);
+    P.prior = d_prep;
+    P.raw = d_raw;
+    P.n = n;
+    P.D = D;
+    P.seed = seed;
+    P.first_walker = first_walker;
+    P.domain = domain;
+    const dim3 grid = prior_util_geom(P), block(256);
+    if (grid.x == 0) return KABC_OK;
+    // rand(prior) -> push_p in place (a thread reads a word before it writes it) -> logpdf of the pushed row
+    P.out = d_theta;
+    P.mode = 2;
+    if (m_rand) KABC_HIP_CHECK(rtc_launch(m_rand, grid, block, &P, s));
+    else hipLaunchKernelGGL(prior_rand_kernel, grid, block, 0, s, P);
+    P.x = d_theta;
+    P.mode = 1;
+    if (m_logpdf) KABC_HIP_CHECK(rtc_launch(m_logpdf, grid, block, &P, s));
+    else hipLaunchKernelGGL(prior_logpdf_kernel, grid, block, 0, s, P);
+    if (d_lp) {
+        P.out = d_lp;
+        P.mode = 0;
+        if (m_logpdf) KABC_HIP_CHECK(rtc_launch(m_logpdf, grid, block, &P, s));
+        else hipLaunchKernelGGL(prior_logpdf_kernel, grid, block, 0, s, P);
+    }
+    KABC_HIP_CHECK(hipGetLastError());
+    return KABC_OK;
+}
+
 }  // namespace kabc
 
 using namespace kabc;

@@ -920,7 +920,7 @@ static PluginKernel rtc_family_kernel(RtcCache* R, const std::string& head, int 
     };
     const bool big = D > KABC_MAX_DIM;  // run-time-dimension kernels: the D = 0 / dyn instantiations
     if (big && family != kPfAisDyn && family != kPfSmcDyn && family != kPfAbcdeInit && family != kPfAbcdeGen &&
-        family != kPfAttempt && family != kPfPriorLogpdf && family != kPfPriorRand)
+        family != kPfAttempt && family != kPfPriorLogpdf && family != kPfPriorRand && family != kPfCostEval)
         return k;
     const std::string d = std::to_string(big ? 0 : D), u = std::to_string(cost);
     // (the dyn kernels dispatch a built-in cost at run time: their COST argument only says "user cost")
@@ -1018,6 +1018,11 @@ static PluginKernel rtc_family_kernel(RtcCache* R, const std::string& head, int 
                                                 "kabc::smc_dyn_part_kernel<" + udyn + ">"};
             if (variant < 0 || variant > 5) return k;
             k.mod = rtc_kernel(R, head, "smc_dyn_kernels.hpp", false, n, n[(size_t)variant]);
+            break;
+        }
+        case kPfCostEval: {
+            const std::string n = "kabc::cost_eval_kernel<" + u + ">";  // (the dimension is a run-time value)
+            k.mod = rtc_kernel(R, head, "cost_eval_kernel.hpp", false, {n}, n);
             break;
         }
         case kPfPriorLogpdf:
@@ -1366,7 +1371,8 @@ extern "C" kabc_status_t kabc_plugin_precompile(int32_t cost_id, int32_t family,
         return KABC_ERR_INVALID_ARG;
     }
     if (family < kPfAis || (family > kPfAttempt && family != kPfSmcSmall && family != kPfAisDyn && family != kPfSmcDyn &&
-                            family != kPfAisSmall && family != kPfAbcdeSmall && family != kPfPfilterBatch)) {
+                            family != kPfAisSmall && family != kPfAbcdeSmall && family != kPfPfilterBatch &&
+                            family != kPfCostEval)) {
         set_error("kabc_plugin_precompile: unknown kernel family %d", family);
         return KABC_ERR_INVALID_ARG;
     }

@@ -61,6 +61,13 @@ inline hipError_t dev_malloc(T** p, size_t bytes) {
 kabc_status_t resolve_priors(kabc_ctx_t* ctx, const kabc_prior_t* prior, int D, kabc_prior_t* out);
 bool prepare_prior(const kabc_prior_t& pr, PriorDev& q);
 bool prepare_priors(const kabc_prior_t* prior, int D, PriorSet& out);
+// Enqueues the Factored utility kernels (prior_util_kernels.hpp; capi_common.hip is the unit that carries them) for
+// rows [first_walker, first_walker + n) of the stream (seed, domain, attempt 0): rand(prior) into d_theta [n][D],
+// push_p in place, and, with d_lp != nullptr, logpdf of the pushed rows into d_lp [n].  m_rand / m_logpdf: the
+// kernels of the prior's run-time compiled unit (user families among the components), else nullptr.
+kabc_status_t enqueue_prior_draw(hipStream_t s, void* m_rand, void* m_logpdf, const PriorDev* d_prep,
+                                 const kabc_prior_t* d_raw, int D, int64_t n, uint64_t seed, uint32_t first_walker,
+                                 uint32_t domain, double* d_theta, double* d_lp);
 
 }  // namespace kabc
 

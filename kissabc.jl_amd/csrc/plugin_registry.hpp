@@ -43,7 +43,10 @@ enum PluginFamily {
     // (hipRTC units) the one-workgroup ABCDE driver of kabc_abcde_run_batch (abcde_small_kernel.hpp)
     kPfAbcdeSmall,
     // (hipRTC user costs) the one-workgroup pfilter driver of kabc_pfilter_run_batch (pfilter_small_kernel.hpp)
-    kPfPfilterBatch
+    kPfPfilterBatch,
+    // (hipRTC user costs) the cost evaluated outside a sampler: kabc_cost_eval / kabc_prior_predictive
+    // (cost_eval_kernel.hpp; a run-time dimension, any D the cost lists)
+    kPfCostEval
 };
 struct PluginKernel {
     void* host = nullptr;

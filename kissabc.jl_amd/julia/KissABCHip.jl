@@ -147,7 +147,9 @@ struct DeviceCost{F}
     data::Vector{Float64}
     cpu::F
 end
-(c::DeviceCost)(x) = c.cpu(x)
+# c(x) of a point: the Julia closure when the cost has one, else the formula the kernels run, evaluated on the GPU
+# (cost_eval below) -- a UserCost without `cpu` is callable too
+(c::DeviceCost)(x) = c.cpu === nothing ? cost_eval(c, collect(Float64, x)) : c.cpu(x)
 devcost(id, params, data, f) = DeviceCost(Int32(id), collect(Float64, params), collect(Float64, data), f)
 
 GaussDist(c) = devcost(1, c, Float64[], x -> sqrt(sum(abs2, collect(x) .- c)))
@@ -178,11 +180,11 @@ A DeviceCost from a C snippet defining `kabc_user_cost` (include/kabc_costs.h,
 KABC_COST_USER), compiled IN PROCESS by hipRTC through `kabc_compile_cost_plugin`
 (include/kabc.h): the snippet is checked here, each kernel family is compiled when a model
 first uses it.  `cpu` is the Julia closure with the same formula (used when the model runs
-through KissABC's own AIS/smc).  With posterior kind CommonLogDensity the snippet returns the
+through KissABC's own AIS/smc); without one, `cost(x)` evaluates the snippet on the GPU (`cost_eval`).  With posterior kind CommonLogDensity the snippet returns the
 log-density.  `posteriors`: bit mask of the posterior kinds to build AIS kernels for
 (1 kernelized, 2 threshold, 4 common; 0 = all).
 """
-function UserCost(csrc::String, dims; params = Float64[], data = Float64[], cpu = x -> NaN,
+function UserCost(csrc::String, dims; params = Float64[], data = Float64[], cpu = nothing,
                   posteriors::Integer = 0)
     d = Int32[Int32(x) for x in dims]
     id = Ref{Int32}(0)
@@ -648,6 +650,50 @@ particles_of(prior, theta, keep) = begin
 end
 kcost(c::DeviceCost) = KabcCost(c.id, length(c.params), pointer(c.params), length(c.data), pointer(c.data))
 
+"""
+    cost_eval(cost, θ; nrep = nothing, seed = 0, first_row = 0)
+The cost at given parameter vectors, on the GPU (kabc_cost_eval, include/kabc.h): `θ` is one vector or a
+D x n matrix (a column per vector, as `smc` returns them); evaluated as given, no prior, no push_p.  Returns a
+number, a vector [n], or with `nrep` replicates an nrep x n matrix.  Replicate j of column i draws from the
+stream (seed, first_row + i, j): `cost_eval(c, θ)[a:b] == cost_eval(c, θ[:, a:b]; first_row = a - 1)`.
+"""
+function cost_eval(cost::DeviceCost, θ::AbstractVecOrMat{<:Real}; nrep = nothing, seed::Integer = 0, first_row::Integer = 0)
+    x = Matrix{Float64}(reshape(θ, size(θ, 1), :))                 # column-major D x n == [n][D]
+    D, n = size(x)
+    R = nrep === nothing ? 1 : Int(nrep)
+    out = Matrix{Float64}(undef, R, n)                              # == [n][nrep]
+    GC.@preserve cost x out begin
+        check(ccall((:kabc_cost_eval, libkabc), Cint,
+                    (Ptr{Cvoid}, Ref{KabcCost}, Int32, Int64, Ptr{Float64}, Int32, UInt64, Int64, Ptr{Float64}),
+                    context(), kcost(cost), D, n, x, R, UInt64(seed), first_row, out))
+    end
+    nrep === nothing ? (θ isa AbstractVector ? out[1] : vec(out)) : (θ isa AbstractVector ? vec(out) : out)
+end
+
+"""
+    prior_predictive(prior, cost, n; nrep = nothing, seed = 0, first_row = 0)
+The pilot simulation `cost.(rand(prior) for _ in 1:n)` in one call (kabc_prior_predictive): n draws
+push_p(prior, rand(prior)), their log-prior and their costs (nrep replicates each) without θ visiting the host
+in between -- `quantile(prior_predictive(prior, cost, 10_000).C, 0.01)` is the ϵ the samplers ask for.
+Returns (P, C, logprior): P as smc bundles it, C [n] or nrep x n.
+"""
+function prior_predictive(prior::Distribution, cost::DeviceCost, n::Integer; nrep = nothing, seed::Integer = 0,
+                          first_row::Integer = 0)
+    pri = lower_prior(prior)
+    D = length(pri)
+    R = nrep === nothing ? 1 : Int(nrep)
+    theta = Matrix{Float64}(undef, D, n)
+    lp = Vector{Float64}(undef, n)
+    out = Matrix{Float64}(undef, R, n)
+    GC.@preserve pri cost theta lp out begin
+        check(ccall((:kabc_prior_predictive, libkabc), Cint,
+                    (Ptr{Cvoid}, Ptr{KabcPrior}, Int32, Ref{KabcCost}, Int64, Int32, UInt64, Int64, Ptr{Float64},
+                     Ptr{Float64}, Ptr{Float64}),
+                    context(), pri, D, kcost(cost), n, R, UInt64(seed), first_row, theta, lp, out))
+    end
+    (P = particles_of(prior, theta, 1:n), C = nrep === nothing ? vec(out) : out, logprior = lp)
+end
+
 # smc(prior, cost::DeviceCost; ...) -- replaces src/smc.jl:92-206, same keywords and defaults
 function KissABC.smc(prior::Distribution, cost::DeviceCost; rng = Random.GLOBAL_RNG,
                      nparticles::Int = 100, alpha = 0.95, mcmc_retrys::Int = 0, mcmc_tol = 0.015,
@@ -787,7 +833,7 @@ function spec_counters()
     (started = out[1], loaded = out[2], failed = out[3], cache_hits = out[4])
 end
 
-export cancel!, clear_cancel!, DeviceCost, UserCost, UserPrior, compile_model, release_model, prefetch_model, spec_counters, set_specialize, rtc_cache_dir, UserMvPrior, InitFrom, InitFromSnippet, GaussDist, Rosenbrock, HierGaussSim, NormalMeanStdSim, DiracSq,
+export cancel!, clear_cancel!, cost_eval, prior_predictive, DeviceCost, UserCost, UserPrior, compile_model, release_model, prefetch_model, spec_counters, set_specialize, rtc_cache_dir, UserMvPrior, InitFrom, InitFromSnippet, GaussDist, Rosenbrock, HierGaussSim, NormalMeanStdSim, DiracSq,
        AbsDiff, NormShell, NoisyQuadDU, Mixture, NoisyBanana, WienerRms, sample_sharded, unique_id,
        comm_init_rank
 end # module
