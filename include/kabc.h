@@ -135,7 +135,8 @@ int32_t kabc_version(void);
 /* sizeof() of the i-th struct of this header as the library was compiled, in declaration order:
  * 0 kabc_prior_t, 1 kabc_cost_t, 2 kabc_model_t, 3 kabc_stats_t, 4 kabc_smc_opts_t,
  * 5 kabc_smc_iter_t, 6 kabc_smc_result_t, 7 kabc_abcde_opts_t, 8 kabc_abcde_result_t,
- * 9 kabc_pfilter_opts_t, 10 kabc_pfilter_result_t; -1 beyond.  A binding that mirrors the
+ * 9 kabc_pfilter_opts_t, 10 kabc_pfilter_result_t; -1 beyond, except the second block
+ * 32 kabc_reject_opts_t, 33 kabc_reject_result_t.  A binding that mirrors the
  * structs by hand (ctypes, Julia `struct`) checks itself against this at load time. */
 int32_t kabc_abi_sizeof(int32_t which);
 /* offsetof() of the field-th member (declaration order, from 0) of the which-th struct (the
@@ -183,6 +184,8 @@ kabc_status_t kabc_ctx_synchronize(kabc_ctx_t* ctx);
  *   kabc_cost_eval, kabc_prior_predictive
  *                     a request pending at entry: nothing is launched; during the call: seen between
  *                     two launches of KABC_EVAL_ROWS rows, the output arrays are then unspecified.
+ *   kabc_abc_reject   a request pending at entry: nothing is launched; during the call: seen between two
+ *                     host looks, the result then holds what the completed rows gave (see the entry point).
  * A call that is never cancelled is unchanged.  Sharded and distributed calls (kabc_ais_create_dist
  * handles, kabc_ais_advance_multi, kabc_smc_run_dist*) do not poll -- a cancel seen on one rank
  * would leave the others in a collective -- and neither do kabc_ais_init, kabc_abcde_run and
@@ -284,6 +287,75 @@ kabc_status_t kabc_prior_predictive(kabc_ctx_t* ctx, const kabc_prior_t* prior, 
  * KABC_EVAL_TIMING=1), [3] rows per launch. */
 void kabc_eval_stats(double out[4]);
 
+/* ---- rejection ABC on the device ----------------------------------------------------
+ * The sampler that sits on a pilot simulation: draw from the prior, simulate, keep the draw if cost <= eps
+ * -- or keep the best k of N draws, the reference's "quantile, then Xs .<= eps" (src/smc.jl:134-139) applied
+ * to a pilot run.  row(i), i = 0, 1, ..., is EXACTLY row i of kabc_prior_predictive(prior, cost, nrep = 1,
+ * seed, first_row): theta_i = push_p(prior, rand(prior)) from (seed, walker = first_row + i, attempt 0,
+ * KABC_DOM_EVAL_DRAW), logprior_i its log-prior, C_i its cost under (seed, walker = first_row + i, t = 0,
+ * KABC_DOM_EVAL_COST).  Nothing else enters a row: not the launch size, not the mode, not the other rows.
+ *
+ * THRESHOLD mode (keep == 0): row i is accepted iff C_i <= eps (a NaN cost never is).  The result is the first
+ * n_accept accepted rows in index order; draws = the index of the n_accept-th accepted row + 1, so
+ * n_out / draws is the acceptance estimate of a stopped run whatever the launches were.  When fewer than
+ * n_accept of the first max_draws rows accept, the result holds those that did, draws = max_draws and
+ * exhausted = 1: KABC_OK, not an error.  max_draws == 0: the whole addressable stream, 2^32 - first_row.
+ * KEEP mode (keep = k > 0; max_draws = N >= 1; eps ignored): the k rows with the smallest (C_i, i) in
+ * lexicographic order among i < N -- ties go to the lower index; NaN costs are excluded, +Inf is kept only
+ * when fewer than k rows cost less; fewer than k rows come back only when fewer than k costs are not NaN.
+ * Rows are returned in index order; result.eps is the largest kept cost (NaN when nothing was kept);
+ * draws = N.
+ * Both modes return, per kept row, theta [D], cost, logprior and the row index i; the output is, bit for
+ * bit, a selection of rows of kabc_prior_predictive(prior, cost, draws, 1, seed, first_row).
+ *
+ * The rows are drawn, evaluated, tested and COMPACTED on the device: only accepted rows are stored or
+ * copied.  course = 0 (fused): one kernel per launch of up to KABC_EVAL_ROWS rows draws each row into
+ * LDS (csrc/abc_reject_kernel.hpp); course = 1 (phases): the kernels of kabc_prior_predictive followed by
+ * a compaction kernel -- user prior families, joint user priors, MvNormal and rows too long for the LDS
+ * tile.  Same bits.  Costs as kabc_cost_eval: built-in ones and user costs in the hipRTC form (kernel
+ * family 17 of kabc_plugin_precompile); a plugin built by hipcc is refused with KABC_ERR_UNSUPPORTED.
+ * The output buffer of a launch has a capacity (KABC_REJECT_CAPACITY rows, default 65 536, read per
+ * call); the device counts accepted rows past it and only suppresses the stores, so the host always sees
+ * an overflow and repeats that row range in pieces that cannot overflow: no accepted row is dropped.
+ *
+ * Checked before ctx is used (KABC_ERR_INVALID_ARG): NULL arguments, D outside 1..KABC_MAX_DIM_DYN,
+ * negative n_accept / max_draws / keep / first_row, result.capacity below n_accept (keep), keep > max_draws,
+ * first_row + max_draws > 2^32, a NaN eps in threshold mode, the cost's params / data lengths.
+ * kabc_ctx_cancel: pending at entry, nothing is launched; during the call it is seen between two host
+ * looks at the launch counters: KABC_ERR_CANCELLED, and the result holds what the completed rows gave --
+ * threshold mode: the rows accepted so far; keep mode: the best k of the rows completed -- in index order,
+ * with draws = the rows completed.  KABC_EVAL_TIMING=1 fills kernel_ms (else -1). */
+typedef struct kabc_reject_opts {
+    double eps;          /* threshold mode: accept iff cost <= eps                            */
+    int64_t n_accept;    /* threshold mode: accepted rows wanted                              */
+    int64_t max_draws;   /* threshold mode: budget (0 = the whole stream); keep mode: N       */
+    int64_t keep;        /* > 0: keep mode, the best `keep` of max_draws rows                 */
+    uint64_t seed;
+    int64_t first_row;
+} kabc_reject_opts_t;
+
+typedef struct kabc_reject_result {
+    double* theta;          /* [capacity][D], caller-allocated                                 */
+    double* cost;           /* [capacity]                                                      */
+    double* logprior;       /* [capacity]                                                      */
+    int64_t* index;         /* [capacity]: the row index i of each kept row                    */
+    int64_t capacity;       /* rows the four arrays hold: >= n_accept (threshold) / keep       */
+    int64_t n_out;          /* rows returned                                                   */
+    int64_t draws;          /* see above                                                       */
+    int64_t accepted_seen;  /* rows the device counted as passing its test, over all launches  */
+    double eps;             /* threshold mode: opts.eps; keep mode: the largest kept cost      */
+    int32_t exhausted;      /* threshold mode: max_draws rows gave fewer than n_accept         */
+    int32_t course;         /* 0 fused, 1 phases                                               */
+    int64_t launches;       /* launches over row ranges, repeats after an overflow included    */
+    double kernel_ms;       /* device time of the launches with KABC_EVAL_TIMING=1, else -1    */
+} kabc_reject_result_t;
+
+/* sizeof / offsetof of the two structs above: kabc_abi_sizeof(32) / (33), kabc_abi_offsetof(32 / 33, f)
+ * -- a second block of the numbering (0..10 is closed: kabc_abi_sizeof(11) stays -1). */
+void kabc_reject_default_opts(kabc_reject_opts_t* opts);
+kabc_status_t kabc_abc_reject(kabc_ctx_t* ctx, const kabc_prior_t* prior, int32_t D, const kabc_cost_t* cost,
+                              const kabc_reject_opts_t* opts, kabc_reject_result_t* result);
+
 /* ---- arithmetic-contract probe (verification only) ---------------------------
  * Evaluates one function of include/kabc_math.h on the device for n host inputs, so
  * that tests can compare the gfx950 code with the host build of the same header bit
@@ -318,7 +390,8 @@ kabc_status_t kabc_compile_cost_plugin(const char* src, const int32_t* dims, int
  * 10 the one-workgroup smc driver, 13 the one-workgroup AIS driver of small ensembles (variant as
  * family 0; prior classes 0 and 2), 14 the one-workgroup ABCDE driver of kabc_abcde_run_batch
  * (variant 0), 15 the one-workgroup pfilter driver of kabc_pfilter_run_batch (variant 0), 16 the
- * evaluation kernel of kabc_cost_eval / kabc_prior_predictive (variant 0; any D the cost lists). */
+ * evaluation kernel of kabc_cost_eval / kabc_prior_predictive (variant 0; any D the cost lists), 17 the
+ * fused draw-evaluate-compact kernel of kabc_abc_reject (variant 0; any D the cost lists). */
 kabc_status_t kabc_plugin_precompile(int32_t cost_id, int32_t family, int32_t D, int32_t variant);
 
 /* ---- user prior families ------------------------------------------------------

@@ -102,6 +102,22 @@ class PfilterResult(C.Structure):
                 ("cost_evals", C.c_uint64)]
 
 
+class RejectOpts(C.Structure):
+    _fields_ = [("eps", C.c_double), ("n_accept", C.c_int64), ("max_draws", C.c_int64), ("keep", C.c_int64),
+                ("seed", C.c_uint64), ("first_row", C.c_int64)]
+
+
+class RejectResult(C.Structure):
+    _fields_ = [("theta", c_double_p), ("cost", c_double_p), ("logprior", c_double_p),
+                ("index", C.POINTER(C.c_int64)), ("capacity", C.c_int64), ("n_out", C.c_int64),
+                ("draws", C.c_int64), ("accepted_seen", C.c_int64), ("eps", C.c_double),
+                ("exhausted", C.c_int32), ("course", C.c_int32), ("launches", C.c_int64),
+                ("kernel_ms", C.c_double)]
+
+
+# kabc_abi_sizeof / kabc_abi_offsetof number of the two structs above (the second block of the numbering)
+ABI_REJECT_OPTS, ABI_REJECT_RESULT = 32, 33
+
 # every symbol include/kabc.h declares: name -> (restype, argtypes)
 VP = C.c_void_p
 PROTOTYPES = {
@@ -132,6 +148,9 @@ PROTOTYPES = {
                                         C.c_int32, C.c_uint64, C.c_int64, c_double_p, c_double_p,
                                         c_double_p]),
     "kabc_eval_stats": (None, [c_double_p]),
+    "kabc_reject_default_opts": (None, [C.POINTER(RejectOpts)]),
+    "kabc_abc_reject": (C.c_int, [VP, C.POINTER(Prior), C.c_int32, C.POINTER(Cost), C.POINTER(RejectOpts),
+                                  C.POINTER(RejectResult)]),
     "kabc_register_cost_plugin": (C.c_int, [C.c_char_p, C.POINTER(C.c_int32)]),
     "kabc_plugin_precompile": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "kabc_compile_cost_plugin": (C.c_int, [C.c_char_p, C.POINTER(C.c_int32), C.c_int32, C.c_int32,

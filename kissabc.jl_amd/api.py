@@ -42,6 +42,14 @@ class Particles:
     def std(self):
         return float(np.std(self.particles, ddof=1))
 
+    def var(self):
+        return float(np.var(self.particles, ddof=1))
+
+    def quantile(self, q):
+        """numpy.quantile of the samples: a float for a scalar q, an array for a sequence"""
+        v = np.quantile(self.particles, q)
+        return float(v) if np.ndim(v) == 0 else v
+
     def isapprox(self, c, nsigma=2.0):
         """MonteCarloMeasurements `p ≈ c`: |mean − c| < nsigma · std."""
         return abs(self.mean() - c) < nsigma * self.std()
@@ -647,8 +655,6 @@ def prior_predictive(prior, cost, n, nrep=None, seed=0, first_row=0, ctx=None, r
     fac = as_factored(prior)
     scalar = isinstance(prior, UnivariateDistribution)
     n, D = int(n), len(fac)
-    if n < 0:
-        raise ValueError("n must be >= 0")
     check_eval_args(cost, D, nrep, first_row, n)
     R = 1 if nrep is None else int(nrep)
     lib = _lib.load()
@@ -669,6 +675,80 @@ def prior_predictive(prior, cost, n, nrep=None, seed=0, first_row=0, ctx=None, r
     if nrep is None:
         Cst = Cst[:, 0]
     return PriorPredictiveResult(theta if return_array else _bundle(theta, scalar), Cst, lp, info)
+
+
+class RejectResult(collections.namedtuple("RejectResult", ["P", "C", "logprior", "eps", "info"])):
+    """abc_reject's result; `.ϵ`/`.ε` alias `.eps`."""
+    __slots__ = ()
+
+    def __getattr__(self, name):
+        if name in ("\u03b5", "\u03f5"):
+            return self.eps
+        raise AttributeError(name)
+
+
+def abc_reject(prior, cost, eps=None, n=None, *, draws=None, keep=None, seed=0, first_row=0, ctx=None,
+               return_array=False):
+    """Rejection ABC on the GPU (kabc_abc_reject, include/kabc.h): draw from the prior, simulate, keep the
+    draw if `cost <= eps` -- the accepted draws are independent draws from prior x 1[cost <= eps].
+
+    `abc_reject(prior, cost, eps, n)`: the first `n` accepted rows in index order; `draws=` bounds the rows
+    drawn (default: the whole stream, 2^32 - first_row).  Fewer than n acceptances within the budget is no
+    error: `info["exhausted"]`.  `abc_reject(prior, cost, draws=N, keep=k)`: the k rows with the smallest
+    (cost, index) of N draws (NaN costs excluded), in index order; `eps` of the result is the largest kept
+    cost -- the reference's `quantile` then `Xs .<= ϵ` (src/smc.jl:134-139) on a pilot run.
+
+    Row i is row i of `prior_predictive(prior, cost, draws, seed=seed, first_row=first_row)`, bit for bit;
+    `info["index"]` holds the i of every returned row.  Rows are drawn, simulated, tested and compacted on
+    the device: only accepted rows cross PCIe.  Returns (P, C, logprior, eps, info): `P` bundled like
+    smc's (or the [n_out][D] array with `return_array`); info: index, draws, accepted_seen, exhausted,
+    course ("fused" / "phases"), launches, kernel_ms (KABC_EVAL_TIMING=1), wall_ms, acceptance = n_out / draws.
+    Context.cancel() / Ctrl-C: Cancelled (its `.result` holds what the completed rows gave) /
+    KeyboardInterrupt."""
+    from .costs import check_reject_args
+    fac = as_factored(prior)
+    scalar = isinstance(prior, UnivariateDistribution)
+    D = len(fac)
+    n_accept, max_draws, k = check_reject_args(cost, D, eps, n, draws, keep, first_row)
+    lib = _lib.load()
+    ctx = ctx or _lib.default_context()
+    t0 = time.perf_counter()
+    o = cd.RejectOpts()
+    lib.kabc_reject_default_opts(C.byref(o))
+    if not k:
+        o.eps = float(eps)
+    o.n_accept, o.max_draws, o.keep, o.seed, o.first_row = n_accept, max_draws, k, int(seed), int(first_row)
+    cap = max(n_accept, k)
+    theta = _lib.result_empty((cap, D))
+    Cst, lp = _lib.result_empty(cap), _lib.result_empty(cap)
+    index = np.empty(cap, dtype=np.int64)
+    r = cd.RejectResult()
+    r.theta = theta.ctypes.data_as(cd.c_double_p)
+    r.cost = Cst.ctypes.data_as(cd.c_double_p)
+    r.logprior = lp.ctypes.data_as(cd.c_double_p)
+    r.index = index.ctypes.data_as(C.POINTER(C.c_int64))
+    r.capacity = cap
+    cc = cost.to_c()
+
+    def result():
+        m = int(r.n_out)
+        info = {"index": index[:m], "draws": int(r.draws), "accepted_seen": int(r.accepted_seen),
+                "exhausted": bool(r.exhausted), "course": "phases" if r.course else "fused",
+                "launches": int(r.launches), "kernel_ms": r.kernel_ms, "wall_ms": (time.perf_counter() - t0) * 1e3,
+                "acceptance": m / r.draws if r.draws else math.nan}
+        P = theta[:m]
+        return RejectResult(P if return_array else _bundle(P, scalar), Cst[:m], lp[:m], r.eps, info)
+
+    with ctx.interruptible():
+        status = lib.kabc_abc_reject(ctx.handle, fac.to_c(), D, C.byref(cc), C.byref(o), C.byref(r))
+        if status == cd.KABC_ERR_CANCELLED:
+            try:
+                _lib.check(status)
+            except _lib.Cancelled as e:
+                e.result = result()
+                raise
+        _lib.check(status)
+    return result()
 
 
 class SmcBatchResult(list):

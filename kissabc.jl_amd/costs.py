@@ -5,6 +5,7 @@ cost is an id + parameter/data arrays whose formula lives in
 include/kabc_costs.h (evaluated by the HIP kernels)."""
 import ctypes as C
 import hashlib
+import math
 import os
 import subprocess
 import threading
@@ -79,8 +80,47 @@ def check_eval_args(cost, D, nrep, first_row, n):
         raise ValueError(f"{cost!r} takes rows of {int(cost.dim)} parameters, got {D}")
     if nrep is not None and int(nrep) < 1:
         raise ValueError("nrep must be >= 1")
-    if int(first_row) < 0 or int(first_row) + n > 1 << 32:
-        raise ValueError("first_row must be >= 0 and first_row + n <= 2^32")
+    check_rows(n, first_row)
+
+
+def check_rows(n, first_row, what="n"):
+    """`n` rows of the stream from `first_row`: a row is addressed by a 32-bit walker word (shared by
+    DeviceCost.evaluate, prior_predictive and abc_reject; `what` names the count in the message)"""
+    if int(n) < 0:
+        raise ValueError(f"{what} must be >= 0")
+    if int(first_row) < 0 or int(first_row) + int(n) > 1 << 32:
+        raise ValueError(f"first_row must be >= 0 and first_row + {what} <= 2^32")
+
+
+def check_reject_args(cost, D, eps, n, draws, keep, first_row):
+    """the refusals of abc_reject that need no library; returns (n_accept, max_draws, keep) as
+    kabc_reject_opts_t takes them (keep = 0: threshold mode; max_draws = 0: the whole stream)"""
+    if not isinstance(cost, DeviceCost):
+        raise TypeError("`cost` must be a DeviceCost on the MI355X path")
+    if not 1 <= D <= cd.KABC_MAX_DIM_DYN:
+        raise ValueError(f"length(θ) = {D} outside 1..{cd.KABC_MAX_DIM_DYN}")
+    if cost.dim is not None and int(cost.dim) != D:
+        raise ValueError(f"{cost!r} takes rows of {int(cost.dim)} parameters, got {D}")
+    if keep is not None:
+        if eps is not None or n is not None:
+            raise ValueError("give either (eps, n) or (draws, keep), not both")
+        if draws is None:
+            raise ValueError("keep needs draws: the best `keep` of `draws` rows")
+        if int(keep) < 1:
+            raise ValueError("keep must be >= 1")
+        if int(draws) < int(keep):
+            raise ValueError("draws must be >= keep")
+    else:
+        if eps is None or n is None:
+            raise ValueError("give either (eps, n) or (draws, keep)")
+        if math.isnan(float(eps)):
+            raise ValueError("eps is NaN")
+        if int(n) < 0:
+            raise ValueError("n must be >= 0")
+        if draws is not None and int(draws) < 1:
+            raise ValueError("draws must be >= 1")
+    check_rows(0 if draws is None else draws, first_row, "draws")
+    return (0 if keep is not None else int(n)), (0 if draws is None else int(draws)), (0 if keep is None else int(keep))
 
 
 def GaussDist(center):

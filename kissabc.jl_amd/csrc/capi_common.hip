@@ -288,6 +288,9 @@ int32_t kabc_abi_sizeof(int32_t which) {
         (int32_t)sizeof(kabc_smc_result_t),   (int32_t)sizeof(kabc_abcde_opts_t),
         (int32_t)sizeof(kabc_abcde_result_t), (int32_t)sizeof(kabc_pfilter_opts_t),
         (int32_t)sizeof(kabc_pfilter_result_t)};
+    // (a second block of the numbering: the structs of kabc_abc_reject; 0..10 is closed)
+    if (which == 32) return (int32_t)sizeof(kabc_reject_opts_t);
+    if (which == 33) return (int32_t)sizeof(kabc_reject_result_t);
     return (which >= 0 && which < (int32_t)(sizeof sz / sizeof sz[0])) ? sz[which] : -1;
 }
 int32_t kabc_abi_offsetof(int32_t which, int32_t field) {
@@ -325,7 +328,19 @@ int32_t kabc_abi_offsetof(int32_t which, int32_t field) {
         {KABC_OFF(kabc_pfilter_result_t, theta), KABC_OFF(kabc_pfilter_result_t, cost), KABC_OFF(kabc_pfilter_result_t, eps),
          KABC_OFF(kabc_pfilter_result_t, eff), KABC_OFF(kabc_pfilter_result_t, iterations),
          KABC_OFF(kabc_pfilter_result_t, nreps), KABC_OFF(kabc_pfilter_result_t, cost_evals)}};
+    static const std::vector<std::vector<int32_t>> off2 = {
+        {KABC_OFF(kabc_reject_opts_t, eps), KABC_OFF(kabc_reject_opts_t, n_accept), KABC_OFF(kabc_reject_opts_t, max_draws),
+         KABC_OFF(kabc_reject_opts_t, keep), KABC_OFF(kabc_reject_opts_t, seed), KABC_OFF(kabc_reject_opts_t, first_row)},
+        {KABC_OFF(kabc_reject_result_t, theta), KABC_OFF(kabc_reject_result_t, cost), KABC_OFF(kabc_reject_result_t, logprior),
+         KABC_OFF(kabc_reject_result_t, index), KABC_OFF(kabc_reject_result_t, capacity), KABC_OFF(kabc_reject_result_t, n_out),
+         KABC_OFF(kabc_reject_result_t, draws), KABC_OFF(kabc_reject_result_t, accepted_seen),
+         KABC_OFF(kabc_reject_result_t, eps), KABC_OFF(kabc_reject_result_t, exhausted), KABC_OFF(kabc_reject_result_t, course),
+         KABC_OFF(kabc_reject_result_t, launches), KABC_OFF(kabc_reject_result_t, kernel_ms)}};
 #undef KABC_OFF
+    if (which == 32 || which == 33) {  // (the second block: see kabc_abi_sizeof)
+        const std::vector<int32_t>& f2 = off2[(size_t)(which - 32)];
+        return (field >= 0 && field < (int32_t)f2.size()) ? f2[(size_t)field] : -1;
+    }
     if (which < 0 || which >= (int32_t)off.size()) return -1;
     const std::vector<int32_t>& f = off[(size_t)which];
     return (field >= 0 && field < (int32_t)f.size()) ? f[(size_t)field] : -1;

@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "cost_eval_kernel.hpp"
+#include "eval_host.hpp"
 #include "host_common.hpp"
 #include "launcher.hpp"
 #include "plugin_registry.hpp"
@@ -22,41 +23,7 @@ CostEvalLaunchFn pick_cost_eval(int id, std::integer_sequence<int, Cs...>) {
     return f;
 }
 
-// rows and replicates of one launch: KABC_EVAL_ROWS rows (default 2^20), at most 2^24 items and 2^25 words of
-// rows -- 128 MB of results and 256 MB of rows on the device, whatever n and nrep are
-constexpr int64_t kEvalMaxItems = (int64_t)1 << 24;
-constexpr int64_t kEvalMaxRowWords = (int64_t)1 << 25;
-int64_t eval_rows_per_launch(int D, int64_t nrep_l) {
-    int64_t rows = (int64_t)1 << 20;
-    if (const char* e = std::getenv("KABC_EVAL_ROWS")) {
-        const long long v = std::atoll(e);
-        if (v >= 1) rows = v;
-    }
-    if (rows > kEvalMaxItems / nrep_l) rows = kEvalMaxItems / nrep_l;
-    if (rows > kEvalMaxRowWords / D) rows = kEvalMaxRowWords / D;
-    return rows < 1 ? 1 : rows;
-}
-
 thread_local double g_eval_stats[4] = {-1.0, 0.0, 0.0, 0.0};
-
-bool eval_timing() {
-    const char* e = std::getenv("KABC_EVAL_TIMING");
-    return e && *e && *e != '0';
-}
-
-struct EvalEvents {
-    std::vector<hipEvent_t> ev;
-    ~EvalEvents() {
-        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
-    }
-    hipError_t mark(hipStream_t s) {
-        hipEvent_t e = nullptr;
-        hipError_t r = hipEventCreate(&e);
-        if (r != hipSuccess) return r;
-        ev.push_back(e);
-        return hipEventRecord(e, s);
-    }
-};
 
 // prior == nullptr: kabc_cost_eval (rows from theta_in); else kabc_prior_predictive (rows drawn on the device,
 // written to theta_out / logprior_out)
@@ -68,23 +35,13 @@ kabc_status_t eval_run(const char* who, kabc_ctx_t* ctx, const kabc_prior_t* pri
         set_error("%s: NULL argument", who);
         return KABC_ERR_INVALID_ARG;
     }
-    if (D < 1 || D > KABC_MAX_DIM_DYN) {
-        set_error("%s: D = %d outside 1..%d", who, D, KABC_MAX_DIM_DYN);
-        return KABC_ERR_INVALID_ARG;
-    }
+    if (kabc_status_t st = eval_check_dim(who, D)) return st;
     if (nrep < 1) {
         set_error("%s: nrep = %d, must be >= 1", who, nrep);
         return KABC_ERR_INVALID_ARG;
     }
-    if (n < 0 || first_row < 0 || first_row > ((int64_t)1 << 32) || n > ((int64_t)1 << 32) - first_row) {
-        set_error("%s: n = %lld rows from first_row = %lld: both >= 0 and first_row + n <= 2^32 (a row's stream is "
-                  "addressed by a 32-bit walker word)", who, (long long)n, (long long)first_row);
-        return KABC_ERR_INVALID_ARG;
-    }
-    if (cost->nparams < 0 || cost->ndata < 0 || (cost->nparams > 0 && !cost->params) || (cost->ndata > 0 && !cost->data)) {
-        set_error("%s: the cost has a NULL params / data array or a negative length", who);
-        return KABC_ERR_INVALID_ARG;
-    }
+    if (kabc_status_t st = eval_check_rows(who, "n", n, first_row)) return st;
+    if (kabc_status_t st = eval_check_cost_arrays(who, cost)) return st;
     if (!ctx) {
         set_error("%s: ctx is NULL", who);
         return KABC_ERR_INVALID_ARG;
@@ -93,29 +50,9 @@ kabc_status_t eval_run(const char* who, kabc_ctx_t* ctx, const kabc_prior_t* pri
         set_error("DeviceCost id %d does not accept D = %d", cost->id, D);
         return KABC_ERR_UNSUPPORTED;
     }
-    {
-        // what a built-in formula reads of params / data (include/kabc_costs.h): nothing is read past the arrays
-        int64_t need_p = 0, need_d = 0;
-        switch (cost->id) {
-            case KABC_COST_GAUSS_DIST: need_p = D; break;
-            case KABC_COST_HIER_GAUSS_SIM: need_d = D - 2; break;
-            case KABC_COST_NORMAL_MEANSTD_SIM: need_p = 3; break;
-            case KABC_COST_WIENER_RMS: need_d = 1; break;
-            case KABC_COST_ROSENBROCK: break;
-            default: need_p = cost->id < KABC_COST_USER ? 1 : 0;
-        }
-        if (cost->nparams < need_p || cost->ndata < need_d) {
-            set_error("%s: DeviceCost id %d at D = %d reads %lld params and %lld data words, the cost holds %d and %lld",
-                      who, cost->id, D, (long long)need_p, (long long)need_d, cost->nparams, (long long)cost->ndata);
-            return KABC_ERR_INVALID_ARG;
-        }
-    }
+    if (kabc_status_t st = eval_check_cost_reads(who, cost, D)) return st;
     const CostPlugin* pl = cost->id >= KABC_COST_USER ? find_plugin(cost->id) : nullptr;
-    if (pl && !pl->rtc) {
-        set_error("%s: a cost plugin built by hipcc (kabc_register_cost_plugin) carries no evaluation kernel; "
-                  "compile the snippet in the hipRTC form (kabc_compile_cost_plugin)", who);
-        return KABC_ERR_UNSUPPORTED;
-    }
+    if (pl && !pl->rtc) return eval_refuse_hipcc_plugin(who);
     std::vector<kabc_prior_t> rp;
     std::vector<PriorDev> prep;
     if (prior) {
@@ -142,7 +79,7 @@ kabc_status_t eval_run(const char* who, kabc_ctx_t* ctx, const kabc_prior_t* pri
         m_cost = plugin_kernel(pl, kPfCostEval, D, 0).mod;
         if (!m_cost) return KABC_ERR_DEVICE;  // (message set by the compilation / load)
     } else {
-        f_cost = pick_cost_eval(cost->id, std::make_integer_sequence<int, KABC_COST__COUNT - 1>{});
+        f_cost = cost_eval_launcher(cost->id);
         if (!f_cost) {
             set_error("%s: no evaluation kernel for DeviceCost id %d", who, cost->id);
             return KABC_ERR_DEVICE;
@@ -249,16 +186,8 @@ kabc_status_t eval_run(const char* who, kabc_ctx_t* ctx, const kabc_prior_t* pri
     g_eval_stats[1] = (double)launches;
     g_eval_stats[3] = (double)rows_l;
     if (timing) {
-        auto total_ms = [](const EvalEvents& E) {
-            double t = 0.0;
-            for (size_t i = 0; i + 1 < E.ev.size(); i += 2) {
-                float ms = 0.f;
-                if (hipEventElapsedTime(&ms, E.ev[i], E.ev[i + 1]) == hipSuccess) t += ms;
-            }
-            return t;
-        };
-        g_eval_stats[0] = total_ms(ev_cost);
-        g_eval_stats[2] = total_ms(ev_prior);
+        g_eval_stats[0] = ev_cost.total_ms();
+        g_eval_stats[2] = ev_prior.total_ms();
     }
     if (cancelled) {
         (void)cancel_take(ctx);
@@ -269,6 +198,10 @@ kabc_status_t eval_run(const char* who, kabc_ctx_t* ctx, const kabc_prior_t* pri
 }
 
 }  // namespace
+
+CostEvalLaunchFn cost_eval_launcher(int cost_id) {
+    return pick_cost_eval(cost_id, std::make_integer_sequence<int, KABC_COST__COUNT - 1>{});
+}
 }  // namespace kabc
 
 extern "C" {

@@ -920,7 +920,8 @@ static PluginKernel rtc_family_kernel(RtcCache* R, const std::string& head, int 
     };
     const bool big = D > KABC_MAX_DIM;  // run-time-dimension kernels: the D = 0 / dyn instantiations
     if (big && family != kPfAisDyn && family != kPfSmcDyn && family != kPfAbcdeInit && family != kPfAbcdeGen &&
-        family != kPfAttempt && family != kPfPriorLogpdf && family != kPfPriorRand && family != kPfCostEval)
+        family != kPfAttempt && family != kPfPriorLogpdf && family != kPfPriorRand && family != kPfCostEval &&
+        family != kPfAbcReject)
         return k;
     const std::string d = std::to_string(big ? 0 : D), u = std::to_string(cost);
     // (the dyn kernels dispatch a built-in cost at run time: their COST argument only says "user cost")
@@ -1023,6 +1024,11 @@ static PluginKernel rtc_family_kernel(RtcCache* R, const std::string& head, int 
         case kPfCostEval: {
             const std::string n = "kabc::cost_eval_kernel<" + u + ">";  // (the dimension is a run-time value)
             k.mod = rtc_kernel(R, head, "cost_eval_kernel.hpp", false, {n}, n);
+            break;
+        }
+        case kPfAbcReject: {
+            const std::string n = "kabc::abc_reject_kernel<" + u + ">";  // (the dimension is a run-time value)
+            k.mod = rtc_kernel(R, head, "abc_reject_kernel.hpp", false, {n}, n);
             break;
         }
         case kPfPriorLogpdf:
@@ -1372,7 +1378,7 @@ extern "C" kabc_status_t kabc_plugin_precompile(int32_t cost_id, int32_t family,
     }
     if (family < kPfAis || (family > kPfAttempt && family != kPfSmcSmall && family != kPfAisDyn && family != kPfSmcDyn &&
                             family != kPfAisSmall && family != kPfAbcdeSmall && family != kPfPfilterBatch &&
-                            family != kPfCostEval)) {
+                            family != kPfCostEval && family != kPfAbcReject)) {
         set_error("kabc_plugin_precompile: unknown kernel family %d", family);
         return KABC_ERR_INVALID_ARG;
     }

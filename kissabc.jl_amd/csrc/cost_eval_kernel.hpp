@@ -97,6 +97,22 @@ __device__ __forceinline__ double cost_eval_one(int cost_id, const double* x, in
     else return kabc_cost_eval(cost_id, x, D, params, data, ndata, rng);
 }
 
+// the cost of row x under the stream (seed, t = rep, walker, KABC_DOM_EVAL_COST): one item of cost_eval_kernel, and
+// the cost of a row of abc_reject_kernel.hpp.  logtab: the workgroup's LDS copy of kabc_log_tab, or nullptr
+template <int COST>
+__device__ __forceinline__ double cost_eval_item(int cost_id, const double* x, int D, const double* params,
+                                                 const double* data, int64_t ndata, uint64_t seed, uint64_t rep,
+                                                 uint32_t walker, const double* logtab) {
+    kabc_cost_rng_t rng = {seed, rep, walker, KABC_DOM_EVAL_COST, 0u, 0u, nullptr, logtab};
+    double aux[KABC_COST_MAX_AUX];
+    if constexpr (COST == KABC_COST_NORMAL_MEANSTD_SIM) {  // (the prepared words, computed here: same bits as in place)
+        cost_eval_meanstd_prepare(params, &rng, aux);
+        rng.aux = aux;
+        rng.aux_stride = 1u;
+    }
+    return cost_eval_one<COST>(cost_id, x, D, params, data, ndata, &rng);
+}
+
 template <int COST>
 __global__ void __launch_bounds__(kEvalBlock) cost_eval_kernel(const CostEvalArgs A) {
     extern __shared__ __attribute__((aligned(16))) double eval_rows[];
@@ -131,16 +147,9 @@ __global__ void __launch_bounds__(kEvalBlock) cost_eval_kernel(const CostEvalArg
     if (tid >= A.ipb || g >= total) return;
     const int64_t row = g / nrep;
     const int rep = (int)(g - row * nrep);
-    kabc_cost_rng_t rng = {A.seed, A.rep0 + (uint64_t)rep, A.walker0 + (uint32_t)row, KABC_DOM_EVAL_COST, 0u, 0u,
-                           nullptr, kTab ? s_logtab : nullptr};
-    double aux[KABC_COST_MAX_AUX];
-    if constexpr (COST == KABC_COST_NORMAL_MEANSTD_SIM) {  // (the prepared words, computed here: same bits as in place)
-        cost_eval_meanstd_prepare(A.cost_params, &rng, aux);
-        rng.aux = aux;
-        rng.aux_stride = 1u;
-    }
-    A.out[g] = cost_eval_one<COST>(A.cost_id, eval_rows + (int)(row - row0) * Dp, D, A.cost_params, A.cost_data,
-                                   A.cost_ndata, &rng);
+    A.out[g] = cost_eval_item<COST>(A.cost_id, eval_rows + (int)(row - row0) * Dp, D, A.cost_params, A.cost_data,
+                                    A.cost_ndata, A.seed, A.rep0 + (uint64_t)rep, A.walker0 + (uint32_t)row,
+                                    kTab ? s_logtab : nullptr);
 }
 
 #ifndef __HIPCC_RTC__  // host side
@@ -178,6 +187,8 @@ inline void launch_cost_eval(CostEvalArgs a, hipStream_t s) {
     a.ipb = G.ipb;
     hipLaunchKernelGGL((cost_eval_kernel<COST>), dim3(G.grid), dim3(G.block), G.lds, s, a);
 }
+// the launcher of a built-in cost's kernel, nullptr for any other id (capi_cost_eval.hip holds the instantiations)
+CostEvalLaunchFn cost_eval_launcher(int cost_id);
 #endif
 
 }  // namespace kabc

@@ -46,7 +46,10 @@ enum PluginFamily {
     kPfPfilterBatch,
     // (hipRTC user costs) the cost evaluated outside a sampler: kabc_cost_eval / kabc_prior_predictive
     // (cost_eval_kernel.hpp; a run-time dimension, any D the cost lists)
-    kPfCostEval
+    kPfCostEval,
+    // (hipRTC user costs) rejection ABC, kabc_abc_reject: the fused draw-evaluate-compact kernel
+    // (abc_reject_kernel.hpp; a run-time dimension, any D the cost lists)
+    kPfAbcReject
 };
 struct PluginKernel {
     void* host = nullptr;

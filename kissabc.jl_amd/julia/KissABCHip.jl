@@ -132,6 +132,32 @@ mutable struct KabcPfilterResult
     cost_evals::UInt64
 end
 
+# kabc_reject_opts_t / kabc_reject_result_t (kabc_abc_reject): numbers 32 / 33 of kabc_abi_sizeof
+mutable struct KabcRejectOpts
+    eps::Float64
+    n_accept::Int64
+    max_draws::Int64
+    keep::Int64
+    seed::UInt64
+    first_row::Int64
+end
+
+mutable struct KabcRejectResult
+    theta::Ptr{Float64}
+    cost::Ptr{Float64}
+    logprior::Ptr{Float64}
+    index::Ptr{Int64}
+    capacity::Int64
+    n_out::Int64
+    draws::Int64
+    accepted_seen::Int64
+    eps::Float64
+    exhausted::Int32
+    course::Int32
+    launches::Int64
+    kernel_ms::Float64
+end
+
 const KABC_ERR_CANCELLED = Cint(7)
 # a cancelled call (cancel!) ends like an interrupted Julia loop would: InterruptException
 check(st) = st == 0 ? nothing : st == KABC_ERR_CANCELLED ? throw(InterruptException()) :
@@ -198,7 +224,9 @@ end
 function __init__()
     mirrors = (KabcPrior, KabcCost, KabcModel, KabcStats, KabcSmcOpts, KabcSmcIter, KabcSmcResult,
                KabcAbcdeOpts, KabcAbcdeResult, KabcPfilterOpts, KabcPfilterResult)
-    for (i, T) in enumerate(mirrors)
+    # (kabc_abi_sizeof numbers 0..10, and the second block from 32 on)
+    numbered = (collect(zip(1:length(mirrors), mirrors))..., (33, KabcRejectOpts), (34, KabcRejectResult))
+    for (i, T) in numbered
         want = ccall((:kabc_abi_sizeof, libkabc), Int32, (Int32,), Int32(i - 1))
         want == sizeof(T) || error("KissABCHip: sizeof($T) = $(sizeof(T)) but libkabc_hip has $want " *
                                    "(include/kabc.h changed; update the struct mirrors)")
@@ -694,6 +722,36 @@ function prior_predictive(prior::Distribution, cost::DeviceCost, n::Integer; nre
     (P = particles_of(prior, theta, 1:n), C = nrep === nothing ? vec(out) : out, logprior = lp)
 end
 
+"""
+    abc_reject(prior, cost; eps, n, draws, keep, seed = 0, first_row = 0)
+Rejection ABC on the GPU (kabc_abc_reject): `eps` and `n` -- the first n draws of the prior with `cost <= eps`, in
+index order (`draws` bounds the rows drawn); `draws` and `keep` -- the `keep` rows with the smallest (cost, index)
+of `draws` draws.  Row i is row i of `prior_predictive(prior, cost, draws; seed, first_row)`, bit for bit; only
+accepted rows leave the device.  Returns (P, C, logprior, eps, index, draws, exhausted).
+"""
+function abc_reject(prior::Distribution, cost::DeviceCost; eps = nothing, n = nothing, draws = nothing, keep = nothing,
+                    seed::Integer = 0, first_row::Integer = 0)
+    (keep === nothing) == (eps === nothing || n === nothing) && error("give either (eps, n) or (draws, keep)")
+    keep === nothing || draws !== nothing || error("keep needs draws")
+    pri = lower_prior(prior)
+    D = length(pri)
+    cap = Int(keep === nothing ? n : keep)
+    theta = Matrix{Float64}(undef, D, cap)
+    C, lp, index = Vector{Float64}(undef, cap), Vector{Float64}(undef, cap), Vector{Int64}(undef, cap)
+    o = Ref(KabcRejectOpts(keep === nothing ? Float64(eps) : NaN, keep === nothing ? cap : 0,
+                           draws === nothing ? 0 : Int(draws), keep === nothing ? 0 : cap, UInt64(seed), first_row))
+    r = Ref(KabcRejectResult(pointer(theta), pointer(C), pointer(lp), pointer(index), cap, 0, 0, 0, NaN, 0, 0, 0, -1.0))
+    GC.@preserve pri cost theta C lp index o r begin
+        # (the two structs go as untyped pointers: their mirrors are checked in __init__)
+        check(ccall((:kabc_abc_reject, libkabc), Cint,
+                    (Ptr{Cvoid}, Ptr{KabcPrior}, Int32, Ref{KabcCost}, Ptr{Cvoid}, Ptr{Cvoid}),
+                    context(), pri, D, kcost(cost), Base.unsafe_convert(Ptr{Cvoid}, o), Base.unsafe_convert(Ptr{Cvoid}, r)))
+    end
+    m = Int(r[].n_out)
+    (P = particles_of(prior, theta, 1:m), C = C[1:m], logprior = lp[1:m], eps = r[].eps, index = index[1:m],
+     draws = Int(r[].draws), exhausted = r[].exhausted != 0)
+end
+
 # smc(prior, cost::DeviceCost; ...) -- replaces src/smc.jl:92-206, same keywords and defaults
 function KissABC.smc(prior::Distribution, cost::DeviceCost; rng = Random.GLOBAL_RNG,
                      nparticles::Int = 100, alpha = 0.95, mcmc_retrys::Int = 0, mcmc_tol = 0.015,
@@ -833,7 +891,7 @@ function spec_counters()
     (started = out[1], loaded = out[2], failed = out[3], cache_hits = out[4])
 end
 
-export cancel!, clear_cancel!, cost_eval, prior_predictive, DeviceCost, UserCost, UserPrior, compile_model, release_model, prefetch_model, spec_counters, set_specialize, rtc_cache_dir, UserMvPrior, InitFrom, InitFromSnippet, GaussDist, Rosenbrock, HierGaussSim, NormalMeanStdSim, DiracSq,
+export cancel!, clear_cancel!, cost_eval, prior_predictive, abc_reject, DeviceCost, UserCost, UserPrior, compile_model, release_model, prefetch_model, spec_counters, set_specialize, rtc_cache_dir, UserMvPrior, InitFrom, InitFromSnippet, GaussDist, Rosenbrock, HierGaussSim, NormalMeanStdSim, DiracSq,
        AbsDiff, NormShell, NoisyQuadDU, Mixture, NoisyBanana, WienerRms, sample_sharded, unique_id,
        comm_init_rank
 end # module

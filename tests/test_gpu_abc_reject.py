@@ -1,0 +1,423 @@
+"""-m gpu: abc_reject (kabc_abc_reject; the kernels of csrc/abc_reject_kernel.hpp).
+
+The contract under test (include/kabc.h): a result is, bit for bit, a SELECTION of rows of
+prior_predictive(prior, cost, draws, seed=seed, first_row=first_row) -- threshold mode the first n rows with
+C <= eps, keep mode the k smallest (C, i).  Every comparison is on the bit patterns (view(np.uint64)), as in
+tests/test_gpu_cost_eval.py; the selections are those of tests/abc_reject_oracle.py, which a subset of the cases
+also feeds from the CPU oracle's own table, so the check is not only GPU against GPU."""
+import math
+import threading
+
+import numpy as np
+import pytest
+
+from abc_reject_oracle import oracle_reject, select_keep, select_threshold
+
+pytestmark = pytest.mark.gpu
+
+FIRST_ROWS = (0, (1 << 31) + 5)                      # those of tests/test_gpu_cost_eval.py
+SEEDS = (3, 0x9E3779B97F4A7C15)
+DIMS = (1, 2, 8, 16, 17, 40, 128)
+
+
+def _bits(a):
+    return np.ascontiguousarray(np.asarray(a, dtype=np.float64)).view(np.uint64)
+
+
+def _same(got, want, what):
+    g, w = _bits(got), _bits(want)
+    assert g.shape == w.shape, (what, g.shape, w.shape)
+    if not np.array_equal(g, w):
+        bad = np.argwhere(g != w)
+        raise AssertionError(f"{what}: {bad.shape[0]} of {g.size} differ, first at {bad[0].tolist()}: "
+                             f"{np.asarray(got).reshape(g.shape)[tuple(bad[0])]!r} != "
+                             f"{np.asarray(want).reshape(w.shape)[tuple(bad[0])]!r}")
+
+
+def _check(r, table, idx, draws, exhausted, what, eps=None):
+    """the RejectResult r against rows idx of the table (P, logprior, C)"""
+    P, lp, C_ = table
+    assert np.array_equal(r.info["index"], idx), (what, r.info["index"][:8], idx[:8], r.info["index"].size, idx.size)
+    _same(r.P, P[idx], (what, "P"))
+    _same(r.C, C_[idx], (what, "C"))
+    _same(r.logprior, lp[idx], (what, "logprior"))
+    assert r.info["draws"] == draws and r.info["exhausted"] == exhausted, (what, r.info, draws, exhausted)
+    if eps is not None:
+        _same([r.eps], [eps], (what, "eps"))
+    assert r.info["acceptance"] == idx.size / draws
+
+
+def _cost_dims(k):
+    """every built-in cost of _cases in tests/test_gpu_cost_eval.py with the dimensions of DIMS it accepts:
+    (name, D -> cost, [D...])"""
+    rng = np.random.default_rng(5)
+    centers = {D: rng.normal(size=D) for D in DIMS}
+    ybars = {D: rng.normal(size=D - 2) for D in DIMS if D >= 3}
+    wiener = np.sqrt(0.25 * np.arange(31.0) ** 2 + 4.0 * np.arange(31.0))
+    return [
+        ("GaussDist", lambda D: k.costs.GaussDist(centers[D]), list(DIMS)),
+        ("Rosenbrock", lambda D: k.costs.Rosenbrock(), [D for D in DIMS if D >= 2]),
+        ("HierGaussSim", lambda D: k.costs.HierGaussSim(ybars[D]), [D for D in DIMS if D >= 3]),
+        ("NormalMeanStdSim", lambda D: k.costs.NormalMeanStdSim(1000, 2.0, 0.04), [2]),
+        ("DiracSq", lambda D: k.costs.DiracSq(1.5), [1]),
+        ("AbsDiff", lambda D: k.costs.AbsDiff(1.5), [1]),
+        ("NormShell", lambda D: k.costs.NormShell(1.5), list(DIMS)),
+        ("NoisyQuadDU", lambda D: k.costs.NoisyQuadDU(5.5), [2]),
+        ("Mixture", lambda D: k.costs.Mixture(0.0), [1]),
+        ("NoisyBanana", lambda D: k.costs.NoisyBanana(0.5), [2]),
+        ("WienerRms", lambda D: k.costs.WienerRms(wiener), [2]),
+    ]
+
+
+def _families(k):
+    """one prior of every prebuilt family"""
+    return [k.Normal(0.3, 1.2), k.Uniform(-2, 3), k.TruncatedNormal(0.5, 1.0, -1.0, 2.5), k.Beta(2.0, 3.0),
+            k.DiscreteUniform(-3, 3), k.NegativeBinomial(3.0, 0.4), k.Exponential(1.5), k.Gamma(2.0, 0.7),
+            k.LogNormal(0.1, 0.5)]
+
+
+def _prior(k, D, shift):
+    fam = _families(k)
+    comps = [fam[(shift + j) % len(fam)] for j in range(D)]
+    return comps[0] if D == 1 else k.Factored(*comps)
+
+
+# ---- 1. identity with prior_predictive ------------------------------------------------------------
+def test_identity_with_prior_predictive(k, gpu_ctx):
+    N = 30000
+    ran_ids, courses, families = set(), set(), set()
+    shift = 0
+    for name, make, dims in _cost_dims(k):
+        for D in dims:
+            cost = make(D)
+            for seed, first_row in zip(SEEDS, FIRST_ROWS):
+                prior = _prior(k, D, shift)
+                families |= {(shift + j) % 9 for j in range(D)}
+                shift += 1
+                t = k.prior_predictive(prior, cost, N, seed=seed, first_row=first_row, return_array=True)
+                table = (t.P, t.logprior, t.C)
+                what = (name, D, seed, first_row)
+                for q in (0.5, 1e-2, 1e-4):
+                    eps = float(np.nanquantile(t.C, q, method="lower"))      # an element of the table
+                    count = int(np.count_nonzero(t.C <= eps))
+                    assert count >= 1, (what, q, eps)
+                    for n in sorted({1, max(1, count // 2), count}):
+                        idx, draws, ex = select_threshold(t.C, eps, n)
+                        assert not ex and draws <= N
+                        r = k.abc_reject(prior, cost, eps, n, draws=N, seed=seed, first_row=first_row, return_array=True)
+                        _check(r, table, idx, draws, False, what + ("eps", q, n), eps)
+                        courses.add(r.info["course"])
+                    idx, draws, ex = select_threshold(t.C, eps, count + 5)   # more than the budget holds
+                    assert ex and draws == N and idx.size == count
+                    r = k.abc_reject(prior, cost, eps, count + 5, draws=N, seed=seed, first_row=first_row,
+                                     return_array=True)
+                    _check(r, table, idx, N, True, what + ("eps", q, "exhausted"), eps)
+                for kk in (1, 100, N // 2):
+                    idx, eps = select_keep(t.C, kk)
+                    r = k.abc_reject(prior, cost, draws=N, keep=kk, seed=seed, first_row=first_row, return_array=True)
+                    _check(r, table, idx, N, False, what + ("keep", kk), eps)
+                    courses.add(r.info["course"])
+                assert r.info["course"] == ("phases" if D == 128 else "fused"), (what, r.info)
+            ran_ids.add(cost.id)
+    # what a case may skip is a dimension its cost does not accept, nothing else
+    assert sorted(ran_ids) == list(range(1, 12)), ran_ids
+    assert courses == {"fused", "phases"}, courses
+    assert families == set(range(9)), families
+
+
+def test_identity_with_the_oracle(k, orc, gpu_ctx):
+    """the same identity with the table made by the CPU oracle (factored_rand, push_p, factored_logpdf, cost_eval)"""
+    rng = np.random.default_rng(11)
+    cases = [
+        (k.Factored(k.Normal(1, 0.5), k.DiscreteUniform(1, 10)), k.costs.NoisyQuadDU(5.5), 3000),
+        (k.Factored(k.Uniform(1, 3), k.Uniform(0, 0.1)), k.costs.NormalMeanStdSim(1000, 2.0, 0.04), 600),
+        (k.Factored(k.Normal(0, 2), k.Normal(0, 2)), k.costs.NoisyBanana(0.5), 3000),
+        (_prior(k, 17, 2), k.costs.Rosenbrock(), 3000),
+        (_prior(k, 40, 5), k.costs.HierGaussSim(rng.normal(size=38)), 2000),
+        (_prior(k, 128, 7), k.costs.GaussDist(rng.normal(size=128)), 1000),
+        (k.Gamma(2.0, 0.7), k.costs.Mixture(0.0), 3000),
+    ]
+    courses = set()
+    for (prior, cost, N), (seed, first_row) in zip(cases, [(SEEDS[i % 2], FIRST_ROWS[(i // 2) % 2]) for i in range(7)]):
+        P, C_, lp, _, idx, _, _ = oracle_reject(orc, prior, cost, draws=N, keep=N, seed=seed, first_row=first_row)
+        finite = np.sort(C_[np.isfinite(C_)])
+        for eps, n in ((float(finite[finite.size // 2]), 50), (float(finite[20]), 21), (float(finite[20]), 40)):
+            Po, Co, lpo, eo, io, do, xo = oracle_reject(orc, prior, cost, eps=eps, n=n, draws=N, seed=seed,
+                                                        first_row=first_row)
+            r = k.abc_reject(prior, cost, eps, n, draws=N, seed=seed, first_row=first_row, return_array=True)
+            what = (cost.name, N, seed, first_row, eps, n)
+            assert np.array_equal(r.info["index"], io), what
+            _same(r.P, Po, what + ("P",))
+            _same(r.C, Co, what + ("C",))
+            _same(r.logprior, lpo, what + ("logprior",))
+            assert (r.info["draws"], r.info["exhausted"]) == (do, xo), (what, r.info)
+            courses.add(r.info["course"])
+        for kk in (1, 100):
+            Po, Co, lpo, eo, io, do, xo = oracle_reject(orc, prior, cost, draws=N, keep=kk, seed=seed,
+                                                        first_row=first_row)
+            r = k.abc_reject(prior, cost, draws=N, keep=kk, seed=seed, first_row=first_row, return_array=True)
+            what = (cost.name, N, seed, first_row, "keep", kk)
+            assert np.array_equal(r.info["index"], io), what
+            _same(r.P, Po, what + ("P",))
+            _same(r.C, Co, what + ("C",))
+            _same(r.logprior, lpo, what + ("logprior",))
+            _same([r.eps], [eo], what + ("eps",))
+    assert courses == {"fused", "phases"}
+
+
+# ---- 2. independence of the cutting ---------------------------------------------------------------
+def test_result_does_not_depend_on_the_launches(k, gpu_ctx, monkeypatch):
+    prior, cost = k.Normal(0, 1), k.costs.Mixture(0.0)
+    calls = [dict(eps=0.002, n=2000, draws=1 << 22), dict(draws=(1 << 21) + 777, keep=500)]
+    base, launches = [], []
+    for rows in ("1000", "65536", None):
+        if rows is None:
+            monkeypatch.delenv("KABC_EVAL_ROWS", raising=False)
+        else:
+            monkeypatch.setenv("KABC_EVAL_ROWS", rows)
+        got = [k.abc_reject(prior, cost, seed=SEEDS[1], first_row=77, return_array=True, **kw) for kw in calls]
+        launches.append([r.info["launches"] for r in got])
+        if not base:
+            base = got
+            continue
+        for r, b, kw in zip(got, base, calls):
+            what = (rows, sorted(kw))
+            assert np.array_equal(r.info["index"], b.info["index"]), what
+            _same(r.P, b.P, what + ("P",))
+            _same(r.C, b.C, what + ("C",))
+            _same(r.logprior, b.logprior, what + ("logprior",))
+            _same([r.eps], [b.eps], what + ("eps",))
+            assert (r.info["draws"], r.info["exhausted"]) == (b.info["draws"], b.info["exhausted"]), what
+    assert base[0].info["draws"] > 1 << 20 and not base[0].info["exhausted"]     # more than one default launch
+    assert len(base[0].C) == 2000 and len(base[1].C) == 500
+    for j in range(2):
+        assert launches[0][j] > launches[1][j] > launches[2][j], launches
+
+
+# ---- 3. overflow ----------------------------------------------------------------------------------
+def test_overflow_returns_every_row(k, gpu_ctx):
+    """eps = +Inf accepts every row whose cost is not NaN: the first launch (300 000 rows against an output buffer
+    of 65 536) overflows, the host sees the cursor and repeats the range in pieces -- no row is lost"""
+    N = 300_000
+    prior = k.Factored(k.Normal(0, 2), k.Normal(0, 2))
+    for cost in (k.costs.GaussDist([0.5, -0.5]), k.costs.NoisyBanana(0.5)):
+        t = k.prior_predictive(prior, cost, N, seed=9, first_row=5, return_array=True)
+        r = k.abc_reject(prior, cost, math.inf, N, draws=N, seed=9, first_row=5, return_array=True)
+        _check(r, (t.P, t.logprior, t.C), np.arange(N), N, False, (cost.name, "eps = +Inf"), math.inf)
+        assert r.info["launches"] >= 1 + -(-N // 65536), r.info       # the launch that overflowed + the pieces
+        assert r.info["accepted_seen"] == N
+        if cost.id == 10:
+            assert 0.45 < np.isinf(r.C).mean() < 0.55
+        # keep mode with every row a candidate
+        r = k.abc_reject(prior, cost, draws=N, keep=N, seed=9, first_row=5, return_array=True)
+        _check(r, (t.P, t.logprior, t.C), np.arange(N), N, False, (cost.name, "keep = N"), float(np.max(t.C)))
+
+
+# ---- 4. exhaustion and NaN ------------------------------------------------------------------------
+NAN_SRC = """
+KABC_HD double kabc_user_cost(const double* x, int D, const double* params, const double* data,
+                              int64_t ndata, kabc_cost_rng_t* rng) {
+    double z0, z1;
+    kabc_cost_rng_normal2(rng, &z0, &z1);
+    if (x[0] < params[0]) return KABC_NAN;
+    return kabc_fabs(x[0] - x[1]) + 0.01 * kabc_fabs(z0);
+}
+"""
+
+
+def test_exhaustion_and_nan(k, gpu_ctx, monkeypatch):
+    N = 50000
+    prior = k.Factored(k.Normal(0, 1), k.Normal(0, 1))
+    cost = k.costs.GaussDist([0.0, 4.0])
+    t = k.prior_predictive(prior, cost, N, seed=2, return_array=True)
+    eps = float(np.nextafter(t.C.min(), -np.inf))
+    r = k.abc_reject(prior, cost, eps, 10, draws=N, seed=2, return_array=True)
+    assert r.P.shape == (0, 2) and r.C.shape == (0,) and r.info["index"].size == 0
+    assert r.info["exhausted"] and r.info["draws"] == N and r.info["acceptance"] == 0.0
+    # a user cost that is NaN on about a third of the rows
+    monkeypatch.setenv("KABC_USER_PLUGIN", "hiprtc")
+    nan_cost = k.costs.UserCost(NAN_SRC, dims=[2], params=[-0.4], name="nan_on_some_rows")
+    t = k.prior_predictive(prior, nan_cost, N, seed=2, first_row=11, return_array=True)
+    table = (t.P, t.logprior, t.C)
+    nn = int(np.isnan(t.C).sum())
+    assert 0.25 * N < nn < 0.45 * N
+    idx, draws, ex = select_threshold(t.C, math.inf, N)
+    assert ex and idx.size == N - nn
+    r = k.abc_reject(prior, nan_cost, math.inf, N, draws=N, seed=2, first_row=11, return_array=True)
+    _check(r, table, idx, N, True, "NaN rows, eps = +Inf", math.inf)
+    assert not np.isnan(r.C).any()
+    for kk in (10, N - nn, N - nn + 1, N):
+        idx, eps = select_keep(t.C, kk)
+        assert idx.size == min(kk, N - nn)
+        r = k.abc_reject(prior, nan_cost, draws=N, keep=kk, seed=2, first_row=11, return_array=True)
+        _check(r, table, idx, N, False, ("NaN rows, keep", kk), eps)
+        assert not np.isnan(r.C).any()
+
+
+# ---- 5. a known law -------------------------------------------------------------------------------
+def _Phi(x):
+    return 0.5 * (1.0 + math.erf(x / math.sqrt(2.0)))
+
+
+def test_accepted_draws_follow_the_truncated_prior(k, gpu_ctx):
+    """Normal(0, 1) prior, |x - 1.5| <= 0.3: the accepted draws are independent draws of the standard normal
+    truncated to [1.2, 1.8].  One-sample Kolmogorov-Smirnov against that CDF: by the Dvoretzky-Kiefer-Wolfowitz
+    inequality P(D_n > sqrt(ln(2 / a) / (2 n))) <= a; a = 1e-6, n = 10 000: 0.0269.  The seed is fixed."""
+    n = 10_000
+    r = k.abc_reject(k.Normal(0, 1), k.costs.AbsDiff(1.5), 0.3, n, seed=20240607, return_array=True)
+    x = np.sort(r.P[:, 0])
+    assert x.size == n and not r.info["exhausted"]
+    lo, hi = _Phi(1.2), _Phi(1.8)
+    cdf = (np.array([_Phi(v) for v in x]) - lo) / (hi - lo)
+    ks = max(np.max(np.arange(1, n + 1) / n - cdf), np.max(cdf - np.arange(0, n) / n))
+    bound = math.sqrt(math.log(2 / 1e-6) / (2 * n))
+    print(f"KS = {ks:.5f} (bound {bound:.4f}); acceptance = {n / r.info['draws']:.5f} (law {hi - lo:.5f})")
+    assert abs(bound - 0.0269) < 5e-5
+    assert ks < bound, (ks, bound)
+    p, draws = hi - lo, r.info["draws"]
+    assert abs(p - 0.0792) < 1e-4                       # (0.07914: the figure the issue quotes, to its digits)
+    assert abs(n / draws - p) < 5 * math.sqrt(p * (1 - p) / draws), (n / draws, p, draws)
+    assert x[0] >= 1.2 - 1e-12 and x[-1] <= 1.8 + 1e-12 and np.all(r.C <= 0.3)
+    assert np.all(np.diff(r.info["index"]) > 0) and r.info["index"][-1] + 1 == draws
+
+
+def test_discrete_component_is_projected(k, gpu_ctx):
+    """Factored(Normal(1, 0.5), DiscreteUniform(1, 10)) with NoisyQuadDU(5.5) (the pfilter tests' problem):
+    the accepted second component is integer-valued -- push_p ran before the cost saw the row"""
+    prior = k.Factored(k.Normal(1, 0.5), k.DiscreteUniform(1, 10))
+    r = k.abc_reject(prior, k.costs.NoisyQuadDU(5.5), 0.1, 2000, seed=4)
+    du = np.asarray(r.P[1])
+    assert du.size == 2000 and np.all(du == np.rint(du)) and du.min() >= 1 and du.max() <= 10
+    assert np.all(r.C <= 0.1) and isinstance(r.P[0], k.Particles)
+    # (n^2 + du) n = 5.5 has a root in n for every du: several values of du are hit
+    assert np.unique(du).size >= 3
+    assert r.eps == 0.1 and r.ε == 0.1
+
+
+# ---- 6. user code ---------------------------------------------------------------------------------
+L1_SRC = """
+KABC_HD double kabc_user_cost(const double* x, int D, const double* params, const double* data,
+                              int64_t ndata, kabc_cost_rng_t* rng) {
+    double z0, z1;
+    kabc_cost_rng_normal2(rng, &z0, &z1);
+    return kabc_fabs(x[0] - params[0]) + kabc_fabs(x[1] - params[1]) + kabc_fabs(x[2]) + 0.01 * kabc_fabs(z0);
+}
+"""
+D20_SRC = """
+KABC_HD double kabc_user_cost(const double* x, int D, const double* params,
+                              const double* data, int64_t ndata, kabc_cost_rng_t* rng) {
+    double z0, z1, s = 0.0;
+    kabc_cost_rng_normal2(rng, &z0, &z1);
+    for (int k = 0; k < D; ++k) s += (x[k] - params[0]) * (x[k] - params[0]);
+    return kabc_sqrt(s) + 0.01 * kabc_fabs(z0);
+}"""
+
+
+def _against_table(k, prior, cost, N, seed, first_row, course, what):
+    t = k.prior_predictive(prior, cost, N, seed=seed, first_row=first_row, return_array=True)
+    table = (t.P, t.logprior, t.C)
+    eps = float(np.nanquantile(t.C, 0.02, method="lower"))
+    count = int(np.count_nonzero(t.C <= eps))
+    idx, draws, ex = select_threshold(t.C, eps, count - 3)
+    r = k.abc_reject(prior, cost, eps, count - 3, draws=N, seed=seed, first_row=first_row, return_array=True)
+    _check(r, table, idx, draws, False, (what, "eps"), eps)
+    assert r.info["course"] == course, (what, r.info)
+    idx, e = select_keep(t.C, 150)
+    r = k.abc_reject(prior, cost, draws=N, keep=150, seed=seed, first_row=first_row, return_array=True)
+    _check(r, table, idx, N, False, (what, "keep"), e)
+    assert r.info["course"] == course, (what, r.info)
+
+
+def test_user_costs_and_user_priors(k, gpu_ctx, monkeypatch):
+    monkeypatch.setenv("KABC_USER_PLUGIN", "hiprtc")
+    rng = np.random.default_rng(4)
+    N = 20000
+    # user costs on the fused course: the plugin family of the fused kernel
+    c3 = k.costs.UserCost(L1_SRC, dims=[3], params=[1.0, -0.5], name="l1_noisy_reject")
+    c20 = k.costs.UserCost(D20_SRC, dims=[20], params=[0.25], name="dyn_user_reject")
+    _against_table(k, k.Factored(k.Normal(0, 2), k.Uniform(-2, 2), k.DiscreteUniform(-2, 2)), c3, N, SEEDS[0],
+                   FIRST_ROWS[1], "fused", "UserCost D = 3")
+    _against_table(k, k.Factored(*[k.Normal(0, 1)] * 19, k.Beta(2.0, 2.0)), c20, N, SEEDS[1], FIRST_ROWS[0],
+                   "fused", "UserCost D = 20")
+    # priors the fused kernel cannot draw: the phases course
+    A = rng.normal(size=(4, 4))
+    _against_table(k, k.Factored(k.Laplace(0.5, 1.5), k.Poisson(3.0)), k.costs.NoisyQuadDU(5.5), N, SEEDS[0],
+                   FIRST_ROWS[0], "phases", "user prior families")
+    _against_table(k, k.Dirichlet([1.5, 2.0, 0.7]), k.costs.GaussDist([0.3, 0.3, 0.4]), N, SEEDS[1], FIRST_ROWS[1],
+                   "phases", "Dirichlet")
+    _against_table(k, k.MvNormal(rng.normal(size=4), A @ A.T + 0.4 * np.eye(4)), k.costs.Rosenbrock(), N, SEEDS[0],
+                   FIRST_ROWS[1], "phases", "MvNormal")
+    # a user cost under a user prior
+    _against_table(k, k.Factored(k.Laplace(0.5, 1.5), k.Normal(0, 1), k.Poisson(3.0)), c3, N, SEEDS[1], FIRST_ROWS[0],
+                   "phases", "UserCost under user prior families")
+    # a dimension the snippet does not list
+    with pytest.raises(k.KabcError) as ei:
+        k.abc_reject(k.Factored(k.Normal(0, 1), k.Normal(0, 1)), c3, 0.5, 10)
+    assert ei.value.status == 5, str(ei.value)          # KABC_ERR_UNSUPPORTED
+
+
+def test_user_cost_hipcc_form_is_refused(k, gpu_ctx, monkeypatch):
+    """a cost plugin .so built by hipcc carries no rejection kernel: KABC_ERR_UNSUPPORTED with the message
+    kabc_cost_eval uses.  (The snippet, dims and posteriors of tests/test_gpu_cost_eval.py's hipcc case: one plugin
+    build serves the files.)"""
+    monkeypatch.setenv("KABC_USER_PLUGIN", "hipcc")
+    cost = k.costs.UserCost(D20_SRC, dims=[20], params=[0.25], name="dyn_user_hipcc", posteriors=["kernelized"])
+    with pytest.raises(k.KabcError) as ei:
+        k.abc_reject(k.Factored(*[k.Normal(0, 1)] * 20), cost, 1.0, 10)
+    assert ei.value.status == 5 and "kabc_compile_cost_plugin" in str(ei.value), str(ei.value)
+
+
+# ---- 7. cancel ------------------------------------------------------------------------------------
+def test_cancel(k, gpu_ctx):
+    prior = k.Factored(k.Uniform(1, 3), k.Uniform(0, 0.1))           # the README problem
+    sim = k.costs.NormalMeanStdSim(1000, 2.0, 0.04)
+    ctx = k.Context(0)
+    try:
+        ctx.cancel()                                     # on an idle context: cancels the next call, nothing is launched
+        with pytest.raises(k.Cancelled) as ei:
+            k.abc_reject(prior, sim, 0.5, 100, seed=2, ctx=ctx, return_array=True)
+        assert ei.value.result.info["launches"] == 0 and ei.value.result.info["draws"] == 0
+        assert ei.value.result.C.size == 0
+        want = k.abc_reject(prior, sim, 0.5, 100, seed=2, return_array=True)          # (the default context)
+        got = k.abc_reject(prior, sim, 0.5, 100, seed=2, ctx=ctx, return_array=True)
+        _same(got.P, want.P, "the call after a cancelled one")
+        # a long call: eps accepts about one row in 10^4, two hundred thousand are asked for of 2^31 draws
+        # (some ten seconds of work); the request comes after 0.3 s.  One call, bounded by its budget.
+        timer = threading.Timer(0.3, ctx.cancel)
+        timer.start()
+        try:
+            with pytest.raises(k.Cancelled) as ei:
+                k.abc_reject(prior, sim, 0.02, 200_000, draws=1 << 31, seed=5, first_row=9, ctx=ctx, return_array=True)
+        finally:
+            timer.cancel()
+        r = ei.value.result
+        idx = r.info["index"]
+        assert 0 < idx.size < 200_000 and not r.info["exhausted"]
+        assert np.all(np.diff(idx) > 0) and idx[-1] < r.info["draws"] < 1 << 31
+        assert np.all(r.C <= 0.02)
+        for j in sorted({0, 1, idx.size // 2, idx.size - 1}):
+            t = k.prior_predictive(prior, sim, 1, seed=5, first_row=9 + int(idx[j]), return_array=True)
+            _same(r.P[j], t.P[0], ("row of a cancelled call", j))
+            _same([r.C[j]], t.C, ("cost of a cancelled call", j))
+            _same([r.logprior[j]], t.logprior, ("log-prior of a cancelled call", j))
+        # the context is usable afterwards
+        got = k.abc_reject(prior, sim, 0.5, 100, seed=2, ctx=ctx, return_array=True)
+        _same(got.C, want.C, "the call after a call cancelled under way")
+    finally:
+        ctx.close()
+
+
+# ---- 8. agreement with a sampler ------------------------------------------------------------------
+def test_agrees_with_smc_on_the_banana(k, gpu_ctx):
+    """test/runtests.jl:240-254: NoisyBanana under Factored(Normal(0, 5), Normal(0, 5)), answer (1, 1) by the
+    reference's own rule `p ≈ c`: |mean - c| < 2 std (Particles.isapprox).  Rejection ABC keeps the best 5000 of
+    2^24 draws; smc as tests/test_gpu_reference_testsets.py runs it."""
+    pp = k.Factored(k.Normal(0, 5), k.Normal(0, 5))
+    cost = k.costs.NoisyBanana(0.0)
+    S = k.smc(pp, cost, alpha=0.9, nparticles=500, epstol=0.01, parallel=True, seed=1).P
+    assert S[0].isapprox(1) and S[1].isapprox(1)
+    r = k.abc_reject(pp, cost, draws=1 << 24, keep=5000, seed=1)
+    R = r.P
+    print(f"banana: abc_reject {R[0]!r}, {R[1]!r} (eps {r.eps:.4g}, {r.info['wall_ms']:.1f} ms); smc {S[0]!r}, {S[1]!r}")
+    assert len(R[0]) == 5000 and r.info["draws"] == 1 << 24
+    assert R[0].isapprox(1) and R[1].isapprox(1)
