@@ -356,6 +356,54 @@ void kabc_reject_default_opts(kabc_reject_opts_t* opts);
 kabc_status_t kabc_abc_reject(kabc_ctx_t* ctx, const kabc_prior_t* prior, int32_t D, const kabc_cost_t* cost,
                               const kabc_reject_opts_t* opts, kabc_reject_result_t* result);
 
+/* Rejection ABC for many datasets in one call.  Run r IS kabc_abc_reject(ctx, prior, D, &costs[r], opts', &results[r])
+ * with opts'.seed = seeds[r] (seeds == NULL: opts->seed for every run) and opts'.eps = eps[r] (eps == NULL:
+ * opts->eps for every run; ignored in keep mode); n_accept, max_draws, keep and first_row are shared.  results[r]'s
+ * theta / cost / logprior / index / n_out / draws / eps / exhausted are what that call fills, bit for bit, in both
+ * modes -- in particular draws is the index of run r's n_accept-th accepted row + 1, however long the batch went on
+ * drawing for slower runs.  costs[r] share id, nparams and ndata; params / data differ.  1 <= nruns <= 65535.
+ *
+ * A row is addressed by (seed, first_row + i) alone, so runs that share a seed draw THE SAME theta rows and the same
+ * log-priors (and a simulator cost the same noise): only params / data differ.  That is the reference table of
+ * rejection ABC -- simulate once, reuse for every dataset -- and common random numbers across the runs: each run is a
+ * valid rejection sample, the runs are not independent of each other.  Distinct seeds give independent runs.
+ *
+ * Courses (kabc_reject_batch_stats out[0]):
+ *   0 table  runs that share a seed share their draws: one launch covers a row range for the list of runs still
+ *            active; a lane draws its row into LDS, projects it and sums its log-prior once, then evaluates every
+ *            run's cost on it (csrc/abc_reject_batch_kernel.hpp).  Taken when at least two runs share a seed (or
+ *            nruns == 1) and the shape has the fused kernel.
+ *   1 grid   every run draws its own rows (a second grid dimension); nothing is shared but launches and host looks.
+ *            Taken when all seeds differ, and with KABC_REJECT_BATCH_COURSE=grid for any seeds.  Same bits.
+ *   2 one after another  kabc_abc_reject's driver for each run in turn: the shapes the batch kernel does not take --
+ *            everything on kabc_abc_reject's phases course (user prior families, joint user priors, MvNormal, rows
+ *            too long for the LDS tile, KABC_REJECT_COURSE=phases), user costs (compiled by hipRTC) -- and
+ *            KABC_REJECT_BATCH=0.  Same bits by construction.
+ * One record buffer (KABC_REJECT_CAPACITY records, at least nruns; keep mode without that variable: room for
+ * min(keep, 1024) rows of every run, within 256 MB) and one cursor serve a look; a record carries its run.  A look
+ * never covers fewer rows than capacity / active runs, unless the budget ends.  An overflow is seen as in kabc_abc_reject and the row range repeated in pieces of capacity / active runs rows,
+ * which cannot overflow: no accepted row is dropped.  (Which course and which compaction form is the default is a
+ * matter of speed only and follows profiles/abc_reject_batch_probe.json; see DESIGN.md for what has been measured.)
+ * In threshold mode a run that has its n_accept rows leaves the
+ * list at the next host look.  KABC_REJECT_BATCH_COMPACT=wg: the workgroup form of the compaction.
+ *
+ * On courses 0 and 1 results[r].accepted_seen counts run r's stored records, and launches / kernel_ms are those of
+ * the WHOLE batch, repeated in every result; course is 0 (the fused kernel family).  On course 2 every field is what
+ * the run's own call filled.
+ * status[r] is run r's own verdict; the return value is KABC_OK or the status of the lowest failing run, named in
+ * kabc_last_error() ("run 3: ...").  Checked before ctx is used (KABC_ERR_INVALID_ARG): the list of kabc_abc_reject,
+ * and nruns out of range, NULL costs / results / status, unequal ids / lengths, a NaN eps[r] in threshold mode, a
+ * results[r].capacity that is too small.  kabc_ctx_cancel as in kabc_abc_reject: pending at entry, nothing is
+ * launched; during the call it is seen between two host looks, every run's result holds what its completed rows gave
+ * and the runs that had not finished carry KABC_ERR_CANCELLED.
+ * kabc_reject_batch_stats (the calling thread's last batch): [0] course, [1] kernel launches, [2] runs per launch
+ * (nruns; 1 on course 2), [3] theta rows drawn (rows x groups over all launches; 0 on course 2). */
+kabc_status_t kabc_abc_reject_batch(kabc_ctx_t* ctx, const kabc_prior_t* prior, int32_t D,
+                                    const kabc_cost_t* costs, int64_t nruns, const uint64_t* seeds,
+                                    const double* eps, const kabc_reject_opts_t* opts,
+                                    kabc_reject_result_t* results, kabc_status_t* status);
+void kabc_reject_batch_stats(int64_t out[4]);
+
 /* ---- arithmetic-contract probe (verification only) ---------------------------
  * Evaluates one function of include/kabc_math.h on the device for n host inputs, so
  * that tests can compare the gfx950 code with the host build of the same header bit

@@ -151,6 +151,10 @@ PROTOTYPES = {
     "kabc_reject_default_opts": (None, [C.POINTER(RejectOpts)]),
     "kabc_abc_reject": (C.c_int, [VP, C.POINTER(Prior), C.c_int32, C.POINTER(Cost), C.POINTER(RejectOpts),
                                   C.POINTER(RejectResult)]),
+    "kabc_abc_reject_batch": (C.c_int, [VP, C.POINTER(Prior), C.c_int32, C.POINTER(Cost), C.c_int64,
+                                        C.POINTER(C.c_uint64), c_double_p, C.POINTER(RejectOpts),
+                                        C.POINTER(RejectResult), C.POINTER(C.c_int)]),
+    "kabc_reject_batch_stats": (None, [C.POINTER(C.c_int64)]),
     "kabc_register_cost_plugin": (C.c_int, [C.c_char_p, C.POINTER(C.c_int32)]),
     "kabc_plugin_precompile": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "kabc_compile_cost_plugin": (C.c_int, [C.c_char_p, C.POINTER(C.c_int32), C.c_int32, C.c_int32,

@@ -751,6 +751,109 @@ def abc_reject(prior, cost, eps=None, n=None, *, draws=None, keep=None, seed=0, 
     return result()
 
 
+class RejectBatchResult(list):
+    """abc_reject_batch's result: one RejectResult per run (a list), and `.info` about the whole call."""
+
+    info = None
+
+
+_REJECT_BATCH_COURSES = {0: "table", 1: "grid", 2: "sequential"}
+
+
+def abc_reject_batch(prior, costs, eps=None, n=None, nruns=None, *, seeds=None, seed=0, draws=None, keep=None,
+                     first_row=0, ctx=None, return_array=False):
+    """Rejection ABC for many datasets in one call (kabc_abc_reject_batch, include/kabc.h): run r is
+    `abc_reject(prior, costs[r], eps[r], n, draws=draws, keep=keep, seed=seeds[r], first_row=first_row)`,
+    bit for bit -- P, C, logprior, eps and info's index / draws / exhausted.
+
+    `costs` is a sequence of DeviceCosts, one per dataset, with the same cost id and the same params / data
+    lengths, or one DeviceCost with `nruns` (or `seeds`): the runs then differ by seed or eps only.  `eps` is a
+    number or one per run.  `seeds=None`: every run uses `seed`.
+
+    Runs that share a seed share their θ draws AND the simulator's noise: row i of every such run is the
+    same draw of the prior, evaluated against each dataset -- the reference table of rejection ABC, drawn and
+    scored once (info["course"] == "table").  These are common random numbers: each run is a valid rejection
+    sample for its dataset, but the runs are NOT independent of each other.  `seeds=chain_seeds(seed, nruns)`
+    gives independent runs (info["course"] == "grid": one launch grid, nothing else shared).  Shapes the
+    batch kernel does not take -- user prior families, MvNormal, very long rows, user costs -- and
+    KABC_REJECT_BATCH=0 run one after another ("sequential").  Same bits on every course.
+
+    Returns a RejectBatchResult: a list of RejectResult, entry r as abc_reject returns it (launches and
+    kernel_ms of an entry are the whole batch's on the table and grid courses); `.info` holds course, launches,
+    runs_per_launch, rows_drawn (θ rows drawn over all launches), nruns, status, wall_ms, kernel_ms
+    (KABC_EVAL_TIMING=1).  Context.cancel() / Ctrl-C: Cancelled (its `.result` is the list, every run holding
+    what its completed rows gave) / KeyboardInterrupt; any other failure: KabcError("run r: ...")."""
+    from .costs import check_reject_batch_args
+    fac = as_factored(prior)
+    scalar = isinstance(prior, UnivariateDistribution)
+    D = len(fac)
+    cost_list, seeds, eps_list, n_accept, max_draws, k = check_reject_batch_args(
+        costs, D, eps, n, nruns, seeds, draws, keep, first_row)
+    R = len(cost_list)
+    lib = _lib.load()
+    ctx = ctx or _lib.default_context()
+    t0 = time.perf_counter()
+    o = cd.RejectOpts()
+    lib.kabc_reject_default_opts(C.byref(o))
+    if eps_list:
+        o.eps = eps_list[0]
+    o.n_accept, o.max_draws, o.keep, o.seed, o.first_row = n_accept, max_draws, k, int(seed), int(first_row)
+    cap = max(n_accept, k)
+    theta = _lib.result_empty((R, cap, D))
+    Cst, lp = _lib.result_empty((R, cap)), _lib.result_empty((R, cap))
+    index = np.empty((R, cap), dtype=np.int64)
+    # the R result records, written through a uint64 view (the fields set here are 8 bytes wide)
+    res = (cd.RejectResult * R)()
+    w = np.frombuffer(res, dtype=np.uint64).reshape(R, C.sizeof(cd.RejectResult) // 8)
+    rr = np.arange(R, dtype=np.uint64)
+    col = lambda f: getattr(cd.RejectResult, f).offset // 8   # noqa: E731
+    w[:, col("theta")] = np.uint64(theta.ctypes.data) + rr * np.uint64(cap * D * 8)
+    w[:, col("cost")] = np.uint64(Cst.ctypes.data) + rr * np.uint64(cap * 8)
+    w[:, col("logprior")] = np.uint64(lp.ctypes.data) + rr * np.uint64(cap * 8)
+    w[:, col("index")] = np.uint64(index.ctypes.data) + rr * np.uint64(cap * 8)
+    w[:, col("capacity")] = np.uint64(cap)
+    cc_of = {}   # (one record per distinct DeviceCost: a repeated one points at the same params)
+    for c in cost_list:
+        if id(c) not in cc_of:
+            cc_of[id(c)] = c.to_c()
+    ccs = (cd.Cost * R)(*[cc_of[id(c)] for c in cost_list])
+    sd = (C.c_uint64 * R)(*seeds) if seeds is not None else None
+    ev = (C.c_double * R)(*eps_list) if eps_list else None
+    st = (C.c_int * R)()
+    with ctx.interruptible():
+        status = lib.kabc_abc_reject_batch(ctx.handle, fac.to_c(), D, ccs, R, sd, ev, C.byref(o), res, st)
+        t1 = time.perf_counter()
+        bs = (C.c_int64 * 4)()
+        lib.kabc_reject_batch_stats(bs)
+
+        def entry(r):
+            x = res[r]
+            m = int(x.n_out)
+            info = {"index": index[r, :m], "draws": int(x.draws), "accepted_seen": int(x.accepted_seen),
+                    "exhausted": bool(x.exhausted), "course": "phases" if x.course else "fused",
+                    "launches": int(x.launches), "kernel_ms": x.kernel_ms,
+                    "acceptance": m / x.draws if x.draws else math.nan}
+            P = theta[r, :m]
+            return RejectResult(P if return_array else _bundle(P, scalar), Cst[r, :m], lp[r, :m], x.eps, info)
+
+        out = RejectBatchResult(entry(r) for r in range(R))
+        kms = [res[r].kernel_ms for r in range(R)]
+        out.info = {"course": _REJECT_BATCH_COURSES.get(int(bs[0]), int(bs[0])), "launches": int(bs[1]),
+                    "runs_per_launch": int(bs[2]), "rows_drawn": int(bs[3]), "nruns": R,
+                    "status": [int(x) for x in st], "wall_ms": (t1 - t0) * 1e3,
+                    "kernel_ms": (sum(kms) if bs[0] == 2 else kms[0]) if kms[0] >= 0 else -1.0}
+        if status != 0:
+            try:
+                _lib.check(status)
+            except _lib.Cancelled as e:
+                e.result = out
+                raise
+            except _lib.KabcError as e:
+                e.results = out
+                raise
+        return out
+
+
 class SmcBatchResult(list):
     """smc_batch's result: one SmcResult per run (a list), and `.info` about the whole call."""
 

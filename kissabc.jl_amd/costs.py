@@ -123,6 +123,44 @@ def check_reject_args(cost, D, eps, n, draws, keep, first_row):
     return (0 if keep is not None else int(n)), (0 if draws is None else int(draws)), (0 if keep is None else int(keep))
 
 
+def check_reject_batch_args(costs, D, eps, n, nruns, seeds, draws, keep, first_row):
+    """the refusals of abc_reject_batch that need no library; returns (cost_list, seeds or None, eps_list or
+    None, n_accept, max_draws, keep): seeds None = one seed for every run, eps_list None = keep mode"""
+    if isinstance(costs, DeviceCost):
+        if nruns is None and seeds is None:
+            raise ValueError("abc_reject_batch: nruns or seeds is required with a single DeviceCost")
+        nruns = len(seeds) if nruns is None else int(nruns)
+        cost_list = [costs] * max(nruns, 0)
+    else:
+        cost_list = list(costs)
+        if not all(isinstance(c, DeviceCost) for c in cost_list):
+            raise TypeError("`costs` must be a DeviceCost or a sequence of DeviceCosts on the MI355X path")
+        nruns = len(cost_list) if nruns is None else int(nruns)
+        if len(cost_list) != nruns:
+            raise ValueError(f"abc_reject_batch: {len(cost_list)} costs for nruns = {nruns}")
+    if not 1 <= nruns <= 65535:
+        raise ValueError(f"abc_reject_batch: nruns = {nruns} is outside 1..65535")
+    c0 = cost_list[0]
+    for i, c in enumerate(cost_list):
+        if c.id != c0.id or c.params.size != c0.params.size or c.data.size != c0.data.size:
+            raise ValueError(f"abc_reject_batch: cost {i} differs from cost 0 in its id or its params / data lengths")
+    if seeds is not None:
+        seeds = [int(x) for x in seeds]
+        if len(seeds) != nruns:
+            raise ValueError(f"abc_reject_batch: len(seeds) = {len(seeds)} != nruns = {nruns}")
+    eps_list = None
+    if keep is None and eps is not None:
+        eps_list = [float(x) for x in eps] if np.ndim(eps) else [float(eps)] * nruns
+        if len(eps_list) != nruns:
+            raise ValueError(f"abc_reject_batch: len(eps) = {len(eps_list)} != nruns = {nruns}")
+        for r, e in enumerate(eps_list):
+            if math.isnan(e):
+                raise ValueError(f"abc_reject_batch: eps of run {r} is NaN")
+    n_accept, max_draws, k = check_reject_args(c0, D, None if eps is None else (eps_list[0] if eps_list else eps),
+                                               n, draws, keep, first_row)
+    return cost_list, seeds, eps_list, n_accept, max_draws, k
+
+
 def GaussDist(center):
     """‖x − c‖₂"""
     return DeviceCost(cd.COST_GAUSS_DIST, params=center, name="gauss_dist")

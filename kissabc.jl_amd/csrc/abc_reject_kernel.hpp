@@ -12,8 +12,8 @@
 // (rows D | 1 words apart as in cost_eval_kernel.hpp, run-time D, the row behind its LDS pointer; no other lane
 // touches it, so the tile needs no barrier), projects it, sums its log-prior and evaluates its cost.  A workgroup
 // walks tiles of blockDim.x rows with a grid stride.
-// abc_reject_compact_kernel (the phases course: user prior families, joint priors, MvNormal, rows too long for
-// the tile): the rows, log-priors and costs were written to global memory by the kernels of kabc_prior_predictive;
+// abc_reject_compact_kernel (defined in capi_abc_reject.hip, the one file that launches it; the phases course: user
+// prior families, joint priors, MvNormal, rows too long for the tile): the rows, log-priors and costs were written to global memory by the kernels of kabc_prior_predictive;
 // a lane reads the cost of its row and appends the row the same way.
 //
 // Compaction (reject_append): a wave-level ballot of the accepting lanes (wave64: a 64-bit mask) gives each its
@@ -126,22 +126,7 @@ __global__ void __launch_bounds__(kRejectBlock) abc_reject_kernel(const AbcRejec
     }
 }
 
-#ifndef __HIPCC_RTC__  // (the phases course never runs a run-time compiled copy of this kernel)
-__global__ void __launch_bounds__(kRejectBlock) abc_reject_compact_kernel(const AbcRejectArgs A) {
-    __shared__ unsigned s_wcnt[kRejectMaxWaves];
-    __shared__ unsigned long long s_wbase[kRejectMaxWaves];
-    const int tid = threadIdx.x, nthreads = blockDim.x;
-    const int64_t ntiles = (A.nrows + nthreads - 1) / nthreads;
-    for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const int64_t row = tile * nthreads + tid;
-        const bool in = row < A.nrows;
-        const double c = in ? A.cost_in[row] : 0.0;
-        const bool acc = in && c <= A.tau;
-        reject_append(A, acc, A.theta_in + (acc ? row : 0) * A.D, c, acc ? A.lp_in[row] : 0.0, A.row0 + row, s_wcnt,
-                      s_wbase);
-    }
-}
-
+#ifndef __HIPCC_RTC__  // (the host side)
 // Launch geometry.  Fused: a workgroup of kRejectBlock lanes when their rows fit the LDS budget of
 // cost_eval_kernel.hpp, else one wavefront when 64 rows fit (D <= 111), else the shape takes the phases course
 // (block == 0).  The grid is capped: a workgroup walks several tiles, the log table is staged once.
@@ -170,11 +155,6 @@ inline void launch_abc_reject(const AbcRejectArgs& a, unsigned block, hipStream_
     const RejectGeom G = reject_geom(a.nrows, block, a.D);
     if (G.grid == 0) return;
     hipLaunchKernelGGL((abc_reject_kernel<COST>), dim3(G.grid), dim3(G.block), G.lds, s, a);
-}
-inline void launch_abc_reject_compact(const AbcRejectArgs& a, hipStream_t s) {
-    const RejectGeom G = reject_geom(a.nrows, kRejectBlock, a.D);
-    if (G.grid == 0) return;
-    hipLaunchKernelGGL(abc_reject_compact_kernel, dim3(G.grid), dim3(G.block), 0, s, a);
 }
 #endif
 

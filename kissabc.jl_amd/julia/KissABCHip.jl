@@ -752,6 +752,59 @@ function abc_reject(prior::Distribution, cost::DeviceCost; eps = nothing, n = no
      draws = Int(r[].draws), exhausted = r[].exhausted != 0)
 end
 
+"""
+    abc_reject_batch(prior, costs; eps, n, draws, keep, seeds = nothing, seed = 0, first_row = 0)
+Rejection ABC for many datasets in one call (kabc_abc_reject_batch): `costs` holds one DeviceCost per dataset (same
+formula, same params / data lengths); run r is `abc_reject(prior, costs[r]; eps = eps[r], seed = seeds[r], ...)`, bit
+for bit.  `eps` is a number or one per run.  Runs that share a seed (`seeds === nothing`: all of them) share their
+draws of the prior and the simulator's noise -- the reference table of rejection ABC, common random numbers across the
+datasets; distinct `seeds` give independent runs.  Returns a vector of abc_reject's named tuples.
+"""
+function abc_reject_batch(prior::Distribution, costs::AbstractVector{<:DeviceCost}; eps = nothing, n = nothing,
+                          draws = nothing, keep = nothing, seeds = nothing, seed::Integer = 0, first_row::Integer = 0)
+    (keep === nothing) == (eps === nothing || n === nothing) && error("give either (eps, n) or (draws, keep)")
+    keep === nothing || draws !== nothing || error("keep needs draws")
+    R = length(costs)
+    1 <= R <= 65535 || error("abc_reject_batch: 1..65535 costs")
+    pri = lower_prior(prior)
+    D = length(pri)
+    cap = Int(keep === nothing ? n : keep)
+    theta = Array{Float64}(undef, D, cap, R)
+    C, lp, index = Matrix{Float64}(undef, cap, R), Matrix{Float64}(undef, cap, R), Matrix{Int64}(undef, cap, R)
+    kc = [kcost(c) for c in costs]
+    sd = seeds === nothing ? fill(UInt64(seed), R) : UInt64[UInt64(x) for x in seeds]
+    ev = keep !== nothing ? fill(NaN, R) : eps isa Number ? fill(Float64(eps), R) : Float64[Float64(x) for x in eps]
+    (length(sd) == R && length(ev) == R) || error("abc_reject_batch: one seed and one eps per cost")
+    o = Ref(KabcRejectOpts(ev[1], keep === nothing ? cap : 0, draws === nothing ? 0 : Int(draws),
+                           keep === nothing ? 0 : cap, UInt64(seed), first_row))
+    # the R result records as 8-byte words (exhausted and course share one)
+    W = sizeof(KabcRejectResult) >> 3
+    word(f) = Int(fieldoffset(KabcRejectResult, findfirst(==(f), fieldnames(KabcRejectResult)))) >> 3 + 1
+    res = zeros(UInt64, W, R)
+    status = zeros(Cint, R)
+    GC.@preserve pri costs kc theta C lp index sd ev o res status begin
+        for r in 1:R
+            res[word(:theta), r] = UInt64(UInt(pointer(theta, 1 + D * cap * (r - 1))))
+            res[word(:cost), r] = UInt64(UInt(pointer(C, 1 + cap * (r - 1))))
+            res[word(:logprior), r] = UInt64(UInt(pointer(lp, 1 + cap * (r - 1))))
+            res[word(:index), r] = UInt64(UInt(pointer(index, 1 + cap * (r - 1))))
+            res[word(:capacity), r] = UInt64(cap)
+        end
+        check(ccall((:kabc_abc_reject_batch, libkabc), Cint,
+                    (Ptr{Cvoid}, Ptr{KabcPrior}, Int32, Ptr{KabcCost}, Int64, Ptr{UInt64}, Ptr{Float64}, Ptr{Cvoid},
+                     Ptr{Cvoid}, Ptr{Cvoid}),
+                    context(), pri, D, kc, R, sd, keep === nothing ? pointer(ev) : Ptr{Float64}(C_NULL),
+                    Base.unsafe_convert(Ptr{Cvoid}, o), pointer(res), pointer(status)))
+    end
+    map(1:R) do r
+        m = Int(reinterpret(Int64, res[word(:n_out), r]))
+        flags = res[word(:exhausted), r]          # (exhausted: the low half of the word, course: the high half)
+        (P = particles_of(prior, theta[:, :, r], 1:m), C = C[1:m, r], logprior = lp[1:m, r],
+         eps = reinterpret(Float64, res[word(:eps), r]), index = index[1:m, r],
+         draws = Int(reinterpret(Int64, res[word(:draws), r])), exhausted = (flags & 0xffffffff) != 0)
+    end
+end
+
 # smc(prior, cost::DeviceCost; ...) -- replaces src/smc.jl:92-206, same keywords and defaults
 function KissABC.smc(prior::Distribution, cost::DeviceCost; rng = Random.GLOBAL_RNG,
                      nparticles::Int = 100, alpha = 0.95, mcmc_retrys::Int = 0, mcmc_tol = 0.015,
@@ -891,7 +944,7 @@ function spec_counters()
     (started = out[1], loaded = out[2], failed = out[3], cache_hits = out[4])
 end
 
-export cancel!, clear_cancel!, cost_eval, prior_predictive, abc_reject, DeviceCost, UserCost, UserPrior, compile_model, release_model, prefetch_model, spec_counters, set_specialize, rtc_cache_dir, UserMvPrior, InitFrom, InitFromSnippet, GaussDist, Rosenbrock, HierGaussSim, NormalMeanStdSim, DiracSq,
+export cancel!, clear_cancel!, cost_eval, prior_predictive, abc_reject, abc_reject_batch, DeviceCost, UserCost, UserPrior, compile_model, release_model, prefetch_model, spec_counters, set_specialize, rtc_cache_dir, UserMvPrior, InitFrom, InitFromSnippet, GaussDist, Rosenbrock, HierGaussSim, NormalMeanStdSim, DiracSq,
        AbsDiff, NormShell, NoisyQuadDU, Mixture, NoisyBanana, WienerRms, sample_sharded, unique_id,
        comm_init_rank
 end # module
