@@ -577,7 +577,13 @@ kabc_status_t kabc_ais_create(kabc_ctx_t* ctx, const kabc_model_t* model, int64_
  * every launch (50 x AIS(12) is 50 workgroups of one launch instead of 50 runs one after the
  * other).  Chain c uses seeds[c] and is bit-identical to a kabc_ais_create handle with that
  * seed.  Host layouts gain a leading chain axis: kabc_ais_advance's out_samples is
- * [ngenerations][nchains][N][D]; get/set_state and get_ensemble use [nchains][N][...]. */
+ * [ngenerations][nchains][N][D]; get/set_state and get_ensemble use [nchains][N][...].
+ * Beyond KABC_MAX_DIM parameters a handle of nchains > 1 runs on the one-workgroup driver alone
+ * (kabc_ais_driver == 1, csrc/ais_dyn_small_kernel.hpp): built-in costs and prior families, and an
+ * ensemble that fits one workgroup's LDS next to a team of lanes.  Any other shape there is refused with
+ * KABC_ERR_UNSUPPORTED; the message names the limit (the compiled unit of a user cost / user prior, the LDS
+ * bytes asked for and available, KABC_AIS_SMALL=0).  Such a handle advances with kabc_ais_advance;
+ * kabc_ais_half_generation refuses it. */
 kabc_status_t kabc_ais_create_batch(kabc_ctx_t* ctx, const kabc_model_t* model, int64_t nparticles,
                                     int32_t nchains, const uint64_t* seeds, kabc_ais_t** out);
 
@@ -588,8 +594,8 @@ kabc_status_t kabc_ais_create_batch(kabc_ctx_t* ctx, const kabc_model_t* model, 
  * device block [nchains][nparams] and one [nchains][ndata]; an array that is byte-equal to chain 0's
  * in every chain is kept once, and a batch whose costs are all equal runs exactly as
  * kabc_ais_create_batch on costs[0].  costs == NULL is kabc_ais_create_batch.  Limits and layouts are
- * kabc_ais_create_batch's (1 <= nchains <= 65535, D <= KABC_MAX_DIM; host arrays gain a leading chain
- * axis), and every entry point below works on such a handle.  No launch shape or buffer size depends
+ * kabc_ais_create_batch's (1 <= nchains <= 65535; beyond KABC_MAX_DIM parameters the shapes of the
+ * one-workgroup driver, see there; host arrays gain a leading chain axis), and every entry point below works on such a handle.  No launch shape or buffer size depends
  * on a cost's values: NormalMeanStdSim's draw count params[0] may differ per chain (each chain's
  * pre-pass and producers read their own).  A cost plugin .so built by hipcc
  * (kabc_register_cost_plugin) is refused with KABC_ERR_UNSUPPORTED when the values differ: its
@@ -655,7 +661,13 @@ kabc_status_t kabc_ais_spec_state(kabc_ais_t* h, int32_t* state, int64_t* launch
  * ensembles (every generation of a call in ONE launch of one workgroup per chain, both halves in
  * LDS: csrc/ais_small_kernel.hpp -- nparticles <= 512, <= 256 from nine parameters on; the shape
  * of every sample() call in the reference's tests and examples, src/KissABC.jl:66-80,
- * test/runtests.jl:82-131), 0 = one launch per half-generation.  Same bits either way.
+ * test/runtests.jl:82-131; beyond KABC_MAX_DIM parameters csrc/ais_dyn_small_kernel.hpp, a team of
+ * lanes per walker: built-in costs and prior families, unsharded, wherever the ensemble's rows of
+ * length(prior) + 2 or 3 doubles, the prior and one team's working rows fit the 160 KiB of a compute unit,
+ * i.e. nparticles <= 842 at 20 parameters, <= 142 at 128; a handle of ONE chain takes it by default only
+ * where every walker of a half has a team of its own in a workgroup of 512 threads, e.g. nparticles <= 256 at
+ * 20 parameters, <= 32 at 128, and beyond that with KABC_AIS_SMALL=1 -- the several-rounds region is not
+ * measured against the other driver), 0 = one launch per half-generation.  Same bits either way.
  * KABC_AIS_SMALL=0 in the environment of kabc_ais_create* keeps every handle on 0. */
 int32_t kabc_ais_driver(const kabc_ais_t* h);
 /* number of walkers this handle owns, and per half */

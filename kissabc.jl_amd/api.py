@@ -301,7 +301,8 @@ class AisEnsemble:
     @property
     def driver(self):
         """"small": kabc_ais_advance runs every generation of a call in one launch of one workgroup
-        per chain (csrc/ais_small_kernel.hpp); "halves": one launch per half-generation."""
+        per chain (csrc/ais_small_kernel.hpp; beyond KABC_MAX_DIM parameters csrc/ais_dyn_small_kernel.hpp);
+        "halves": one launch per half-generation."""
         return "small" if _lib.load().kabc_ais_driver(self._h) else "halves"
 
     def ensemble(self):
@@ -363,11 +364,13 @@ def _bundle(samples, scalar):
     return P[0] if (len(P) == 1 or scalar) else P
 
 
-def _sample_chains(model, N, Ns, seeds, costs, ntransitions, discard_initial, retry_sampling, ctx):
+def _sample_chains(model, N, Ns, seeds, costs, ntransitions, discard_initial, retry_sampling, ctx, ens=None):
     """len(seeds) independent chains of AIS(N) in ONE batch handle (costs: one DeviceCost per chain, or
-    None): the first Ns samples of each, [Nc][Ns][D], and the handle's driver"""
+    None; ens: that handle where the caller has created it, closed here): the first Ns samples of each,
+    [Nc][Ns][D], and the handle's driver"""
     Nc, D = len(seeds), len(model)
-    ens = AisEnsemble(model, N, ctx=ctx, seeds=seeds, costs=costs)
+    if ens is None:
+        ens = AisEnsemble(model, N, ctx=ctx, seeds=seeds, costs=costs)
     gk = max(1, -(-Ns // N))
     big = gk * Nc * N * D * 8 > (1 << 20)   # (a small trace is not worth a helper thread: see sample)
     pool = concurrent.futures.ThreadPoolExecutor(1) if big else None
@@ -402,11 +405,26 @@ def sample(model, spl, *args, ntransitions=1, discard_initial=0, retry_sampling=
     if args and isinstance(args[0], MCMCThreads):
         # chains are a grid dimension of ONE device handle: every launch advances all Nc
         # ensembles (kabc_ais_create_batch); chain c is bit-identical to a single-chain run
-        # with its seed
+        # with its seed.  A shape the batch handle refuses (KABC_ERR_UNSUPPORTED: beyond KABC_MAX_DIM
+        # parameters an ensemble too large for one workgroup's LDS, a user cost) runs the chains one
+        # after another with the same seeds: the reference's signature never fails on shape alone.
+        # Only the handle's CREATION decides that; an error of init() or advance() is the caller's.
         _, Ns, Nc = args
         Ns, Nc, D = int(Ns), int(Nc), len(model)
-        chains, _ = _sample_chains(model, spl.nparticles, Ns, chain_seeds(seed, Nc), None, ntransitions,
-                                   discard_initial, retry_sampling, ctx)
+        seeds = chain_seeds(seed, Nc)
+        try:
+            ens = AisEnsemble(model, spl.nparticles, ctx=ctx, seeds=seeds)
+        except _lib.KabcError as e:
+            if e.status != cd.KABC_ERR_UNSUPPORTED:
+                raise
+            ens = None
+        if ens is not None:
+            chains, _ = _sample_chains(model, spl.nparticles, Ns, seeds, None, ntransitions,
+                                       discard_initial, retry_sampling, ctx, ens=ens)
+        else:
+            chains = np.stack([sample(model, spl, Ns, ntransitions=ntransitions, discard_initial=discard_initial,
+                                      retry_sampling=retry_sampling, seed=sd, ctx=ctx, return_array=True)
+                               for sd in seeds])
         stacked = chains.reshape(Nc * Ns, D)  # chainsstack, src/KissABC.jl:96-104
         return stacked if return_array else _bundle(stacked, model.scalar)
     (Ns,) = args
@@ -457,7 +475,7 @@ def _model_difference(m, m0):
 
 
 def sample_batch(model, spl, Ns, nruns=None, *, seeds=None, seed=0, ntransitions=1, discard_initial=0,
-                 retry_sampling=100, ctx=None, return_array=False):
+                 retry_sampling=100, ctx=None, return_array=False, course=None):
     """One model fitted to many datasets, or one dataset under many seeds, in one call: run r is
     sample(model_r, spl, Ns, seed=seeds[r], <the same keywords>), bit for bit.
 
@@ -467,11 +485,16 @@ def sample_batch(model, spl, Ns, nruns=None, *, seeds=None, seed=0, ntransitions
     length(prior) <= KABC_MAX_DIM the runs are the chains of ONE batch handle (kabc_ais_create_batch_costs:
     info["course"] == "grid", info["driver"] "small" or "halves"); other shapes, and a cost plugin built
     by hipcc whose runs differ in their cost values, run as sample() calls one after another
-    ("sequential").  Returns a list with one entry per run; its `.info` holds the course, the driver,
+    ("sequential").  `course` overrides that choice: "grid" asks for the batch handle at any
+    length(prior) -- beyond KABC_MAX_DIM it exists for built-in costs and prior families whose ensemble
+    fits one workgroup's LDS (csrc/ais_dyn_small_kernel.hpp) -- and raises KabcError where the shape is
+    refused; "sequential" forces the loop of sample() calls.  Same bits on either course.  Returns a list with one entry per run; its `.info` holds the course, the driver,
     nruns and the wall time.  A failed initial draw raises KabcError("run r: <the reference's message>");
     Context.cancel() / Ctrl-C behave as they do for sample()."""
     if not isinstance(spl, AIS):
         raise TypeError("sampler must be AIS(nparticles)")
+    if course not in (None, "grid", "sequential"):
+        raise ValueError(f'sample_batch: course must be None, "grid" or "sequential", not {course!r}')
     if isinstance(model, _ApproxModel):
         if nruns is None:
             raise ValueError("sample_batch: nruns is required with a single model")
@@ -499,7 +522,7 @@ def sample_batch(model, spl, Ns, nruns=None, *, seeds=None, seed=0, ntransitions
     kw = dict(ntransitions=ntransitions, discard_initial=discard_initial, retry_sampling=retry_sampling)
     t0 = time.perf_counter()
     chains, driver = None, None
-    if D <= cd.KABC_MAX_DIM:
+    if course == "grid" or (course is None and D <= cd.KABC_MAX_DIM):
         try:
             chains, driver = _sample_chains(m0, N, Ns, seeds, [m.cost for m in models], ctx=ctx, **kw)
         except _lib.Cancelled:
@@ -508,7 +531,7 @@ def sample_batch(model, spl, Ns, nruns=None, *, seeds=None, seed=0, ntransitions
             msg = str(e)
             if msg.startswith("chain "):   # (a failed initial draw: "chain r: ...")
                 raise _lib.KabcError(e.status, "run " + msg[len("chain "):]) from None
-            if e.status != cd.KABC_ERR_UNSUPPORTED:
+            if e.status != cd.KABC_ERR_UNSUPPORTED or course == "grid":
                 raise
             # (a shape the batch handle refuses: the runs one after another, each with sample()'s own checks)
     if chains is not None:
@@ -523,7 +546,7 @@ def sample_batch(model, spl, Ns, nruns=None, *, seeds=None, seed=0, ntransitions
                 raise
             except _lib.KabcError as e:
                 raise _lib.KabcError(e.status, f"run {r}: {e}") from None
-        course, driver = "sequential", "halves"   # (the run-time-dimension kernels, a hipcc plugin's kernels)
+        course, driver = "sequential", "halves"   # (each run on the driver its own handle picks)
     out.info = {"course": course, "driver": driver, "nruns": nruns,
                 "wall_ms": (time.perf_counter() - t0) * 1e3}
     return out

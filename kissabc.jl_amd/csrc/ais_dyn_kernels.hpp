@@ -36,6 +36,15 @@ struct AisDynArgs {
     const PriorDev* prior;        // [D] prepared components (device)
     const kabc_prior_t* raw;      // [D] raw components (device; init only)
     unsigned long long retry_budget;
+    // step(init) of a batch handle (the last members: a plugin .so built from older headers reads the
+    // ones before them): chain = blockIdx.y draws from seeds[chain] into x_act + chain * stride_act,
+    // lp / ll + chain * stride_own, counts its re-draws in chain_retries[chain] and reads its own cost
+    // (params_stride / data_stride doubles between two chains, 0 = shared).  seeds == NULL: one chain.
+    const uint64_t* seeds;
+    unsigned long long* chain_retries;
+    int64_t stride_act, stride_own, stride_scratch;
+    int64_t params_stride, data_stride;
+    int32_t nchains;
 };
 
 template <int COST>
@@ -366,9 +375,23 @@ __global__ void __launch_bounds__(kWave) ais_dyn_half_kernel(const AisDynArgs A)
 
 // step(init) -- src/KissABC.jl:35-64 -- with the dimension at run time
 template <int COST>
-__global__ void __launch_bounds__(kWave) ais_dyn_init_kernel(const AisDynArgs A) {
+__global__ void __launch_bounds__(kWave) ais_dyn_init_kernel(const AisDynArgs A0) {
     const int64_t r = (int64_t)blockIdx.x * kWave + threadIdx.x;
-    if (r >= A.rows_owned) return;
+    if (r >= A0.rows_owned) return;
+    // a batch handle's chain: its seed, its rows, its retry counter, its cost
+    AisDynArgs A = A0;
+    unsigned long long* retries = &A0.counters->retries;
+    if (A0.seeds) {
+        const int64_t chain = (int64_t)blockIdx.y;
+        A.seed = A0.seeds[chain];
+        A.x_act = A0.x_act + chain * A0.stride_act;
+        A.lp = A0.lp + chain * A0.stride_own;
+        A.ll = A0.ll + chain * A0.stride_own;
+        A.scratch = A0.scratch + chain * A0.stride_scratch;
+        A.cost_params = A0.cost_params + chain * A0.params_stride;
+        A.cost_data = A0.cost_data + chain * A0.data_stride;
+        retries = A0.chain_retries + chain;
+    }
     const int D = A.D;
     const int64_t row = A.row_first + r;
     const uint32_t w = A.id_base + (uint32_t)row;
@@ -385,7 +408,7 @@ __global__ void __launch_bounds__(kWave) ais_dyn_init_kernel(const AisDynArgs A)
         bool ev;
         dyn_loglike<COST>(A, x, xp, &rng, lp, ll, ev);
         if (ld_valid(A.posterior, lp, ll)) break;
-        const unsigned long long used = atomicAdd(&A.counters->retries, 1ull) + 1ull;
+        const unsigned long long used = atomicAdd(retries, 1ull) + 1ull;
         if (used > A.retry_budget) {
             A.counters->init_failed = 1;
             break;
@@ -440,7 +463,9 @@ template <int COST>
 inline void launch_ais_dyn(const AisDynArgs& a, hipStream_t s, int init) {
     if (a.rows_owned <= 0) return;
     if (init) {
-        hipLaunchKernelGGL((ais_dyn_init_kernel<COST>), dim3((unsigned)((a.rows_owned + kWave - 1) / kWave)), dim3(kWave), 0, s, a);
+        hipLaunchKernelGGL((ais_dyn_init_kernel<COST>),
+                           dim3((unsigned)((a.rows_owned + kWave - 1) / kWave), (unsigned)(a.seeds ? a.nchains : 1)),
+                           dim3(kWave), 0, s, a);
         return;
     }
     // (a team of T lanes per walker, the walkers' rows and the prior in dynamic LDS)

@@ -12,6 +12,7 @@
 
 #include "ais_aux_kernels.hpp"
 #include "ais_dyn_kernels.hpp"
+#include "ais_dyn_small_kernel.hpp"
 #include "ais_small_kernel.hpp"
 #include "host_common.hpp"
 #include "plugin_registry.hpp"
@@ -194,7 +195,11 @@ struct kabc_ais {
     bool small_ok = false;
     AisSmallLaunch small;
     int32_t small_pcx = 0;          // the prebuilt table's variant (prior class BOX / NORMAL / GENERAL + posterior kind)
-    double* d_strace = nullptr;     // its device trace buffer
+    // ... and of small ensembles beyond KABC_MAX_DIM parameters (ais_dyn_small_kernel.hpp): small_ok with
+    // `dsmall` set; the plan is the team width, the workgroup size and the LDS bytes of every launch
+    AisDynSmallLaunchFn dsmall = nullptr;
+    AisDynSmallPlan dplan;
+    double* d_strace = nullptr;     // the one-workgroup drivers' device trace buffer
     size_t strace_cap = 0;          // bytes
     ModelUnit* unit = nullptr;      // run-time compiled unit (user prior families / specialised model), else NULL
     // the model's own kernels (the default, non-blocking specialisation: plugin_registry.hpp)
@@ -313,7 +318,7 @@ static kabc_status_t ais_alloc(kabc_ais_t* h, const kabc_model_t* m, void* ext0,
         KABC_HIP_CHECK(dev_malloc(&h->d_raw, sizeof(kabc_prior_t) * D));
         KABC_HIP_CHECK(hipMemcpyAsync(h->d_raw, h->raw_dyn.data(), sizeof(kabc_prior_t) * D,
                                       hipMemcpyHostToDevice, s));
-        KABC_HIP_CHECK(dev_malloc(&h->d_scratch, sizeof(double) * (rmax ? rmax : 1) * 2 * D));
+        KABC_HIP_CHECK(dev_malloc(&h->d_scratch, sizeof(double) * (rmax ? rmax : 1) * 2 * D * nch));
     } else {
         KABC_HIP_CHECK(dev_malloc(&h->d_prior, sizeof(PriorSet)));
         KABC_HIP_CHECK(hipMemcpyAsync(h->d_prior, &h->prior, sizeof(PriorSet), hipMemcpyHostToDevice, s));
@@ -379,11 +384,8 @@ static kabc_status_t ais_validate(kabc_ctx_t* ctx, const kabc_model_t* m, kabc_a
     mres.prior = resolved.data();
     m = &mres;
     const bool dyn = m->D > KABC_MAX_DIM;
-    if (dyn && nchains != 1) {
-        set_error("length(prior) = %d > %d runs on the run-time-dimension kernels: one chain per handle",
-                  m->D, KABC_MAX_DIM);
-        return KABC_ERR_UNSUPPORTED;
-    }
+    // (many chains beyond KABC_MAX_DIM parameters: ais_resolve_kernels, where the kernels are known)
+    (void)nchains;
     // src/KissABC.jl:43-48
     if (n_total < m->D + 5) {
         set_error("nparticles = %lld is insufficient, set number of particles in AIS(⋅) atleast to %d",
@@ -503,13 +505,47 @@ static kabc_status_t ais_resolve_kernels(kabc_ais_t* h, const kabc_model_t* m) {
             return KABC_ERR_UNSUPPORTED;
         }
     }
+    // Small ensembles beyond KABC_MAX_DIM parameters (ais_dyn_small_kernel.hpp): one workgroup per chain, a team
+    // of lanes per walker, every generation of a call in one launch.  Built-in costs and prior families on an
+    // unsharded handle that owns its halves, where ais_dyn_small_plan finds room for the ensemble and one team
+    // per wavefront in a CU's LDS.  A handle of many chains has no other driver beyond KABC_MAX_DIM parameters:
+    // a shape that is not eligible is refused, and the message names the limit it hit.
+    // A single chain has the launch per half-generation to fall back on, which spreads the walkers over the
+    // device: it takes this driver by default only where every walker of a half has a team of its own
+    // (plan.rounds == 1).  Where LDS leaves fewer teams one workgroup works through a half in several rounds;
+    // that region's timing is not measured, so a single chain enters it only with KABC_AIS_SMALL=1.
+    const char* e = std::getenv("KABC_AIS_SMALL");
+    const bool off = e && e[0] == '0', asked = e && e[0] == '1';
+    if (dyn) {
+        const bool builtin = !unit && m->cost.id < KABC_COST_USER && aux_prepass_words(m->cost.id) == 0;
+        const bool own = !h->comm && h->world == 1 && h->own_halves;
+        const AisDynSmallPlan plan = ais_dyn_small_plan(m->D, h->N);
+        const bool wanted = h->nchains > 1 || plan.rounds == 1 || asked;
+        if (!off && builtin && own && plan.T != 0 && wanted) {
+            h->dsmall = find_ais_dyn_small_kernel(m->cost.id);
+            h->dplan = plan;
+            h->small_ok = h->dsmall != nullptr;
+        }
+        if (h->nchains > 1 && !h->small_ok) {
+            if (!builtin)
+                set_error("length(prior) = %d > %d with a user cost, user prior families or a joint prior runs on "
+                          "the run-time-dimension kernels of its compiled unit: one chain per handle",
+                          m->D, KABC_MAX_DIM);
+            else if (off)
+                set_error("length(prior) = %d > %d: KABC_AIS_SMALL=0 keeps the launch per half-generation, which "
+                          "holds one chain per handle beyond %d parameters", m->D, KABC_MAX_DIM, KABC_MAX_DIM);
+            else
+                set_error("length(prior) = %d > %d with nparticles = %lld: one workgroup per chain would need %zu "
+                          "bytes of LDS for the ensemble and one team of lanes, a compute unit has %zu; many "
+                          "chains in one handle need an ensemble that fits",
+                          m->D, KABC_MAX_DIM, (long long)h->N, plan.lds, kAisDynSmallLdsBudget);
+            return KABC_ERR_UNSUPPORTED;
+        }
+    }
     // Small ensembles (both halves fit one workgroup's LDS, ais_small_kernel.hpp): one workgroup per
     // chain runs every generation of a kabc_ais_advance call in one launch (a cost with a grid-wide
     // pre-pass, ais_aux_kernels.hpp: one pre-pass launch per half for all of the call's sub-steps first).
-    // Not for sharded handles, caller-lent halves, the run-time-dimension kernels; KABC_AIS_SMALL=0 keeps
-    // the launch per half-generation.
-    const char* e = std::getenv("KABC_AIS_SMALL");
-    const bool off = e && e[0] == '0';
+    // Not for sharded handles or caller-lent halves; KABC_AIS_SMALL=0 keeps the launch per half-generation.
     if (!off && !dyn && !h->comm && h->world == 1 && h->own_halves &&
         (h->N + 1) / 2 <= (int64_t)ais_small_rmax(m->D)) {
         const int pk_off = kPriorClasses * (m->posterior - 1);
@@ -652,12 +688,13 @@ template <class A>
 static void fill_args(A& a, const kabc_ais_t* h) {
     constexpr bool aux = std::is_same_v<A, AuxArgs>, init = std::is_same_v<A, InitArgs>;
     constexpr bool dyn = std::is_same_v<A, AisDynArgs>, small = std::is_same_v<A, AisSmallArgs>;
+    constexpr bool dsm = std::is_same_v<A, AisDynSmallArgs>;
     std::memset(&a, 0, sizeof a);
     a.cost_params = h->d_cost_params;
     a.cost_data = h->d_cost_data;
     a.cost_ndata = h->cost_ndata;
     a.seed = h->seed;
-    if constexpr (!dyn) a.seeds = h->d_seeds;  // (a run-time-dimension handle holds one chain)
+    a.seeds = h->d_seeds;  // (the run-time-dimension kernels: step(init) and the one-workgroup driver read them)
     if constexpr (!aux) {
         a.counters = h->d_counters;
         a.eps = h->eps;
@@ -668,12 +705,13 @@ static void fill_args(A& a, const kabc_ais_t* h) {
         a.reps = (h->posterior == KABC_POSTERIOR_COMMON) ? 1.0 : 1.0 / h->eps;
         a.prior = h->d_prior;
     }
-    if constexpr (!aux && !dyn && !init) a.box_lp = h->box_lp;
+    if constexpr (!aux && !dyn && !dsm && !init) a.box_lp = h->box_lp;
     if constexpr (!aux && !small) a.posterior = h->posterior;
-    if constexpr (dyn || init) a.cost_id = h->cost_id;
-    // per-chain costs (a run-time-dimension handle holds one chain; the pre-pass reads params only)
-    if constexpr (!dyn) a.params_stride = h->params_stride;
-    if constexpr (!dyn && !aux) a.data_stride = h->data_stride;
+    if constexpr (dyn || dsm || init) a.cost_id = h->cost_id;
+    if constexpr (dyn || dsm) a.D = h->D;
+    // per-chain costs (the pre-pass reads params only)
+    a.params_stride = h->params_stride;
+    if constexpr (!aux) a.data_stride = h->data_stride;
 }
 
 // a size knob of the environment (tests, tuning) in `unit` bytes, else `dflt`; read at every call, as
@@ -834,8 +872,13 @@ static AisDynArgs dyn_args(kabc_ais_t* h, int half, const kabc_ais::Seg& sg) {
     a.rows_owned = sg.count;
     a.n_comp = h->rows[1 - half];
     a.id_base = h->id_base[half];
-    a.D = h->D;
     a.raw = h->d_raw;
+    // step(init) of a batch handle (an unsharded one: its segment is the half)
+    a.chain_retries = h->d_chain_retries;
+    a.nchains = h->nchains;
+    a.stride_act = h->rows[half] * h->D;
+    a.stride_own = h->rows_owned[half];
+    a.stride_scratch = (h->rows_owned[0] > h->rows_owned[1] ? h->rows_owned[0] : h->rows_owned[1]) * 2 * h->D;
     return a;
 }
 
@@ -1091,6 +1134,11 @@ static kabc_status_t launch_half_seg(kabc_ais_t* h, int32_t half, const kabc_ais
     if (h->spec_state == KABC_SPEC_PENDING && !h->small_ok) ais_poll_spec(h);
     if (!h->launch && !h->dyn)
         if (kabc_status_t st = ais_resolve_half(h)) return st;
+    if (h->dyn && h->nchains > 1) {  // (the half-generation kernel of the run-time-dimension path holds one chain)
+        set_error("a handle of %d chains beyond %d parameters advances with kabc_ais_advance (the one-workgroup "
+                  "driver); kabc_ais_half_generation drives one chain per handle there", h->nchains, KABC_MAX_DIM);
+        return KABC_ERR_UNSUPPORTED;
+    }
     h->launches++;
     // debug records: layout [N_owned][nt][6] in the order of the owned rows (half 0 first)
     int32_t* dbg = nullptr;
@@ -1199,6 +1247,16 @@ kabc_status_t kabc_ais_end_generation(kabc_ais_t* h, int32_t ntransitions) {
 
 // units (batch, sub-step) of one generation a consumer of the small kernel may have to count
 static int64_t ais_small_units_per_gen(const kabc_ais_t* h, int32_t ntransitions) {
+    if (h->dsmall) {
+        // beyond KABC_MAX_DIM parameters a unit is a round of the workgroup's teams over a sub-step; its time
+        // grows with the sequential part of a transition.  ESTIMATE, not a measurement: ~0.2 us per parameter
+        // against kCancelUnitUs = 0.6, from the lead lane's dependent adds and the cost's loop.  The poll
+        // interval and the many-chain block cap rest on it; tests/test_gpu_ais_dyn_small.py bounds the cancel
+        // latency it leads to at D = 20, and tools/ais_dyn_small_probe.py reports the time per round.
+        const int64_t teams = h->dplan.block / h->dplan.T;
+        const int64_t rounds = (h->rows[0] + teams - 1) / teams + (h->rows[1] + teams - 1) / teams;
+        return rounds * (int64_t)ntransitions * (int64_t)((h->D + 2) / 3);
+    }
     return ((h->rows[0] + kBatch - 1) / kBatch + (h->rows[1] + kBatch - 1) / kBatch) * (int64_t)ntransitions;
 }
 
@@ -1277,24 +1335,30 @@ static kabc_status_t ais_small_run(kabc_ais_t* h, int64_t ngenerations, int32_t 
         if (h->spec_state == KABC_SPEC_PENDING) ais_poll_spec(h);
         h->launches++;
         AisSmallArgs a;
-        fill_args(a, h);
-        for (int hf = 0; hf < 2; ++hf) {
-            a.x[hf] = h->d_half[hf];
-            a.lp[hf] = h->d_lp[hf];
-            a.ll[hf] = h->d_ll[hf];
-            a.rows[hf] = (int32_t)h->rows[hf];
-            a.id_base[hf] = h->id_base[hf];
-        }
-        a.trace = out_samples ? h->d_strace : nullptr;
-        // debug records: [N][nt][6] in walker order (those of the block's last generation remain)
-        a.dbg = (h->d_dbg && h->N * (int64_t)ntransitions * 6 <= h->dbg_cap) ? h->d_dbg : nullptr;
-        a.t0 = h->t;
-        a.nt = ntransitions;
-        a.ngen = (int32_t)gc;
-        a.trace_from = 0;
-        a.nchains = h->nchains;
-        a.cancel = dev_poll ? h->ctx->cancel_d : nullptr;
-        a.poll_every = (int32_t)poll_every;
+        AisDynSmallArgs ad;
+        // (the members the two one-workgroup kernels' arguments share by name)
+        auto fill_block = [&](auto& q) {
+            fill_args(q, h);
+            for (int hf = 0; hf < 2; ++hf) {
+                q.x[hf] = h->d_half[hf];
+                q.lp[hf] = h->d_lp[hf];
+                q.ll[hf] = h->d_ll[hf];
+                q.rows[hf] = (int32_t)h->rows[hf];
+                q.id_base[hf] = h->id_base[hf];
+            }
+            q.trace = out_samples ? h->d_strace : nullptr;
+            // debug records: [N][nt][6] in walker order (those of the block's last generation remain)
+            q.dbg = (h->d_dbg && h->N * (int64_t)ntransitions * 6 <= h->dbg_cap) ? h->d_dbg : nullptr;
+            q.t0 = h->t;
+            q.nt = ntransitions;
+            q.ngen = (int32_t)gc;
+            q.trace_from = 0;
+            q.nchains = h->nchains;
+            q.cancel = dev_poll ? h->ctx->cancel_d : nullptr;
+            q.poll_every = (int32_t)poll_every;
+        };
+        if (h->dsmall) fill_block(ad);
+        else fill_block(a);
         const bool t_on = h->timing && (h->ev_used + 2 <= h->ev.size());
         if (t_on && h->open_count == 0) KABC_HIP_CHECK(hipEventRecord(h->ev[h->ev_used], s));
         if (auxW) {  // (inside the timed region, like the half-generation path's pre-pass)
@@ -1305,7 +1369,8 @@ static kabc_status_t ais_small_run(kabc_ais_t* h, int64_t ngenerations, int32_t 
                 base += (size_t)a.stride_aux[hf] * (size_t)h->nchains;
             }
         }
-        h->small(a, s);
+        if (h->dsmall) KABC_HIP_CHECK(h->dsmall(ad, s, h->dplan));
+        else h->small(a, s);
         if (t_on && ++h->open_count >= h->timing_stride)
             if (kabc_status_t st = timing_close_pair(h)) return st;
         KABC_HIP_CHECK(hipGetLastError());
