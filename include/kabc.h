@@ -413,6 +413,18 @@ void kabc_reject_batch_stats(int64_t out[4]);
 kabc_status_t kabc_math_probe(kabc_ctx_t* ctx, int32_t fn, int64_t n, const double* x,
                               double* out);
 
+/* ---- working-memory probe (verification only) ----------------------------------
+ * KABC_POISON_ALLOC (read once per process: unset, empty or 0 off; 1 byte 0xA5; 0xNN that byte) fills
+ * every working buffer of the library with one byte before use.  The hook is silent, so tests prove it
+ * was in force with this call: it allocates n bytes (1..2^24) the way the drivers do and copies them
+ * back.  fresh[n]: a new allocation.  pooled[n]: a first allocation through ctx's buffer pool, which is
+ * then written over with 0x3C and handed back.  recycled[n]: a second allocation through the pool, of
+ * n - n/4 bytes, which the best-fit rule serves with the first one's buffer.  info[0]: the byte in force,
+ * -1 when the hook is off; info[1]: 1 when the second allocation did get the first one's buffer from
+ * the pool (not with KABC_POOL_MB=0; recycled[] past n - n/4 then reads 0). */
+kabc_status_t kabc_poison_probe(kabc_ctx_t* ctx, int64_t n, uint8_t* fresh, uint8_t* pooled,
+                                uint8_t* recycled, int32_t info[2]);
+
 /* ---- user DeviceCost plugins ------------------------------------------------
  * Replaces "cost is an arbitrary closure" (src/types.jl:42,55; src/smc.jl:94) for
  * costs that can be written as a C function (signature: include/kabc_costs.h,

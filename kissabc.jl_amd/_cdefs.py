@@ -134,6 +134,8 @@ PROTOTYPES = {
     "kabc_ctx_clear_cancel": (C.c_int, [VP]),
     "kabc_ctx_cancel_on_sigint": (C.c_int, [VP, C.c_int32]),
     "kabc_math_probe": (C.c_int, [VP, C.c_int32, C.c_int64, c_double_p, c_double_p]),
+    "kabc_poison_probe": (C.c_int, [VP, C.c_int64, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8),
+                                    C.POINTER(C.c_uint8), C.POINTER(C.c_int32)]),
     "kabc_host_alloc": (C.c_int, [C.c_size_t, C.POINTER(VP)]),
     "kabc_host_free": (C.c_int, [VP]),
     "kabc_factored_logpdf": (C.c_int, [VP, C.POINTER(Prior), C.c_int32, C.c_int64, c_double_p,

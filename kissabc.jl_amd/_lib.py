@@ -256,3 +256,42 @@ def math_probe(name, x, ctx=None):
                                  x.ctypes.data_as(_cdefs.c_double_p),
                                  out.ctypes.data_as(_cdefs.c_double_p)))
     return out.reshape(-1, 2) if ow == 2 else out
+
+
+_poison_byte = ()            # (KABC_POISON_ALLOC as it stood at the first question: once per process, as in the library)
+
+
+def poison_byte_requested():
+    """The byte the library's working buffers are filled with (KABC_POISON_ALLOC), None when the hook is
+    off.  Read once per process, like the library's own look at the variable."""
+    global _poison_byte
+    if _poison_byte == ():
+        _poison_byte = poison_byte_rule(os.environ.get("KABC_POISON_ALLOC"))
+    return _poison_byte
+
+
+def poison_byte_rule(e):
+    """The library's rule (csrc/host_common.hpp poison_byte): None when off (unset, empty, a leading 0
+    that is no 0xNN), 0xNN that byte, anything else 0xA5."""
+    if not e:
+        return None
+    if e[:2] in ("0x", "0X"):
+        digits = e[2:]
+        ok = 1 <= len(digits) and all(ch in "0123456789abcdefABCDEF" for ch in digits)
+        return int(digits, 16) if ok and int(digits, 16) <= 0xFF else 0xA5
+    return None if e[0] == "0" else 0xA5
+
+
+def poison_probe(n, ctx=None):
+    """kabc_poison_probe (verification only): the bytes of a fresh working buffer, of a first
+    buffer from the context's pool and of the recycled one a second allocation got, as uint8
+    arrays of n, plus (byte in force or -1, whether the second allocation was recycled)."""
+    import numpy as np
+    n = int(n)
+    fresh, pooled, recycled = (np.empty(max(n, 0), dtype=np.uint8) for _ in range(3))
+    info = (C.c_int32 * 2)()
+    ctx = ctx or default_context()
+    u8 = C.POINTER(C.c_uint8)
+    check(load().kabc_poison_probe(ctx.handle, n, fresh.ctypes.data_as(u8), pooled.ctypes.data_as(u8),
+                                   recycled.ctypes.data_as(u8), info))
+    return fresh, pooled, recycled, (int(info[0]), int(info[1]))

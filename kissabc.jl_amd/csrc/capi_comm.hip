@@ -430,10 +430,10 @@ kabc_status_t kabc_comm_init_rank(kabc_ctx_t* ctx, const uint8_t id[KABC_COMM_ID
     c->grp = nullptr;
     c->d_scratch = nullptr;
     c->xstream = nullptr;
-    if (hipMalloc(&c->d_scratch, 64 * sizeof(double)) != hipSuccess) {
+    if (dev_malloc(&c->d_scratch, 64 * sizeof(double)) != hipSuccess) {
         (void)R->CommDestroy(nc);
         delete c;
-        set_error("kabc_comm_init_rank: hipMalloc failed");
+        set_error("kabc_comm_init_rank: device allocation failed");
         return KABC_ERR_DEVICE;
     }
     *out = c;

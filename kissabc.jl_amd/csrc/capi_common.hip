@@ -124,7 +124,7 @@ kabc_status_t resolve_priors(kabc_ctx_t* ctx, const kabc_prior_t* prior, int D, 
         d = it->second;
     } else {
         KABC_HIP_CHECK(hipSetDevice(ctx->device));
-        KABC_HIP_CHECK(hipMalloc(&d, sizeof(double) * e->host.size()));
+        KABC_HIP_CHECK(dev_malloc(&d, sizeof(double) * e->host.size()));
         KABC_HIP_CHECK(hipMemcpy(d, e->host.data(), sizeof(double) * e->host.size(), hipMemcpyHostToDevice));
         KABC_HIP_CHECK(hipDeviceSynchronize());  // (once per handle and device: the contexts' streams are non-blocking)
         e->dev[ctx->device] = d;
@@ -566,8 +566,8 @@ static kabc_status_t prior_util(kabc_ctx_t* ctx, const kabc_prior_t* prior, int3
     }
     PriorDev* d_prep = nullptr;
     kabc_prior_t* d_raw = nullptr;
-    KABC_HIP_CHECK(hipMalloc(&d_prep, sizeof(PriorDev) * D));
-    KABC_HIP_CHECK(hipMalloc(&d_raw, sizeof(kabc_prior_t) * D));
+    KABC_HIP_CHECK(dev_malloc(&d_prep, sizeof(PriorDev) * D));
+    KABC_HIP_CHECK(dev_malloc(&d_raw, sizeof(kabc_prior_t) * D));
     KABC_HIP_CHECK(hipMemcpyAsync(d_prep, prep.data(), sizeof(PriorDev) * D, hipMemcpyHostToDevice, ctx->stream));
     KABC_HIP_CHECK(hipMemcpyAsync(d_raw, prior, sizeof(kabc_prior_t) * D, hipMemcpyHostToDevice, ctx->stream));
     A.prior = d_prep;
@@ -576,10 +576,10 @@ static kabc_status_t prior_util(kabc_ctx_t* ctx, const kabc_prior_t* prior, int3
     const size_t out_bytes = sizeof(double) * n * ((mode == 0) ? 1 : D);
     double *dx = nullptr, *dout = nullptr;
     if (mode != 2) {
-        KABC_HIP_CHECK(hipMalloc(&dx, in_bytes));
+        KABC_HIP_CHECK(dev_malloc(&dx, in_bytes));
         KABC_HIP_CHECK(hipMemcpyAsync(dx, x, in_bytes, hipMemcpyHostToDevice, ctx->stream));
     }
-    KABC_HIP_CHECK(hipMalloc(&dout, out_bytes));
+    KABC_HIP_CHECK(dev_malloc(&dout, out_bytes));
     A.x = dx;
     A.out = dout;
     A.n = n;
@@ -668,8 +668,8 @@ kabc_status_t kabc_math_probe(kabc_ctx_t* ctx, int32_t fn, int64_t n, const doub
     KABC_HIP_CHECK(hipSetDevice(ctx->device));
     const int in_w = (fn == 10 || fn == 11) ? 2 : 1, out_w = (fn == 4 || fn == 10) ? 2 : 1;
     double *dx = nullptr, *dout = nullptr;
-    KABC_HIP_CHECK(hipMalloc(&dx, sizeof(double) * n * in_w));
-    KABC_HIP_CHECK(hipMalloc(&dout, sizeof(double) * n * out_w));
+    KABC_HIP_CHECK(dev_malloc(&dx, sizeof(double) * n * in_w));
+    KABC_HIP_CHECK(dev_malloc(&dout, sizeof(double) * n * out_w));
     KABC_HIP_CHECK(hipMemcpyAsync(dx, x, sizeof(double) * n * in_w, hipMemcpyHostToDevice,
                                   ctx->stream));
     const int blocks = (int)((n + 255) / 256 < 65535 ? (n + 255) / 256 : 65535);
@@ -681,6 +681,49 @@ kabc_status_t kabc_math_probe(kabc_ctx_t* ctx, int32_t fn, int64_t n, const doub
     KABC_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     KABC_HIP_CHECK(hipFree(dx));
     KABC_HIP_CHECK(hipFree(dout));
+    return KABC_OK;
+}
+
+kabc_status_t kabc_poison_probe(kabc_ctx_t* ctx, int64_t n, uint8_t* fresh, uint8_t* pooled,
+                                uint8_t* recycled, int32_t info[2]) {
+    if (!ctx || !fresh || !pooled || !recycled || !info || n < 1 || n > (int64_t)(1 << 24)) {
+        set_error("kabc_poison_probe: bad argument (n must be 1..%d)", 1 << 24);
+        return KABC_ERR_INVALID_ARG;
+    }
+    info[0] = poison_byte();
+    info[1] = 0;
+    KABC_HIP_CHECK(hipSetDevice(ctx->device));
+    uint8_t* d = nullptr;
+    KABC_HIP_CHECK(dev_malloc(&d, (size_t)n));
+    hipError_t e = hipMemcpy(fresh, d, (size_t)n, hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    KABC_HIP_CHECK(e);
+    // a first owner takes n bytes through the context's pool, writes them over (the previous run's
+    // bytes) and hands them back; a second owner asks for three quarters of that, which the
+    // best-fit rule serves with the same buffer
+    uint8_t *p1 = nullptr, *p2 = nullptr;
+    {
+        DevBufs b;
+        b.ctx = ctx;
+        KABC_HIP_CHECK(b.alloc(&p1, (size_t)n));
+        KABC_HIP_CHECK(hipMemcpy(pooled, p1, (size_t)n, hipMemcpyDeviceToHost));
+        KABC_HIP_CHECK(hipMemset(p1, 0x3C, (size_t)n));
+        KABC_HIP_CHECK(hipDeviceSynchronize());
+    }
+    bool cached = false;
+    {
+        std::lock_guard<std::mutex> lk(ctx->pool_mu);
+        for (const auto& pe : ctx->pool) cached = cached || pe.second == (void*)p1;
+    }
+    DevBufs b2;
+    b2.ctx = ctx;
+    KABC_HIP_CHECK(b2.alloc(&p2, (size_t)(n - n / 4)));
+    info[1] = (cached && p2 == p1) ? 1 : 0;
+    // (a recycled buffer is poisoned over its whole size; a fresh one has n - n / 4 bytes: the
+    // rest of `recycled` then reads 0)
+    const size_t got = b2.held.back().first < (size_t)n ? b2.held.back().first : (size_t)n;
+    std::memset(recycled, 0, (size_t)n);
+    KABC_HIP_CHECK(hipMemcpy(recycled, p2, got, hipMemcpyDeviceToHost));
     return KABC_OK;
 }
 

@@ -32,21 +32,31 @@ const char* get_error();
 // derived constants of one Factored component.  Host libm supplies the one-off
 // normalisers (lgamma, erfc); everything evaluated per walker goes through the
 // math contract.  Returns false for invalid parameters.
-// hipMalloc for the library's working buffers.  KABC_POISON_ALLOC=1 (tests) fills every buffer --
-// fresh or recycled from a context's pool -- with 0xA5 bytes first: fresh device memory usually
-// reads as zero, so a kernel that relies on that passes every test until the driver hands out a
-// recycled page (several processes starting on one GPU).
-inline bool poison_alloc() {
-    static const bool on = [] {
+// hipMalloc for the library's working buffers.  KABC_POISON_ALLOC (tests) fills every buffer -- fresh
+// or recycled from a context's pool -- with one byte first: fresh device memory usually reads as
+// zero, so a kernel that relies on that passes every test until the driver hands out a recycled
+// page (several processes starting on one GPU).  Values: unset, empty or 0: off; 0xNN (one or two
+// hex digits): that byte -- 0xff reads as NaN doubles and all-ones integers, where 0xA5 bytes read as
+// a double of about -2^-421 that an accumulator absorbs silently; anything else (1): byte 0xA5.
+// Read once per process.  Returns the byte, or -1 when off.
+inline int poison_byte() {
+    static const int byte = [] {
         const char* e = std::getenv("KABC_POISON_ALLOC");
-        return e && *e && *e != '0';
+        if (!e || !*e) return -1;
+        if (e[0] == '0' && (e[1] == 'x' || e[1] == 'X')) {
+            char* end = nullptr;
+            const unsigned long v = std::strtoul(e + 2, &end, 16);
+            return (end != e + 2 && *end == '\0' && v <= 0xFFul) ? (int)v : 0xA5;
+        }
+        return e[0] == '0' ? -1 : 0xA5;
     }();
-    return on;
+    return byte;
 }
+inline bool poison_alloc() { return poison_byte() >= 0; }
 // (hipMemset on the null stream is not ordered against the contexts' non-blocking streams and may
 // return before it has run: wait for it, or it lands on top of the run's own initialisation)
 inline hipError_t poison_fill(void* p, size_t bytes) {
-    hipError_t e = hipMemset(p, 0xA5, bytes);
+    hipError_t e = hipMemset(p, poison_byte(), bytes);
     return e == hipSuccess ? hipDeviceSynchronize() : e;
 }
 template <class T>

@@ -26,6 +26,18 @@ from . import _lib
 from .api import AisEnsemble
 
 
+def _half_buffer(shape, device):
+    """One torch-owned half of the ensemble: zeros, or, with KABC_POISON_ALLOC set, the same byte
+    pattern the library's own working buffers get (every row is written by the first half-generation
+    or the exchange before it is read; the tests run on poisoned halves to show it)."""
+    byte = _lib.poison_byte_requested()
+    if byte is None:
+        return torch.zeros(shape, dtype=torch.float64, device=device)
+    buf = torch.empty(shape, dtype=torch.float64, device=device)
+    buf.view(torch.uint8).fill_(byte)
+    return buf
+
+
 class HipEngine:
     """Per-rank compute: the gfx950 kernels updating this rank's rows in place
     inside torch-owned global half buffers.
@@ -44,8 +56,8 @@ class HipEngine:
         self.stream = torch.cuda.Stream(self.device)
         with torch.cuda.stream(self.stream):
             self.half = half_buffers or [
-                torch.zeros((n0, D), dtype=torch.float64, device=self.device),
-                torch.zeros((n1, D), dtype=torch.float64, device=self.device)]
+                _half_buffer((n0, D), self.device),
+                _half_buffer((n1, D), self.device)]
         self.ctx = _lib.Context(self.device.index or 0, self.stream.cuda_stream)
         self.ens = AisEnsemble(model, n_total, seed=seed, ctx=self.ctx,
                                sharded=(rank, world, self.half[0].data_ptr(),

@@ -87,3 +87,24 @@ def test_product_never_touches_the_oracle():
 def test_host_closure_is_rejected(k):
     with pytest.raises(TypeError):
         k.ApproxKernelizedPosterior(k.Normal(0, 1), lambda x: abs(x - 1.5), 0.01)
+
+
+def test_poison_probe_prototype_and_arguments(k):
+    """kabc_poison_probe (verification only): declared, bound, and refusing bad arguments before it touches a
+    device; the Python mirror of the KABC_POISON_ALLOC byte rule (csrc/host_common.hpp poison_byte)"""
+    from kissabc_jl_amd import _cdefs as cd, _lib
+    lib = _lib.load()
+    res, args = cd.PROTOTYPES["kabc_poison_probe"]
+    u8 = C.POINTER(C.c_uint8)
+    assert res is C.c_int and args == [cd.VP, C.c_int64, u8, u8, u8, C.POINTER(C.c_int32)]
+    buf, info = (C.c_uint8 * 16)(), (C.c_int32 * 2)()
+    fake = C.c_void_p(C.addressof(C.create_string_buffer(4096)))   # (the checks come before any look at the context)
+    for ctx, n, a, b, c, i in [(None, 16, buf, buf, buf, info), (fake, 16, None, buf, buf, info),
+                               (fake, 16, buf, None, buf, info), (fake, 16, buf, buf, None, info),
+                               (fake, 16, buf, buf, buf, None), (fake, 0, buf, buf, buf, info),
+                               (fake, -1, buf, buf, buf, info), (fake, (1 << 24) + 1, buf, buf, buf, info)]:
+        assert lib.kabc_poison_probe(ctx, n, a, b, c, i) == cd.KABC_ERR_INVALID_ARG, (n, a, b, c, i)
+        assert b"kabc_poison_probe" in lib.kabc_last_error()
+    rule = _lib.poison_byte_rule
+    assert [rule(v) for v in ("", "0", "00", "1", "yes", "0xff", "0XA5", "0x0", "0x3c", "0x100", "0xzz", "0x")] == \
+        [None, None, None, 0xA5, 0xA5, 0xFF, 0xA5, 0, 0x3C, 0xA5, 0xA5, 0xA5]

@@ -421,3 +421,25 @@ def test_agrees_with_smc_on_the_banana(k, gpu_ctx):
     print(f"banana: abc_reject {R[0]!r}, {R[1]!r} (eps {r.eps:.4g}, {r.info['wall_ms']:.1f} ms); smc {S[0]!r}, {S[1]!r}")
     assert len(R[0]) == 5000 and r.info["draws"] == 1 << 24
     assert R[0].isapprox(1) and R[1].isapprox(1)
+
+
+@pytest.mark.parametrize("mode", ["threshold", "keep"])
+def test_forced_phases_course_equals_fused_at_d2(k, orc, gpu_ctx, monkeypatch, mode):
+    """KABC_REJECT_COURSE=phases on a shape that takes the fused kernel otherwise: the same rows, against the
+    oracle's table"""
+    prior, cost = k.Factored(k.Normal(0, 5), k.Normal(0, 5)), k.costs.GaussDist([1.0, -0.5])
+    kw = dict(eps=2.0, n=40, draws=3000) if mode == "threshold" else dict(draws=3000, keep=37)
+    Po, Co, lpo, eo, io, do, xo = oracle_reject(orc, prior, cost, seed=3, first_row=7, **kw)
+    for course in ("fused", "phases"):
+        if course == "phases":
+            monkeypatch.setenv("KABC_REJECT_COURSE", "phases")
+        else:
+            monkeypatch.delenv("KABC_REJECT_COURSE", raising=False)
+        if mode == "threshold":
+            r = k.abc_reject(prior, cost, 2.0, 40, draws=3000, seed=3, first_row=7, return_array=True)
+        else:
+            r = k.abc_reject(prior, cost, draws=3000, keep=37, seed=3, first_row=7, return_array=True)
+        assert r.info["course"] == course, r.info
+        assert np.array_equal(r.info["index"], io) and np.array_equal(r.P, Po) and np.array_equal(r.C, Co), course
+        assert np.array_equal(r.logprior, lpo) and r.eps == eo, course
+        assert (r.info["draws"], r.info["exhausted"]) == (do, xo), course

@@ -231,3 +231,17 @@ def test_cancel_from_a_host_thread(k, orc):
     o = orc.OracleAIS(model, N, seed=11)
     o.set_state(x, lp, ll, t)
     assert np.array_equal(tr, o.generations_sync(20, nt))
+
+
+@pytest.mark.parametrize("waves", ["1", "16"])
+def test_lds_waves_knob_same_bits(k, orc, gpu_ctx, monkeypatch, waves):
+    """KABC_DYN_LDS_WAVES (A/B runs: the wavefronts per CU the rows in LDS leave room for, hence the team width)
+    promises the same bits: D = 20, N = 2048 on the launch-per-half-generation driver"""
+    monkeypatch.setenv("KABC_DYN_LDS_WAVES", waves)
+    model, N = _d20(k, 0.2), 2048
+    e = k.AisEnsemble(model, N, seed=3).init()
+    assert e.driver == "halves"
+    o = orc.OracleAIS(model, N, seed=3).init()
+    assert np.array_equal(e.advance(2, 3, collect=True), o.generations_sync(2, 3)) and _same(e.state(), o.state())
+    assert e.stats() == o.stats()
+    e.close()

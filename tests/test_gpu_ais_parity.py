@@ -137,3 +137,28 @@ def test_prepared_cost_prepass_batched_chains(k, orc, gpu_ctx, monkeypatch):
     for c, sd in enumerate(seeds):
         ref = orc.OracleAIS(model, 12, seed=sd).init().generations_sync(3, 4)
         assert np.array_equal(got[:, c], ref), f"chain {c}"
+
+
+@pytest.mark.parametrize("cls", ["normal", "simple"])
+def test_prebuilt_general_class_same_bits(k, orc, gpu_ctx, monkeypatch, cls):
+    """KABC_PREBUILT_CLASS=g (A/B runs: the GENERAL-class prebuilt kernel for a NORMAL / SIMPLE prior) promises
+    the same bits: D = 2, N = 130 on the launch-per-half-generation driver, no run-time specialisation"""
+    monkeypatch.setenv("KABC_AIS_SMALL", "0")
+    monkeypatch.setenv("KABC_SPECIALIZE", "0")
+    second = k.Normal(0, 5) if cls == "normal" else k.Uniform(-5, 5)
+    model = k.ApproxKernelizedPosterior(k.Factored(k.Normal(0, 5), second), k.costs.GaussDist([1.0, -0.5]), 0.1)
+    N, gens, nt, seed = 130, 3, 4, 11
+    ref = orc.OracleAIS(model, N, seed=seed).init()
+    tro = ref.generations_sync(gens, nt)
+    for forced in (False, True):
+        if forced:
+            monkeypatch.setenv("KABC_PREBUILT_CLASS", "g")
+        else:
+            monkeypatch.delenv("KABC_PREBUILT_CLASS", raising=False)
+        ens = k.AisEnsemble(model, N, seed=seed).init()
+        assert ens.driver == "halves"
+        assert np.array_equal(ens.advance(gens, nt, collect=True), tro), forced
+        for a, b in zip(ens.state(), ref.state()):
+            assert np.array_equal(a, b), forced
+        assert ens.stats() == ref.stats()
+        ens.close()

@@ -155,3 +155,20 @@ def test_smc_dynamic_dimension_bit_exact(k, orc, gpu_ctx, name, team, monkeypatc
     assert np.array_equal(got.info["theta_all"], ref["theta_all"])
     assert np.array_equal(got.info["alive"], ref["alive"]) and np.array_equal(got.C, ref["C"])
     assert got.info["cost_evals"] == ref["cost_evals"] and got.info["proposals"] == ref["proposals"]
+
+
+@pytest.mark.parametrize("waves", ["1", "16"])
+def test_smc_lds_waves_knob_same_bits(k, orc, gpu_ctx, monkeypatch, waves):
+    """KABC_DYN_LDS_WAVES (A/B runs: the wavefronts per CU whose rows LDS must hold, hence the team width)
+    promises the same bits for smc at D = 20"""
+    monkeypatch.delenv("KABC_SMC_DYN_TEAM", raising=False)
+    monkeypatch.setenv("KABC_DYN_LDS_WAVES", waves)
+    rng = np.random.default_rng(8)
+    pri, cost = k.Factored(*[k.Normal(0, 2)] * 20), k.costs.GaussDist(rng.normal(size=20))
+    kw = dict(nparticles=3000, alpha=0.9, epstol=3.0)
+    got = k.smc(pri, cost, seed=4, return_array=True, **kw)
+    ref = orc.smc(pri, cost, seed=4, **kw)
+    assert got.info["log"] == ref["log"] and got.eps == ref["eps"] and len(ref["log"]) >= 2
+    assert np.array_equal(got.info["theta_all"], ref["theta_all"])
+    assert np.array_equal(got.info["alive"], ref["alive"]) and np.array_equal(got.C, ref["C"])
+    assert got.info["cost_evals"] == ref["cost_evals"] and got.info["proposals"] == ref["proposals"]

@@ -389,3 +389,25 @@ def test_nan_cost_is_the_references_quantile_error(k, orc, gpu_ctx, monkeypatch,
         with pytest.raises(k.KabcError) as e:
             k.smc(prior, cost, return_array=True, **kw)
         assert str(e.value) == "quantiles are undefined in presence of NaNs"
+
+
+@pytest.mark.parametrize("knob,value", [("KABC_DSEL2_G", "1"), ("KABC_DSEL2_G", "3"),
+                                        ("KABC_DSEL2_DECIDE_G", "1"), ("KABC_DSEL2_DECIDE_G", "2")])
+def test_one_exchange_grid_knobs_same_bits(k, orc, gpu_ctx, monkeypatch, knob, value):
+    """KABC_DSEL2_G / KABC_DSEL2_DECIDE_G (A/B runs: the grids of the one-exchange course's kernels) promise the
+    same bits: with one workgroup, or a few, each has to stride over everything.  6000 particles, the smallest
+    ensemble the selection-edge tests drive this course with."""
+    monkeypatch.setenv("KABC_SMC_LOOP", "0")
+    monkeypatch.setenv("KABC_SMC_SPEC_SELECT", "1")
+    monkeypatch.delenv("KABC_DSEL2_G", raising=False)
+    monkeypatch.delenv("KABC_DSEL2_DECIDE_G", raising=False)
+    monkeypatch.setenv(knob, value)
+    prior, cost = k.Factored(k.Normal(0, 5), k.Normal(0, 5)), k.costs.GaussDist([1.0, -0.5])
+    kw = dict(nparticles=6000, alpha=0.9, epstol=0.05, seed=5)
+    got = k.smc(prior, cost, return_array=True, **kw)
+    ref = orc.smc(prior, cost, **kw)
+    assert got.info["dist"]["one_exchange_selections"] > 0, got.info["dist"]
+    assert got.info["iterations"] == ref["iterations"] and got.info["log"] == ref["log"] and got.eps == ref["eps"]
+    assert np.array_equal(got.info["alive"], ref["alive"]) and np.array_equal(got.info["theta_all"], ref["theta_all"])
+    assert np.array_equal(got.C, ref["C"])
+    assert got.info["cost_evals"] == ref["cost_evals"] and got.info["proposals"] == ref["proposals"]
