@@ -4,7 +4,7 @@
 // user plugin extends with its own branch).
 #pragma once
 
-#include "kabc_device.hpp"
+#include "dyn_model.hpp"
 #ifndef __HIPCC_RTC__
 #include "launcher.hpp"
 #endif
@@ -85,22 +85,12 @@ __device__ __forceinline__ void store_row_n(double* __restrict__ p, const double
         for (int k = 0; k < n; ++k) p[k] = v[k];
 }
 // push_p + logpdf(d::Factored, x): compile-time D from the by-value PriorSet, run-time D from
-// the device array (same formulas: comp_logpdf_general_body)
+// the device array (dyn_model.hpp)
 template <int D>
 __device__ __forceinline__ double logpdf_push_n(const PriorSet& P, const PriorDev* dP, int n,
                                                 const double* x, double* xp) {
     if constexpr (D != 0) return factored_logpdf_push<D>(P, x, xp);
-    else {
-        double s = 0.0;
-        for (int k = 0; k < n; ++k) {
-            const PriorDev q = dP[k];
-            const double v = q.discrete ? kabc_rint(x[k]) : x[k];
-            xp[k] = v;
-            const double l = comp_logpdf_general_body(q.kind, q.p[0], q.p[1], q.p[2], q.p[3], q.c0, q.c1, q.rb, v);
-            s = (k == 0) ? l : s + l;
-        }
-        return joint_logpdf_or(s, dP[0].kind, xp, n, dP, kabc_log_tab);
-    }
+    else return dyn_logpdf_push(dP, n, x, xp);
 }
 
 // k-th smallest (0-based) of the first c indices of the cost-sorted order

@@ -4,14 +4,16 @@
 // The reference puts no bound on length(prior) (src/priors.jl:10-13).  The fast kernels
 // (ais_kernels.hpp) keep a walker in registers and are instantiated for D = 1..KABC_MAX_DIM;
 // beyond that the walker's row, the proposal and its push_p image live in LDS rows sized at launch,
-// the prepared prior in a device array, and a walker belongs to a TEAM of 16 lanes (see the half-
-// generation kernel below).  Same draws (the
-// counter-based streams of include/kabc_philox.h), same operation order: bit-identical to the
-// oracle like the fast path (tests/test_gpu_dyn_dim.py).  Built-in DeviceCosts are
-// dispatched at run time (kabc_cost_eval); COST = KABC_COST_USER instantiates it for a plugin.
+// the prepared prior in a device array, and a walker belongs to a TEAM of 4 .. 64 lanes (see the
+// half-generation kernel below).  Same draws (the counter-based streams of include/kabc_philox.h),
+// same operation order: bit-identical to the oracle like the fast path (tests/test_gpu_dyn_dim.py).
+// The transition's formulas -- the draws, the three proposals, push_p and the prior's log-density,
+// loglike, accept, the cost's dispatch -- are in dyn_model.hpp, shared with ais_dyn_small_kernel.hpp
+// and smc_dyn_kernels.hpp; this file is staging, loops and data movement.
 #pragma once
 
 #include "ais_kernels.hpp"
+#include "dyn_model.hpp"
 
 namespace kabc {
 
@@ -46,56 +48,6 @@ struct AisDynArgs {
     int64_t params_stride, data_stride;
     int32_t nchains;
 };
-
-template <int COST>
-__device__ __forceinline__ double dyn_cost(int cost_id, const double* x, int D, const double* params,
-                                           const double* data, int64_t ndata, kabc_cost_rng_t* rng) {
-#ifdef KABC_USER_COST_DEFINED
-    if constexpr (COST == KABC_COST_USER) return kabc_user_cost(x, D, params, data, ndata, rng);
-#endif
-    // the built-in costs that take any number of parameters, dispatched at compile time: a kernel that carries
-    // every built-in cost allocates the registers of the hungriest one (292 against ~150: one wavefront per
-    // SIMD instead of three)
-    if constexpr (COST == KABC_COST_GAUSS_DIST) return kabc_cost_gauss_dist(x, D, params);
-    else if constexpr (COST == KABC_COST_ROSENBROCK) return kabc_cost_rosenbrock(x, D);
-    else if constexpr (COST == KABC_COST_HIER_GAUSS_SIM) return kabc_cost_hier_gauss_sim(x, D, data, rng);
-    else if constexpr (COST == KABC_COST_NORM_SHELL) return kabc_cost_norm_shell(x, D, params);
-    else return kabc_cost_eval(cost_id, x, D, params, data, ndata, rng);
-}
-
-// loglike(density, push_p(density, y)) with y, xp in memory, by ONE thread (step(init))
-template <int COST>
-__device__ __forceinline__ void dyn_loglike(const AisDynArgs& A, const double* y, double* xp,
-                                            kabc_cost_rng_t* rng, double& lp, double& ll, bool& ev) {
-    const int D = A.D;
-    if (A.posterior == KABC_POSTERIOR_COMMON) {
-        lp = 0.0;
-        ev = true;
-        ll = dyn_cost<COST>(A.cost_id, y, D, A.cost_params, A.cost_data, A.cost_ndata, rng);
-        return;
-    }
-    double s = 0.0;
-    for (int k = 0; k < D; ++k) {
-        const PriorDev q = A.prior[k];
-        const double v = q.discrete ? kabc_rint(y[k]) : y[k];
-        xp[k] = v;
-        const double l = comp_logpdf_general_body(q.kind, q.p[0], q.p[1], q.p[2], q.p[3], q.c0, q.c1, q.rb, v);
-        s = (k == 0) ? l : s + l;
-    }
-    lp = joint_logpdf_or(s, A.prior[0].kind, xp, D, A.prior, kabc_log_tab);
-    ev = kabc_isfinite(lp);
-    if (A.posterior == KABC_POSTERIOR_KERNELIZED) {
-        ll = lp;
-        if (ev) {
-            const double c = dyn_cost<COST>(A.cost_id, xp, D, A.cost_params, A.cost_data, A.cost_ndata, rng);
-            const double q = kabc_div_rc(c, A.eps, A.reps);
-            ll = -0.5 * (q * q);
-        }
-    } else {
-        ll = -lp;
-        if (ev) ll = dyn_cost<COST>(A.cost_id, xp, D, A.cost_params, A.cost_data, A.cost_ndata, rng);
-    }
-}
 
 // ---- the half-generation kernel: a TEAM of T lanes per walker ------------------------------------
 // Round 6.  Thread-per-walker, every lane walked all three moves' coordinate loops and a DE lane its
@@ -156,37 +108,15 @@ __global__ void __launch_bounds__(kWave) ais_dyn_half_kernel(const AisDynArgs A)
         const int nchunk = (D + KB * T - 1) / (KB * T);
         for (int s = 0; s < A.nt; ++s) {
             const uint64_t t = A.t0 + (uint64_t)s;
-            // -- the move, its partners, the accept variate: blocks 0, 1, 2 of the stream, ONE Philox
-            //    evaluation per wavefront (lane j < 3 of a team expands block j) handed round the team
+            // -- the move, its partners, the accept variate: blocks 0, 1, 2 of the stream
             kabc_u128_t B0, B1, B2;
-            {
-                const kabc_u128_t Bm = kabc_stream_block(A.seed, w, t, tl < 3 ? (uint32_t)tl : 0u, KABC_DOM_AIS_MOVE);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    B0.w[i] = (uint32_t)__shfl((int)Bm.w[i], team * T, kWave);
-                    B1.w[i] = (uint32_t)__shfl((int)Bm.w[i], team * T + 1, kWave);
-                    B2.w[i] = (uint32_t)__shfl((int)Bm.w[i], team * T + 2, kWave);
-                }
-            }
-            const uint32_t m7 = (uint32_t)(((uint64_t)B0.w[2] * 7u) >> 32);  // rand((1,1,1,1,2,2,3))
-            const int move = (m7 < 4u) ? 1 : (m7 < 6u) ? 2 : 3;
-            const int64_t a = (int64_t)kabc_index32(kabc_lo64(B0), nc);
-            int64_t b = -1, c = -1;
+            dyn_team_blocks<T>(A.seed, w, t, KABC_DOM_AIS_MOVE, team, tl, B0, B1, B2);
+            int move;
+            int64_t a, b, c;
+            ais_dyn_draw_move(B0, B2, nc, move, a, b, c);
             const double* xa = A.x_comp + a * D;
-            const double* xb = xa;
-            const double* xc = xa;
-            if (move >= 2) {
-                b = (int64_t)kabc_index32(kabc_lo64(B2), nc - 1u);
-                b += (b >= a);
-                xb = A.x_comp + b * D;
-                if (move == 3) {
-                    const int64_t lo = a < b ? a : b, hi = a < b ? b : a;
-                    c = (int64_t)kabc_index32(kabc_hi64(B2), nc - 2u);
-                    c += (c >= lo);
-                    c += (c >= hi);
-                    xc = A.x_comp + c * D;
-                }
-            }
+            const double* xb = move >= 2 ? A.x_comp + b * D : xa;
+            const double* xc = move == 3 ? A.x_comp + c * D : xa;
             // -- the partner rows' first chunk is requested now (they come from the frozen half: WHEN they
             //    are read cannot matter), the move's normals are generated while it is in flight
             double va[KB], vb[KB], vc[KB];
@@ -201,151 +131,39 @@ __global__ void __launch_bounds__(kWave) ais_dyn_half_kernel(const AisDynArgs A)
                 }
             };
             fetch(0);
-            double corr = 0.0, f0 = 0.0, f1 = 0.0, f2 = 0.0;  // the move's scalars: Z | gamma | z0, z1, z2
-            // -- the normal pairs of the wavefront's DE / walk moves (pair m of a walker = block 3 + m of its
-            //    stream; DE: gamma's and one per coordinate, D + 1 values; walk: three), dealt out over ALL 64
-            //    lanes: with a team of 4 and 17 parameters a DE walker's nine pairs were three rounds of
-            //    Philox + Box-Muller on its own four lanes while the stretch walkers' lanes idled -- and every
-            //    wavefront holds all three moves, so every wavefront paid them.  Now the wavefront's pairs
-            //    (about 0.29 (D + 2) / 2 + 0.29 per walker) are one list, a pair per lane and round.
-            {
-                const unsigned long long de_mask = __ballot(lead && move == 2), wk_mask = __ballot(lead && move == 3);
-                const int np_de = (D + 2) / 2;
-                int pre[kWalkers + 1];
-                pre[0] = 0;
-#pragma unroll
-                for (int q = 0; q < kWalkers; ++q)
-                    pre[q + 1] = pre[q] + (((de_mask >> (q * T)) & 1ull) ? np_de : ((wk_mask >> (q * T)) & 1ull) ? 2 : 0);
-                const int total = pre[kWalkers];
-                // (the lanes here: the wavefront's active teams = its first lanes)
-                const int nlanes = (int)__popcll(__ballot(true));
-                for (int item = lane; item < total; item += nlanes) {
-                    int tt = 0;
-#pragma unroll
-                    for (int q = 1; q < kWalkers; ++q) tt += (item >= pre[q]) ? 1 : 0;
-                    int base = 0;
-#pragma unroll
-                    for (int q = 1; q < kWalkers; ++q) base = (q == tt) ? pre[q] : base;
-                    const int m = item - base;
-                    const uint32_t wt = A.id_base + (uint32_t)(A.row_first + (int64_t)blockIdx.x * kWalkers + tt);
-                    double* const znt = rows0 + (size_t)tt * 5 * Dp + 4 * (size_t)Dp;
-                    const kabc_u128_t Bn = kabc_stream_block(A.seed, wt, t, 3u + (uint32_t)m, KABC_DOM_AIS_MOVE);
-                    double z0, z1;
-                    kabc_normal_pair(kabc_lo64(Bn), kabc_hi64(Bn), &z0, &z1);
-                    znt[2 * m] = z0;
-                    znt[2 * m + 1] = z1;
-                }
-                wave_lds_fence();
-            }
-            if (move == 1) {  // stretch_propose  src/transition.jl:51-59
-                const double sq3 = kabc_sqrt(3.0), isq3 = kabc_sqrt(1.0 / 3.0);
-                const double u = kabc_u01(kabc_hi64(B1));
-                const double tz = u * (sq3 - isq3) + isq3;
-                f0 = tz * tz;
-                corr = (double)(D - 1) * kabc_log_pn(f0);
-            } else if (move == 2) {  // de_propose  src/transition.jl:2-22
-                f0 = 2.38 / kabc_sqrt((double)(2 * D)) * kabc_exp_bounded(zn[0] * 0.1);
-            } else {                 // ais_walk_propose  src/transition.jl:24-43
-                f0 = zn[0];
-                f1 = zn[1];
-                f2 = zn[2];
-            }
+            ais_dyn_deal_normals<T>(A.seed, t, A.id_base + (uint32_t)(A.row_first + (int64_t)blockIdx.x * kWalkers), lead,
+                                    move, D, lane, rows0, 5 * (size_t)Dp, 4 * (size_t)Dp);
+            double corr, f0, f1, f2;
+            ais_dyn_move_scalars(move, D, B1, zn, corr, f0, f1, f2);
             for (int ch = 0; ch < nchunk; ++ch) {
                 if (ch > 0) fetch(ch);
 #pragma unroll
                 for (int j = 0; j < KB; ++j) {
                     const int kk = (ch * KB + j) * T + tl;
-                    if (kk < D) {
-                        const double xk = xs[kk];
-                        double yk;
-                        if (move == 1) {
-                            const double W = (xk - va[j]) * f0;
-                            yk = va[j] + W;
-                        } else if (move == 2) {
-                            const double Wk = (va[j] - vb[j]) * f0;
-                            const double sk = kabc_fabs(va[j] - vb[j]) + kabc_fabs(xk - vb[j]) + kabc_fabs(va[j] - xk);
-                            const double Tk = kabc_div_rc(f0 * sk, 300.0, 1.0 / 300.0) * zn[1 + kk];
-                            yk = xk + Wk + Tk;
-                        } else {
-                            const double Xs = kabc_div_rc(va[j] + (vb[j] + vc[j]), 3.0, 1.0 / 3.0);
-                            const double Wk = f0 * (va[j] - Xs) + f1 * (vb[j] - Xs) + f2 * (vc[j] - Xs);
-                            yk = xk + Wk;
-                        }
-                        y[kk] = yk;
-                    }
+                    if (kk < D) y[kk] = ais_dyn_propose(move, xs[kk], va[j], vb[j], vc[j], f0, f1, f2, zn + 1 + kk);
                 }
             }
             // -- push_p and the components' log-densities, a coordinate per lane
-            if (A.posterior != KABC_POSTERIOR_COMMON) {
-                for (int k = tl; k < D; k += T) {
-                    const PriorDev q = sp[k];
-                    const double v = q.discrete ? kabc_rint(y[k]) : y[k];
-                    xp[k] = v;
-                    lk[k] = comp_logpdf_general_body(q.kind, q.p[0], q.p[1], q.p[2], q.p[3], q.c0, q.c1, q.rb, v);
-                }
-            }
+            if (A.posterior != KABC_POSTERIOR_COMMON)
+                for (int k = tl; k < D; k += T) dyn_logpdf_push_comp(sp, k, y[k], xp, lk);
             wave_lds_fence();
             // -- ld = loglike(density, push_p(density, p)) and accept(...), the team's lane 0
-            //    (src/transition.jl:75-80; src/types.jl:51-75, :84-104, :117-128)
             int acc_i = 0;
             if (lead) {
                 kabc_cost_rng_t rng = {A.seed, t, w, KABC_DOM_AIS_COST, 0u};
-                double nlp, nll;
+                double nlp = 0.0, nll;
                 bool ev;
-                if (A.posterior == KABC_POSTERIOR_COMMON) {
-                    nlp = 0.0;
-                    ev = true;
-                    nll = dyn_cost<COST>(A.cost_id, y, D, A.cost_params, A.cost_data, A.cost_ndata, &rng);
-                } else {
-                    double sm = lk[0];  // left to right, as logpdf(d::Factored, x) sums (src/priors.jl:30-36)
-                    for (int k = 1; k < D; ++k) sm = sm + lk[k];
-                    nlp = joint_logpdf_or(sm, sp[0].kind, xp, D, sp, kabc_log_tab);
-                    ev = kabc_isfinite(nlp);
-                    if (A.posterior == KABC_POSTERIOR_KERNELIZED) {
-                        nll = nlp;
-                        if (ev) {
-                            const double cst = dyn_cost<COST>(A.cost_id, xp, D, A.cost_params, A.cost_data, A.cost_ndata, &rng);
-                            const double q = kabc_div_rc(cst, A.eps, A.reps);
-                            nll = -0.5 * (q * q);
-                        }
-                    } else {
-                        nll = -nlp;
-                        if (ev) nll = dyn_cost<COST>(A.cost_id, xp, D, A.cost_params, A.cost_data, A.cost_ndata, &rng);
-                    }
-                }
+                if (A.posterior != KABC_POSTERIOR_COMMON) nlp = dyn_logpdf_sum(sp, D, xp, lk);
+                ais_dyn_loglike<COST>(A.posterior, nlp, y, xp, D, A.cost_id, A.cost_params, A.cost_data, A.cost_ndata, A.eps,
+                                      A.reps, &rng, nll, ev);
                 n_eval += ev ? 1u : 0u;
-                bool acc = false;
-                if (!kabc_isfinite(corr)) err = err ? err : 1;
-                else if (ld_valid(A.posterior, nlp, nll)) {
-                    const double e = -kabc_log_pn(kabc_u01(kabc_lo64(B1)));  // randexp(rng)
-                    if (A.posterior == KABC_POSTERIOR_KERNELIZED) {
-                        const double lW = corr + (nlp + nll) - (lp + ll);
-                        acc = (-e <= lW);
-                    } else if (A.posterior == KABC_POSTERIOR_COMMON) {
-                        const double lW = corr + nll - ll;
-                        acc = (-e <= lW);
-                    } else {
-                        const double lW = corr + nlp - lp;
-                        const double mx = (A.eps > ll) ? A.eps : ll;
-                        const double lW2 = mx - nll;
-                        acc = (-e <= lW) && (lW2 >= 0.0);
-                    }
-                }
-                if (acc) {
+                if (ais_dyn_accept(A.posterior, corr, B1, lp, ll, nlp, nll, A.eps, err)) {
                     lp = nlp;
                     ll = nll;
                     n_acc += 1u;
+                    acc_i = 1;
                 }
-                acc_i = acc ? 1 : 0;
-                if (A.dbg) {
-                    int32_t* d = A.dbg + (r * A.nt + s) * 6;
-                    d[0] = move;
-                    d[1] = acc_i;
-                    d[2] = (int32_t)a;
-                    d[3] = (int32_t)b;
-                    d[4] = (int32_t)c;
-                    d[5] = ev ? 1 : 0;
-                }
+                if (A.dbg) ais_dyn_debug_record(A.dbg + (r * A.nt + s) * 6, move, acc_i, a, b, c, ev);
             }
             // the verdict goes to the team; accepted: x_i <- y  (src/transition.jl:77-78)
             acc_i = __shfl(acc_i, team * T, kWave);
@@ -406,7 +224,11 @@ __global__ void __launch_bounds__(kWave) ais_dyn_init_kernel(const AisDynArgs A0
         }
         kabc_cost_rng_t rng = {A.seed, attempt, w, KABC_DOM_AIS_INIT_COST, 0u};
         bool ev;
-        dyn_loglike<COST>(A, x, xp, &rng, lp, ll, ev);
+        // loglike(density, push_p(density, x)), x and xp in memory
+        lp = 0.0;
+        if (A.posterior != KABC_POSTERIOR_COMMON) lp = dyn_logpdf_push(A.prior, D, x, xp);
+        ais_dyn_loglike<COST>(A.posterior, lp, x, xp, D, A.cost_id, A.cost_params, A.cost_data, A.cost_ndata, A.eps, A.reps,
+                              &rng, ll, ev);
         if (ld_valid(A.posterior, lp, ll)) break;
         const unsigned long long used = atomicAdd(retries, 1ull) + 1ull;
         if (used > A.retry_budget) {

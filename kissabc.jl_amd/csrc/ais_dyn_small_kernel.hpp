@@ -14,6 +14,8 @@
 // no synchronisation beyond its own wavefront (the complementary half is frozen), and a half-step ends in
 // ONE workgroup barrier.  There is no producer ring: what a transition draws is generated inline, by the
 // lanes of the walker's wavefront, as in ais_dyn_half_kernel.
+// The transition itself -- draws, proposals, push_p, loglike, accept -- is the code of dyn_model.hpp that
+// ais_dyn_half_kernel calls; the two kernels differ in where the rows live and in their loops.
 // Same draws (include/kabc_philox.h, addressed by (seed, walker, t, block)), same expressions, same order
 // of every sum: bit-identical to ais_dyn_half_kernel launched per half-generation and to the oracle
 // (tests/test_gpu_ais_dyn_small.py) -- state, trace rows push_p(x_i) of every generation
@@ -162,172 +164,45 @@ __global__ void __launch_bounds__(kAisDynSmallMaxBlock) ais_dyn_small_kernel(con
 #pragma unroll 1
                     for (int s = 0; s < nt; ++s) {
                         const uint64_t t = A.t0 + (uint64_t)g * (uint64_t)nt + (uint64_t)s;
-                        // -- the move, its partners, the accept variate: blocks 0, 1, 2 of the stream, ONE Philox
-                        //    evaluation per wavefront (lane j < 3 of a team expands block j) handed round the team
+                        // -- the move, its partners, the accept variate: blocks 0, 1, 2 of the stream
                         kabc_u128_t B0, B1, B2;
-                        {
-                            const kabc_u128_t Bm = kabc_stream_block(seed, w, t, tl < 3 ? (uint32_t)tl : 0u, KABC_DOM_AIS_MOVE);
-#pragma unroll
-                            for (int i = 0; i < 4; ++i) {
-                                B0.w[i] = (uint32_t)__shfl((int)Bm.w[i], team * T, kWave);
-                                B1.w[i] = (uint32_t)__shfl((int)Bm.w[i], team * T + 1, kWave);
-                                B2.w[i] = (uint32_t)__shfl((int)Bm.w[i], team * T + 2, kWave);
-                            }
-                        }
-                        const uint32_t m7 = (uint32_t)(((uint64_t)B0.w[2] * 7u) >> 32);  // rand((1,1,1,1,2,2,3))
-                        const int move = (m7 < 4u) ? 1 : (m7 < 6u) ? 2 : 3;
-                        const int64_t a = (int64_t)kabc_index32(kabc_lo64(B0), nc);
-                        int64_t b = -1, c = -1;
+                        dyn_team_blocks<T>(seed, w, t, KABC_DOM_AIS_MOVE, team, tl, B0, B1, B2);
+                        int move;
+                        int64_t a, b, c;
+                        ais_dyn_draw_move(B0, B2, nc, move, a, b, c);
                         const double* xa = xcomp + (size_t)a * Dp;
-                        const double* xb = xa;
-                        const double* xc = xa;
-                        if (move >= 2) {
-                            b = (int64_t)kabc_index32(kabc_lo64(B2), nc - 1u);
-                            b += (b >= a);
-                            xb = xcomp + (size_t)b * Dp;
-                            if (move == 3) {
-                                const int64_t lo = a < b ? a : b, hi = a < b ? b : a;
-                                c = (int64_t)kabc_index32(kabc_hi64(B2), nc - 2u);
-                                c += (c >= lo);
-                                c += (c >= hi);
-                                xc = xcomp + (size_t)c * Dp;
-                            }
-                        }
-                        double corr = 0.0, f0 = 0.0, f1 = 0.0, f2 = 0.0;  // the move's scalars: Z | gamma | z0, z1, z2
-                        // -- the normal pairs of the wavefront's DE / walk moves (pair m of a walker = block 3 + m of
-                        //    its stream; DE: gamma's and one per coordinate, D + 1 values; walk: three), ONE list
-                        //    dealt out over the wavefront's lanes, a pair per lane and round (ais_dyn_half_kernel)
-                        {
-                            const unsigned long long de_mask = __ballot(lead && move == 2), wk_mask = __ballot(lead && move == 3);
-                            const int np_de = (D + 2) / 2;
-                            int pre[kWalkers + 1];
-                            pre[0] = 0;
-#pragma unroll
-                            for (int q = 0; q < kWalkers; ++q)
-                                pre[q + 1] = pre[q] + (((de_mask >> (q * T)) & 1ull) ? np_de : ((wk_mask >> (q * T)) & 1ull) ? 2 : 0);
-                            const int total = pre[kWalkers];
-                            const int nlanes = (int)__popcll(__ballot(true));
-                            for (int item = lane; item < total; item += nlanes) {
-                                int tt = 0;
-#pragma unroll
-                                for (int q = 1; q < kWalkers; ++q) tt += (item >= pre[q]) ? 1 : 0;
-                                int pbase = 0;
-#pragma unroll
-                                for (int q = 1; q < kWalkers; ++q) pbase = (q == tt) ? pre[q] : pbase;
-                                const int m = item - pbase;
-                                const uint32_t wt = A.id_base[h] + (uint32_t)(base + tt);
-                                double* const znt = wrows + ((size_t)tt * kAisDynSmallTeamRows + 3) * Dp;
-                                const kabc_u128_t Bn = kabc_stream_block(seed, wt, t, 3u + (uint32_t)m, KABC_DOM_AIS_MOVE);
-                                double z0, z1;
-                                kabc_normal_pair(kabc_lo64(Bn), kabc_hi64(Bn), &z0, &z1);
-                                znt[2 * m] = z0;
-                                znt[2 * m + 1] = z1;
-                            }
-                            wave_lds_fence();
-                        }
-                        if (move == 1) {  // stretch_propose  src/transition.jl:51-59
-                            const double sq3 = kabc_sqrt(3.0), isq3 = kabc_sqrt(1.0 / 3.0);
-                            const double u = kabc_u01(kabc_hi64(B1));
-                            const double tz = u * (sq3 - isq3) + isq3;
-                            f0 = tz * tz;
-                            corr = (double)(D - 1) * kabc_log_pn(f0);
-                        } else if (move == 2) {  // de_propose  src/transition.jl:2-22
-                            f0 = 2.38 / kabc_sqrt((double)(2 * D)) * kabc_exp_bounded(zn[0] * 0.1);
-                        } else {                 // ais_walk_propose  src/transition.jl:24-43
-                            f0 = zn[0];
-                            f1 = zn[1];
-                            f2 = zn[2];
-                        }
+                        const double* xb = move >= 2 ? xcomp + (size_t)b * Dp : xa;
+                        const double* xc = move == 3 ? xcomp + (size_t)c * Dp : xa;
+                        ais_dyn_deal_normals<T>(seed, t, A.id_base[h] + (uint32_t)base, lead, move, D, lane, wrows,
+                                                kAisDynSmallTeamRows * (size_t)Dp, 3 * (size_t)Dp);
+                        double corr, f0, f1, f2;
+                        ais_dyn_move_scalars(move, D, B1, zn, corr, f0, f1, f2);
                         // -- the proposal, push_p and the components' log-densities, a coordinate per lane
                         for (int k = tl; k < D; k += T) {
-                            const double xk = xs[k], va = xa[k];
-                            double yk;
-                            if (move == 1) {
-                                const double W = (xk - va) * f0;
-                                yk = va + W;
-                            } else if (move == 2) {
-                                const double vb = xb[k];
-                                const double Wk = (va - vb) * f0;
-                                const double sk = kabc_fabs(va - vb) + kabc_fabs(xk - vb) + kabc_fabs(va - xk);
-                                const double Tk = kabc_div_rc(f0 * sk, 300.0, 1.0 / 300.0) * zn[1 + k];
-                                yk = xk + Wk + Tk;
-                            } else {
-                                const double vb = xb[k], vc = xc[k];
-                                const double Xs = kabc_div_rc(va + (vb + vc), 3.0, 1.0 / 3.0);
-                                const double Wk = f0 * (va - Xs) + f1 * (vb - Xs) + f2 * (vc - Xs);
-                                yk = xk + Wk;
-                            }
+                            const double va = xa[k], vb = move >= 2 ? xb[k] : 0.0, vc = move == 3 ? xc[k] : 0.0;
+                            const double yk = ais_dyn_propose(move, xs[k], va, vb, vc, f0, f1, f2, zn + 1 + k);
                             y[k] = yk;
-                            if (A.posterior != KABC_POSTERIOR_COMMON) {
-                                const PriorDev q = sp[k];
-                                const double v = q.discrete ? kabc_rint(yk) : yk;
-                                xp[k] = v;
-                                lk[k] = comp_logpdf_general_body(q.kind, q.p[0], q.p[1], q.p[2], q.p[3], q.c0, q.c1, q.rb, v);
-                            }
+                            if (A.posterior != KABC_POSTERIOR_COMMON) dyn_logpdf_push_comp(sp, k, yk, xp, lk);
                         }
                         wave_lds_fence();
                         // -- ld = loglike(density, push_p(density, p)) and accept(...), the team's lane 0
-                        //    (src/transition.jl:75-80; src/types.jl:51-75, :84-104, :117-128)
                         int acc_i = 0;
                         if (lead) {
                             kabc_cost_rng_t rng = {seed, t, w, KABC_DOM_AIS_COST, 0u};
-                            double nlp, nll;
+                            double nlp = 0.0, nll;
                             bool ev;
-                            if (A.posterior == KABC_POSTERIOR_COMMON) {
-                                nlp = 0.0;
-                                ev = true;
-                                nll = dyn_cost<COST>(A.cost_id, y, D, cparams, cdata, A.cost_ndata, &rng);
-                            } else {
-                                double sm = lk[0];  // left to right, as logpdf(d::Factored, x) sums (src/priors.jl:30-36)
-                                for (int k = 1; k < D; ++k) sm = sm + lk[k];
-                                nlp = joint_logpdf_or(sm, sp[0].kind, xp, D, sp, kabc_log_tab);
-                                ev = kabc_isfinite(nlp);
-                                if (A.posterior == KABC_POSTERIOR_KERNELIZED) {
-                                    nll = nlp;
-                                    if (ev) {
-                                        const double cst = dyn_cost<COST>(A.cost_id, xp, D, cparams, cdata, A.cost_ndata, &rng);
-                                        const double q = kabc_div_rc(cst, A.eps, A.reps);
-                                        nll = -0.5 * (q * q);
-                                    }
-                                } else {
-                                    nll = -nlp;
-                                    if (ev) nll = dyn_cost<COST>(A.cost_id, xp, D, cparams, cdata, A.cost_ndata, &rng);
-                                }
-                            }
+                            if (A.posterior != KABC_POSTERIOR_COMMON) nlp = dyn_logpdf_sum(sp, D, xp, lk);
+                            ais_dyn_loglike<COST>(A.posterior, nlp, y, xp, D, A.cost_id, cparams, cdata, A.cost_ndata, A.eps,
+                                                  A.reps, &rng, nll, ev);
                             n_eval += ev ? 1u : 0u;
-                            bool acc = false;
-                            if (!kabc_isfinite(corr)) err = err ? err : 1;
-                            else if (ld_valid(A.posterior, nlp, nll)) {
-                                const double e = -kabc_log_pn(kabc_u01(kabc_lo64(B1)));  // randexp(rng)
-                                if (A.posterior == KABC_POSTERIOR_KERNELIZED) {
-                                    const double lW = corr + (nlp + nll) - (lp + ll);
-                                    acc = (-e <= lW);
-                                } else if (A.posterior == KABC_POSTERIOR_COMMON) {
-                                    const double lW = corr + nll - ll;
-                                    acc = (-e <= lW);
-                                } else {
-                                    const double lW = corr + nlp - lp;
-                                    const double mx = (A.eps > ll) ? A.eps : ll;
-                                    const double lW2 = mx - nll;
-                                    acc = (-e <= lW) && (lW2 >= 0.0);
-                                }
-                            }
-                            if (acc) {
+                            if (ais_dyn_accept(A.posterior, corr, B1, lp, ll, nlp, nll, A.eps, err)) {
                                 lp = nlp;
                                 ll = nll;
                                 n_acc += 1u;
+                                acc_i = 1;
                             }
-                            acc_i = acc ? 1 : 0;
-                            if (A.dbg) {
-                                const int64_t rg = (int64_t)(h ? rows0 : 0) + r;
-                                int32_t* d = A.dbg + (rg * nt + s) * 6;
-                                d[0] = move;
-                                d[1] = acc_i;
-                                d[2] = (int32_t)a;
-                                d[3] = (int32_t)b;
-                                d[4] = (int32_t)c;
-                                d[5] = ev ? 1 : 0;
-                            }
+                            if (A.dbg)
+                                ais_dyn_debug_record(A.dbg + (((int64_t)(h ? rows0 : 0) + r) * nt + s) * 6, move, acc_i, a, b, c, ev);
                         }
                         // the verdict goes to the team; accepted: x_i <- y  (src/transition.jl:77-78)
                         acc_i = __shfl(acc_i, team * T, kWave);

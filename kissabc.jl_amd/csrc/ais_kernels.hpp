@@ -152,14 +152,6 @@ struct RecBuf {
 template <int D>
 using ChunkRec = RecBuf<D, kChunk>;
 
-template <int POSTERIOR_RUNTIME = 0>
-__device__ __forceinline__ bool ld_valid(int posterior, double lp, double ll) {
-    // is_valid_logdensity: src/types.jl:60 and :93-94
-    // (CommonLogDensity, :121: isfinite(ld), held as lp = 0, ll = lπ)
-    return posterior != KABC_POSTERIOR_THRESHOLD ? kabc_isfinite(lp + ll)
-                                                 : (kabc_isfinite(ll) && kabc_isfinite(lp));
-}
-
 // Prior classes (chosen on the host, identical results):
 //   BOX     every component is Uniform / DiscreteUniform: logpdf is the constant
 //           c0_1 + ... + c0_D (summed left to right on the host, as
@@ -370,14 +362,6 @@ __device__ __forceinline__ void loglike(const PriorDev* __restrict__ P, const Bo
             if (ev) ll = eval_cost<COST, D>(yp, cost_params, cost_data, ndata, rng);
         }
     }
-}
-
-__device__ __forceinline__ void wave_lds_fence() {
-    // LDS traffic of one wavefront completes in order; this only stops the
-    // compiler from moving LDS accesses across the point.
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 // PRODUCER: fill sub-step `si` (transition counter t) of a record buffer for the

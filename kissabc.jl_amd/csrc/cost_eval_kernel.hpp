@@ -8,14 +8,14 @@
 // piece of theta -- in LDS with coalesced loads: a row shared by the lanes of a wavefront is fetched once, and with
 // nrep == 1 nobody reads 64 strided streams.  LDS rows are D | 1 words apart (an odd stride: the lanes of a
 // ds_read_b64 group that hold different rows hit different banks).  The dimension is a run-time value, the row
-// stays behind its LDS pointer (the costs loop over it); one kernel per cost.
+// stays behind its LDS pointer (the costs loop over it); one kernel per cost (cost_of, dyn_model.hpp).
 //
 // Stream contract (include/kabc_philox.h): replicate j of row i draws from
 // kabc_cost_rng_t{seed, t = j, walker = first_row + i, KABC_DOM_EVAL_COST}.  The value of an item depends on
 // (seed, first_row + i, j, theta[i], cost) alone; this file only decides who computes which item.
 #pragma once
 
-#include "kabc_device.hpp"
+#include "dyn_model.hpp"
 
 namespace kabc {
 
@@ -76,27 +76,6 @@ __device__ __forceinline__ void cost_eval_meanstd_prepare(const double* params, 
     kabc_cost_normal_meanstd_moments(n, va, vb, aux);
 }
 
-// compile-time dispatch: a kernel that carries every cost allocates the registers of the hungriest one
-template <int COST>
-__device__ __forceinline__ double cost_eval_one(int cost_id, const double* x, int D, const double* params,
-                                                const double* data, int64_t ndata, kabc_cost_rng_t* rng) {
-#ifdef KABC_USER_COST_DEFINED
-    if constexpr (COST == KABC_COST_USER) return kabc_user_cost(x, D, params, data, ndata, rng);
-#endif
-    if constexpr (COST == KABC_COST_GAUSS_DIST) return kabc_cost_gauss_dist(x, D, params);
-    else if constexpr (COST == KABC_COST_ROSENBROCK) return kabc_cost_rosenbrock(x, D);
-    else if constexpr (COST == KABC_COST_HIER_GAUSS_SIM) return kabc_cost_hier_gauss_sim(x, D, data, rng);
-    else if constexpr (COST == KABC_COST_NORMAL_MEANSTD_SIM) return kabc_cost_normal_meanstd_sim(x, params, rng);
-    else if constexpr (COST == KABC_COST_DIRAC_SQ) return kabc_cost_dirac_sq(x, params);
-    else if constexpr (COST == KABC_COST_ABS_DIFF) return kabc_cost_abs_diff(x, params);
-    else if constexpr (COST == KABC_COST_NORM_SHELL) return kabc_cost_norm_shell(x, D, params);
-    else if constexpr (COST == KABC_COST_NOISY_QUAD_DU) return kabc_cost_noisy_quad_du(x, params, rng);
-    else if constexpr (COST == KABC_COST_MIXTURE) return kabc_cost_mixture(x, params, rng);
-    else if constexpr (COST == KABC_COST_NOISY_BANANA) return kabc_cost_noisy_banana(x, params, rng);
-    else if constexpr (COST == KABC_COST_WIENER_RMS) return kabc_cost_wiener_rms(x, data, ndata, rng);
-    else return kabc_cost_eval(cost_id, x, D, params, data, ndata, rng);
-}
-
 // the cost of row x under the stream (seed, t = rep, walker, KABC_DOM_EVAL_COST): one item of cost_eval_kernel, and
 // the cost of a row of abc_reject_kernel.hpp.  logtab: the workgroup's LDS copy of kabc_log_tab, or nullptr
 template <int COST>
@@ -110,7 +89,7 @@ __device__ __forceinline__ double cost_eval_item(int cost_id, const double* x, i
         rng.aux = aux;
         rng.aux_stride = 1u;
     }
-    return cost_eval_one<COST>(cost_id, x, D, params, data, ndata, &rng);
+    return cost_of<COST>(cost_id, x, D, params, data, ndata, &rng);
 }
 
 template <int COST>

@@ -533,6 +533,22 @@ __device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
     return v;
 }
 
+__device__ __forceinline__ void wave_lds_fence() {
+    // LDS traffic of one wavefront completes in order; this only stops the
+    // compiler from moving LDS accesses across the point.
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+template <int POSTERIOR_RUNTIME = 0>
+__device__ __forceinline__ bool ld_valid(int posterior, double lp, double ll) {
+    // is_valid_logdensity: src/types.jl:60 and :93-94
+    // (CommonLogDensity, :121: isfinite(ld), held as lp = 0, ll = lπ)
+    return posterior != KABC_POSTERIOR_THRESHOLD ? kabc_isfinite(lp + ll)
+                                                 : (kabc_isfinite(ll) && kabc_isfinite(lp));
+}
+
 // inclusive prefix sum over the 64 lanes with DPP (row_shr 1/2/4/8, row_bcast 15/31): six
 // VALU instructions instead of six LDS-crossbar shuffles (each ~100 cycles of latency)
 __device__ __forceinline__ unsigned wave_scan_incl(unsigned v) {

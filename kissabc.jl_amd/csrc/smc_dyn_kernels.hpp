@@ -2,8 +2,11 @@
 // :160-191 (propose + accept) with the dimension as a RUN-TIME value, rows in memory.  Same
 // draws and operation order as smc_init_kernel / smc_mcmc_kernel (bit-identical to the oracle);
 // it plugs into the kernel-per-phase path (select / pass_end / finalize do not depend on D).
+// push_p + the prior's log-density, the cost's dispatch and the team's three stream blocks are in
+// dyn_model.hpp, shared with the AIS kernels of ais_dyn_kernels.hpp.
 #pragma once
 
+#include "dyn_model.hpp"
 #include "smc_kernels.hpp"
 
 namespace kabc {
@@ -31,34 +34,6 @@ struct SmcDynArgs {
 };
 
 template <int COST>
-__device__ __forceinline__ double smc_dyn_cost(int cost_id, const double* x, int D, const double* params,
-                                               const double* data, int64_t ndata, kabc_cost_rng_t* rng) {
-#ifdef KABC_USER_COST_DEFINED
-    if constexpr (COST == KABC_COST_USER) return kabc_user_cost(x, D, params, data, ndata, rng);
-#endif
-    // the built-in costs that take any number of parameters, dispatched at compile time: a kernel that carries
-    // every built-in cost allocates the registers of the hungriest one (292 against ~150: one wavefront per
-    // SIMD instead of three)
-    if constexpr (COST == KABC_COST_GAUSS_DIST) return kabc_cost_gauss_dist(x, D, params);
-    else if constexpr (COST == KABC_COST_ROSENBROCK) return kabc_cost_rosenbrock(x, D);
-    else if constexpr (COST == KABC_COST_HIER_GAUSS_SIM) return kabc_cost_hier_gauss_sim(x, D, data, rng);
-    else if constexpr (COST == KABC_COST_NORM_SHELL) return kabc_cost_norm_shell(x, D, params);
-    else return kabc_cost_eval(cost_id, x, D, params, data, ndata, rng);
-}
-
-__device__ __forceinline__ double smc_dyn_logpdf_push(const SmcDynArgs& A, const double* x, double* xp) {
-    double s = 0.0;
-    for (int k = 0; k < A.D; ++k) {
-        const PriorDev q = A.prior[k];
-        const double v = q.discrete ? kabc_rint(x[k]) : x[k];
-        xp[k] = v;
-        const double l = comp_logpdf_general_body(q.kind, q.p[0], q.p[1], q.p[2], q.p[3], q.c0, q.c1, q.rb, v);
-        s = (k == 0) ? l : s + l;
-    }
-    return joint_logpdf_or(s, A.prior[0].kind, xp, A.D, A.prior, kabc_log_tab);
-}
-
-template <int COST>
 __global__ void __launch_bounds__(kSmcBlock) smc_dyn_init_kernel(const SmcDynArgs A) {
     const int64_t i = (int64_t)blockIdx.x * kSmcBlock + threadIdx.x;
     double c = 0.0;
@@ -70,9 +45,9 @@ __global__ void __launch_bounds__(kSmcBlock) smc_dyn_init_kernel(const SmcDynArg
             kabc_slotwin_t win = {A.seed, 0ull, (uint32_t)i, KABC_DOM_SMC_INIT, (uint32_t)k * KABC_SLOTS_PER_DIM};
             x[k] = kabc_sample_prior(&A.raw[k], &win);  // (a pointer INTO the array: joint priors, kabc_sampling.h)
         }
-        const double lp = smc_dyn_logpdf_push(A, x, xp);
+        const double lp = dyn_logpdf_push(A.prior, D, x, xp);
         kabc_cost_rng_t rng = {A.seed, 0ull, (uint32_t)i, KABC_DOM_SMC_INIT_COST, 0u};
-        c = smc_dyn_cost<COST>(A.cost_id, xp, D, A.cost_params, A.cost_data, A.cost_ndata, &rng);
+        c = cost_of<COST>(A.cost_id, xp, D, A.cost_params, A.cost_data, A.cost_ndata, &rng);
         A.X[0][i] = c;
         A.lpi[0][i] = lp;
         A.alive[i] = 1;
@@ -136,14 +111,13 @@ __global__ void __launch_bounds__(kSmcBlock) smc_dyn_mcmc_kernel(const SmcDynArg
             }
             const double lprob = kabc_log(kabc_u01(kabc_lo64(B2)));
             n_prop = 1;
-            const double lpp = smc_dyn_logpdf_push(A, prop, xp);
+            const double lpp = dyn_logpdf_push(A.prior, D, prop, xp);
             if (!(lpp < 0.0 && !kabc_isfinite(lpp))) {  // :173
                 double lM = lpp - lpi + 0.0;
                 if (!(lM < 0.0)) lM = (lM != lM) ? lM : 0.0;
                 if (lprob < lM) {
                     kabc_cost_rng_t rng = {A.seed, pass, w, KABC_DOM_SMC_COST, 0u};
-                    const double Xp =
-                        smc_dyn_cost<COST>(A.cost_id, xp, D, A.cost_params, A.cost_data, A.cost_ndata, &rng);
+                    const double Xp = cost_of<COST>(A.cost_id, xp, D, A.cost_params, A.cost_data, A.cost_ndata, &rng);
                     n_eval = 1;
                     const double eps = A.ctrl->eps;
                     const bool reject = A.ctrl->flag ? (Xp > eps) : (Xp >= eps);
@@ -186,11 +160,6 @@ __global__ void __launch_bounds__(kSmcBlock) smc_dyn_mcmc_kernel(const SmcDynArg
 // proposal's push_p image and the log-densities live in LDS (2 rows of D per particle, dynamic), the
 // prepared prior too.  The per-64-particle statistics the selection reads (smc_block_stats) come from a
 // second, tiny kernel: a workgroup of this one is a wavefront of 64 / T particles.
-__device__ __forceinline__ void smc_dyn_lds_fence() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 __host__ __device__ inline int smc_dyn_row(int D) { return (D + 1) & ~1; }
 
 template <int COST, int T>
@@ -242,15 +211,7 @@ __global__ void __launch_bounds__(kWave) smc_dyn_team_kernel(const SmcDynArgs A)
             const uint32_t w = (uint32_t)i;
             // blocks 0, 1, 2 of the particle's stream: lane j < 3 of the team expands block j
             kabc_u128_t B0, B1, B2;
-            {
-                const kabc_u128_t Bm = kabc_stream_block(A.seed, w, pass, tl < 3 ? (uint32_t)tl : 0u, KABC_DOM_SMC_MOVE);
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    B0.w[q] = (uint32_t)__shfl((int)Bm.w[q], team * T, kWave);
-                    B1.w[q] = (uint32_t)__shfl((int)Bm.w[q], team * T + 1, kWave);
-                    B2.w[q] = (uint32_t)__shfl((int)Bm.w[q], team * T + 2, kWave);
-                }
-            }
+            dyn_team_blocks<T>(A.seed, w, pass, KABC_DOM_SMC_MOVE, team, tl, B0, B1, B2);
             // while a==i ... ; while b==i || b==a ...  (src/smc.jl:163-164)
             int64_t a = (int64_t)kabc_index32(kabc_lo64(B0), (uint32_t)N - 1u);
             a += (a >= i);
@@ -266,26 +227,19 @@ __global__ void __launch_bounds__(kWave) smc_dyn_team_kernel(const SmcDynArgs A)
             // proposal, push_p, the components' log-densities: a coordinate per lane
             for (int k = tl; k < D; k += T) {
                 const double W = (tb[k] - ta[k]) * s;
-                const double pk = th[k] + W;
-                const PriorDev q = sp[k];
-                const double v = q.discrete ? kabc_rint(pk) : pk;
-                xp[k] = v;
-                lk[k] = comp_logpdf_general_body(q.kind, q.p[0], q.p[1], q.p[2], q.p[3], q.c0, q.c1, q.rb, v);
+                dyn_logpdf_push_comp(sp, k, th[k] + W, xp, lk);
             }
-            smc_dyn_lds_fence();
+            wave_lds_fence();
             if (lead) {
                 const double lprob = kabc_log(kabc_u01(kabc_lo64(B2)));
                 n_prop = 1;
-                double sm = lk[0];  // left to right, as logpdf(d::Factored, x) sums
-                for (int k = 1; k < D; ++k) sm = sm + lk[k];
-                const double lpp = joint_logpdf_or(sm, sp[0].kind, xp, D, sp, kabc_log_tab);
+                const double lpp = dyn_logpdf_sum(sp, D, xp, lk);
                 if (!(lpp < 0.0 && !kabc_isfinite(lpp))) {  // :173
                     double lM = lpp - lpi + 0.0;
                     if (!(lM < 0.0)) lM = (lM != lM) ? lM : 0.0;
                     if (lprob < lM) {
                         kabc_cost_rng_t rng = {A.seed, pass, w, KABC_DOM_SMC_COST, 0u};
-                        const double Xp =
-                            smc_dyn_cost<COST>(A.cost_id, xp, D, A.cost_params, A.cost_data, A.cost_ndata, &rng);
+                        const double Xp = cost_of<COST>(A.cost_id, xp, D, A.cost_params, A.cost_data, A.cost_ndata, &rng);
                         n_eval = 1;
                         const bool reject = flag ? (Xp > eps) : (Xp >= eps);
                         if (!reject) {

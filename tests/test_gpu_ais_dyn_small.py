@@ -65,6 +65,21 @@ def test_oracle_parity(k, orc, gpu_ctx, monkeypatch, name, nt):
         assert d.driver == "halves"
         d.close()
         monkeypatch.setenv("KABC_AIS_SMALL", "1")
+    _oracle_parity(k, orc, monkeypatch, model, N, nt, gens, seed)
+
+
+@pytest.mark.parametrize("N", [30, 200])
+def test_oracle_parity_team_widths(k, orc, gpu_ctx, monkeypatch, N):
+    """teams of 32 and of 4 lanes (the sizes above land on 8, 16 and 64).  ais_dyn_small_plan at D = 17: the
+    coordinates can use Tcap = 32 lanes; T halves from there while a workgroup of 512 has fewer than
+    rows0 = ceil(N / 2) teams.  N = 30: 512 / 32 = 16 >= 15, T = 32.  N = 200: 16, 32, 64 < 100, T = 4
+    (128 teams, one round; 118 KB of LDS)"""
+    monkeypatch.delenv("KABC_AIS_SMALL", raising=False)
+    model, _ = _models(k)["rosen_d17_box"]
+    _oracle_parity(k, orc, monkeypatch, model, N, nt=3, gens=4, seed=21)
+
+
+def _oracle_parity(k, orc, monkeypatch, model, N, nt, gens, seed):
     e = k.AisEnsemble(model, N, seed=seed).init()
     assert e.driver == "small"
     h = _halves(k, monkeypatch, model, N, seed=seed).init()

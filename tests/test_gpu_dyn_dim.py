@@ -31,8 +31,14 @@ def _models(k):
                                   "hier_d34_mixed", "gauss_d128"])
 def test_dynamic_dimension_bit_exact(k, orc, gpu_ctx, name):
     model, N = _models(k)[name]
-    nt, gens, seed = 6, 3, 21
+    _bit_exact(k, orc, model, N, nt=6, gens=3, seed=21)
+
+
+def _bit_exact(k, orc, model, N, nt, gens, seed, driver=None):
+    """state, trace, debug records and stats of 1 + gens generations against the oracle"""
     e = k.AisEnsemble(model, N, seed=seed).init()
+    if driver is not None:
+        assert e.driver == driver
     o = orc.OracleAIS(model, N, seed=seed).init()
     for got, ref in zip(e.state()[:3], o.state()[:3]):
         assert np.array_equal(got, ref)                      # step(init)
@@ -52,6 +58,30 @@ def test_dynamic_dimension_bit_exact(k, orc, gpu_ctx, name):
         assert np.array_equal(got, ref)
     assert e.stats() == o.stats()
     e.close()
+
+
+@pytest.mark.parametrize("driver,N", [("halves", 130), ("small", 40)])
+def test_common_logdensity_beyond_16_parameters(k, orc, gpu_ctx, monkeypatch, driver, N):
+    """the KABC_POSTERIOR_COMMON branches of ais_dyn_init_kernel and of both AIS kernels: no prior term, the
+    cost of the proposal as it is (src/types.jl:105-128)"""
+    if driver == "halves":
+        monkeypatch.setenv("KABC_AIS_SMALL", "0")
+    else:
+        monkeypatch.delenv("KABC_AIS_SMALL", raising=False)
+    monkeypatch.delenv("KABC_DYN_TEAM", raising=False)
+    model = k.CommonLogDensity(17, k.Factored(*[k.Normal(0, 1)] * 17), k.costs.NormShell(3.0))
+    _bit_exact(k, orc, model, N, nt=3, gens=2, seed=21, driver=driver)
+
+
+@pytest.mark.parametrize("team", ["4", "8", "16", "32"])
+def test_half_generation_team_widths(k, orc, gpu_ctx, monkeypatch, team):
+    """every instantiation of ais_dyn_half_kernel at a small ensemble (the host alone picks 64 lanes per walker
+    there).  4 lanes, 17 parameters: two chunks of coordinates, the second with one; a last workgroup with 1 of 16
+    walkers, whose 4 lanes deal out the normals; nine pairs per DE walker in zn[0..17] of a 20-word row"""
+    monkeypatch.setenv("KABC_AIS_SMALL", "0")
+    monkeypatch.setenv("KABC_DYN_TEAM", team)
+    model, _ = _models(k)["rosen_d17_box"]
+    _bit_exact(k, orc, model, 130, nt=3, gens=2, seed=21, driver="halves")
 
 
 def test_dynamic_dimension_limits_and_sharding(k, orc, gpu_ctx):
