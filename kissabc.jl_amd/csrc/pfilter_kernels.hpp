@@ -3,7 +3,8 @@
 // here is one ATTEMPT of the rejection loop (:306-325) for every particle that is
 // still "bad": the host repeats passes until none is left.  Survivors are read-only
 // during an iteration and bad particles write only themselves, so passes are
-// race-free exactly as the reference's threaded loop is.
+// race-free exactly as the reference's threaded loop is.  The one-workgroup kernel's quantile position
+// and value are the functions of smc_model.hpp.
 #pragma once
 
 #include "kabc_device.hpp"
@@ -229,22 +230,16 @@ __global__ void __launch_bounds__(kPfSmallBlock) pf_small_kernel(const PfSmallAr
             rank += (kj < ki || (kj == ki && j < tid)) ? 1u : 0u;
         }
         const long long n = N;
-        const double aleph = (double)n * S.q + (1.0 - S.q);
-        long long jq = (long long)aleph;
-        if (jq < 1) jq = 1;
-        if (jq > n - 1) jq = n - 1;
-        if (n == 1) jq = 1;
-        double gq = aleph - (double)jq;
-        gq = gq < 0.0 ? 0.0 : (gq > 1.0 ? 1.0 : gq);
+        long long jq;
+        double gq;
+        smc_quantile_pos(n, S.q, &jq, &gq);
         if (in) {
             if ((long long)rank == jq - 1) s_ab[0] = Ci;
             if ((long long)rank == (n == 1 ? 0 : jq)) s_ab[1] = Ci;
         }
         __syncthreads();
         const double qa = s_ab[0], qb = s_ab[1];
-        double eps;
-        if (kabc_isfinite(qa) && kabc_isfinite(qb)) eps = qa + gq * (qb - qa);
-        else eps = (1.0 - gq) * qa + gq * qb;
+        const double eps = smc_quantile_value(qa, qb, gq);
         // ---- ok = !(C > ϵ) as the select kernel writes it, idxok ascending (:299-301)
         const bool ok = in && Ci <= eps;
         const unsigned long long okb = __ballot(ok);

@@ -16,7 +16,7 @@
 //     holds one of the kernel's wavefronts and a CU four -- two runs of 100 particles (two wavefronts
 //     each) share a CU, a run of 256 has it alone;
 //   * ϵ = quantile(C, q) (type 7) by rank counting, ok = C <= ϵ, idxok from wave ballots: the
-//     arithmetic of pf_small_kernel;
+//     arithmetic of pf_small_kernel (the quantile's position and value: smc_model.hpp);
 //   * THE REJECTION PHASE (:304-325) is parallel over ATTEMPTS.  Every draw of attempt a of particle i
 //     is addressed by (seed, i, iteration << 24 | a, domain); the survivors are read-only during an
 //     iteration and a bad particle writes only itself: any lane can evaluate any (particle, attempt)
@@ -198,22 +198,16 @@ __global__ void __launch_bounds__(kPfBatchBlock) pf_batch_kernel(const PfBatchAr
             rank += (kj < ki || (kj == ki && j < tid)) ? 1u : 0u;
         }
         const long long n = N;
-        const double aleph = (double)n * A.q + (1.0 - A.q);
-        long long jq = (long long)aleph;
-        if (jq < 1) jq = 1;
-        if (jq > n - 1) jq = n - 1;
-        if (n == 1) jq = 1;
-        double gq = aleph - (double)jq;
-        gq = gq < 0.0 ? 0.0 : (gq > 1.0 ? 1.0 : gq);
+        long long jq;
+        double gq;
+        smc_quantile_pos(n, A.q, &jq, &gq);
         if (in) {
             if ((long long)rank == jq - 1) s_ab[0] = Ci;
             if ((long long)rank == (n == 1 ? 0 : jq)) s_ab[1] = Ci;
         }
         __syncthreads();
         const double qa = s_ab[0], qb = s_ab[1];
-        double eps;
-        if (kabc_isfinite(qa) && kabc_isfinite(qb)) eps = qa + gq * (qb - qa);
-        else eps = (1.0 - gq) * qa + gq * qb;
+        const double eps = smc_quantile_value(qa, qb, gq);
         // ---- ok = !(C > ϵ) as the select kernel writes it, idxok ascending (:299-301)
         const bool ok = in && Ci <= eps;
         const unsigned long long okb = __ballot(ok);

@@ -27,7 +27,7 @@
 //   finish   idx = repeat(idxalive, ...) source list assembled from the ranks' segments; control block
 //
 // The arithmetic is smc_select_kernel's (smc_kernels.hpp), phase by phase: same keys, same narrowing,
-// same ε -- the result equals kabc_smc_run's bit for bit.  Single-workgroup kernels decide, grids
+// same ε (the rules of smc_model.hpp) -- the result equals kabc_smc_run's bit for bit.  Single-workgroup kernels decide, grids
 // without any device-wide barrier make the passes; the host drives the phases and looks at the
 // DselState between them (the sharded path is host-synchronous per pass already).
 #pragma once
@@ -122,11 +122,9 @@ __device__ __forceinline__ void dsel_fail(const DselArgs& A, int err) {
 __device__ __forceinline__ void dsel_set_eps(const DselArgs& A, DselState& S) {
     const double a = val_of(S.keya);
     const double b = (S.n == 1) ? a : val_of(S.keyb);
-    double eps;
-    if (kabc_isfinite(a) && kabc_isfinite(b)) eps = a + S.gq * (b - a);
-    else eps = (1.0 - S.gq) * a + S.gq * b;
+    const double eps = smc_quantile_value(a, b, S.gq);
     S.eps = eps;
-    S.flag = (eps > S.mn) ? 0 : 1;
+    S.flag = smc_flag(eps, S.mn);
     S.state = 3;
 }
 
@@ -183,14 +181,8 @@ __global__ void __launch_bounds__(kSelBlock) dsel_begin_kernel(const DselArgs A)
         }
         const uint64_t kmax = ~kmaxn;
         S.mn = val_of(kmin);  // minimum(Xs[alive])
-        // ranks of the two bracketing order statistics (Statistics.quantile, type 7)
-        const double aleph = (double)n * A.alpha + (1.0 - A.alpha);
-        long long j = (long long)aleph;
-        if (j < 1) j = 1;
-        if (j > n - 1) j = n - 1;
-        if (n == 1) j = 1;
-        double gq = aleph - (double)j;
-        S.gq = gq < 0.0 ? 0.0 : (gq > 1.0 ? 1.0 : gq);
+        long long j;
+        smc_quantile_pos(n, A.alpha, &j, &S.gq);
         S.klo = kmin;
         S.khi = kmax;
         S.kt = j - 1;
@@ -512,7 +504,7 @@ __global__ void __launch_bounds__(kSelBlock) dsel_compact_kernel(const DselArgs 
     for (int r = 0; r < A.world; ++r) ESS += (long long)A.misc[(size_t)r * 8 + 1];
     long long base = 0;  // inside this rank's segment
     for (unsigned b = 0; b < blockIdx.x; ++b) base += (long long)A.sub_cnt[b];
-    const int resample = (A.alpha * (double)ESS <= (double)A.N * A.min_r_ess) ? 1 : 0;
+    const int resample = smc_resample_due(A.alpha, ESS, A.N, A.min_r_ess) ? 1 : 0;
     const bool fail = resample && ESS == 0;
     int32_t* __restrict__ seg = A.seg + (size_t)A.rank * A.seg_len;
     for (int64_t tile0 = tile_lo; tile0 < tile_hi; tile0 += 4) {
@@ -702,7 +694,7 @@ __global__ void __launch_bounds__(kSmcSlots) dsel2_begin_kernel(const DselArgs A
                 A.ctrl->passes += 1;
                 A.ctrl->cur ^= 1;
                 A.ctrl->use_ridx = 0;
-                if ((double)A.ctrl->accepted >= E.mcmc_tol * (double)A.N) A.ctrl->pass_open = 0;
+                if (smc_enough(A.ctrl->accepted, E.mcmc_tol, A.N)) A.ctrl->pass_open = 0;
             }
             smc_iter_end(A.ctrl, E.log, E.log_cap, A.N, E.P);
             s_go = A.ctrl->done ? 0 : 1;
@@ -903,14 +895,8 @@ __global__ void __launch_bounds__(kSelBlock) dsel2_decide_kernel(const DselArgs 
             if (n == 0 || nn > 0) {
                 stall = -((nn > 0) ? 1 : 2);  // an error of the run, not of the course
             } else {
-                // ranks of the two bracketing order statistics (Statistics.quantile, type 7)
-                const double aleph = (double)n * A.alpha + (1.0 - A.alpha);
-                long long j = (long long)aleph;
-                if (j < 1) j = 1;
-                if (j > n - 1) j = n - 1;
-                if (n == 1) j = 1;
-                gq = aleph - (double)j;
-                gq = gq < 0.0 ? 0.0 : (gq > 1.0 ? 1.0 : gq);
+                long long j;
+                smc_quantile_pos(n, A.alpha, &j, &gq);
                 kt = j - 1 - (long long)below;
                 if (over) stall = 2;                                          // a slot too full
                 else if (kt < 0 || kt >= (long long)ncs) stall = 3;            // the target rank outside the window
@@ -1134,11 +1120,9 @@ __global__ void __launch_bounds__(kSelBlock) dsel2_decide_kernel(const DselArgs 
     const double gq = s_gq;
     const double a = val_of(s_keya);
     const double b = (n == 1) ? a : val_of(s_keyb);
-    double eps;
-    if (kabc_isfinite(a) && kabc_isfinite(b)) eps = a + gq * (b - a);
-    else eps = (1.0 - gq) * a + gq * b;
+    const double eps = smc_quantile_value(a, b, gq);
     const double mn = val_of(s_kmin);  // minimum(Xs[alive])
-    const int flag = (eps > mn) ? 0 : 1;
+    const int flag = smc_flag(eps, mn);
     long long inbin = 0;
     for (unsigned q = tid; q < nc; q += kSelBlock) {
         const double x = val_of(cand[q]);
@@ -1152,7 +1136,7 @@ __global__ void __launch_bounds__(kSelBlock) dsel2_decide_kernel(const DselArgs 
             return;
         }
         const long long ESS = s_before + inbin;
-        const int resample = (A.alpha * (double)ESS <= (double)A.N * A.min_r_ess) ? 1 : 0;
+        const int resample = smc_resample_due(A.alpha, ESS, A.N, A.min_r_ess) ? 1 : 0;
         DselState S = {};
         S.wlo = wlo;
         S.whi = whi;

@@ -3,7 +3,8 @@
 // draws and operation order as smc_init_kernel / smc_mcmc_kernel (bit-identical to the oracle);
 // it plugs into the kernel-per-phase path (select / pass_end / finalize do not depend on D).
 // push_p + the prior's log-density, the cost's dispatch and the team's three stream blocks are in
-// dyn_model.hpp, shared with the AIS kernels of ais_dyn_kernels.hpp.
+// dyn_model.hpp, shared with the AIS kernels of ais_dyn_kernels.hpp; the rules of src/smc.jl (partners,
+// stretch, prior gate, ε test, resample index) are in smc_model.hpp, shared with the fixed-dimension kernels.
 #pragma once
 
 #include "dyn_model.hpp"
@@ -75,10 +76,9 @@ __global__ void __launch_bounds__(kSmcBlock) smc_dyn_mcmc_kernel(const SmcDynArg
     double Xfin = 0.0;
     bool alive_i = false;
     if (i < A.p1) {
-        // idx = repeat(idxalive, ceil(N/m))[1:N]  (src/smc.jl:146-147), evaluated on the fly
         const bool remap = gather && A.ctrl->resampled != 0;
         const unsigned ess = (unsigned)A.ctrl->ess;
-        const int64_t si = remap ? (int64_t)A.cidx[(unsigned)i % ess] : i;
+        const int64_t si = smc_remap(A.cidx, i, ess, remap);
         const double* th = theta_src + si * D;
         double Xi = A.X[cur][si];
         double lpi = A.lpi[cur][si];
@@ -86,23 +86,17 @@ __global__ void __launch_bounds__(kSmcBlock) smc_dyn_mcmc_kernel(const SmcDynArg
         bool accepted = false;
         alive_i = A.alive[i] != 0;
         if (alive_i) {
-            const uint64_t N = (uint64_t)A.N;
             const uint32_t w = (uint32_t)i;
             const kabc_u128_t B0 = kabc_stream_block(A.seed, w, pass, 0u, KABC_DOM_SMC_MOVE);
             const kabc_u128_t B1 = kabc_stream_block(A.seed, w, pass, 1u, KABC_DOM_SMC_MOVE);
             const kabc_u128_t B2 = kabc_stream_block(A.seed, w, pass, 2u, KABC_DOM_SMC_MOVE);
-            // while a==i ... ; while b==i || b==a ...  (src/smc.jl:163-164)
-            int64_t a = (int64_t)kabc_index32(kabc_lo64(B0), (uint32_t)N - 1u);
-            a += (a >= i);
-            const int64_t lo = a < i ? a : i, hi = a < i ? i : a;
-            int64_t b = (int64_t)kabc_index32(kabc_hi64(B0), (uint32_t)N - 2u);
-            b += (b >= lo);
-            b += (b >= hi);
+            int64_t a, b;
+            smc_partners(B0, i, A.N, &a, &b);
             double z0, z1;
             kabc_normal_pair(kabc_lo64(B1), kabc_hi64(B1), &z0, &z1);
-            const double s = A.max_stretch * z0 / kabc_sqrt((double)D);
-            const double* ta = theta_src + (remap ? (int64_t)A.cidx[(unsigned)a % ess] : a) * D;
-            const double* tb = theta_src + (remap ? (int64_t)A.cidx[(unsigned)b % ess] : b) * D;
+            const double s = smc_stretch(A.max_stretch, z0, kabc_sqrt((double)D));
+            const double* ta = theta_src + smc_remap(A.cidx, a, ess, remap) * D;
+            const double* tb = theta_src + smc_remap(A.cidx, b, ess, remap) * D;
             double* prop = A.scratch + (i * 2) * D;
             double* xp = prop + D;
             for (int k = 0; k < D; ++k) {
@@ -112,22 +106,17 @@ __global__ void __launch_bounds__(kSmcBlock) smc_dyn_mcmc_kernel(const SmcDynArg
             const double lprob = kabc_log(kabc_u01(kabc_lo64(B2)));
             n_prop = 1;
             const double lpp = dyn_logpdf_push(A.prior, D, prop, xp);
-            if (!(lpp < 0.0 && !kabc_isfinite(lpp))) {  // :173
-                double lM = lpp - lpi + 0.0;
-                if (!(lM < 0.0)) lM = (lM != lM) ? lM : 0.0;
-                if (lprob < lM) {
-                    kabc_cost_rng_t rng = {A.seed, pass, w, KABC_DOM_SMC_COST, 0u};
-                    const double Xp = cost_of<COST>(A.cost_id, xp, D, A.cost_params, A.cost_data, A.cost_ndata, &rng);
-                    n_eval = 1;
-                    const double eps = A.ctrl->eps;
-                    const bool reject = A.ctrl->flag ? (Xp > eps) : (Xp >= eps);
-                    if (!reject) {
-                        for (int k = 0; k < D; ++k) dst[k] = prop[k];
-                        Xi = Xp;
-                        lpi = lpp;
-                        n_acc = 1;
-                        accepted = true;
-                    }
+            if (smc_prior_gate(lpp, lpi, lprob)) {
+                kabc_cost_rng_t rng = {A.seed, pass, w, KABC_DOM_SMC_COST, 0u};
+                const double Xp = cost_of<COST>(A.cost_id, xp, D, A.cost_params, A.cost_data, A.cost_ndata, &rng);
+                n_eval = 1;
+                const double eps = A.ctrl->eps;
+                if (!smc_eps_rejects(A.ctrl->flag, Xp, eps)) {
+                    for (int k = 0; k < D; ++k) dst[k] = prop[k];
+                    Xi = Xp;
+                    lpi = lpp;
+                    n_acc = 1;
+                    accepted = true;
                 }
             }
         }
@@ -138,13 +127,7 @@ __global__ void __launch_bounds__(kSmcBlock) smc_dyn_mcmc_kernel(const SmcDynArg
         Xfin = Xi;
     }
     smc_block_stats(A.part, alive_i, Xfin, A.p0 / kSmcBlock + (int64_t)blockIdx.x);
-    const unsigned long long se = wave_sum(n_eval), sa = wave_sum(n_acc), sp = wave_sum(n_prop);
-    if ((threadIdx.x & (kWave - 1)) == 0) {
-        unsigned long long* sl = A.slots + (size_t)(blockIdx.x & (kSmcSlots - 1)) * 8;
-        if (sa) atomicAdd(&sl[0], sa);
-        if (se) atomicAdd(&sl[1], se);
-        if (sp) atomicAdd(&sl[2], sp);
-    }
+    smc_add_counts(A.slots, n_acc, n_eval, n_prop);
 }
 
 
@@ -193,7 +176,7 @@ __global__ void __launch_bounds__(kWave) smc_dyn_team_kernel(const SmcDynArgs A)
     const double* __restrict__ theta_src = A.theta[cur];
     if (i < A.p1) {  // (team-uniform)
         const bool remap = gather && resampled != 0;
-        const int64_t si = remap ? (int64_t)A.cidx[(unsigned)i % ess] : i;
+        const int64_t si = smc_remap(A.cidx, i, ess, remap);
         const double* th = theta_src + si * D;
         double* dst = A.theta[1 - cur] + i * D;
         double Xi = 0.0, lpi = 0.0;
@@ -207,23 +190,17 @@ __global__ void __launch_bounds__(kWave) smc_dyn_team_kernel(const SmcDynArgs A)
         const double* tb = th;
         double s = 0.0;
         if (alive_i) {
-            const uint64_t N = (uint64_t)A.N;
             const uint32_t w = (uint32_t)i;
             // blocks 0, 1, 2 of the particle's stream: lane j < 3 of the team expands block j
             kabc_u128_t B0, B1, B2;
             dyn_team_blocks<T>(A.seed, w, pass, KABC_DOM_SMC_MOVE, team, tl, B0, B1, B2);
-            // while a==i ... ; while b==i || b==a ...  (src/smc.jl:163-164)
-            int64_t a = (int64_t)kabc_index32(kabc_lo64(B0), (uint32_t)N - 1u);
-            a += (a >= i);
-            const int64_t lo = a < i ? a : i, hi = a < i ? i : a;
-            int64_t b = (int64_t)kabc_index32(kabc_hi64(B0), (uint32_t)N - 2u);
-            b += (b >= lo);
-            b += (b >= hi);
-            ta = theta_src + (remap ? (int64_t)A.cidx[(unsigned)a % ess] : a) * D;
-            tb = theta_src + (remap ? (int64_t)A.cidx[(unsigned)b % ess] : b) * D;
+            int64_t a, b;
+            smc_partners(B0, i, A.N, &a, &b);
+            ta = theta_src + smc_remap(A.cidx, a, ess, remap) * D;
+            tb = theta_src + smc_remap(A.cidx, b, ess, remap) * D;
             double z0, z1;
             kabc_normal_pair(kabc_lo64(B1), kabc_hi64(B1), &z0, &z1);
-            s = A.max_stretch * z0 / kabc_sqrt((double)D);
+            s = smc_stretch(A.max_stretch, z0, kabc_sqrt((double)D));
             // proposal, push_p, the components' log-densities: a coordinate per lane
             for (int k = tl; k < D; k += T) {
                 const double W = (tb[k] - ta[k]) * s;
@@ -234,20 +211,15 @@ __global__ void __launch_bounds__(kWave) smc_dyn_team_kernel(const SmcDynArgs A)
                 const double lprob = kabc_log(kabc_u01(kabc_lo64(B2)));
                 n_prop = 1;
                 const double lpp = dyn_logpdf_sum(sp, D, xp, lk);
-                if (!(lpp < 0.0 && !kabc_isfinite(lpp))) {  // :173
-                    double lM = lpp - lpi + 0.0;
-                    if (!(lM < 0.0)) lM = (lM != lM) ? lM : 0.0;
-                    if (lprob < lM) {
-                        kabc_cost_rng_t rng = {A.seed, pass, w, KABC_DOM_SMC_COST, 0u};
-                        const double Xp = cost_of<COST>(A.cost_id, xp, D, A.cost_params, A.cost_data, A.cost_ndata, &rng);
-                        n_eval = 1;
-                        const bool reject = flag ? (Xp > eps) : (Xp >= eps);
-                        if (!reject) {
-                            Xi = Xp;
-                            lpi = lpp;
-                            n_acc = 1;
-                            acc_i = 1;
-                        }
+                if (smc_prior_gate(lpp, lpi, lprob)) {
+                    kabc_cost_rng_t rng = {A.seed, pass, w, KABC_DOM_SMC_COST, 0u};
+                    const double Xp = cost_of<COST>(A.cost_id, xp, D, A.cost_params, A.cost_data, A.cost_ndata, &rng);
+                    n_eval = 1;
+                    if (!smc_eps_rejects(flag, Xp, eps)) {
+                        Xi = Xp;
+                        lpi = lpp;
+                        n_acc = 1;
+                        acc_i = 1;
                     }
                 }
             }
@@ -266,13 +238,7 @@ __global__ void __launch_bounds__(kWave) smc_dyn_team_kernel(const SmcDynArgs A)
             A.lpi[1 - cur][i] = lpi;
         }
     }
-    const unsigned long long se = wave_sum(n_eval), sa = wave_sum(n_acc), sp2 = wave_sum(n_prop);
-    if (lane == 0) {
-        unsigned long long* sl = A.slots + (size_t)(blockIdx.x & (kSmcSlots - 1)) * 8;
-        if (sa) atomicAdd(&sl[0], sa);
-        if (se) atomicAdd(&sl[1], se);
-        if (sp2) atomicAdd(&sl[2], sp2);
-    }
+    smc_add_counts(A.slots, n_acc, n_eval, n_prop);
 }
 
 // count / NaNs / key range of the alive costs of every 64 particles of the pass just made (what the

@@ -10,9 +10,12 @@
 //                        cost threshold; the resample gather is fused in through the
 //                        index array, the ensemble is double-buffered
 //   smc_finalize_kernel: :200      push_p of the final positions
+// The rules of src/smc.jl these kernels apply (quantile, flag, resample decision and index, partners,
+// prior gate, ε test, stop tests) are in smc_model.hpp, shared with the other courses.
 #pragma once
 
 #include "kabc_device.hpp"
+#include "smc_model.hpp"
 #ifndef __HIPCC_RTC__
 #include "launcher.hpp"
 #endif
@@ -44,11 +47,6 @@ struct SmcCtrl {
     unsigned long long accepted;    // accumulated in this iteration
     unsigned long long cost_evals;  // cumulative
     unsigned long long proposals;   // cumulative
-};
-
-struct SmcLoopParams {
-    double mcmc_tol, epstol, r_epstol;
-    long long max_iterations;
 };
 
 struct SmcInitArgs {
@@ -160,7 +158,6 @@ struct SmcFinalArgs {
 };
 
 constexpr int kSmcBlock = 64;
-constexpr int kSmcSlots = 256;
 constexpr int kSelBlock = 1024;
 
 // order-preserving map double -> u64 (total order with -0 < +0, NaNs at the ends)
@@ -465,13 +462,9 @@ __global__ void __launch_bounds__(kSelBlock) smc_select_kernel(const SmcSelectAr
     KABC_STAMP(0)
 
     // (b) ranks of the two bracketing order statistics (Statistics.quantile, type 7)
-    const double aleph = (double)n * A.alpha + (1.0 - A.alpha);
-    long long j = (long long)aleph;
-    if (j < 1) j = 1;
-    if (j > n - 1) j = n - 1;
-    if (n == 1) j = 1;
-    double gq = aleph - (double)j;
-    gq = gq < 0.0 ? 0.0 : (gq > 1.0 ? 1.0 : gq);
+    long long j;
+    double gq;
+    smc_quantile_pos(n, A.alpha, &j, &gq);
 
     // (c) narrowing for the key of rank j-1 (0-based) inside [klo, khi]
     if (tid == 0) {
@@ -679,11 +672,9 @@ __global__ void __launch_bounds__(kSelBlock) smc_select_kernel(const SmcSelectAr
     if (tid == 0) {
         const double a = val_of(s_keya);
         const double b = (n == 1) ? a : val_of(s_keyb);
-        double eps;
-        if (kabc_isfinite(a) && kabc_isfinite(b)) eps = a + gq * (b - a);
-        else eps = (1.0 - gq) * a + gq * b;
+        const double eps = smc_quantile_value(a, b, gq);
         s_eps = eps;
-        s_flag = (A.mode == 1) ? 1 : ((eps > mn) ? 0 : 1);  // src/smc.jl:135-141
+        s_flag = (A.mode == 1) ? 1 : smc_flag(eps, mn);
     }
     __syncthreads();
     const double eps = s_eps;
@@ -751,9 +742,7 @@ __global__ void __launch_bounds__(kSelBlock) smc_select_kernel(const SmcSelectAr
         __syncthreads();
     }
     KABC_STAMP(4)
-    // Step 2 decision: α*ESS <= nparticles*min_r_ess  (src/smc.jl:145)
-    const int resample =
-        (A.mode == 0 && A.alpha * (double)ESS <= (double)N * A.min_r_ess) ? 1 : 0;
+    const int resample = (A.mode == 0 && smc_resample_due(A.alpha, ESS, N, A.min_r_ess)) ? 1 : 0;
     const bool fail = resample && ESS == 0;
     if (resample && !fail) {
         // idx = repeat(idxalive, ceil(N/m))[1:N]  (src/smc.jl:146-147) is not materialised:
@@ -877,11 +866,10 @@ __global__ void __launch_bounds__(kSmcBlock) smc_mcmc_kernel(const SmcMcmcArgs A
     const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x >> 6;
     const bool in = i < A.N;
     if (kCoop ? (i - lane < A.N) : in) {
-        // idx = repeat(idxalive, ceil(N/m))[1:N]  (src/smc.jl:146-147), evaluated on the fly
         const bool remap = gather && A.ctrl->resampled != 0;
         const unsigned ess = (unsigned)A.ctrl->ess;
         const int64_t ii = in ? i : 0;
-        const int64_t si = remap ? (int64_t)A.cidx[(unsigned)ii % ess] : ii;
+        const int64_t si = smc_remap(A.cidx, ii, ess, remap);
         double th[D];
         CoopGather<kCoop ? D : 4> gth, gta, gtb;
         if constexpr (kCoop) gth.issue(theta_src, si, lane);
@@ -890,23 +878,17 @@ __global__ void __launch_bounds__(kSmcBlock) smc_mcmc_kernel(const SmcMcmcArgs A
         double lpi = lpi_src[si];
         alive_i = in && A.alive[ii] != 0;
         if (kCoop || alive_i) {
-            const uint64_t N = (uint64_t)A.N;
             const uint32_t w = (uint32_t)ii;
             const kabc_u128_t B0 = kabc_stream_block(A.seed, w, pass, 0u, KABC_DOM_SMC_MOVE);
             const kabc_u128_t B1 = kabc_stream_block(A.seed, w, pass, 1u, KABC_DOM_SMC_MOVE);
             const kabc_u128_t B2 = kabc_stream_block(A.seed, w, pass, 2u, KABC_DOM_SMC_MOVE);
-            // while a==i ... ; while b==i || b==a ...  (src/smc.jl:163-164)
-            int64_t a = (int64_t)kabc_index32(kabc_lo64(B0), (uint32_t)N - 1u);
-            a += (a >= ii);
-            const int64_t lo = a < ii ? a : ii, hi = a < ii ? ii : a;
-            int64_t b = (int64_t)kabc_index32(kabc_hi64(B0), (uint32_t)N - 2u);
-            b += (b >= lo);
-            b += (b >= hi);
+            int64_t a, b;
+            smc_partners(B0, ii, A.N, &a, &b);
             double z0, z1;
             kabc_normal_pair_tab(kabc_lo64(B1), kabc_hi64(B1), &z0, &z1, s_logtab);
-            const double s = A.max_stretch * z0 / kabc_sqrt((double)D);
-            const int64_t sa = remap ? (int64_t)A.cidx[(unsigned)a % ess] : a;
-            const int64_t sb = remap ? (int64_t)A.cidx[(unsigned)b % ess] : b;
+            const double s = smc_stretch(A.max_stretch, z0, kabc_sqrt((double)D));
+            const int64_t sa = smc_remap(A.cidx, a, ess, remap);
+            const int64_t sb = smc_remap(A.cidx, b, ess, remap);
             double ta[D], tb[D], prop[D], xp[D];
             if constexpr (kCoop) {
                 gta.issue(theta_src, sa, lane);
@@ -927,28 +909,17 @@ __global__ void __launch_bounds__(kSmcBlock) smc_mcmc_kernel(const SmcMcmcArgs A
             const double lprob = kabc_log_t(kabc_u01(kabc_lo64(B2)), s_logtab);
             n_prop = 1;
             const double lpp = factored_logpdf_push<D, SIMPLE>(A.prior.c, prop, xp, s_logtab);
-            if (!(lpp < 0.0 && !kabc_isfinite(lpp))) {  // :173
-                double lM = lpp - lpi + 0.0;
-                if (!(lM < 0.0)) lM = (lM != lM) ? lM : 0.0;
-                if (lprob < lM) {
-                    kabc_cost_rng_t rng = {A.seed, pass, w, KABC_DOM_SMC_COST, 0u, 0u, nullptr, s_logtab};
-                    if (A.aux) {
-                        const int64_t sl = A.aux_ring > 1 ? (int64_t)(pass % (uint64_t)A.aux_ring) : 0;
-                        rng.aux = A.aux + sl * (int64_t)kabc_cost_aux_words(COST) * A.N + i;
-                        rng.aux_stride = (uint32_t)A.N;
-                    }
-                    const double Xp =
-                        eval_cost<COST, D>(xp, A.cost_params, A.cost_data, A.cost_ndata, &rng);
-                    n_eval = 1;
-                    const double eps = A.ctrl->eps;
-                    const bool reject = A.ctrl->flag ? (Xp > eps) : (Xp >= eps);
-                    if (!reject) {
+            if (smc_prior_gate(lpp, lpi, lprob)) {
+                kabc_cost_rng_t rng = smc_cost_rng<COST>(A.seed, pass, w, s_logtab, A.aux, A.aux_ring, A.N, i);
+                const double Xp = eval_cost<COST, D>(xp, A.cost_params, A.cost_data, A.cost_ndata, &rng);
+                n_eval = 1;
+                const double eps = A.ctrl->eps;
+                if (!smc_eps_rejects(A.ctrl->flag, Xp, eps)) {
 #pragma unroll
-                        for (int k = 0; k < D; ++k) th[k] = prop[k];
-                        Xi = Xp;
-                        lpi = lpp;
-                        n_acc = 1;
-                    }
+                    for (int k = 0; k < D; ++k) th[k] = prop[k];
+                    Xi = Xp;
+                    lpi = lpp;
+                    n_acc = 1;
                 }
             }
           }  // (alive_i)
@@ -961,15 +932,7 @@ __global__ void __launch_bounds__(kSmcBlock) smc_mcmc_kernel(const SmcMcmcArgs A
         }
     }
     smc_block_stats(A.part, alive_i, Xfin, wg);
-    // one counter line per workgroup (mod kSmcSlots): same-line atomics from 512
-    // workgroups cost ~20 us per launch
-    const unsigned long long se = wave_sum(n_eval), sa = wave_sum(n_acc), sp = wave_sum(n_prop);
-    if ((threadIdx.x & (kWave - 1)) == 0) {
-        unsigned long long* sl = A.slots + (size_t)(blockIdx.x & (kSmcSlots - 1)) * 8;
-        if (sa) atomicAdd(&sl[0], sa);
-        if (se) atomicAdd(&sl[1], se);
-        if (sp) atomicAdd(&sl[2], sp);
-    }
+    smc_add_counts(A.slots, n_acc, n_eval, n_prop);
 }
 
 #ifdef KABC_SMC_SINGLE_UNIT
@@ -986,7 +949,7 @@ __global__ void __launch_bounds__(256) smc_finalize_kernel(const SmcFinalArgs A)
     A.Xout[i] = A.X[cur][i];
 }
 
-// end of an ε-iteration: log it and apply the stop tests of src/smc.jl:194-198 (one thread)
+// end of an ε-iteration: log it and apply the stop tests (one thread)
 __device__ __forceinline__ void smc_iter_end(SmcCtrl* ctrl, kabc_smc_iter_t* log, int64_t log_cap,
                                              int64_t N, const SmcLoopParams& P) {
     ctrl->pass_open = 0;
@@ -1003,15 +966,12 @@ __device__ __forceinline__ void smc_iter_end(SmcCtrl* ctrl, kabc_smc_iter_t* log
         L.reserved = 0;
         log[it - 1] = L;
     }
-    const double acc = (double)ctrl->accepted;
-    if (2.0 * kabc_fabs(epsv - eps) < P.r_epstol * (kabc_fabs(epsv) + kabc_fabs(eps)) ||
-        eps <= P.epstol || acc < P.mcmc_tol * (double)N || it >= P.max_iterations)
-        ctrl->done = 1;
+    if (smc_stop(epsv, eps, ctrl->accepted, it, N, P)) ctrl->done = 1;
 }
 
 // after every MCMC pass: fold the per-workgroup counter lines, flip the buffers,
-// apply `accepted[] >= mcmc_tol * nparticles && break` (src/smc.jl:192); after the last
-// pass of an iteration (end_iter) also the iteration's end, in the same launch
+// apply the retry break (smc_enough); after the last pass of an iteration (end_iter) also the
+// iteration's end, in the same launch
 __global__ void __launch_bounds__(kSmcSlots) smc_pass_end_kernel(SmcCtrl* ctrl,
                                                                  unsigned long long* slots,
                                                                  int64_t N, double mcmc_tol,
@@ -1048,7 +1008,7 @@ __global__ void __launch_bounds__(kSmcSlots) smc_pass_end_kernel(SmcCtrl* ctrl,
             ctrl->passes += 1;
             ctrl->cur ^= 1;
             ctrl->use_ridx = 0;
-            if ((double)ctrl->accepted >= mcmc_tol * (double)N) ctrl->pass_open = 0;
+            if (smc_enough(ctrl->accepted, mcmc_tol, N)) ctrl->pass_open = 0;
         }
     }
     if (end_iter && tid == 0) smc_iter_end(ctrl, log, log_cap, N, P);

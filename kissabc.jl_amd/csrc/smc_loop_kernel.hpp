@@ -35,6 +35,7 @@
 // half the cost of cooperative groups' grid.sync()).  The kernel is launched with
 // hipLaunchCooperativeKernel, so all G workgroups are co-resident by construction; the spin is
 // bounded all the same (5 s of s_memrealtime) and ends in an error, never in a hung GPU.
+// The rules of src/smc.jl themselves are the functions of smc_model.hpp; this file is their schedule.
 #pragma once
 
 #include "smc_kernels.hpp"
@@ -611,17 +612,13 @@ __global__ void __launch_bounds__(kLoopBlock) smc_loop_kernel(const SmcLoopArgs 
             const kabc_u128_t B0 = kabc_stream_block(seed_v, w, nps, 0u, KABC_DOM_SMC_MOVE);
             const kabc_u128_t B1 = kabc_stream_block(seed_v, w, nps, 1u, KABC_DOM_SMC_MOVE);
             const kabc_u128_t B2 = kabc_stream_block(seed_v, w, nps, 2u, KABC_DOM_SMC_MOVE);
-            int64_t a = (int64_t)kabc_index32(kabc_lo64(B0), (uint32_t)N - 1u);
-            a += (a >= i);
-            const int64_t lo = a < i ? a : i, hi = a < i ? i : a;
-            int64_t b = (int64_t)kabc_index32(kabc_hi64(B0), (uint32_t)N - 2u);
-            b += (b >= lo);
-            b += (b >= hi);
+            int64_t a, b;
+            smc_partners(B0, i, N, &a, &b);
             nx_a = (unsigned)a;
             nx_b = (unsigned)b;
             double z0, z1;
             kabc_normal_pair_tab(kabc_lo64(B1), kabc_hi64(B1), &z0, &z1, s_logtab);
-            nx_s = A.max_stretch * z0 / kabc_sqrt((double)D);
+            nx_s = smc_stretch(A.max_stretch, z0, kabc_sqrt((double)D));
             nx_lprob = kabc_log_pn_tab(kabc_u01(kabc_lo64(B2)), s_logtab);  // u01 is a positive normal
             // the cost's normal pairs: the first half here, the rest in the shadow of B2
             if constexpr (kPre > 0) {
@@ -678,7 +675,7 @@ __global__ void __launch_bounds__(kLoopBlock) smc_loop_kernel(const SmcLoopArgs 
             pass += 1;
             passes_iter += 1;
             cur ^= 1;
-            const bool enough = (double)acc_iter >= A.loop.mcmc_tol * (double)N;  // :192
+            const bool enough = smc_enough(acc_iter, A.loop.mcmc_tol, N);
             if (passes_iter < A.retry_n && !enough) {
                 remap_pass = 0;  // later passes of an iteration read particle j from row j
                 expand_rest();
@@ -695,11 +692,7 @@ __global__ void __launch_bounds__(kLoopBlock) smc_loop_kernel(const SmcLoopArgs 
                 L.reserved = 0;
                 A.log[iteration - 1] = L;
             }
-            const double acc = (double)acc_iter;  // :194-198
-            if (2.0 * kabc_fabs(eps_prev - eps) < A.loop.r_epstol * (kabc_fabs(eps_prev) + kabc_fabs(eps)) ||
-                eps <= A.loop.epstol || acc < A.loop.mcmc_tol * (double)N ||
-                iteration >= A.loop.max_iterations)
-                break;
+            if (smc_stop(eps_prev, eps, acc_iter, iteration, N, A.loop)) break;
             if (F.b >> 63) {  // a cancel: the same records, the same decision in every workgroup
                 cancelled = 1;
                 break;
@@ -717,13 +710,9 @@ __global__ void __launch_bounds__(kLoopBlock) smc_loop_kernel(const SmcLoopArgs 
             passes_iter = 0;
             const uint64_t kmax = ~kmaxn;
             const double mn = val_of(kmin);
-            const double aleph = (double)n * A.alpha + (1.0 - A.alpha);
-            long long j = (long long)aleph;
-            if (j < 1) j = 1;
-            if (j > n - 1) j = n - 1;
-            if (n == 1) j = 1;
-            double gq = aleph - (double)j;
-            gq = gq < 0.0 ? 0.0 : (gq > 1.0 ? 1.0 : gq);
+            long long j;
+            double gq;
+            smc_quantile_pos(n, A.alpha, &j, &gq);
             long long kt = j - 1;             // rank (0-based) of order statistic a inside the range
             const bool need_b = (n > 1);      // order statistic b = rank kt + 1
             uint64_t rlo = kmin, rhi = kmax;  // key range known to hold rank kt
@@ -935,13 +924,11 @@ __global__ void __launch_bounds__(kLoopBlock) smc_loop_kernel(const SmcLoopArgs 
             {
                 const double a = val_of(ka);
                 const double b = need_b ? val_of(kb) : a;
-                double e;
-                if (kabc_isfinite(a) && kabc_isfinite(b)) e = a + gq * (b - a);
-                else e = (1.0 - gq) * a + gq * b;
+                const double e = smc_quantile_value(a, b, gq);
                 eps_prev = eps;  // ϵv = ϵ
                 eps = e;
                 min_alive = mn;
-                flag = (e > mn) ? 0 : 1;  // :135-141
+                flag = smc_flag(e, mn);
             }
             // alive = Xs .< ϵ (or .<=): below the bin -> set; inside the bin -> by comparison.
             // Each thread owns `per` consecutive mask words (from the ballots); the candidates'
@@ -1014,8 +1001,7 @@ __global__ void __launch_bounds__(kLoopBlock) smc_loop_kernel(const SmcLoopArgs 
             KABC_LSTAMP(14)
             ++q;
             KABC_LOOP_RECYCLE()
-            // Step 2 decision: α*ESS <= nparticles*min_r_ess  (:145)
-            resampled = (A.alpha * (double)ess <= (double)N * A.min_r_ess) ? 1 : 0;
+            resampled = smc_resample_due(A.alpha, ess, N, A.min_r_ess) ? 1 : 0;
             if (resampled && ess == 0) {  // (ε = NaN: nothing to resample from)
                 error = 5;
                 break;
@@ -1092,21 +1078,15 @@ __global__ void __launch_bounds__(kLoopBlock) smc_loop_kernel(const SmcLoopArgs 
                         asm volatile("" :: "v"(lpp));
                         KABC_LSTAMP(19)
                     }
-                    if (!(lpp < 0.0 && !kabc_isfinite(lpp))) {  // :173
-                        double lM = lpp - lpi + 0.0;
-                        if (!(lM < 0.0)) lM = (lM != lM) ? lM : 0.0;
-                        if (lprob < lM) {
-                            const double Xp =
-                                eval_cost<COST, D>(xp, A.cost_params, A.cost_data, A.cost_ndata, &rng);
-                            n_eval = 1;
-                            const bool reject = flag ? (Xp > eps) : (Xp >= eps);
-                            if (!reject) {
+                    if (smc_prior_gate(lpp, lpi, lprob)) {
+                        const double Xp = eval_cost<COST, D>(xp, A.cost_params, A.cost_data, A.cost_ndata, &rng);
+                        n_eval = 1;
+                        if (!smc_eps_rejects(flag, Xp, eps)) {
 #pragma unroll
-                                for (int k = 0; k < D; ++k) th[k] = prop[k];
-                                Xn = Xp;
-                                lpi = lpp;
-                                n_acc = 1;
-                            }
+                            for (int k = 0; k < D; ++k) th[k] = prop[k];
+                            Xn = Xp;
+                            lpi = lpp;
+                            n_acc = 1;
                         }
                     }
                 }

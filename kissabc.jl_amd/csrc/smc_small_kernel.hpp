@@ -21,7 +21,8 @@
 // many: ais_aux_kernels.hpp) or until the loop ends, and leaves the state where the other drivers
 // keep it (theta / X / lpi of buffer set ctrl->cur, alive, SmcCtrl), so the finalize kernel and the
 // host code are shared.  Same draws (counter streams keyed by particle and pass), same operation
-// order: bit-identical to the other two drivers and to the oracle.
+// order: bit-identical to the other two drivers and to the oracle -- the rules of src/smc.jl are the
+// functions of smc_model.hpp, here as there.
 // Independent runs (kabc_smc_run_batch): workgroup r runs run r, its state, seed, cost params and
 // data offset by r (SmcSmallArgs::seeds, params_stride, data_stride); one run is a grid of one with
 // every offset 0.
@@ -156,14 +157,9 @@ __global__ void __launch_bounds__(kSmallBlock) smc_small_kernel(const SmcSmallAr
             const unsigned long long kj = s_key[j];  // (broadcast read)
             rank += (kj < ki || (kj == ki && j < tid)) ? 1u : 0u;
         }
-        // ranks of the two bracketing order statistics (Statistics.quantile, type 7)
-        const double aleph = (double)n * A.alpha + (1.0 - A.alpha);
-        long long jq = (long long)aleph;
-        if (jq < 1) jq = 1;
-        if (jq > (long long)n - 1) jq = (long long)n - 1;
-        if (n == 1u) jq = 1;
-        double gq = aleph - (double)jq;
-        gq = gq < 0.0 ? 0.0 : (gq > 1.0 ? 1.0 : gq);
+        long long jq;
+        double gq;
+        smc_quantile_pos((long long)n, A.alpha, &jq, &gq);
         if (alive_i) {
             if ((long long)rank == jq - 1) s_ab[0] = Xi;
             if ((long long)rank == (n == 1u ? 0 : jq)) s_ab[1] = Xi;
@@ -171,10 +167,8 @@ __global__ void __launch_bounds__(kSmallBlock) smc_small_kernel(const SmcSmallAr
         }
         __syncthreads();
         const double qa = s_ab[0], qb = s_ab[1], mn = s_ab[2];
-        double eps;
-        if (kabc_isfinite(qa) && kabc_isfinite(qb)) eps = qa + gq * (qb - qa);
-        else eps = (1.0 - gq) * qa + gq * qb;
-        const int flag = (eps > mn) ? 0 : 1;  // :136-141
+        const double eps = smc_quantile_value(qa, qb, gq);
+        const int flag = smc_flag(eps, mn);
         alive_i = in && (flag ? (Xi <= eps) : (Xi < eps));  // over ALL particles (:137,:139)
         // ESS and the compacted index idxalive = (1:N)[alive]
         const unsigned long long bm = __ballot(alive_i);
@@ -189,7 +183,7 @@ __global__ void __launch_bounds__(kSmallBlock) smc_small_kernel(const SmcSmallAr
         if (alive_i) s_cidx[woff + (unsigned)__popcll(bm & below)] = tid;
         __syncthreads();
         // ================= Step 2 (:145-153): cyclic resample
-        const int resampled = (A.alpha * (double)ESS <= (double)N * A.min_r_ess) ? 1 : 0;
+        const int resampled = smc_resample_due(A.alpha, (long long)ESS, N, A.min_r_ess) ? 1 : 0;
         if (resampled && ESS == 0u) {  // (ε = NaN: nothing to resample from)
             c.error = 5;
             c.done = 1;
@@ -238,16 +232,11 @@ __global__ void __launch_bounds__(kSmallBlock) smc_small_kernel(const SmcSmallAr
                 const kabc_u128_t B0 = kabc_stream_block(seed, w, pass, 0u, KABC_DOM_SMC_MOVE);
                 const kabc_u128_t B1 = kabc_stream_block(seed, w, pass, 1u, KABC_DOM_SMC_MOVE);
                 const kabc_u128_t B2 = kabc_stream_block(seed, w, pass, 2u, KABC_DOM_SMC_MOVE);
-                // while a==i ... ; while b==i || b==a ...  (src/smc.jl:163-164)
-                int64_t a = (int64_t)kabc_index32(kabc_lo64(B0), (uint32_t)N - 1u);
-                a += (a >= i);
-                const int64_t lo = a < i ? a : i, hi = a < i ? i : a;
-                int64_t b = (int64_t)kabc_index32(kabc_hi64(B0), (uint32_t)N - 2u);
-                b += (b >= lo);
-                b += (b >= hi);
+                int64_t a, b;
+                smc_partners(B0, i, N, &a, &b);
                 double z0, z1;
                 kabc_normal_pair_tab(kabc_lo64(B1), kabc_hi64(B1), &z0, &z1, s_logtab);
-                const double s = A.max_stretch * z0 / sqrtD;
+                const double s = smc_stretch(A.max_stretch, z0, sqrtD);
                 double prop[D], xp[D];
 #pragma unroll
                 for (int k = 0; k < D; ++k) {
@@ -256,26 +245,16 @@ __global__ void __launch_bounds__(kSmallBlock) smc_small_kernel(const SmcSmallAr
                 }
                 const double lprob = kabc_log_t(kabc_u01(kabc_lo64(B2)), s_logtab);
                 const double lpp = factored_logpdf_push<D, SIMPLE, false>(s_prior, prop, xp, s_logtab);
-                if (!(lpp < 0.0 && !kabc_isfinite(lpp))) {  // :173
-                    double lM = lpp - s_lpi[tid] + 0.0;
-                    if (!(lM < 0.0)) lM = (lM != lM) ? lM : 0.0;
-                    if (lprob < lM) {
-                        kabc_cost_rng_t rng = {seed, pass, w, KABC_DOM_SMC_COST, 0u, 0u, nullptr, s_logtab};
-                        if (aux) {
-                            const int64_t sl = A.aux_ring > 1 ? (int64_t)(pass % (uint64_t)A.aux_ring) : 0;
-                            rng.aux = aux + sl * (int64_t)kabc_cost_aux_words(COST) * A.N + i;
-                            rng.aux_stride = (uint32_t)A.N;
-                        }
-                        const double Xp = eval_cost<COST, D>(xp, cost_params, cost_data, A.cost_ndata, &rng);
-                        evald = true;
-                        const bool reject = flag ? (Xp > eps) : (Xp >= eps);
-                        if (!reject) {
+                if (smc_prior_gate(lpp, s_lpi[tid], lprob)) {
+                    kabc_cost_rng_t rng = smc_cost_rng<COST>(seed, pass, w, s_logtab, aux, A.aux_ring, A.N, i);
+                    const double Xp = eval_cost<COST, D>(xp, cost_params, cost_data, A.cost_ndata, &rng);
+                    evald = true;
+                    if (!smc_eps_rejects(flag, Xp, eps)) {
 #pragma unroll
-                            for (int k = 0; k < D; ++k) nth[k] = prop[k];
-                            nX = Xp;
-                            nlp = lpp;
-                            acc = true;
-                        }
+                        for (int k = 0; k < D; ++k) nth[k] = prop[k];
+                        nX = Xp;
+                        nlp = lpp;
+                        acc = true;
                     }
                 }
             }
@@ -295,9 +274,9 @@ __global__ void __launch_bounds__(kSmallBlock) smc_small_kernel(const SmcSmallAr
             c.pass += 1;
             c.passes += 1;
             --passes_left;
-            if ((double)c.accepted >= A.loop.mcmc_tol * (double)N) break;  // :192
+            if (smc_enough(c.accepted, A.loop.mcmc_tol, N)) break;
         }
-        // ================= end of the iteration: log, stop tests (:194-198)
+        // ================= end of the iteration: log, stop tests
         if (tid == 0 && A.log && c.iteration <= A.log_cap) {
             kabc_smc_iter_t L;
             L.eps = c.eps;
@@ -309,9 +288,7 @@ __global__ void __launch_bounds__(kSmallBlock) smc_small_kernel(const SmcSmallAr
             L.reserved = 0;
             A.log[run * A.log_cap + c.iteration - 1] = L;
         }
-        const double acc_it = (double)c.accepted;
-        if (2.0 * kabc_fabs(c.eps_prev - c.eps) < A.loop.r_epstol * (kabc_fabs(c.eps_prev) + kabc_fabs(c.eps)) ||
-            c.eps <= A.loop.epstol || acc_it < A.loop.mcmc_tol * (double)N || c.iteration >= A.loop.max_iterations) {
+        if (smc_stop(c.eps_prev, c.eps, c.accepted, c.iteration, N, A.loop)) {
             c.done = 1;
             break;
         }
