@@ -22,6 +22,14 @@ static void launch_half(const AisArgs& a, hipStream_t s, unsigned nchains) {
     hipLaunchKernelGGL((ais_half_kernel<D, COST, PC, PK>), dim3(grid, nchains), dim3(kAisBlock), 0, s, a);
 }
 
+// the wide geometry (ais_kernels.hpp WideGeom): 512 threads, two batches per workgroup
+template <int D, int COST, int PC, int PK, int K, int NC>
+static void launch_half_wide(const AisArgs& a, hipStream_t s, unsigned nchains) {
+    const dim3 grid = ais_wide_geom(a, nchains);
+    if (grid.x == 0) return;
+    hipLaunchKernelGGL((ais_half_wide_kernel<D, COST, PC, PK, K, NC>), grid, dim3(kWideBlock), 0, s, a);
+}
+
 // (one translation unit instantiates the dimensions KABC_INST_DLO .. KABC_INST_DHI of some prior
 // classes: the Makefile builds three per cost, one of them scheduled differently -- AIS_SCHED there)
 #ifndef KABC_INST_DLO
@@ -46,17 +54,27 @@ static AisLaunchFn pick() {
     else return nullptr;
 }
 
-template <int COST, int PCX, int... Ds>
+template <int COST, int D, int PCX>
+static AisLaunchFn pick_wide() {
+    constexpr bool is_normal = (PCX % kPriorClasses) == kPriorNormal;
+    constexpr bool pc_ok = KABC_INST_PCSEL == 0 || (KABC_INST_PCSEL == 1) == is_normal;
+    if constexpr (pc_ok && D >= KABC_INST_DLO && D <= KABC_INST_DHI && cost_dim_ok_c(COST, D) &&
+                  ais_wide_ok_c(COST, D))
+        return &launch_half_wide<D, COST, PCX % kPriorClasses, PCX / kPriorClasses + 1, kWideK, kWideNC>;
+    else return nullptr;
+}
+
+template <int COST, int PCX, bool WIDE, int... Ds>
 static AisLaunchFn row(int D, std::integer_sequence<int, Ds...>) {
-    AisLaunchFn f[] = {pick<COST, Ds + 1, PCX>()...};
+    AisLaunchFn f[] = {(WIDE ? pick_wide<COST, Ds + 1, PCX>() : pick<COST, Ds + 1, PCX>())...};
     return (D >= 1 && D <= (int)sizeof...(Ds)) ? f[D - 1] : nullptr;
 }
 
-template <int COST, int... PCXs>
+template <int COST, bool WIDE, int... PCXs>
 static AisLaunchFn table(int D, int pcx, std::integer_sequence<int, PCXs...>) {
     using Dims = std::make_integer_sequence<int, KABC_MAX_DIM>;
     AisLaunchFn r = nullptr;
-    ((pcx == PCXs ? (void)(r = row<COST, PCXs>(D, Dims{})) : (void)0), ...);
+    ((pcx == PCXs ? (void)(r = row<COST, PCXs, WIDE>(D, Dims{})) : (void)0), ...);
     return r;
 }
 
@@ -88,7 +106,11 @@ static AisSmallLaunchFn table_small(int D, int pcx, std::integer_sequence<int, P
 #define KABC_CAT2(a, b) a##b
 #define KABC_CAT(a, b) KABC_CAT2(a, b)
 AisLaunchFn KABC_CAT(KABC_CAT(find_ais_kernel_cost_, KABC_INST_COST), KABC_INST_SUFFIX)(int D, int pcx) {
-    return table<KABC_INST_COST>(D, pcx, std::make_integer_sequence<int, kAisVariants>{});
+    return table<KABC_INST_COST, false>(D, pcx, std::make_integer_sequence<int, kAisVariants>{});
+}
+
+AisLaunchFn KABC_CAT(KABC_CAT(find_ais_wide_kernel_cost_, KABC_INST_COST), KABC_INST_SUFFIX)(int D, int pcx) {
+    return table<KABC_INST_COST, true>(D, pcx, std::make_integer_sequence<int, kAisVariants>{});
 }
 
 AisSmallLaunchFn KABC_CAT(KABC_CAT(find_ais_small_kernel_cost_, KABC_INST_COST), KABC_INST_SUFFIX)(int D, int pcx) {

@@ -122,6 +122,29 @@ constexpr int kAisBlock = 256;
 constexpr int kBatch = 64;   // walkers per workgroup
 constexpr int kChunk = 3;    // sub-steps per record buffer = number of producer waves
 
+// A workgroup's geometry as a type: the kernel body (ais_half_body) is written once over it.
+//   HalfGeom            the geometry above: producer wave q fills sub-step q - 1 of every chunk.
+//   WideGeom<K, NC>     512 threads = 8 wavefronts = TWO batches: waves 0, 1 consume batches 0, 1
+//                       of the workgroup, waves 2..7 produce.  A chunk is K sub-steps x 2 batches
+//                       = 2K tasks, dealt to the producers by where the hardware PLACED them: a
+//                       producer that shares its SIMD with a consumer takes NC tasks per chunk, the
+//                       others split the rest (NC < 0: equal shares whatever the placement).  The
+//                       table is derived once per launch from the SIMD ids the waves publish in
+//                       LDS; a placement it does not expect gets equal shares.  A record is a pure
+//                       function of (seed, walker, t, slot): which wave writes it, and when, cannot
+//                       change a value.
+struct HalfGeom {
+    static constexpr bool kWide = false;
+    static constexpr int kBlock = kAisBlock, kBatches = 1, kCh = kChunk, kNC = -1;
+};
+template <int K, int NC>
+struct WideGeom {
+    static_assert(K >= 1 && K <= 8 && NC <= K, "the consumer spells out up to 8 sub-steps");
+    static constexpr bool kWide = true;
+    static constexpr int kBlock = 512, kBatches = 2, kCh = K, kNC = NC;
+};
+constexpr int kWideBlock = 512, kWideBatches = 2;
+
 template <int D>
 struct RecGeom {
     static constexpr int NB = (D + 2) / 2;                 // normal blocks of a DE move
@@ -570,9 +593,12 @@ __device__ __forceinline__ void prepare_cost_aux(const AisArgs& A, uint64_t t, u
 // PK = posterior kind (KABC_POSTERIOR_*) as a compile-time constant: with the kind read
 // from the arguments the consumer carried three run-time branches per sub-step in
 // loglike/accept and the SGPRs to feed them -- 8 % of the launch.
-template <int D, int COST, int PC, int PK>
-__global__ void __launch_bounds__(kAisBlock) __attribute__((amdgpu_waves_per_eu(2, 2)))
-ais_half_kernel(const AisArgs A0) {
+// G = the workgroup's geometry (HalfGeom / WideGeom above): one body, two kernels below.
+template <int D, int COST, int PC, int PK, class G>
+__device__ __forceinline__ void ais_half_body(const AisArgs& A0) {
+    constexpr int CH = G::kCh;         // sub-steps per record buffer
+    constexpr int NBAT = G::kBatches;  // batches (= consumer waves) per workgroup
+    constexpr int NPROD = G::kBlock / kWave - NBAT;
     AisArgs A = A0;
     if (A0.seeds) {  // wave-uniform: one chain of a batch per blockIdx.y
         const int64_t c = (int64_t)blockIdx.y;
@@ -586,8 +612,10 @@ ais_half_kernel(const AisArgs A0) {
         A.cost_params += c * A0.params_stride;
         A.cost_data += c * A0.data_stride;
     }
-    __shared__ ChunkRec<D> rec[2];
-    __shared__ uint8_t listB[kChunk][kBatch];
+    __shared__ RecBuf<D, CH> rec[2][NBAT];
+    __shared__ uint8_t listB[NPROD][kBatch];  // (wave-private work lists, one per producer wave)
+    // wide geometry: the SIMD each wave runs on (HW_REG_HW_ID), published before the first barrier
+    [[maybe_unused]] __shared__ uint32_t ssimd[G::kWide ? G::kBlock / kWave : 1];
 
     // prepared prior components: read by the consumer with wave-uniform LDS
     // addresses (broadcast).  By-value kernel arguments made hipcc pin ~250 SGPRs
@@ -607,7 +635,7 @@ ais_half_kernel(const AisArgs A0) {
     // prepared costs (include/kabc_costs.h): the parameter-independent part of the cost
     // of every sub-step, computed by the producers; word j of lane l at [buf][si][j][l]
     constexpr int kAuxW = cost_aux_c(COST);
-    __shared__ double saux[2][kChunk][kAuxW > 0 ? kAuxW : 1][kBatch];
+    __shared__ double saux[2][NBAT][CH][kAuxW > 0 ? kAuxW : 1][kBatch];
     // stochastic costs whose stream STARTS with normal pairs whatever the parameters
     // (cost_pre_blocks: the hierarchical simulator's D - 2 group noises, ...): the producers
     // expand those blocks for the sub-steps ahead -- all 64 lanes busy, three waves sharing the
@@ -617,15 +645,20 @@ ais_half_kernel(const AisArgs A0) {
     // are counter-based, so expanding them early (or for a proposal the prior then rejects)
     // changes nothing.
     constexpr int kPre = ais_pre_blocks(COST, D);
-    __shared__ double spre[2][kChunk][kPre > 0 ? 2 * kPre : 1][kBatch];
+    __shared__ double spre[2][NBAT][CH][kPre > 0 ? 2 * kPre : 1][kBatch];
 
     // (wave index as a scalar: role branches and record addresses are wave-uniform)
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & (kWave - 1);
-    const int64_t r0 = (int64_t)blockIdx.x * kBatch;
+    // the batch of this wave: the one it consumes; a wide producer's is its task's (batch_of below)
+    const int bmine = (G::kWide && wave < NBAT) ? wave : 0;
+    const int64_t r0_wg = (int64_t)blockIdx.x * (NBAT * kBatch);  // first owned row of the workgroup
+    const int64_t r0 = r0_wg + bmine * kBatch;
     const int64_t rem = A.rows_owned - r0;
-    const int n_active = rem >= kBatch ? kBatch : (int)rem;
+    // (the second batch of the last wide workgroup may be empty)
+    const int n_active = rem >= kBatch ? kBatch : (G::kWide && rem < 0) ? 0 : (int)rem;
     const uint32_t w_base = A.id_base + (uint32_t)(A.row_first + r0);
-    const int nchunks = (A.nt + kChunk - 1) / kChunk;
+    const int nchunks = (A.nt + CH - 1) / CH;
+    const bool consumer = G::kWide ? wave < NBAT : wave == 0;
     // KABC_ABLATE=128 (with debug records on): cycles each wave spends at the barriers
     const bool tprobe = (KABL & 128) && A.dbg;
     unsigned long long t_begin = 0, t_bar = 0;
@@ -647,8 +680,8 @@ ais_half_kernel(const AisArgs A0) {
         return reinterpret_cast<const double*>(reinterpret_cast<const char*>(A.x_comp) +
                                                (size_t)(idx * (uint32_t)(D * sizeof(double))));
     };
-    // consumer state (wave 0)
-    const bool active = (wave == 0) && (lane < n_active);
+    // consumer state (wave 0; wide: waves 0 and 1)
+    const bool active = consumer && (lane < n_active);
     const int64_t r = r0 + lane;
     const int64_t row = A.row_first + r;
     double x[D];
@@ -663,8 +696,11 @@ ais_half_kernel(const AisArgs A0) {
     }
 
     // the table's loads are issued here and land in LDS right before the barrier below
-    static_assert(KABC_MATH_TAB_WORDS == 2 * kAisBlock, "two table words per thread");
-    const double tab0 = kabc_log_tab[threadIdx.x], tab1 = kabc_log_tab[threadIdx.x + kAisBlock];
+    static_assert(KABC_MATH_TAB_WORDS == 2 * kAisBlock && (G::kBlock == kAisBlock || G::kBlock == 2 * kAisBlock),
+                  "two table words per thread, or one");
+    const double tab0 = kabc_log_tab[threadIdx.x];
+    [[maybe_unused]] double tab1 = 0.0;
+    if constexpr (G::kBlock == kAisBlock) tab1 = kabc_log_tab[threadIdx.x + kAisBlock];
     if (threadIdx.x < D * (int)(sizeof(PriorDev) / 8))
         reinterpret_cast<double*>(sprior)[threadIdx.x] =
             reinterpret_cast<const double*>(A.prior)[threadIdx.x];
@@ -690,16 +726,24 @@ ais_half_kernel(const AisArgs A0) {
 
     // while the table's loads are in flight the producers expand the two Philox blocks
     // every lane of their first sub-step needs (they depend on nothing else)
-    kabc_u128_t pro01[2] = {};
-    if (wave > 0 && wave - 1 < A.nt && lane < n_active) {
-        const uint32_t w = w_base + (uint32_t)lane;
-        const uint64_t t = A.t0 + (uint64_t)(wave - 1);
-        pro01[0] = kabc_stream_block(A.seed, w, t, 0u, KABC_DOM_AIS_MOVE);
-        pro01[1] = kabc_stream_block(A.seed, w, t, 1u, KABC_DOM_AIS_MOVE);
+    // (not in the wide geometry: its launches are long, and a producer's first task is the table's)
+    [[maybe_unused]] kabc_u128_t pro01[2] = {};
+    if constexpr (!G::kWide) {
+        if (wave > 0 && wave - 1 < A.nt && lane < n_active) {
+            const uint32_t w = w_base + (uint32_t)lane;
+            const uint64_t t = A.t0 + (uint64_t)(wave - 1);
+            pro01[0] = kabc_stream_block(A.seed, w, t, 0u, KABC_DOM_AIS_MOVE);
+            pro01[1] = kabc_stream_block(A.seed, w, t, 1u, KABC_DOM_AIS_MOVE);
+        }
     }
-    // the log table is staged by all four waves and read by the producers right away
+    // the log table is staged by every wave and read by the producers right away
     slogtab[threadIdx.x] = tab0;
-    slogtab[threadIdx.x + kAisBlock] = tab1;
+    if constexpr (G::kBlock == kAisBlock) slogtab[threadIdx.x + kAisBlock] = tab1;
+    if constexpr (G::kWide) {
+        uint32_t hw;
+        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
+        if (lane == 0) ssimd[wave] = (hw >> 4) & 3u;
+    }
     // NegativeBinomial components (GENERAL class, launches long enough to pay for it): slot j of
     // snb = lgamma(k + r_j); which components have a slot is recomputed below from the same scan
 #ifdef KABC_MODEL_SPEC
@@ -710,21 +754,23 @@ ais_half_kernel(const AisArgs A0) {
     [[maybe_unused]] const bool nb_on = kNbTabs > 0 && A.nt >= 8;
 #endif
     if constexpr (kNbTabs > 0) {
-        static_assert(kNbEntries == kAisBlock, "one table entry per thread");
+        static_assert(kNbEntries == kAisBlock, "one table entry per thread (of the first 256)");
+        const bool nb_thread = !G::kWide || threadIdx.x < (unsigned)kNbEntries;  // (wave-uniform)
         int slot = 0;
         bool has_nb = false;
         for (int k = 0; k < D; ++k) {  // (wave-uniform)
             if (A.prior[k].kind == KABC_PRIOR_NEGBINOMIAL) {
                 has_nb = true;
                 if (nb_on && slot < kNbTabs) {
-                    snb[slot * kNbEntries + threadIdx.x] =
-                        kabc_lgamma_t((double)threadIdx.x + A.prior[k].p[0], kabc_log_tab);
+                    if (nb_thread)
+                        snb[slot * kNbEntries + threadIdx.x] =
+                            kabc_lgamma_t((double)threadIdx.x + A.prior[k].p[0], kabc_log_tab);
                     ++slot;
                 }
             }
         }
         // the lgamma(k + 1) block: always there for a prior with such a component (one load per thread)
-        if (has_nb) snb[kNbLg1Block * kNbEntries + threadIdx.x] = kabc_lgamma1_tab[threadIdx.x];
+        if (has_nb && nb_thread) snb[kNbLg1Block * kNbEntries + threadIdx.x] = kabc_lgamma1_tab[threadIdx.x];
     }
     KABC_TIMED_BARRIER();
     if constexpr (kNbTabs > 0) {
@@ -765,18 +811,87 @@ ais_half_kernel(const AisArgs A0) {
     constexpr bool kLate = D > kLateFrom;
     double r0a[D], r0b[D], r1a[kLate ? 1 : D], r1b[kLate ? 1 : D];
     // (wave-uniform and, outside the probes build, a compile-time constant)
-    const bool pro_rows = !(KABL & 5);
+    const bool pro_rows = !G::kWide && !(KABL & 5);
+    // wide geometry: this producer's tasks of a chunk, bit 2 si + b = sub-step si of batch b, so that
+    // each batch's earliest sub-steps come first.  Every wave derives the same table from the same
+    // LDS words -- scalar code, once per launch; shares and SIMD ids packed four bits apiece.
+    [[maybe_unused]] uint32_t my_tasks = 0;
+    if constexpr (G::kWide) {
+        constexpr int NT = 2 * CH;
+        uint32_t sd = 0;
+#pragma unroll
+        for (int w = 0; w < NBAT + NPROD; ++w)
+            sd |= (uint32_t)__builtin_amdgcn_readfirstlane((int)ssimd[w]) << (4 * w);
+        const uint32_t sc0 = sd & 15u, sc1 = (sd >> 4) & 15u;
+        uint32_t cot = 0;  // bit p: producer p shares its SIMD with a consumer
+        int n0 = 0, n1 = 0;
+#pragma unroll
+        for (int p = 0; p < NPROD; ++p) {
+            const uint32_t sp = (sd >> (4 * (NBAT + p))) & 15u;
+            n0 += sp == sc0 ? 1 : 0;
+            n1 += sp == sc1 ? 1 : 0;
+            cot |= (sp == sc0 || sp == sc1) ? 1u << p : 0u;
+        }
+        // the placement the shares are made for: the consumers on two SIMDs, one producer beside
+        // each.  Anything else (both consumers on one SIMD, three waves on one ...): equal shares.
+        const bool by_place = G::kNC >= 0 && sc0 != sc1 && n0 == 1 && n1 == 1;
+        uint32_t cap = 0;
+        if (by_place) {
+            constexpr int nc = G::kNC >= 0 ? G::kNC : 0;
+            constexpr int rest = NT - 2 * nc, others = NPROD - 2;
+            int seen = 0;
+#pragma unroll
+            for (int p = 0; p < NPROD; ++p) {
+                int n = nc;
+                if (!((cot >> p) & 1u)) {
+                    n = rest / others + (seen < rest % others ? 1 : 0);
+                    ++seen;
+                }
+                cap |= (uint32_t)n << (4 * p);
+            }
+        } else {
+#pragma unroll
+            for (int p = 0; p < NPROD; ++p) cap |= (uint32_t)(NT / NPROD + (p < NT % NPROD ? 1 : 0)) << (4 * p);
+        }
+        // (the shares add up to NT: the search for a producer with room ends)
+        int p = 0;
+        for (int task = 0; task < NT; ++task) {
+            while (((cap >> (4 * p)) & 15u) == 0u) p = p + 1 < NPROD ? p + 1 : 0;
+            if (p == wave - NBAT) my_tasks |= 1u << task;
+            cap -= 1u << (4 * p);
+            p = p + 1 < NPROD ? p + 1 : 0;
+        }
+    }
+    // PRODUCER: sub-step si (transition s of the launch) of batch b into record buffer `buf`, by
+    // producer wave pw
+    auto fill = [&](int buf, int b, int si, int s, int pw, int64_t rb, int nact, uint32_t wb,
+                    const kabc_u128_t* pre01, auto mid) __attribute__((always_inline)) {
+        produce_substep<D>(A, seed_v, rec[buf][b], si, A.t0 + (uint64_t)s, wb, nact, listB[pw], lane, slogtab,
+                           pre01, mid);
+        if constexpr (kAuxW > 0)
+            prepare_cost_aux<COST, kAuxW>(A, A.t0 + (uint64_t)s, wb, lane, saux[buf][b][si], slogtab, rb, nact);
+        if constexpr (kPre > 0)
+            produce_cost_normals<kPre>(seed_v, A.t0 + (uint64_t)s, wb, lane, spre[buf][b][si], slogtab);
+    };
+    // wide geometry: this wave's tasks of the chunk whose first sub-step is `sbase`
+    [[maybe_unused]] auto fill_tasks = [&](int buf, int sbase) __attribute__((always_inline)) {
+#pragma unroll 1
+        for (uint32_t m = my_tasks; m != 0u; m &= m - 1u) {
+            const int task = __builtin_ctz(m);
+            const int si = task >> 1, b = task & 1;
+            const int64_t rb = r0_wg + b * kBatch, left = A.rows_owned - rb;
+            if (sbase + si < A.nt && left > 0)  // (scalar; an empty second batch has no tasks)
+                fill(buf, b, si, sbase + si, wave - NBAT, rb, left >= kBatch ? kBatch : (int)left,
+                     A.id_base + (uint32_t)(A.row_first + rb), nullptr, NoMid());
+        }
+    };
     // prologue: producers fill chunk 0
-    if (wave > 0) {
+    if constexpr (G::kWide) {
+        if (!consumer && !(KABL & 4)) fill_tasks(0, 0);
+    } else if (wave > 0) {
         const int si = wave - 1;
         if (si < A.nt && !(KABL & 4)) {
-            produce_substep<D>(A, seed_v, rec[0], si, A.t0 + (uint64_t)si, w_base, n_active, listB[si],
-                               lane, slogtab, pro01, [] { __syncthreads(); });
-            if constexpr (kAuxW > 0)
-                prepare_cost_aux<COST, kAuxW>(A, A.t0 + (uint64_t)si, w_base, lane, saux[0][si],
-                                              slogtab, r0, n_active);
-            if constexpr (kPre > 0)
-                produce_cost_normals<kPre>(seed_v, A.t0 + (uint64_t)si, w_base, lane, spre[0][si], slogtab);
+            fill(0, 0, si, si, si, r0, n_active, w_base, pro01, [] { __syncthreads(); });
         } else {
             __syncthreads();
         }
@@ -784,8 +899,8 @@ ais_half_kernel(const AisArgs A0) {
         __syncthreads();  // (the partner rows of every sub-step of chunk 0 are in the record)
 #ifndef KABC_NO_XCHUNK_PREFETCH  // (A/B builds: tools/ab_ais_variant.sh)
         if (active && pro_rows) {
-            load_row<D>(comp_row(rec[0].mva[0][lane] & 0x3fffffffu), r0a);
-            load_row<D>(comp_row(rec[0].bb[0][lane]), r0b);
+            load_row<D>(comp_row(rec[0][0].mva[0][lane] & 0x3fffffffu), r0a);
+            load_row<D>(comp_row(rec[0][0].bb[0][lane]), r0b);
         }
 #endif
     }
@@ -796,22 +911,18 @@ ais_half_kernel(const AisArgs A0) {
     // walker's state and the box for the consumer -- then never occupy the other role's
     // registers (one shared loop made both sets live through both bodies: scalar-register
     // spills and re-materialised constants in every sub-step).
-    if (wave > 0) {
+    if (!consumer) {
 #pragma unroll 1
         for (int c = 0; c < nchunks; ++c) {
-            const int s0 = c * kChunk;
-            // PRODUCER: sub-step (s0 + kChunk + wave - 1) of the next chunk
-            const int si = wave - 1;
-            const int s = s0 + kChunk + si;
-            if (s < A.nt && !(KABL & 2)) {
-                produce_substep<D>(A, seed_v, rec[(c + 1) & 1], si, A.t0 + (uint64_t)s, w_base, n_active,
-                                   listB[si], lane, slogtab);
-                if constexpr (kAuxW > 0)
-                    prepare_cost_aux<COST, kAuxW>(A, A.t0 + (uint64_t)s, w_base, lane,
-                                                  saux[(c + 1) & 1][si], slogtab, r0, n_active);
-                if constexpr (kPre > 0)
-                    produce_cost_normals<kPre>(seed_v, A.t0 + (uint64_t)s, w_base, lane,
-                                               spre[(c + 1) & 1][si], slogtab);
+            const int s0 = c * CH;
+            if constexpr (G::kWide) {
+                // PRODUCER: this wave's tasks of the next chunk
+                if (!(KABL & 2)) fill_tasks((c + 1) & 1, s0 + CH);
+            } else {
+                // PRODUCER: sub-step (s0 + kChunk + wave - 1) of the next chunk
+                const int si = wave - 1;
+                const int s = s0 + CH + si;
+                if (s < A.nt && !(KABL & 2)) fill((c + 1) & 1, 0, si, s, si, r0, n_active, w_base, nullptr, NoMid());
             }
             KABC_TIMED_BARRIER();
         }
@@ -834,11 +945,11 @@ ais_half_kernel(const AisArgs A0) {
         const bool dbg_on = __builtin_amdgcn_readfirstlane(A.dbg != nullptr ? 1 : 0) != 0;
 #pragma unroll 1
         for (int c = 0; c < nchunks; ++c) {
-            const int s0 = c * kChunk;
+            const int s0 = c * CH;
             if (active && !(KABL & 1)) {
                 // CONSUMER
-                const ChunkRec<D>& R = rec[(KABL & 2) ? 0 : (c & 1)];
-                const int ns = (A.nt - s0 < kChunk) ? (A.nt - s0) : kChunk;
+                const RecBuf<D, CH>& R = rec[(KABL & 2) ? 0 : (c & 1)][bmine];
+                const int ns = (A.nt - s0 < CH) ? (A.nt - s0) : CH;
                 // partner rows: (pa, pb) serve this sub-step, (na, nb) are the next one's, in
                 // flight while this one computes.  Both rows are fetched for every lane
                 // whatever its move (bb defaults to a): no divergence around the loads.
@@ -860,7 +971,7 @@ ais_half_kernel(const AisArgs A0) {
                     const uint64_t t = A.t0 + (uint64_t)(s0 + si);
                     // (1) every LDS word of this sub-step in one batch, plus the partner
                     //     ids of the next one
-                    constexpr int sq = si + 1 < kChunk ? si + 1 : si;
+                    constexpr int sq = si + 1 < CH ? si + 1 : si;
                     const uint32_t mva = R.mva[si][lane];
                     uint32_t mvan = R.mva[sq][lane], bn = R.bb[sq][lane];
                     if (si + 1 >= ns) {  // (scalar) the chunk's last sub-step: no next one in it
@@ -928,11 +1039,11 @@ ais_half_kernel(const AisArgs A0) {
                     kabc_cost_rng_t rng = {A.seed, t, w_base + (uint32_t)lane, KABC_DOM_AIS_COST, 0u,
                                            0u, nullptr, slogtab};
                     if constexpr (kAuxW > 0) {
-                        rng.aux = &saux[(KABL & 2) ? 0 : (c & 1)][si][0][lane];
+                        rng.aux = &saux[(KABL & 2) ? 0 : (c & 1)][bmine][si][0][lane];
                         rng.aux_stride = kBatch;
                     }
                     if constexpr (kPre > 0) {
-                        rng.pre = &spre[(KABL & 2) ? 0 : (c & 1)][si][0][lane];
+                        rng.pre = &spre[(KABL & 2) ? 0 : (c & 1)][bmine][si][0][lane];
                         rng.pre_n = (uint32_t)kPre;
                         rng.pre_stride = (uint32_t)kBatch;
                     }
@@ -993,15 +1104,30 @@ ais_half_kernel(const AisArgs A0) {
                 // an error (src/types.jl:69-70) is sticky and reported after the launch; the
                 // remaining sub-steps still run (their result is discarded by the host), which
                 // keeps the loop bounds wave-uniform
-                static_assert(kChunk == 3, "the consumer spells out kChunk sub-steps");
-                if constexpr (kLate) {
-                    substep(SubStepIx<0>{}, r0a, r0b, r0a, r0b);
-                    if (ns > 1) substep(SubStepIx<1>{}, r0a, r0b, r0a, r0b);
-                    if (ns > 2) substep(SubStepIx<2>{}, r0a, r0b, r0a, r0b);
-                } else {
-                    substep(SubStepIx<0>{}, r0a, r0b, r1a, r1b);
-                    if (ns > 1) substep(SubStepIx<1>{}, r1a, r1b, r0a, r0b);
-                    if (ns > 2) substep(SubStepIx<2>{}, r0a, r0b, r1a, r1b);
+                static_assert(CH >= 1 && CH <= 8, "the consumer spells out up to 8 sub-steps");
+                // sub-step Q of the chunk, where the geometry has one (a generic lambda: the
+                // branch not taken is never instantiated, so R.mva[Q] stays within the record)
+                auto sub_even = [&](auto SI) __attribute__((always_inline)) {
+                    if constexpr (decltype(SI)::value < CH) {
+                        if constexpr (kLate) substep(SI, r0a, r0b, r0a, r0b);
+                        else substep(SI, r0a, r0b, r1a, r1b);
+                    }
+                };
+                auto sub_odd = [&](auto SI) __attribute__((always_inline)) {
+                    if constexpr (decltype(SI)::value < CH) {
+                        if constexpr (kLate) substep(SI, r0a, r0b, r0a, r0b);
+                        else substep(SI, r1a, r1b, r0a, r0b);
+                    }
+                };
+                sub_even(SubStepIx<0>{});
+                if (ns > 1) sub_odd(SubStepIx<1>{});
+                if (ns > 2) sub_even(SubStepIx<2>{});
+                if constexpr (CH > 3) {
+                    if (ns > 3) sub_odd(SubStepIx<3>{});
+                    if (ns > 4) sub_even(SubStepIx<4>{});
+                    if (ns > 5) sub_odd(SubStepIx<5>{});
+                    if (ns > 6) sub_even(SubStepIx<6>{});
+                    if (ns > 7) sub_odd(SubStepIx<7>{});
                 }
             }
             KABC_TIMED_BARRIER();
@@ -1010,7 +1136,7 @@ ais_half_kernel(const AisArgs A0) {
 
     if (tprobe && lane == 0) {
         const unsigned long long t_end = __builtin_amdgcn_s_memtime();
-        int32_t* d = A.dbg + (r0 * A.nt) * 6 + 8 + wave * 2;
+        int32_t* d = A.dbg + (r0_wg * A.nt) * 6 + 2 * (NBAT + NPROD) + wave * 2;
         d[0] = (int32_t)(t_end - t_begin);
         d[1] = (int32_t)t_bar;
     }
@@ -1018,9 +1144,9 @@ ais_half_kernel(const AisArgs A0) {
         // placement probe (KABC_ABLATE=64 with debug records on): HW_ID of each wave
         uint32_t hw;
         asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-        A.dbg[(r0 * A.nt) * 6 + wave] = (int32_t)hw;
+        A.dbg[(r0_wg * A.nt) * 6 + wave] = (int32_t)hw;
     }
-    if (wave == 0) {
+    if (consumer) {
         if (active) {
             store_row<D>(A.x_act + row * D, x);
             A.lp[r] = lp;
@@ -1037,15 +1163,29 @@ ais_half_kernel(const AisArgs A0) {
         // one atomic per batch and counter
         const unsigned long long se = wave_total_u32(n_eval);   // n <= ntransitions per lane
         const unsigned long long sa = wave_total_u32(n_acc);
-        if (lane == 0) {
+        if (lane == 0 && (!G::kWide || n_active > 0)) {
             unsigned long long* sl =
-                A.slots + (size_t)((blockIdx.x + blockIdx.y * gridDim.x) & (kCounterSlots - 1)) * 8;
+                A.slots + (size_t)((blockIdx.x * NBAT + bmine + blockIdx.y * gridDim.x * NBAT) & (kCounterSlots - 1)) * 8;
             atomicAdd(&sl[0], (unsigned long long)n_active * (unsigned long long)A.nt);
             atomicAdd(&sl[1], se);
             atomicAdd(&sl[2], sa);
         }
         if (err) atomicMax(&A.counters->error, err);
     }
+#undef KABC_TIMED_BARRIER
+}
+
+template <int D, int COST, int PC, int PK>
+__global__ void __launch_bounds__(kAisBlock) __attribute__((amdgpu_waves_per_eu(2, 2)))
+ais_half_kernel(const AisArgs A0) {
+    ais_half_body<D, COST, PC, PK, HalfGeom>(A0);
+}
+
+// the wide geometry (WideGeom above): same registers per wave, one workgroup per CU
+template <int D, int COST, int PC, int PK, int K, int NC>
+__global__ void __launch_bounds__(kWideBlock) __attribute__((amdgpu_waves_per_eu(2, 2)))
+ais_half_wide_kernel(const AisArgs A0) {
+    ais_half_body<D, COST, PC, PK, WideGeom<K, NC>>(A0);
 }
 
 // step(rng, model, spl::AIS; retry_sampling): one thread per owned walker; the
@@ -1127,6 +1267,27 @@ inline dim3 ais_init_geom(const InitArgs& a, unsigned nchains) {
 }
 // pcx = prior class + kPriorClasses * (posterior kind - 1)
 AisLaunch find_ais_kernel(int cost_id, int D, int pcx);
+// The wide geometry as shipped: (K, n_c) chosen by measurement (profiles/ais_wide.md: C3 110.2 ->
+// 105.4 us per launch in the final A/B; K = 5 and K = 3 with the same n_c LOSE 6 % and 1.5 %).  With n_c = 1 the two
+// producers beside a consumer fill one sub-step per chunk each, the other four 2, 2, 1, 1.
+constexpr int kWideK = 4, kWideNC = 1;
+// first cut: the dimensions measured (D = 8) and below -- the box bounds in registers, two sets of
+// partner rows; larger D keeps the existing geometry
+constexpr int kWideMaxDim = 8;
+// what the wide kernel is instantiated for: prebuilt costs whose producers only fill records (no
+// prepared cost words, no cost normals), and the dimensions whose 4 K record buffers fit the
+// 160 KB of LDS beside the tables (12 KB covers the GENERAL class's)
+constexpr bool ais_wide_ok_c(int cost, int D) {
+    const int nz = (D + 2 > 4) ? (D + 2) : 4;
+    if (D > kWideMaxDim) return false;
+    return cost < KABC_COST_USER && cost_aux_c(cost) == 0 && ais_pre_blocks(cost, D) == 0 &&
+           4 * kWideK * kBatch * (20 + 8 * nz) + (12 << 10) <= (160 << 10);
+}
+inline dim3 ais_wide_geom(const AisArgs& a, unsigned nchains) {
+    return dim3((unsigned)((a.rows_owned + kWideBatches * kBatch - 1) / (kWideBatches * kBatch)), nchains);
+}
+// nullptr: no wide kernel for this (cost, D, class, kind)
+AisLaunch find_ais_wide_kernel(int cost_id, int D, int pcx);
 constexpr int kAisVariants = 3 * kPriorClasses;
 struct ModelUnit;
 bool launch_ais_init(int D, const InitArgs& a, hipStream_t s, unsigned nchains, ModelUnit* unit);

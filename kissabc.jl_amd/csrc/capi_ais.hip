@@ -25,6 +25,9 @@ namespace kabc {
     AisLaunchFn find_ais_kernel_cost_##id(int D, int pc);                 \
     AisLaunchFn find_ais_kernel_cost_##id##_nrm(int D, int pc);           \
     AisLaunchFn find_ais_kernel_cost_##id##_hi(int D, int pc);            \
+    AisLaunchFn find_ais_wide_kernel_cost_##id(int D, int pc);            \
+    AisLaunchFn find_ais_wide_kernel_cost_##id##_nrm(int D, int pc);      \
+    AisLaunchFn find_ais_wide_kernel_cost_##id##_hi(int D, int pc);       \
     AisSmallLaunchFn find_ais_small_kernel_cost_##id(int D, int pc);      \
     AisSmallLaunchFn find_ais_small_kernel_cost_##id##_nrm(int D, int pc); \
     AisSmallLaunchFn find_ais_small_kernel_cost_##id##_hi(int D, int pc);
@@ -67,6 +70,18 @@ AisLaunch find_ais_kernel(int cost_id, int D, int pc) {
             if (k.mod) return AisLaunch(k.mod, &ais_half_geom, (unsigned)kAisBlock);
             return nullptr;
         }
+    }
+}
+
+// the wide geometry of the half-generation kernel (ais_kernels.hpp WideGeom): prebuilt costs only
+AisLaunch find_ais_wide_kernel(int cost_id, int D, int pc) {
+    switch (cost_id) {
+#define KABC_WIDE_CASE(id) \
+    case id: return ais_inst_pick(D, pc, find_ais_wide_kernel_cost_##id, find_ais_wide_kernel_cost_##id##_nrm, find_ais_wide_kernel_cost_##id##_hi);
+        KABC_WIDE_CASE(1) KABC_WIDE_CASE(2) KABC_WIDE_CASE(3) KABC_WIDE_CASE(4) KABC_WIDE_CASE(5) KABC_WIDE_CASE(6)
+        KABC_WIDE_CASE(7) KABC_WIDE_CASE(8) KABC_WIDE_CASE(9) KABC_WIDE_CASE(10) KABC_WIDE_CASE(11)
+#undef KABC_WIDE_CASE
+        default: return nullptr;
     }
 }
 
@@ -189,6 +204,7 @@ struct kabc_ais {
     uint64_t seed = 0, t = 0;
     int32_t rank = 0, world = 1;
     AisLaunch launch;      // half-generation kernel (a small-ensemble handle resolves it at first need)
+    AisLaunch launch_wide; // its wide geometry, where `launch` is a prebuilt kernel that has one
     int32_t pc = 0;        // its prior class
     // the one-workgroup driver of small ensembles (ais_small_kernel.hpp): kabc_ais_advance runs every
     // generation of a call in ONE launch; spec_state / spec_variant then describe THIS kernel
@@ -351,6 +367,7 @@ static kabc_status_t ais_resolve_half(kabc_ais_t* h) {
         if (const char* e = std::getenv("KABC_PREBUILT_CLASS"))
             if (e[0] == 'g' && pc != kPriorBox) pc = kPriorGeneral;
         fn = find_ais_kernel(h->cost_id, h->D, pc + pk_off);
+        if (fn) h->launch_wide = find_ais_wide_kernel(h->cost_id, h->D, pc + pk_off);
         if (!fn && h->pc == kPriorNormal)  // plugins instantiate SIMPLE only
             fn = find_ais_kernel(h->cost_id, h->D, kPriorSimple + pk_off);
     }
@@ -1118,12 +1135,46 @@ static void ais_poll_spec(kabc_ais_t* h) {
     const PluginKernel k = unit_kernel(h->unit, h->small_ok ? kPfAisSmall : kPfAis, h->D, h->spec_variant, &st);
     if (st == KABC_SPEC_ACTIVE && k.mod) {
         if (h->small_ok) h->small = AisSmallLaunch(k.mod, &ais_small_geom, (unsigned)kAisSmallBlock);
-        else h->launch = AisLaunch(k.mod, &ais_half_geom, (unsigned)kAisBlock);
+        else {
+            h->launch = AisLaunch(k.mod, &ais_half_geom, (unsigned)kAisBlock);
+            h->launch_wide = nullptr;  // (the model's own kernels have the one geometry)
+        }
         h->spec_state = KABC_SPEC_ACTIVE;
         h->spec_switch_at = h->launches;
     } else if (st == KABC_SPEC_FAILED) {
         h->spec_state = KABC_SPEC_FAILED;
     }
+}
+
+// Which geometry a launch of `nt` sub-steps over `rows` owned rows takes.  The wide kernel exists for
+// the prebuilt costs whose records fit the LDS (ais_wide_ok_c) and needs two full batches; single-chain,
+// unsharded handles only (ais_can_wide).  By default it is taken where it was measured to win
+// (profiles/ais_wide.md): from kAisWideFrom sub-steps on (its prologue is longer), and only where the
+// existing geometry would put two workgroups on every compute unit, i.e. at least two batches per
+// unit -- below that a batch of the existing geometry has its unit to itself, the wide one packs two
+// on half as many units, and nobody has measured that.  KABC_AIS_WIDE=0 keeps the existing geometry,
+// =1 takes the wide one wherever it can run, =2 does the same and makes a launch that cannot take
+// it an error, raised before anything is enqueued (read per launch: the tests flip it).  Same bits
+// either way.
+constexpr int32_t kAisWideFrom = 32;
+static bool ais_can_wide(const kabc_ais_t* h, int64_t rows) {
+    return h->launch_wide && h->nchains == 1 && h->world == 1 && !h->comm && rows >= kWideBatches * kBatch;
+}
+static int64_t ais_wide_min_rows() {  // two batches per compute unit of the device
+    static const int64_t v = [] {
+        int dev = 0, cus = 0;
+        if (hipGetDevice(&dev) != hipSuccess ||
+            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)
+            cus = 256;
+        return (int64_t)kWideBatches * kBatch * cus;
+    }();
+    return v;
+}
+static bool ais_use_wide(const kabc_ais_t* h, int64_t rows, int32_t nt) {
+    if (!ais_can_wide(h, rows)) return false;
+    const char* e = std::getenv("KABC_AIS_WIDE");
+    if (e && e[0]) return e[0] != '0';
+    return nt >= kAisWideFrom && rows >= ais_wide_min_rows();
 }
 
 // one launch: `ntransitions` transitions for the owned rows of segment `sg` of `half`
@@ -1138,6 +1189,14 @@ static kabc_status_t launch_half_seg(kabc_ais_t* h, int32_t half, const kabc_ais
         set_error("a handle of %d chains beyond %d parameters advances with kabc_ais_advance (the one-workgroup "
                   "driver); kabc_ais_half_generation drives one chain per handle there", h->nchains, KABC_MAX_DIM);
         return KABC_ERR_UNSUPPORTED;
+    }
+    if (!h->dyn && !ais_can_wide(h, sg.count)) {
+        const char* e = std::getenv("KABC_AIS_WIDE");
+        if (e && e[0] == '2') {
+            set_error("KABC_AIS_WIDE=2: no wide half-generation kernel for this launch (cost id %d, D = %d, "
+                      "%lld rows, %d chains)", h->cost_id, h->D, (long long)sg.count, h->nchains);
+            return KABC_ERR_UNSUPPORTED;
+        }
     }
     h->launches++;
     // debug records: layout [N_owned][nt][6] in the order of the owned rows (half 0 first)
@@ -1211,7 +1270,7 @@ static kabc_status_t launch_half_seg(kabc_ais_t* h, int32_t half, const kabc_ais
                 a.aux = h->d_aux;
                 a.stride_aux = enqueue_aux(h, half, sg.first, sg.count, a.t0, nb, h->d_aux);
             }
-            h->launch(a, s, (unsigned)h->nchains);
+            (ais_use_wide(h, sg.count, nb) ? h->launch_wide : h->launch)(a, s, (unsigned)h->nchains);
         }
     }
     if (t_on && ++h->open_count >= h->timing_stride)

@@ -1,13 +1,18 @@
 """How long does each wave of an AIS batch wait at the workgroup barriers?
 KABC_ABLATE=128: every wave writes (lifetime, time inside __syncthreads) in s_memtime
-ticks (100 MHz) into the debug records; printed as means over the 512 batches of the
-C3 launch for the consumer (wave 0) and the producers (waves 1-3)."""
+ticks (100 MHz) into the debug records; printed as means over the workgroups of the
+C3 launch per wave.  The geometry is the one KABC_AIS_WIDE names (default 0): 0 = four
+waves per 64-row workgroup (wave 0 consumes, 1-3 produce), 1 = the wide geometry, eight
+waves per 128-row workgroup (waves 0, 1 consume, 2-7 produce; the words sit behind the
+eight HW_ID words of placement_probe.py)."""
 import os
 import sys
 
 os.environ["KABC_PROBES"] = "1"   # the library variant with the probes compiled in
 
 os.environ["KABC_ABLATE"] = "128"
+WIDE = os.environ.setdefault("KABC_AIS_WIDE", "0") != "0"   # (never the default rule: the layout follows it)
+NW, ROWS, NCONS = (8, 128, 2) if WIDE else (4, 64, 1)       # waves and rows per workgroup, consumers
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np  # noqa: E402
 
@@ -20,8 +25,8 @@ e.advance(2, nt)
 e.set_debug(nt)
 e.advance(1, nt)
 d = e.get_debug(nt).reshape(65536, -1)
-t = d[0:32768:64, 8:16].astype(np.float64).reshape(-1, 4, 2)   # [block][wave][life, barrier]
-print("nt", nt, "ticks are s_memtime units")
-for w in range(4):
+t = d[0:32768:ROWS, 2 * NW:4 * NW].astype(np.float64).reshape(-1, NW, 2)   # [workgroup][wave][life, barrier]
+print("geometry", "wide" if WIDE else "existing", "nt", nt, "ticks are s_memtime units")
+for w in range(NW):
     life, bar = t[:, w, 0].mean(), t[:, w, 1].mean()
-    print(f"wave {w} ({'consumer' if w == 0 else 'producer'}): life {life:9.1f}  at barriers {bar:9.1f}  = {100 * bar / life:5.1f} %")
+    print(f"wave {w} ({'consumer' if w < NCONS else 'producer'}): life {life:9.1f}  at barriers {bar:9.1f}  = {100 * bar / life:5.1f} %")
