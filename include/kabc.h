@@ -170,6 +170,8 @@ kabc_status_t kabc_ctx_synchronize(kabc_ctx_t* ctx);
  *   kabc_smc_run      stops at an iteration boundary: result holds the population after the k
  *                     completed iterations (theta, cost, alive, eps, iterations = k, the first k
  *                     log records), bit-identical to the same call with max_iterations = k.
+ *                     kabc_smc_run_from also leaves the state after those k iterations, and
+ *                     continuing from it gives the bits of a run that was never interrupted.
  *   kabc_smc_run_batch, kabc_abcde_run_batch
  *                     every run of the launch grid stops at an iteration / generation boundary with
  *                     its population after the k it completed (an ABCDE run: bit-identical to the
@@ -840,6 +842,59 @@ void kabc_smc_default_opts(kabc_smc_opts_t* o);
 kabc_status_t kabc_smc_run(kabc_ctx_t* ctx, const kabc_prior_t* prior, int32_t D,
                            const kabc_cost_t* cost, const kabc_smc_opts_t* opts,
                            kabc_smc_result_t* result);
+
+/* ---- continuing a stopped run ---------------------------------------------------------------
+ * What an smc run holds at an iteration boundary, enough to go on from there: a run stopped by its
+ * own stop rules, by max_iterations or by kabc_ctx_cancel is continued by kabc_smc_run_from, and the
+ * continued run IS the uninterrupted one, bit for bit (theta, cost, alive, eps, iterations, the log,
+ * cost_evals, proposals) -- every draw is keyed by (seed, pass, particle), and the state carries the
+ * pass counter.  That equality needs the same prior, cost, seed and options (max_iterations and the
+ * stop tolerances aside) in every segment; nothing checks it: a state continued with another seed or
+ * other options is a valid run of its own, not a piece of the original one.
+ * The arrays belong to the caller ([N][D] / [N] doubles, [N] bytes), for `from` and for `to`. */
+typedef struct kabc_smc_state {
+    int64_t nparticles;
+    int32_t D;
+    int32_t reserved;
+    uint64_t seed;       /* of the run that left the state (informative)                       */
+    int64_t iteration;   /* iterations completed; -1: the run that was to fill the state failed */
+    uint64_t pass;       /* global pass counter = transition counter of the streams            */
+    double eps;          /* ϵ after the last completed iteration (Inf at iteration 0)          */
+    double eps_prev;     /* ϵv                                                                  */
+    uint64_t accepted;   /* accepted[] of the last completed iteration                          */
+    uint64_t cost_evals; /* cumulative                                                          */
+    uint64_t proposals;  /* cumulative                                                          */
+    int64_t n_alive;     /* sum(alive)                                                          */
+    double* theta;       /* host [N][D]: the walkers as the loop holds them, NOT push_p'ed (a   */
+                         /* discrete prior's walkers sit between integers)                      */
+    double* cost;        /* host [N]                                                            */
+    double* logprior;    /* host [N]                                                            */
+    uint8_t* alive;      /* host [N]                                                            */
+} kabc_smc_state_t;
+/* sizeof(kabc_smc_state_t) as the library was compiled (the struct is not in kabc_abi_sizeof's table) */
+int64_t kabc_smc_state_sizeof(void);
+/* kabc_smc_run, started from `from` instead of the initial draw (NULL: the initial draw) and leaving
+ * the state it ended in in `to` (NULL: none).  from == NULL && to == NULL is kabc_smc_run.
+ *   to      is filled whenever result is: a normal end, max_iterations, KABC_ERR_CANCELLED.  A run
+ *           that fails (a NaN cost, no alive particle) leaves to->iteration = -1.  `to` and `from`
+ *           are two structs with arrays of their own (`from` is read again when a run is repeated
+ *           on another course): a shared struct or array is KABC_ERR_INVALID_ARG.
+ *   from    result->iterations, cost_evals, proposals and mcmc_launches are TOTALS: they continue the
+ *           state's counts, and opts->max_iterations bounds the total.  result->iter_log[0..] holds
+ *           the records of the iterations THIS call ran (iterations - from->iteration of them).
+ *           Before the first new iteration the stop tests of src/smc.jl:194-198 are applied to the
+ *           state's (eps_prev, eps, accepted, iteration) with this call's options (not at iteration
+ *           0): if one fires, the population is returned unchanged, with no new iteration.  So a
+ *           finished run continued with the same options stays as it is, with a smaller epstol it
+ *           goes on, and a run stopped by max_iterations or a cancel goes on.
+ * KABC_ERR_INVALID_ARG, before anything is launched: a NULL array in a state, from->nparticles !=
+ * opts->nparticles, from->D != D, from->iteration < 0, from->n_alive != the number of nonzero
+ * alive[i], `to` sharing its struct or an array with `from`.  Single GPU only: kabc_smc_run_dist, kabc_smc_run_dist_mode and kabc_smc_run_batch
+ * take no state. */
+kabc_status_t kabc_smc_run_from(kabc_ctx_t* ctx, const kabc_prior_t* prior, int32_t D,
+                                const kabc_cost_t* cost, const kabc_smc_opts_t* opts,
+                                const kabc_smc_state_t* from, kabc_smc_state_t* to,
+                                kabc_smc_result_t* result);
 
 /* smc with its COST LOOP sharded over the communicator's ranks -- the reference's own parallel
  * leg (`parallel = true`: Threads.@threads over the cost evaluations, src/smc.jl:120-123,168).

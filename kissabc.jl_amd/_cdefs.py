@@ -79,6 +79,15 @@ class SmcResult(C.Structure):
                 ("kernel_ms_mcmc", C.c_double), ("mcmc_launches", C.c_int64)]
 
 
+class SmcState(C.Structure):
+    _fields_ = [("nparticles", C.c_int64), ("D", C.c_int32), ("reserved", C.c_int32),
+                ("seed", C.c_uint64), ("iteration", C.c_int64), ("pass_", C.c_uint64),
+                ("eps", C.c_double), ("eps_prev", C.c_double), ("accepted", C.c_uint64),
+                ("cost_evals", C.c_uint64), ("proposals", C.c_uint64), ("n_alive", C.c_int64),
+                ("theta", c_double_p), ("cost", c_double_p), ("logprior", c_double_p),
+                ("alive", C.POINTER(C.c_uint8))]
+
+
 class AbcdeOpts(C.Structure):
     _fields_ = [("nparticles", C.c_int64), ("generations", C.c_int64), ("eps_target", C.c_double),
                 ("alpha", C.c_double), ("proposal_width", C.c_double), ("earlystop", C.c_int32),
@@ -225,6 +234,10 @@ PROTOTYPES = {
                                    C.POINTER(PfilterOpts), C.POINTER(PfilterResult)]),
     "kabc_smc_run": (C.c_int, [VP, C.POINTER(Prior), C.c_int32, C.POINTER(Cost),
                                C.POINTER(SmcOpts), C.POINTER(SmcResult)]),
+    "kabc_smc_state_sizeof": (C.c_int64, []),
+    "kabc_smc_run_from": (C.c_int, [VP, C.POINTER(Prior), C.c_int32, C.POINTER(Cost),
+                                    C.POINTER(SmcOpts), C.POINTER(SmcState), C.POINTER(SmcState),
+                                    C.POINTER(SmcResult)]),
     "kabc_smc_run_dist": (C.c_int, [VP, C.POINTER(Prior), C.c_int32, C.POINTER(Cost),
                                C.POINTER(SmcOpts), C.POINTER(SmcResult)]),
     "kabc_smc_run_dist_mode": (C.c_int, [VP, C.POINTER(Prior), C.c_int32, C.POINTER(Cost),

@@ -562,10 +562,79 @@ class SmcResult(collections.namedtuple("SmcResult", ["P", "C", "eps", "info"])):
         raise AttributeError(name)
 
 
-def smc(prior, cost, *, nparticles=100, alpha=0.95, mcmc_retrys=0, mcmc_tol=0.015, epstol=0.0,
-        r_epstol=None, min_r_ess=None, max_stretch=2.0, verbose=False, parallel=False, seed=0,
-        ctx=None, return_array=False, comm=None, shard=None, max_iterations=None):
-    """smc(prior, cost; ...) -- src/smc.jl:92-206, same keywords and defaults.
+_SMC_LOG_KEYS = ("eps", "ess", "accepted", "resampled", "flag", "passes")
+
+
+class SmcState:
+    """What an smc run holds at an iteration boundary (kabc_smc_state_t, include/kabc.h): enough to go on
+    from there with `smc(prior, cost, resume=state, ...)`, bit for bit as if the run had never stopped --
+    given the same prior, cost, seed and options.  `theta` [N][D] holds the walkers as the loop holds them,
+    NOT push_p'ed (a discrete prior's walkers sit between integers); `cost`, `logprior` [N] and `alive`
+    [N] belong to them.  `iteration` counts the completed iterations, `pass_count` the propose / accept
+    passes (the transition counter of the random streams), `log` holds the records of those iterations.
+    `save(path)` / `load(path)`: one .npz of arrays and scalars, no pickle."""
+
+    _INTS = ("seed", "iteration", "pass_count", "accepted", "cost_evals", "proposals", "n_alive")
+    _UNSIGNED = ("seed", "pass_count", "accepted", "cost_evals", "proposals")
+
+    def __init__(self, theta, cost, logprior, alive, *, seed, iteration, pass_count, eps, eps_prev,
+                 accepted, cost_evals, proposals, n_alive, log=()):
+        self.theta = np.ascontiguousarray(theta, dtype=np.float64)
+        if self.theta.ndim != 2:
+            raise ValueError("SmcState: theta must be [nparticles][D]")
+        n = self.theta.shape[0]
+        self.cost = np.ascontiguousarray(cost, dtype=np.float64).reshape(-1)
+        self.logprior = np.ascontiguousarray(logprior, dtype=np.float64).reshape(-1)
+        self.alive = np.ascontiguousarray(alive, dtype=np.uint8).reshape(-1)
+        for name in ("cost", "logprior", "alive"):
+            if getattr(self, name).shape[0] != n:
+                raise ValueError(f"SmcState: {name} has {getattr(self, name).shape[0]} entries for {n} particles")
+        for name in self._INTS:
+            setattr(self, name, int(locals()[name]))
+        self.eps, self.eps_prev = float(eps), float(eps_prev)
+        self.log = [dict(rec) for rec in log]
+
+    nparticles = property(lambda self: self.theta.shape[0])
+    D = property(lambda self: self.theta.shape[1])
+
+    def save(self, path):
+        """Write the state to `path` as one .npz (the name is used as given)."""
+        arrays = {"theta": self.theta, "cost": self.cost, "logprior": self.logprior, "alive": self.alive,
+                  "eps": np.float64(self.eps), "eps_prev": np.float64(self.eps_prev)}
+        for name in self._INTS:
+            arrays[name] = (np.uint64 if name in self._UNSIGNED else np.int64)(getattr(self, name))
+        for key in _SMC_LOG_KEYS:
+            arrays["log_" + key] = np.array([rec[key] for rec in self.log],
+                                            dtype=np.float64 if key == "eps" else np.int64)
+        with open(path, "wb") as f:
+            np.savez(f, **arrays)
+
+    @classmethod
+    def load(cls, path):
+        with np.load(path, allow_pickle=False) as z:
+            cols = {key: z["log_" + key] for key in _SMC_LOG_KEYS}
+            log = [{key: (float(cols[key][i]) if key == "eps" else int(cols[key][i])) for key in _SMC_LOG_KEYS}
+                   for i in range(len(cols["eps"]))]
+            return cls(z["theta"], z["cost"], z["logprior"], z["alive"], eps=float(z["eps"]),
+                       eps_prev=float(z["eps_prev"]), log=log, **{name: int(z[name]) for name in cls._INTS})
+
+    def _to_c(self):
+        st = cd.SmcState()
+        st.nparticles, st.D, st.seed = self.nparticles, self.D, self.seed
+        st.iteration, st.pass_, st.eps, st.eps_prev = self.iteration, self.pass_count, self.eps, self.eps_prev
+        st.accepted, st.cost_evals, st.proposals, st.n_alive = self.accepted, self.cost_evals, self.proposals, self.n_alive
+        st.theta = self.theta.ctypes.data_as(cd.c_double_p)
+        st.cost = self.cost.ctypes.data_as(cd.c_double_p)
+        st.logprior = self.logprior.ctypes.data_as(cd.c_double_p)
+        st.alive = self.alive.ctypes.data_as(C.POINTER(C.c_uint8))
+        return st
+
+
+def smc(prior, cost, *, nparticles=None, alpha=0.95, mcmc_retrys=0, mcmc_tol=0.015, epstol=0.0,
+        r_epstol=None, min_r_ess=None, max_stretch=2.0, verbose=False, parallel=False, seed=None,
+        ctx=None, return_array=False, comm=None, shard=None, max_iterations=None, return_state=False,
+        resume=None):
+    """smc(prior, cost; ...) -- src/smc.jl:92-206, same keywords and defaults (nparticles = 100, seed = 0).
     `parallel` is accepted and ignored (every particle is a GPU lane).
     `comm` (a comm.Comm): the cost loop is sharded over the communicator's ranks
     (kabc_smc_run_dist -- the reference's `parallel = true` leg across GPUs, for expensive
@@ -576,11 +645,33 @@ def smc(prior, cost, *, nparticles=100, alpha=0.95, mcmc_retrys=0, mcmc_tol=0.01
     `max_iterations` bounds the outer loop (default 100 000).  Context.cancel() or Ctrl-C stops a
     single-GPU run at an iteration boundary: Cancelled (its `.result` holds the population after the
     iterations that completed) or KeyboardInterrupt.
+    `return_state=True` (kabc_smc_run_from): info["state"] is the SmcState the run ended in -- also on
+    Cancelled.result.  `resume=state` continues from it instead of drawing from the prior: `nparticles`
+    and `seed` default to the state's; iterations, cost_evals, proposals and `max_iterations` count from
+    the start of the run; info["log"] is the state's log followed by this call's records, and
+    info["first_iteration"] tells where this call began (with a state in or out the log holds every
+    iteration; a plain call keeps its first 4096 records).  With the same prior, cost, seed and options
+    the continued run is the uninterrupted one, bit for bit.  The stop tests are applied to the state
+    first: a run that ended by rule stays as it is under the same options and goes on under a smaller
+    `epstol`; one stopped by `max_iterations` or a cancel goes on.  Single GPU only (no `comm`).
     Returns (P, C, ϵ) as the reference does (+ an `info` dict)."""
     fac = as_factored(prior)
     scalar = isinstance(prior, UnivariateDistribution)
     if not isinstance(cost, DeviceCost):
         raise TypeError("`cost` must be a DeviceCost on the MI355X path")
+    if comm is not None and (resume is not None or return_state):
+        raise ValueError("smc: resume= and return_state= are single-GPU only (no comm=)")
+    if resume is not None:
+        if not isinstance(resume, SmcState):
+            raise TypeError("smc: resume must be an SmcState")
+        if nparticles is not None and int(nparticles) != resume.nparticles:
+            raise ValueError(f"smc: nparticles = {int(nparticles)}, the state holds {resume.nparticles} particles")
+        if len(fac) != resume.D:
+            raise ValueError(f"smc: length(prior) = {len(fac)}, the state's walkers have {resume.D} parameters")
+        nparticles = resume.nparticles
+        seed = resume.seed if seed is None else seed
+    nparticles = 100 if nparticles is None else nparticles
+    seed = 0 if seed is None else seed
     lib = _lib.load()
     ctx = ctx or _lib.default_context()
     o = cd.SmcOpts()
@@ -603,13 +694,19 @@ def smc(prior, cost, *, nparticles=100, alpha=0.95, mcmc_retrys=0, mcmc_tol=0.01
     theta = _lib.result_empty((n_alloc, D))
     Cst = _lib.result_empty(n_alloc)
     alive = np.zeros(n_alloc, dtype=np.uint8)
-    log = (cd.SmcIter * 4096)()
+    # the log: 4096 records; with a state in or out, every iteration this call can run -- a state's log has
+    # no gaps, its record i is iteration i + 1
+    log_cap = 4096
+    if return_state or resume is not None:
+        first = resume.iteration if resume is not None else 0
+        log_cap = max((o.max_iterations if o.max_iterations > 0 else 100000) - first, 1)
+    log = (cd.SmcIter * log_cap)()
     r = cd.SmcResult()
     r.theta = theta.ctypes.data_as(cd.c_double_p)
     r.cost = Cst.ctypes.data_as(cd.c_double_p)
     r.alive = alive.ctypes.data_as(C.POINTER(C.c_uint8))
     r.iter_log = log
-    r.iter_log_cap = 4096
+    r.iter_log_cap = log_cap
     cc = cost.to_c()
     if shard not in (None, "cost_loop", "particles"):
         raise ValueError('shard is None, "cost_loop" or "particles"')
@@ -619,26 +716,44 @@ def smc(prior, cost, *, nparticles=100, alpha=0.95, mcmc_retrys=0, mcmc_tol=0.01
     elif comm is not None:
         _lib.check(lib.kabc_smc_run_dist(comm.handle, fac.to_c(), D, C.byref(cc), C.byref(o), C.byref(r)))
     else:
+        # (a state in or out: kabc_smc_run_from; else kabc_smc_run, which copies nothing more)
+        to = st_from = st_to = None
+        if return_state:
+            to = SmcState(np.empty((n_alloc, D)), np.empty(n_alloc), np.empty(n_alloc), np.zeros(n_alloc, np.uint8),
+                          seed=0, iteration=-1, pass_count=0, eps=math.inf, eps_prev=math.inf, accepted=0,
+                          cost_evals=0, proposals=0, n_alive=0)
+            st_to = to._to_c()
+        if resume is not None:
+            st_from = resume._to_c()
         with ctx.interruptible():
-            status = lib.kabc_smc_run(ctx.handle, fac.to_c(), D, C.byref(cc), C.byref(o), C.byref(r))
+            if to is None and resume is None:
+                status = lib.kabc_smc_run(ctx.handle, fac.to_c(), D, C.byref(cc), C.byref(o), C.byref(r))
+            else:
+                status = lib.kabc_smc_run_from(ctx.handle, fac.to_c(), D, C.byref(cc), C.byref(o),
+                                               C.byref(st_from) if st_from is not None else None,
+                                               C.byref(st_to) if st_to is not None else None, C.byref(r))
             if status == cd.KABC_ERR_CANCELLED:
                 # the population after the iterations that completed travels with the exception
                 try:
                     _lib.check(status)
                 except _lib.Cancelled as e:
                     e.result = _smc_result(lib, r, theta, Cst, alive, log, n_alloc, N, return_array,
-                                           scalar, t_host0, time.perf_counter())
+                                           scalar, t_host0, time.perf_counter(), resume, to, st_to)
                     raise
             _lib.check(status)
+        return _smc_result(lib, r, theta, Cst, alive, log, n_alloc, N, return_array, scalar, t_host0,
+                           time.perf_counter(), resume, to, st_to)
     return _smc_result(lib, r, theta, Cst, alive, log, n_alloc, N, return_array, scalar, t_host0,
                        time.perf_counter())
 
 
-def _smc_result(lib, r, theta, Cst, alive, log, n_alloc, N, return_array, scalar, t_host0, t_host1):
+def _smc_result(lib, r, theta, Cst, alive, log, n_alloc, N, return_array, scalar, t_host0, t_host1,
+                resume=None, to=None, st_to=None):
     mask = alive.view(np.bool_)          # (the library writes 0 / 1)
     # every particle alive (the usual end of a run): the result IS the array, not a gathered copy
     kept = theta if (r.n_alive == n_alloc and N > 0) else theta[mask]
-    nit = min(r.iterations, 4096)
+    first = resume.iteration if resume is not None else 0   # (the library's log holds this call's iterations)
+    nit = min(r.iterations - first, len(log))
     info = {
         "iterations": r.iterations, "n_alive": r.n_alive, "cost_evals": r.cost_evals,
         "proposals": r.proposals, "alive": mask, "theta_all": theta,
@@ -647,6 +762,15 @@ def _smc_result(lib, r, theta, Cst, alive, log, n_alloc, N, return_array, scalar
                      resampled=log[i].resampled, flag=log[i].flag, passes=log[i].mcmc_passes)
                 for i in range(nit)],
     }
+    if resume is not None:
+        info["log"] = [dict(rec) for rec in resume.log] + info["log"]
+        info["first_iteration"] = first
+    if to is not None:   # the scalars the library wrote into the struct; the arrays it filled in place
+        for name in SmcState._INTS:
+            setattr(to, name, int(getattr(st_to, "pass_" if name == "pass_count" else name)))
+        to.eps, to.eps_prev = st_to.eps, st_to.eps_prev
+        to.log = [dict(rec) for rec in info["log"]]
+        info["state"] = to
     if True:   # how the run was driven (kabc_smc_dist_stats)
         ds = (C.c_int64 * 8)()
         lib.kabc_smc_dist_stats(ds)

@@ -238,6 +238,10 @@ struct SmcMode {
     bool force_coop = false;  // cooperative launches of the select kernel from the start
     bool no_loop = false;     // the kernel-per-phase path only (a repetition after the loop kernel gave up)
     int dist_mode = 0;        // what the ranks of the communicator share out (KABC_SMC_DIST_*)
+    // kabc_smc_run_from: the state the run continues from (NULL: the initial draw) and the one it leaves
+    // (NULL: none); a repetition on another course starts from the same state
+    const kabc_smc_state_t* from = nullptr;
+    kabc_smc_state_t* to = nullptr;
 };
 
 enum class SmcCourse { none, small, loop, one_exchange, looked };
@@ -306,6 +310,7 @@ struct SmcRun {
     int64_t mcmc_timed = 0;
     long dsel_calls = 0, dsel_rounds = 0, dsel_lists = 0, dsel_scans = 0, dsel_resamples = 0;  // (KABC_SMC_STAMPS)
     SmcCtrl hc;
+    unsigned long long first_pass = 0;  // passes made before this call (a continued run's state)
     SmcCourse course = SmcCourse::none;
     // kabc_smc_run_batch: `nruns` independent runs of the one-workgroup kernel (costs[r], seeds[r], results
     // [r]); every per-run buffer is [nruns] of a single run's; hcs holds their control blocks
@@ -593,6 +598,8 @@ kabc_status_t setup(SmcRun& r) {
     r.lpz.epstol = o->epstol;
     r.lpz.r_epstol = r.r_epstol;
     r.lpz.max_iterations = o->max_iterations > 0 ? o->max_iterations : 100000;
+    r.lpz.first_iteration = r.mode.from ? r.mode.from->iteration : 0;
+    r.first_pass = r.mode.from ? r.mode.from->pass : 0;
     std::memset(&r.hc, 0, sizeof r.hc);
     KABC_HIP_CHECK(hipSetDevice(ctx->device));
     hipStream_t s = r.s = ctx->stream;
@@ -674,6 +681,37 @@ kabc_status_t setup(SmcRun& r) {
     return KABC_OK;
 }
 
+// kabc_smc_run_from: the state's walkers, costs, log-priors and alive mask into buffer set 0, then what the
+// initial draw leaves behind for the courses (smc_restore_kernel)
+kabc_status_t restore(SmcRun& r) {
+    const kabc_smc_state_t& f = *r.mode.from;
+    const int64_t N = r.N;
+    hipStream_t s = r.s;
+    KABC_HIP_CHECK(hipMemcpyAsync(r.th[0], f.theta, sizeof(double) * N * r.D, hipMemcpyHostToDevice, s));
+    KABC_HIP_CHECK(hipMemcpyAsync(r.X[0], f.cost, sizeof(double) * N, hipMemcpyHostToDevice, s));
+    KABC_HIP_CHECK(hipMemcpyAsync(r.lp[0], f.logprior, sizeof(double) * N, hipMemcpyHostToDevice, s));
+    KABC_HIP_CHECK(hipMemcpyAsync(r.alive, f.alive, (size_t)N, hipMemcpyHostToDevice, s));
+    SmcRestoreArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.X = r.X[0];
+    a.alive = r.alive;
+    a.ctrl = r.ctrl;
+    a.part = r.part;
+    a.N = N;
+    a.state.eps = f.eps;
+    a.state.eps_prev = f.eps_prev;
+    a.state.iteration = f.iteration;
+    a.state.n_alive = f.n_alive;
+    a.state.pass = f.pass;
+    a.state.accepted = f.accepted;
+    a.state.cost_evals = f.cost_evals;
+    a.state.proposals = f.proposals;
+    a.P = r.lpz;
+    hipLaunchKernelGGL(smc_restore_kernel, dim3((unsigned)r.npart), dim3(kSmcBlock), 0, s, a);
+    KABC_HIP_CHECK(hipGetLastError());
+    return r.look();  // (the stop tests may have ended the run before its first iteration)
+}
+
 // the initial ensemble: :119-125
 kabc_status_t init(SmcRun& r) {
     const int D = r.D;
@@ -702,8 +740,12 @@ kabc_status_t init(SmcRun& r) {
         da.p1 = N;
         // (a sharded run: every rank draws and costs ALL particles at the start -- the draws are counter-based,
         // the ranks end up with the same ensemble, nothing is exchanged; the passes are shared out)
-        r.dyn_fn(da, s, 1);
-        KABC_HIP_CHECK(hipGetLastError());
+        if (r.mode.from) {
+            if (kabc_status_t st = restore(r)) return st;
+        } else {
+            r.dyn_fn(da, s, 1);
+            KABC_HIP_CHECK(hipGetLastError());
+        }
         if (r.comm) {
             da.p0 = std::min<int64_t>(r.wg_lo * kSmcBlock, N);
             da.p1 = std::min<int64_t>((r.wg_lo + r.wg_n) * kSmcBlock, N);
@@ -711,6 +753,7 @@ kabc_status_t init(SmcRun& r) {
         }
         return KABC_OK;
     }
+    if (r.mode.from) return restore(r);
     SmcInitArgs a;
     fill_args(a, r);
     a.cost_id = cost->id;
@@ -732,6 +775,7 @@ kabc_status_t init(SmcRun& r) {
         c0.eps = INFINITY;
         c0.eps_prev = INFINITY;
         c0.cost_evals = (unsigned long long)N;
+        c0.n_alive = N;
         KABC_HIP_CHECK(hipMemcpyAsync(r.ctrl, &c0, sizeof c0, hipMemcpyHostToDevice, s));
         KABC_HIP_CHECK(hipStreamSynchronize(s));  // (c0 is on this stack frame)
     }
@@ -934,7 +978,7 @@ kabc_status_t run_small(SmcRun& r) {
         }
     }
     float ms = 0.f;
-    const unsigned long long pass = r.hc.pass;
+    const unsigned long long pass = r.hc.pass - r.first_pass;  // (of this call)
     if (pass > 0 && hipEventElapsedTime(&ms, r.ev.a, r.ev.b) == hipSuccess) {
         const unsigned long long first = auxW ? (pass < (unsigned long long)r.aux_ring ? pass : (unsigned long long)r.aux_ring) : pass;
         r.mcmc_ms = ms / (double)first;  // the first launch per pass: there is no separate propose+accept kernel
@@ -990,8 +1034,8 @@ kabc_status_t run_loop(SmcRun& r) {
     KABC_HIP_CHECK(hipMemcpyAsync(&r.hc, r.ctrl, sizeof r.hc, hipMemcpyDeviceToHost, s));
     KABC_HIP_CHECK(hipStreamSynchronize(s));
     float ms = 0.f;
-    if (r.hc.pass > 0 && hipEventElapsedTime(&ms, r.ev.a, r.ev.b) == hipSuccess) {
-        r.mcmc_ms = ms / (double)r.hc.pass;  // the whole loop per pass: there is no
+    if (r.hc.pass > r.first_pass && hipEventElapsedTime(&ms, r.ev.a, r.ev.b) == hipSuccess) {
+        r.mcmc_ms = ms / (double)(r.hc.pass - r.first_pass);  // the whole loop per pass: there is no
         r.mcmc_timed = 1;                    // separate propose+accept kernel here
     }
     r.course = SmcCourse::loop;
@@ -1290,13 +1334,37 @@ kabc_status_t copy_out(SmcRun& r) {
     if (res->alive)
         KABC_HIP_CHECK(hipMemcpyAsync(res->alive, r.alive, (size_t)N, hipMemcpyDeviceToHost, s));
     const SmcCtrl& hc = r.hc;
-    const int64_t nlog = hc.iteration < r.log_cap ? hc.iteration : r.log_cap;
+    const int64_t first = r.lpz.first_iteration, ran = hc.iteration - first;  // (the log: this call's iterations)
+    const int64_t nlog = ran < r.log_cap ? ran : r.log_cap;
     if (nlog > 0)
         KABC_HIP_CHECK(hipMemcpyAsync(res->iter_log, r.d_log, sizeof(kabc_smc_iter_t) * nlog, hipMemcpyDeviceToHost, s));
+    // the state a later call continues from: the walkers as the loop holds them (buffer set hc.cur, no
+    // push_p), their costs and log-priors
+    kabc_smc_state_t* to = r.mode.to;
+    if (to) {
+        KABC_HIP_CHECK(hipMemcpyAsync(to->theta, r.th[hc.cur], sizeof(double) * N * D, hipMemcpyDeviceToHost, s));
+        KABC_HIP_CHECK(hipMemcpyAsync(to->cost, r.X[hc.cur], sizeof(double) * N, hipMemcpyDeviceToHost, s));
+        KABC_HIP_CHECK(hipMemcpyAsync(to->logprior, r.lp[hc.cur], sizeof(double) * N, hipMemcpyDeviceToHost, s));
+        KABC_HIP_CHECK(hipMemcpyAsync(to->alive, r.alive, (size_t)N, hipMemcpyDeviceToHost, s));
+    }
     KABC_HIP_CHECK(hipStreamSynchronize(s));
+    if (to) {
+        to->nparticles = N;
+        to->D = D;
+        to->reserved = 0;
+        to->seed = r.o->seed;
+        to->iteration = hc.iteration;
+        to->pass = hc.pass;
+        to->eps = hc.eps;
+        to->eps_prev = hc.eps_prev;
+        to->accepted = hc.accepted;
+        to->cost_evals = hc.cost_evals;
+        to->proposals = hc.proposals;
+        to->n_alive = hc.n_alive;
+    }
     if (r.o->verbose)  // @show iteration, ϵ, ESS  (src/smc.jl:143)
         for (int64_t i = 0; i < nlog; ++i)
-            fprintf(stderr, "(iteration, ϵ, ESS) = (%lld, %.17g, %lld)\n", (long long)(i + 1),
+            fprintf(stderr, "(iteration, ϵ, ESS) = (%lld, %.17g, %lld)\n", (long long)(first + i + 1),
                     res->iter_log[i].eps, (long long)res->iter_log[i].ess);
     res->eps = hc.eps;
     res->iterations = hc.iteration;
@@ -1344,13 +1412,15 @@ kabc_status_t finish(SmcRun& r) {
     if (looped && !r.mode.no_loop && std::getenv("KABC_SMC_LOOP_GIVE_UP")) hc.error = 4;
     // (test hook: KABC_SMC_SELECT_TIME_OUT=1 makes the first, ordinary-launch run count as timed out)
     const bool coop = select_cooperative(r.mode.force_coop);
-    if (!looped && !coop && hc.error == 0 && std::getenv("KABC_SMC_SELECT_TIME_OUT")) hc.error = 3;
-    if ((hc.error == 3 && !looped && !coop) || (hc.error == 4 && looped && !r.mode.no_loop)) {
+    const bool ran = r.course != SmcCourse::none;  // (a continued run may end at its state: no course ran)
+    if (ran && !looped && !coop && hc.error == 0 && std::getenv("KABC_SMC_SELECT_TIME_OUT")) hc.error = 3;
+    if ((hc.error == 3 && ran && !looped && !coop) || (hc.error == 4 && looped && !r.mode.no_loop)) {
         // 3: an ordinary launch of the select grid did not become co-resident within 0.2 s: the same run
         // with cooperative launches (co-residency asserted by the runtime; ~21 us per launch dearer).
         // Single-rank runs only: a sharded run launches cooperatively from its first selection
         // (kabc_smc_run_dist_mode), so no rank can take this turn on its own while its peers go on
         // exchanging passes.  4: the loop kernel gave up (single-rank runs only): the kernel-per-phase path.
+        // A continued run (kabc_smc_run_from) is repeated from its state, not from a fresh draw: `again` keeps it.
         SmcMode again = r.mode;
         (hc.error == 3 ? again.force_coop : again.no_loop) = true;
         (void)hipStreamSynchronize(r.s);
@@ -1384,6 +1454,31 @@ kabc_status_t finish(SmcRun& r) {
     return rc;
 }
 
+// kabc_smc_run_from's states, before anything is launched
+kabc_status_t check_state(const SmcMode& mode, int32_t D, const kabc_smc_opts_t* o) {
+    auto bad = [](const char* what) {
+        set_error("kabc_smc_run_from: %s", what);
+        return KABC_ERR_INVALID_ARG;
+    };
+    if (const kabc_smc_state_t* t = mode.to)
+        if (!t->theta || !t->cost || !t->logprior || !t->alive) return bad("an array of `to` is NULL");
+    const kabc_smc_state_t* f = mode.from;
+    if (!f) return KABC_OK;
+    // (`to` is written while `from` is still needed: by the repetitions on another course, which start from it again)
+    if (const kabc_smc_state_t* t = mode.to)
+        if (t == f || t->theta == f->theta || t->cost == f->cost || t->logprior == f->logprior || t->alive == f->alive)
+            return bad("`to` shares its struct or an array with `from`");
+    if (!f->theta || !f->cost || !f->logprior || !f->alive) return bad("an array of `from` is NULL");
+    if (f->nparticles != o->nparticles) return bad("the state's nparticles differs from opts->nparticles");
+    if (f->D != D) return bad("the state's D differs from the call's");
+    if (f->iteration < 0) return bad("the state's iteration is negative (a failed run leaves -1)");
+    if (f->nparticles < 1) return bad("the state's nparticles must be >= 1");
+    int64_t n = 0;
+    for (int64_t i = 0; i < f->nparticles; ++i) n += f->alive[i] != 0;
+    if (n != f->n_alive) return bad("the state's n_alive is not the number of alive particles");
+    return KABC_OK;
+}
+
 kabc_status_t smc_run_impl(kabc_ctx_t* ctx, kabc_comm_t* comm, const kabc_prior_t* prior, int32_t D,
                            const kabc_cost_t* cost, const kabc_smc_opts_t* o, kabc_smc_result_t* res,
                            SmcMode mode) {
@@ -1393,12 +1488,18 @@ kabc_status_t smc_run_impl(kabc_ctx_t* ctx, kabc_comm_t* comm, const kabc_prior_
         set_error("kabc_smc_run: NULL argument");
         return KABC_ERR_INVALID_ARG;
     }
+    const kabc_status_t cs = check_state(mode, D, o);
+    // (until the result is filled; a refused `to` that IS `from` stays the caller's state)
+    if (mode.to && static_cast<const kabc_smc_state_t*>(mode.to) != mode.from) mode.to->iteration = -1;
+    if (cs) return cs;
     SmcRun r{ctx, comm, prior, D, cost, o, res, mode};
     if (kabc_status_t st = setup(r)) return st;
     if (kabc_status_t st = init(r)) return st;
     if (kabc_status_t st = prepare_passes(r)) return st;
-    // the first course whose conditions hold runs (run_looked always does)
+    // the first course whose conditions hold runs (run_looked always does); none when the stop tests ended
+    // a continued run at its state (restore)
     for (auto run : {run_small, run_loop, run_one_exchange, run_looked}) {
+        if (mode.from && r.hc.done) break;
         if (kabc_status_t st = run(r)) return st;
         if (r.course != SmcCourse::none) break;
     }
@@ -1631,6 +1732,17 @@ kabc_status_t kabc_smc_run(kabc_ctx_t* ctx, const kabc_prior_t* prior, int32_t D
                            const kabc_cost_t* cost, const kabc_smc_opts_t* o,
                            kabc_smc_result_t* res) {
     return smc_run_impl(ctx, nullptr, prior, D, cost, o, res, SmcMode());
+}
+
+int64_t kabc_smc_state_sizeof(void) { return (int64_t)sizeof(kabc_smc_state_t); }
+
+kabc_status_t kabc_smc_run_from(kabc_ctx_t* ctx, const kabc_prior_t* prior, int32_t D, const kabc_cost_t* cost,
+                                const kabc_smc_opts_t* o, const kabc_smc_state_t* from, kabc_smc_state_t* to,
+                                kabc_smc_result_t* res) {
+    SmcMode m;
+    m.from = from;
+    m.to = to;
+    return smc_run_impl(ctx, nullptr, prior, D, cost, o, res, m);
 }
 
 kabc_status_t kabc_smc_run_dist_mode(kabc_comm_t* comm, const kabc_prior_t* prior, int32_t D,

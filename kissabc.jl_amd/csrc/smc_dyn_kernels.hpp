@@ -2,6 +2,9 @@
 // :160-191 (propose + accept) with the dimension as a RUN-TIME value, rows in memory.  Same
 // draws and operation order as smc_init_kernel / smc_mcmc_kernel (bit-identical to the oracle);
 // it plugs into the kernel-per-phase path (select / pass_end / finalize do not depend on D).
+// A run continued from a state (kabc_smc_run_from) needs no kernel of its own here: what smc_dyn_init_kernel leaves
+// besides the rows -- the per-workgroup cost statistics and the control block -- is rebuilt by smc_restore_kernel
+// (smc_kernels.hpp), which reads costs and the alive mask only.
 // push_p + the prior's log-density, the cost's dispatch and the team's three stream blocks are in
 // dyn_model.hpp, shared with the AIS kernels of ais_dyn_kernels.hpp; the rules of src/smc.jl (partners,
 // stretch, prior gate, ε test, resample index) are in smc_model.hpp, shared with the fixed-dimension kernels.
@@ -57,6 +60,7 @@ __global__ void __launch_bounds__(kSmcBlock) smc_dyn_init_kernel(const SmcDynArg
             cc.eps = KABC_INF;  // ϵ = Inf  (src/smc.jl:127)
             cc.eps_prev = KABC_INF;
             cc.cost_evals = (unsigned long long)A.N;
+            cc.n_alive = A.N;  // everybody is alive at the start (:125)
             *A.ctrl = cc;
         }
     }

@@ -10,6 +10,7 @@
 //                        cost threshold; the resample gather is fused in through the
 //                        index array, the ensemble is double-buffered
 //   smc_finalize_kernel: :200      push_p of the final positions
+//   smc_restore_kernel : in place of smc_init_kernel when a run continues from a state (kabc_smc_run_from)
 // The rules of src/smc.jl these kernels apply (quantile, flag, resample decision and index, partners,
 // prior gate, ε test, stop tests) are in smc_model.hpp, shared with the other courses.
 #pragma once
@@ -224,6 +225,7 @@ __global__ void __launch_bounds__(kSmcBlock) smc_init_kernel(const SmcInitArgs A
         cc.eps = KABC_INF;       // ϵ = Inf  (src/smc.jl:127)
         cc.eps_prev = KABC_INF;
         cc.cost_evals = (unsigned long long)A.N;
+        cc.n_alive = A.N;  // everybody is alive at the start (:125)
         A.ctrl[run] = cc;
     }
     smc_block_stats(A.part, i < A.N, c, wg);
@@ -949,13 +951,42 @@ __global__ void __launch_bounds__(256) smc_finalize_kernel(const SmcFinalArgs A)
     A.Xout[i] = A.X[cur][i];
 }
 
+// kabc_smc_run_from: what the initial draw leaves behind, rebuilt from a state the host has uploaded into
+// buffer set 0 (X, the alive mask) -- the per-workgroup statistics of the alive costs the first selection
+// reads, and the control block.  The counter lines are zero already (the host clears them once, every pass
+// end leaves them so).  The stop tests of src/smc.jl:194-198 are applied to the state's last iteration with
+// THIS call's options: a run that ended by rule is not continued by the same options, one that ended by
+// max_iterations or a cancel is.  Does not depend on length(prior): the run-time-dimension course shares it.
+struct SmcRestoreArgs {
+    const double* X;
+    const uint8_t* alive;
+    SmcCtrl* ctrl;
+    unsigned long long* part;  // [workgroups][4], see smc_block_stats
+    int64_t N;
+    SmcCtrl state;    // cur = 0, done = 0, use_ridx = 0, pass_open = 0
+    SmcLoopParams P;
+};
+__global__ void __launch_bounds__(kSmcBlock) smc_restore_kernel(const SmcRestoreArgs A) {
+    const int64_t i = (int64_t)blockIdx.x * kSmcBlock + threadIdx.x;
+    const bool in = i < A.N;
+    const bool alive_i = in && A.alive[i] != 0;
+    const double x = in ? A.X[i] : 0.0;
+    smc_block_stats(A.part, alive_i, x);
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        SmcCtrl c = A.state;
+        if (c.iteration > 0 && smc_stop(c.eps_prev, c.eps, c.accepted, c.iteration, A.N, A.P)) c.done = 1;
+        *A.ctrl = c;
+    }
+}
+
 // end of an ε-iteration: log it and apply the stop tests (one thread)
 __device__ __forceinline__ void smc_iter_end(SmcCtrl* ctrl, kabc_smc_iter_t* log, int64_t log_cap,
                                              int64_t N, const SmcLoopParams& P) {
     ctrl->pass_open = 0;
     const long long it = ctrl->iteration;
     const double eps = ctrl->eps, epsv = ctrl->eps_prev;
-    if (log && it <= log_cap) {
+    const long long lslot = smc_log_slot(it, log_cap, P);
+    if (log && lslot >= 0) {
         kabc_smc_iter_t L;
         L.eps = eps;
         L.ess = ctrl->ess;
@@ -964,7 +995,7 @@ __device__ __forceinline__ void smc_iter_end(SmcCtrl* ctrl, kabc_smc_iter_t* log
         L.flag = ctrl->flag;
         L.mcmc_passes = ctrl->passes;
         L.reserved = 0;
-        log[it - 1] = L;
+        log[lslot] = L;
     }
     if (smc_stop(epsv, eps, ctrl->accepted, it, N, P)) ctrl->done = 1;
 }

@@ -489,6 +489,17 @@ __global__ void __launch_bounds__(kLoopBlock) smc_loop_kernel(const SmcLoopArgs 
         reinterpret_cast<double*>(s_prior)[tid] = reinterpret_cast<const double*>(A.prior)[tid];
     for (int j = tid; j < KABC_MATH_TAB_WORDS; j += kLoopBlock) s_logtab[j] = kabc_log_tab[j];
     __syncthreads();
+    // what the run starts from, read BEFORE the first barrier: workgroup 0 rewrites the control block in its
+    // epilogue, which no workgroup reaches before all have arrived here
+    // (field by field: a copy of the whole block goes through scratch memory)
+    const int cur0 = A.ctrl->cur;
+    const double eps0 = A.ctrl->eps, eps_prev0 = A.ctrl->eps_prev;
+    const long long iteration0 = A.ctrl->iteration, n_alive0 = A.ctrl->n_alive;
+    const unsigned long long pass0 = A.ctrl->pass, accepted0 = A.ctrl->accepted, evals0 = A.ctrl->cost_evals,
+                             props0 = A.ctrl->proposals;
+    const SmcLogView lv = smc_log_view(A.log, A.log_cap, A.loop);
+    const double X0 = in ? A.X[cur0][i] : 0.0;
+    const bool alive0 = in && A.alive[i] != 0;
     // the XCD populations of the XCD-aware barrier: counted here, published by one plain barrier
     LoopXcd X;
     X.xcd = loop_xcc_id();
@@ -496,20 +507,21 @@ __global__ void __launch_bounds__(kLoopBlock) smc_loop_kernel(const SmcLoopArgs 
     const bool prologue_ok = loop_plain_barrier(g, G, 0u, &s_ok);
     X.members = (unsigned)loop_ld(&g->xmembers[X.xcd].v);
     X.nxcd = (unsigned)loop_ld(&g->nxcd.v);
-    // loop state, identical in every workgroup
+    // loop state, identical in every workgroup: from the control block (read above) -- the initial draw's
+    // (ϵ = Inf, iteration 0, pass 0, N cost evaluations) or a state's (kabc_smc_run_from)
     unsigned q = 0;  // barriers passed
-    int cur = 0;
-    double eps = KABC_INF, eps_prev = KABC_INF, min_alive = 0.0;
+    int cur = cur0;
+    double eps = eps0, eps_prev = eps_prev0, min_alive = 0.0;
     int flag = 0, resampled = 0, remap_pass = 0;
-    long long iteration = 0, ess = 0, n_alive_now = N;
-    unsigned long long pass = 0, acc_iter = 0, tot_evals = (unsigned long long)N, tot_props = 0;
+    long long iteration = iteration0, ess = 0, n_alive_now = n_alive0;
+    unsigned long long pass = pass0, acc_iter = accepted0, tot_evals = evals0, tot_props = props0;
     int passes_iter = 0;
     int error = prologue_ok ? 0 : 3;
     int cancelled = 0;
     uint32_t cw = 0u;  // (workgroup 0, thread 0: the cancel word as last read)
     // own particle
-    double Xi = in ? A.X[0][i] : 0.0;
-    bool alive_i = in;
+    double Xi = X0;
+    bool alive_i = alive0;
     unsigned n_acc = 0, n_eval = 0, n_prop = 0;  // of the pass that just ended
     // draws of the next pass, prepared in the shadow of B1
     constexpr int kPre = cost_pre_blocks(COST, D);
@@ -607,7 +619,7 @@ __global__ void __launch_bounds__(kLoopBlock) smc_loop_kernel(const SmcLoopArgs 
         // write-back anyway.  With the XCD-aware release an arrival is 1 us, and 3 us of arithmetic
         // in front of it would delay the XCD's last arrival -- the one that starts the write-back.)
         if (in) {
-            nps = pass + (iteration > 0 ? 2u : 1u);
+            nps = pass + 1u;
             const uint32_t w = (uint32_t)i;
             const kabc_u128_t B0 = kabc_stream_block(seed_v, w, nps, 0u, KABC_DOM_SMC_MOVE);
             const kabc_u128_t B1 = kabc_stream_block(seed_v, w, nps, 1u, KABC_DOM_SMC_MOVE);
@@ -670,10 +682,9 @@ __global__ void __launch_bounds__(kLoopBlock) smc_loop_kernel(const SmcLoopArgs 
         KABC_LOOP_RECYCLE()
         n_acc = n_eval = n_prop = 0;
 
-        if (iteration > 0) {
-            // a pass of iteration `iteration` has ended: flip, retry or close the iteration
-            pass += 1;
-            passes_iter += 1;
+        if (passes_iter > 0) {
+            // a pass of iteration `iteration` has ended (counted where it ended, below; the first turn of a
+            // launch comes from the initial draw or from a state: no pass): flip, retry or close the iteration
             cur ^= 1;
             const bool enough = smc_enough(acc_iter, A.loop.mcmc_tol, N);
             if (passes_iter < A.retry_n && !enough) {
@@ -681,7 +692,7 @@ __global__ void __launch_bounds__(kLoopBlock) smc_loop_kernel(const SmcLoopArgs 
                 expand_rest();
                 goto mcmc_pass;
             }
-            if (bid == 0 && tid == 0 && A.log && iteration <= A.log_cap) {
+            if (bid == 0 && tid == 0 && lv.base && iteration <= lv.last) {
                 kabc_smc_iter_t L;
                 L.eps = eps;
                 L.ess = ess;
@@ -690,7 +701,7 @@ __global__ void __launch_bounds__(kLoopBlock) smc_loop_kernel(const SmcLoopArgs 
                 L.flag = flag;
                 L.mcmc_passes = passes_iter;
                 L.reserved = 0;
-                A.log[iteration - 1] = L;
+                lv.base[iteration - 1] = L;
             }
             if (smc_stop(eps_prev, eps, acc_iter, iteration, N, A.loop)) break;
             if (F.b >> 63) {  // a cancel: the same records, the same decision in every workgroup
@@ -1099,6 +1110,8 @@ __global__ void __launch_bounds__(kLoopBlock) smc_loop_kernel(const SmcLoopArgs 
                 A.lpi[1 - cur][i] = lpi;
                 Xi = Xn;
             }
+            pass += 1;
+            passes_iter += 1;
         }
         KABC_LSTAMP(7)
     }

@@ -15,7 +15,8 @@ namespace kabc {
 
 struct SmcLoopParams {
     double mcmc_tol, epstol, r_epstol;
-    long long max_iterations;
+    long long max_iterations;   // bounds ctrl->iteration: the iterations of a continued run count from its state's
+    long long first_iteration;  // iterations completed before this call (kabc_smc_run_from; 0: a fresh run)
 };
 
 // ---- Step 1: ε = quantile(Xs[alive], α)  (src/smc.jl:134-143) ----------------------------------------
@@ -120,6 +121,26 @@ __device__ __forceinline__ bool smc_stop(double eps_prev, double eps, unsigned l
     const double acc = (double)accepted;
     return 2.0 * kabc_fabs(eps_prev - eps) < P.r_epstol * (kabc_fabs(eps_prev) + kabc_fabs(eps)) || eps <= P.epstol ||
            acc < P.mcmc_tol * (double)N || iteration >= P.max_iterations;
+}
+// where iteration `it`'s record goes in the log of the call that ran it -- a continued run's log starts at
+// its first own iteration, the records before are in the state it came from; -1: beyond the log
+__device__ __forceinline__ long long smc_log_slot(long long it, int64_t log_cap, const SmcLoopParams& P) {
+    const long long slot = it - 1 - P.first_iteration;
+    return slot < (long long)log_cap ? slot : -1;
+}
+// The same rule for a kernel that lives through the whole run and has no scalar register to spare (the loop
+// kernel: first_iteration kept live beside the log pointer cost it 68 bytes of scratch memory per lane): the
+// log seen from iteration 1, taken once per launch -- iteration `it`'s record is base[it - 1] while it <= last.
+// base lies first_iteration records before the log; nothing below base[first_iteration] is ever touched.
+struct SmcLogView {
+    kabc_smc_iter_t* base;  // NULL: no log
+    long long last;
+};
+__device__ __forceinline__ SmcLogView smc_log_view(kabc_smc_iter_t* log, int64_t log_cap, const SmcLoopParams& P) {
+    SmcLogView v;
+    v.base = log ? log - P.first_iteration : nullptr;
+    v.last = (long long)log_cap + P.first_iteration;
+    return v;
 }
 
 }  // namespace kabc

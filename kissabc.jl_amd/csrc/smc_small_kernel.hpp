@@ -277,7 +277,8 @@ __global__ void __launch_bounds__(kSmallBlock) smc_small_kernel(const SmcSmallAr
             if (smc_enough(c.accepted, A.loop.mcmc_tol, N)) break;
         }
         // ================= end of the iteration: log, stop tests
-        if (tid == 0 && A.log && c.iteration <= A.log_cap) {
+        const long long lslot = smc_log_slot(c.iteration, A.log_cap, A.loop);
+        if (tid == 0 && A.log && lslot >= 0) {
             kabc_smc_iter_t L;
             L.eps = c.eps;
             L.ess = c.ess;
@@ -286,7 +287,7 @@ __global__ void __launch_bounds__(kSmallBlock) smc_small_kernel(const SmcSmallAr
             L.flag = c.flag;
             L.mcmc_passes = c.passes;
             L.reserved = 0;
-            A.log[run * A.log_cap + c.iteration - 1] = L;
+            A.log[run * A.log_cap + lslot] = L;
         }
         if (smc_stop(c.eps_prev, c.eps, c.accepted, c.iteration, N, A.loop)) {
             c.done = 1;
