@@ -172,6 +172,15 @@ kabc_status_t kabc_ctx_synchronize(kabc_ctx_t* ctx);
  *                     log records), bit-identical to the same call with max_iterations = k.
  *                     kabc_smc_run_from also leaves the state after those k iterations, and
  *                     continuing from it gives the bits of a run that was never interrupted.
+ *   kabc_abcde_run    stops at a generation boundary: result (and kabc_abcde_run_from's `to`) hold the
+ *                     population after the k completed generations, bit-identical to the same call
+ *                     with generations = k; continuing from the state gives the bits of a run that was
+ *                     never interrupted.  A request pending at entry: nothing is launched, result and
+ *                     `to` are left untouched.
+ *   kabc_pfilter_run  stops at an iteration boundary: a call stopped after k >= 1 iterations holds the
+ *                     result (and state) of the same call with max_iters = k - 1; k = 0: the initial
+ *                     draw, the state has iteration 0.  A request pending at entry: nothing is
+ *                     launched, result and `to` are left untouched.
  *   kabc_smc_run_batch, kabc_abcde_run_batch
  *                     every run of the launch grid stops at an iteration / generation boundary with
  *                     its population after the k it completed (an ABCDE run: bit-identical to the
@@ -188,10 +197,10 @@ kabc_status_t kabc_ctx_synchronize(kabc_ctx_t* ctx);
  *                     two launches of KABC_EVAL_ROWS rows, the output arrays are then unspecified.
  *   kabc_abc_reject   a request pending at entry: nothing is launched; during the call: seen between two
  *                     host looks, the result then holds what the completed rows gave (see the entry point).
- * A call that is never cancelled is unchanged.  Sharded and distributed calls (kabc_ais_create_dist
+ * A call that is never cancelled computes what it computed before (what the looks cost kabc_abcde_run and
+ * kabc_pfilter_run: profiles/stop_continue_probe.json).  Sharded and distributed calls (kabc_ais_create_dist
  * handles, kabc_ais_advance_multi, kabc_smc_run_dist*) do not poll -- a cancel seen on one rank
- * would leave the others in a collective -- and neither do kabc_ais_init, kabc_abcde_run and
- * kabc_pfilter_run. */
+ * would leave the others in a collective -- and neither does kabc_ais_init. */
 /* Response time: the device paths look at the word at bounded intervals of WORK, not of time: the one-
  * workgroup AIS kernel once per ~1 ms of modelled work (0.6 us per batch of 64 walkers and sub-step),
  * batch handles between launch blocks of ~25 ms of modelled work, the half-generation path before every
@@ -204,7 +213,14 @@ kabc_status_t kabc_ctx_synchronize(kabc_ctx_t* ctx);
  * per replaced particle, down to eff_tol), so its response time is one iteration of the slowest resident
  * run; workgroups not yet started end at once.  With the built-in costs that is well within 0.1 s; an expensive
  * cost (a simulator, a user cost) at small ensembles stretches it by the same factor as a generation
- * or an iteration. */
+ * or an iteration.
+ * kabc_abcde_run: the one-workgroup kernel at the head of every generation requests the word and decides
+ * on it after its reduction; the host enqueues 64 generations at a time, at most two such blocks ahead of
+ * the device, and looks between them, so a cancelled call ends after the running generation and the empty
+ * launches of at most 128 more.  kabc_pfilter_run: the one-workgroup kernel (up to 256 particles) reads the
+ * word behind the first barrier of every iteration and decides at that iteration's boundary; the launch-per-phase courses look where the host waits anyway: after every
+ * 4 iterations (every one when verbose), under KABC_PF_PASSES=1 at the end of the iteration.  An
+ * iteration is not a bounded amount of work: nothing is promised inside one. */
 kabc_status_t kabc_ctx_cancel(kabc_ctx_t* ctx);
 kabc_status_t kabc_ctx_clear_cancel(kabc_ctx_t* ctx);
 /* Ctrl-C for a blocking call: on = 1 arms ctx, on = 0 disarms it.  While at least one context is
@@ -1016,6 +1032,48 @@ kabc_status_t kabc_abcde_run(kabc_ctx_t* ctx, const kabc_prior_t* prior, int32_t
                              const kabc_cost_t* cost, const kabc_abcde_opts_t* opts,
                              kabc_abcde_result_t* result);
 
+/* ---- continuing a stopped run ---------------------------------------------------------------
+ * What an ABCDE run holds at a generation boundary, enough to go on from there: a run that used up
+ * opts->generations or was stopped by kabc_ctx_cancel is continued by kabc_abcde_run_from, and the
+ * continued run IS the uninterrupted one, bit for bit (theta, cost, reached_eps, generations_run, nsims)
+ * -- every draw is keyed by (seed, particle, generation), and the state carries the generation counter.
+ * That equality needs the same prior, cost, seed and options (generations aside) in every segment;
+ * nothing checks it: a state continued with another seed or other options is a valid run of its own.
+ * The arrays belong to the caller ([N][D] / [N] doubles), for `from` and for `to`. */
+typedef struct kabc_abcde_state {
+    int64_t nparticles;
+    int32_t D;
+    int32_t reserved;
+    uint64_t seed;       /* of the run that left the state (informative)                              */
+    int64_t generation;  /* generations whose moves have run = the generation counter of the streams; */
+                         /* -1: the run that was to fill the state failed.  A run that ended in the    */
+                         /* earlystop break reports generations_run = generation + 1: the reference    */
+                         /* counts the breaking iteration (:373 before :379), which draws nothing     */
+    uint64_t nsims;      /* cumulative                                                                 */
+    double* theta;       /* host [N][D]: the particles as the loop holds them, NOT push_p'ed (a       */
+                         /* discrete prior's particles sit between integers)                          */
+    double* cost;        /* host [N]                                                                   */
+    double* logprior;    /* host [N]                                                                   */
+} kabc_abcde_state_t;
+/* sizeof(kabc_abcde_state_t) as the library was compiled (the struct is not in kabc_abi_sizeof's table) */
+int64_t kabc_abcde_state_sizeof(void);
+/* kabc_abcde_run, started from `from` instead of the initial draw (NULL: the initial draw) and leaving
+ * the state it ended in in `to` (NULL: none).  from == NULL && to == NULL is kabc_abcde_run.
+ *   to      is filled whenever result is: a normal end, KABC_ERR_CANCELLED.  KABC_ERR_RETRY_EXHAUSTED
+ *           leaves to->generation = -1.
+ *   from    opts->generations bounds the TOTAL, result->generations_run and nsims are totals.  With
+ *           from->generation >= opts->generations the population comes back unchanged (push_p'ed in
+ *           result).  A run that ended in the earlystop break, continued with the same options, takes
+ *           the break again and reports the same generations_run; with a smaller eps_target it goes on.
+ * KABC_ERR_INVALID_ARG, before anything is launched: a NULL array in a state, from->nparticles !=
+ * opts->nparticles, from->D != D, from->generation < 0, a cost[i] or logprior[i] that is not finite (the
+ * invariant of :354-366), `to` sharing its struct or an array with `from`.  Single GPU, single run:
+ * kabc_abcde_run_batch takes no state. */
+kabc_status_t kabc_abcde_run_from(kabc_ctx_t* ctx, const kabc_prior_t* prior, int32_t D,
+                                  const kabc_cost_t* cost, const kabc_abcde_opts_t* opts,
+                                  const kabc_abcde_state_t* from, kabc_abcde_state_t* to,
+                                  kabc_abcde_result_t* result);
+
 /* nruns INDEPENDENT ABCDE runs -- one per seed, or one per dataset -- in one call: run r is
  * kabc_abcde_run(prior, costs[r]) with opts->seed replaced by seeds[r] (every other option is shared),
  * and results[r] is filled as that call fills it, bit for bit.  A failed run's theta / cost arrays may
@@ -1079,6 +1137,49 @@ int64_t kabc_pfilter_nparticles(int64_t N, double q, int32_t D);
 kabc_status_t kabc_pfilter_run(kabc_ctx_t* ctx, const kabc_prior_t* prior, int32_t D,
                                const kabc_cost_t* cost, const kabc_pfilter_opts_t* opts,
                                kabc_pfilter_result_t* result);
+
+/* ---- continuing a stopped run ---------------------------------------------------------------
+ * What a pfilter run holds at an iteration boundary, enough to go on from there: a run stopped by its own
+ * stop rules, by max_iters or by kabc_ctx_cancel is continued by kabc_pfilter_run_from, and the continued
+ * run IS the uninterrupted one, bit for bit (theta, cost, eps, eff, iterations, nreps, cost_evals) --
+ * every draw is keyed by (seed, particle, iteration, attempt), and the state carries the iteration counter.
+ * That equality needs the same prior, cost, seed and options (max_iters and the tolerances aside) in every
+ * segment; nothing checks it.  The arrays belong to the caller ([N][D] / [N] doubles). */
+typedef struct kabc_pfilter_state {
+    int64_t nparticles;  /* the effective N: kabc_pfilter_nparticles(opts->nparticles, q, D)           */
+    int32_t D;
+    int32_t reserved;
+    uint64_t seed;       /* of the run that left the state (informative)                              */
+    int64_t iteration;   /* iterations completed; 0: the initial draw; -1: the run that was to fill   */
+                         /* the state failed                                                           */
+    double eps;          /* ϵ of the last completed iteration (Inf at iteration 0)                    */
+    double eff;          /* eff of the last completed iteration (NaN at iteration 0)                  */
+    uint64_t nreps;      /* cumulative                                                                 */
+    uint64_t cost_evals; /* cumulative                                                                 */
+    double* theta;       /* host [N][D], NOT push_p'ed                                                 */
+    double* cost;        /* host [N]                                                                   */
+    double* logprior;    /* host [N]                                                                   */
+} kabc_pfilter_state_t;
+/* sizeof(kabc_pfilter_state_t) as the library was compiled (the struct is not in kabc_abi_sizeof's table) */
+int64_t kabc_pfilter_state_sizeof(void);
+/* kabc_pfilter_run, started from `from` instead of the initial draw (NULL: the initial draw) and leaving
+ * the state it ended in in `to` (NULL: none).  from == NULL && to == NULL is kabc_pfilter_run.
+ *   to      is filled whenever result is: a normal end, max_iters, KABC_ERR_CANCELLED.  A run that fails
+ *           leaves to->iteration = -1.
+ *   from    result->iterations, nreps and cost_evals are TOTALS, and opts->max_iters bounds the total.
+ *           With from->iteration > 0 the stop tests of src/smc.jl:330-332, and "nothing was bad: eff is
+ *           NaN", are applied to the state's (eps, eff, iteration) with THIS call's options before the
+ *           first new iteration: if one fires, the population is returned unchanged.  So a finished run
+ *           continued with the same options stays as it is; with a smaller epstol or eff_tol, or a
+ *           larger max_iters, it goes on.
+ * KABC_ERR_INVALID_ARG, before anything is launched: a NULL array in a state, from->nparticles != the
+ * effective N, from->D != D, from->iteration < 0, a cost[i] or logprior[i] that is not finite (the
+ * invariant of :283-294), `to` sharing its struct or an array with `from`.  Single GPU, single run:
+ * kabc_pfilter_run_batch takes no state. */
+kabc_status_t kabc_pfilter_run_from(kabc_ctx_t* ctx, const kabc_prior_t* prior, int32_t D,
+                                    const kabc_cost_t* cost, const kabc_pfilter_opts_t* opts,
+                                    const kabc_pfilter_state_t* from, kabc_pfilter_state_t* to,
+                                    kabc_pfilter_result_t* result);
 
 /* nruns INDEPENDENT pfilter runs -- one per seed, or one per dataset -- in one call: run r is
  * kabc_pfilter_run(prior, costs[r]) with opts->seed replaced by seeds[r] (every other option is shared),

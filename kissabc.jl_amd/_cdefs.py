@@ -99,6 +99,12 @@ class AbcdeResult(C.Structure):
                 ("reserved", C.c_int32), ("generations_run", C.c_int64), ("nsims", C.c_uint64)]
 
 
+class AbcdeState(C.Structure):
+    _fields_ = [("nparticles", C.c_int64), ("D", C.c_int32), ("reserved", C.c_int32),
+                ("seed", C.c_uint64), ("generation", C.c_int64), ("nsims", C.c_uint64),
+                ("theta", c_double_p), ("cost", c_double_p), ("logprior", c_double_p)]
+
+
 class PfilterOpts(C.Structure):
     _fields_ = [("nparticles", C.c_int64), ("q", C.c_double), ("eff_tol", C.c_double),
                 ("epstol", C.c_double), ("proposal_width", C.c_double), ("max_iters", C.c_int64),
@@ -109,6 +115,13 @@ class PfilterResult(C.Structure):
     _fields_ = [("theta", c_double_p), ("cost", c_double_p), ("eps", C.c_double),
                 ("eff", C.c_double), ("iterations", C.c_int64), ("nreps", C.c_uint64),
                 ("cost_evals", C.c_uint64)]
+
+
+class PfilterState(C.Structure):
+    _fields_ = [("nparticles", C.c_int64), ("D", C.c_int32), ("reserved", C.c_int32),
+                ("seed", C.c_uint64), ("iteration", C.c_int64), ("eps", C.c_double), ("eff", C.c_double),
+                ("nreps", C.c_uint64), ("cost_evals", C.c_uint64),
+                ("theta", c_double_p), ("cost", c_double_p), ("logprior", c_double_p)]
 
 
 class RejectOpts(C.Structure):
@@ -228,10 +241,18 @@ PROTOTYPES = {
     "kabc_abcde_default_opts": (None, [C.POINTER(AbcdeOpts)]),
     "kabc_abcde_run": (C.c_int, [VP, C.POINTER(Prior), C.c_int32, C.POINTER(Cost),
                                  C.POINTER(AbcdeOpts), C.POINTER(AbcdeResult)]),
+    "kabc_abcde_state_sizeof": (C.c_int64, []),
+    "kabc_abcde_run_from": (C.c_int, [VP, C.POINTER(Prior), C.c_int32, C.POINTER(Cost),
+                                      C.POINTER(AbcdeOpts), C.POINTER(AbcdeState), C.POINTER(AbcdeState),
+                                      C.POINTER(AbcdeResult)]),
     "kabc_pfilter_default_opts": (None, [C.POINTER(PfilterOpts)]),
     "kabc_pfilter_nparticles": (C.c_int64, [C.c_int64, C.c_double, C.c_int32]),
     "kabc_pfilter_run": (C.c_int, [VP, C.POINTER(Prior), C.c_int32, C.POINTER(Cost),
                                    C.POINTER(PfilterOpts), C.POINTER(PfilterResult)]),
+    "kabc_pfilter_state_sizeof": (C.c_int64, []),
+    "kabc_pfilter_run_from": (C.c_int, [VP, C.POINTER(Prior), C.c_int32, C.POINTER(Cost),
+                                        C.POINTER(PfilterOpts), C.POINTER(PfilterState),
+                                        C.POINTER(PfilterState), C.POINTER(PfilterResult)]),
     "kabc_smc_run": (C.c_int, [VP, C.POINTER(Prior), C.c_int32, C.POINTER(Cost),
                                C.POINTER(SmcOpts), C.POINTER(SmcResult)]),
     "kabc_smc_state_sizeof": (C.c_int64, []),

@@ -1165,16 +1165,159 @@ class AbcdeResult(collections.namedtuple("AbcdeResult", ["P", "C", "reached_eps"
         raise AttributeError(name)
 
 
-def ABCDE(prior, cost, eps_target, *, nparticles=50, generations=20, α=0.0, alpha=None,
-          parallel=False, earlystop=False, verbose=False, proposal_width=1.0, seed=0, ctx=None,
-          return_array=False):
-    """ABCDE(prior, cost, ϵ_target; ...) -- src/smc.jl:347-430, same keywords
-    (`alpha` is an ASCII alias of `α`; `parallel` is accepted and ignored).
+def _check_with_result(status, result):
+    """_lib.check; a cancelled call's exception carries what the library left in the result (`.result`)"""
+    if status == cd.KABC_ERR_CANCELLED:
+        try:
+            _lib.check(status)
+        except _lib.Cancelled as e:
+            e.result = result()
+            raise
+    _lib.check(status)
+
+
+class _PopulationState:
+    """What AbcdeState and PfilterState share: `theta` [N][D] as the loop holds it (NOT push_p'ed: a discrete
+    prior's particles sit between integers), `cost` and `logprior` [N], integer and float scalars named by
+    the subclass; `save(path)` / `load(path)` as one .npz of arrays and scalars, no pickle."""
+
+    _INTS = ()
+    _UNSIGNED = ()
+    _FLOATS = ()
+    _COUNTER = None    # the counter of completed generations / iterations (-1: the run that was to fill it failed)
+    _CSTRUCT = None
+
+    def __init__(self, theta, cost, logprior, **scalars):
+        name = type(self).__name__
+        self.theta = np.ascontiguousarray(theta, dtype=np.float64)
+        if self.theta.ndim != 2:
+            raise ValueError(f"{name}: theta must be [nparticles][D]")
+        n = self.theta.shape[0]
+        self.cost = np.ascontiguousarray(cost, dtype=np.float64).reshape(-1)
+        self.logprior = np.ascontiguousarray(logprior, dtype=np.float64).reshape(-1)
+        for key in ("cost", "logprior"):
+            if getattr(self, key).shape[0] != n:
+                raise ValueError(f"{name}: {key} has {getattr(self, key).shape[0]} entries for {n} particles")
+        if set(scalars) != set(self._INTS) | set(self._FLOATS):
+            raise TypeError(f"{name}: the scalars are {', '.join(self._INTS + self._FLOATS)}")
+        for key in self._INTS:
+            setattr(self, key, int(scalars[key]))
+        for key in self._FLOATS:
+            setattr(self, key, float(scalars[key]))
+
+    nparticles = property(lambda self: self.theta.shape[0])
+    D = property(lambda self: self.theta.shape[1])
+
+    @classmethod
+    def _empty(cls, n, D):
+        """the state a call fills: the counter at -1 until it has"""
+        scalars = {key: 0 for key in cls._INTS}
+        scalars.update({key: math.nan for key in cls._FLOATS})
+        scalars[cls._COUNTER] = -1
+        return cls(np.empty((n, D)), np.empty(n), np.empty(n), **scalars)
+
+    def save(self, path):
+        """Write the state to `path` as one .npz (the name is used as given)."""
+        arrays = {"theta": self.theta, "cost": self.cost, "logprior": self.logprior}
+        for key in self._INTS:
+            arrays[key] = (np.uint64 if key in self._UNSIGNED else np.int64)(getattr(self, key))
+        for key in self._FLOATS:
+            arrays[key] = np.float64(getattr(self, key))
+        with open(path, "wb") as f:
+            np.savez(f, **arrays)
+
+    @classmethod
+    def load(cls, path):
+        with np.load(path, allow_pickle=False) as z:
+            return cls(z["theta"], z["cost"], z["logprior"], **{key: int(z[key]) for key in cls._INTS},
+                       **{key: float(z[key]) for key in cls._FLOATS})
+
+    def _to_c(self):
+        st = self._CSTRUCT()
+        st.nparticles, st.D = self.nparticles, self.D
+        for key in self._INTS + self._FLOATS:
+            setattr(st, key, getattr(self, key))
+        st.theta = self.theta.ctypes.data_as(cd.c_double_p)
+        st.cost = self.cost.ctypes.data_as(cd.c_double_p)
+        st.logprior = self.logprior.ctypes.data_as(cd.c_double_p)
+        return st
+
+    def _take_scalars(self, st):
+        """the scalars the library wrote into the struct; the arrays it filled in place"""
+        for key in self._INTS + self._FLOATS:
+            setattr(self, key, getattr(st, key))
+
+
+class AbcdeState(_PopulationState):
+    """What an ABCDE run holds at a generation boundary (kabc_abcde_state_t, include/kabc.h): enough to go
+    on from there with `ABCDE(prior, cost, ϵ_target, resume=state, ...)`, bit for bit as if the run had never
+    stopped -- given the same prior, cost, seed and options.  `generation` counts the generations whose
+    moves have run (the generation counter of the random streams), `nsims` the simulations so far."""
+
+    _INTS = ("seed", "generation", "nsims")
+    _UNSIGNED = ("seed", "nsims")
+    _COUNTER = "generation"
+    _CSTRUCT = cd.AbcdeState
+
+
+class PfilterState(_PopulationState):
+    """What a pfilter run holds at an iteration boundary (kabc_pfilter_state_t, include/kabc.h): enough to go
+    on from there with `pfilter(prior, cost, N, resume=state, ...)`, bit for bit as if the run had never
+    stopped -- given the same prior, cost, seed and options.  `nparticles` is the effective N
+    (kabc_pfilter_nparticles), `iteration` counts the completed iterations (0: the initial draw), `eps`
+    and `eff` are those of the last one (Inf / NaN at iteration 0), `nreps` and `cost_evals` are totals."""
+
+    _INTS = ("seed", "iteration", "nreps", "cost_evals")
+    _UNSIGNED = ("seed", "nreps", "cost_evals")
+    _FLOATS = ("eps", "eff")
+    _COUNTER = "iteration"
+    _CSTRUCT = cd.PfilterState
+
+
+def _resume_keywords(name, state_cls, resume, nparticles, what, D, seed):
+    """smc()'s rules for `nparticles` and `seed` against a state, raised before the library is touched"""
+    if not isinstance(resume, state_cls):
+        raise TypeError(f"{name}: resume must be a{'n' if state_cls.__name__[0] in 'AEIOU' else ''} "
+                        f"{state_cls.__name__}")
+    if nparticles is not None and int(nparticles) != resume.nparticles:
+        raise ValueError(f"{name}: {what} = {int(nparticles)}, the state holds {resume.nparticles} particles")
+    if D != resume.D:
+        raise ValueError(f"{name}: length(prior) = {D}, the state's particles have {resume.D} parameters")
+    return resume.nparticles, (resume.seed if seed is None else seed)
+
+
+class _Default(int):
+    """a keyword's documented default, told apart from the same number given by the caller: with resume= the
+    state's value holds unless the caller names one"""
+
+
+_ABCDE_NPARTICLES = _Default(50)
+
+
+def ABCDE(prior, cost, eps_target, *, nparticles=_ABCDE_NPARTICLES, generations=20, α=0.0, alpha=None,
+          parallel=False, earlystop=False, verbose=False, proposal_width=1.0, seed=None, ctx=None,
+          return_array=False, return_state=False, resume=None):
+    """ABCDE(prior, cost, ϵ_target; ...) -- src/smc.jl:347-430, same keywords and defaults (nparticles = 50,
+    seed = 0; `alpha` is an ASCII alias of `α`; `parallel` is accepted and ignored).
+    Context.cancel() or Ctrl-C stops the run at a generation boundary: Cancelled (its `.result` holds the
+    population after the k generations that completed, the result of `generations = k`) or
+    KeyboardInterrupt.
+    `return_state=True` (kabc_abcde_run_from): info["state"] is the AbcdeState the run ended in -- also on
+    Cancelled.result.  `resume=state` continues from it instead of drawing from the prior: `nparticles` and
+    `seed` default to the state's; `generations` bounds the total, and info["generations_run"] and
+    info["nsims"] count from the start of the run.  With the same prior, cost, seed and options the continued
+    run is the uninterrupted one, bit for bit; a state that already holds `generations` generations comes
+    back unchanged.
     Returns (P, C, reached_ϵ) as the reference does (+ info)."""
     fac = as_factored(prior)
     scalar = isinstance(prior, UnivariateDistribution)
     if not isinstance(cost, DeviceCost):
         raise TypeError("`cost` must be a DeviceCost on the MI355X path")
+    if resume is not None:
+        nparticles, seed = _resume_keywords("ABCDE", AbcdeState, resume,
+                                            None if nparticles is _ABCDE_NPARTICLES else nparticles, "nparticles",
+                                            len(fac), seed)
+    seed = 0 if seed is None else seed
     lib = _lib.load()
     ctx = ctx or _lib.default_context()
     o = cd.AbcdeOpts()
@@ -1190,10 +1333,27 @@ def ABCDE(prior, cost, eps_target, *, nparticles=50, generations=20, α=0.0, alp
     r.theta = theta.ctypes.data_as(cd.c_double_p)
     r.cost = Cst.ctypes.data_as(cd.c_double_p)
     cc = cost.to_c()
-    _lib.check(lib.kabc_abcde_run(ctx.handle, fac.to_c(), D, C.byref(cc), C.byref(o), C.byref(r)))
-    info = {"generations_run": r.generations_run, "nsims": r.nsims}
-    return AbcdeResult(theta if return_array else _bundle(theta, scalar), Cst,
-                       bool(r.reached_eps), info)
+    to = AbcdeState._empty(N, D) if return_state else None
+    st_to = to._to_c() if to is not None else None
+    st_from = resume._to_c() if resume is not None else None
+
+    def result():
+        info = {"generations_run": r.generations_run, "nsims": r.nsims}
+        if to is not None:
+            to._take_scalars(st_to)
+            info["state"] = to
+        return AbcdeResult(theta if return_array else _bundle(theta, scalar), Cst, bool(r.reached_eps), info)
+
+    with ctx.interruptible():
+        # (a state in or out: kabc_abcde_run_from; else kabc_abcde_run, which copies nothing more)
+        if to is None and resume is None:
+            status = lib.kabc_abcde_run(ctx.handle, fac.to_c(), D, C.byref(cc), C.byref(o), C.byref(r))
+        else:
+            status = lib.kabc_abcde_run_from(ctx.handle, fac.to_c(), D, C.byref(cc), C.byref(o),
+                                             C.byref(st_from) if st_from is not None else None,
+                                             C.byref(st_to) if st_to is not None else None, C.byref(r))
+        _check_with_result(status, result)
+    return result()
 
 
 class AbcdeBatchResult(list):
@@ -1309,15 +1469,31 @@ def ABCDE_batch(prior, cost, eps_target, nruns=None, *, seeds=None, seed=0, npar
 PfilterResult = collections.namedtuple("PfilterResult", ["P", "C", "info"])
 
 
-def pfilter(prior, cost, N, *, q=0.7, eff_tol=0.1, epstol=-math.inf, max_iters=math.inf,
-            proposal_width=0.75, verbose=False, parallel=False, seed=0, ctx=None,
-            return_array=False):
-    """pfilter(prior, cost, N; ...) -- src/smc.jl:275-340, same keywords
-    (`parallel` accepted and ignored).  Returns (P, C) as the reference does (+ info)."""
+def pfilter(prior, cost, N=None, *, q=0.7, eff_tol=0.1, epstol=-math.inf, max_iters=math.inf,
+            proposal_width=0.75, verbose=False, parallel=False, seed=None, ctx=None,
+            return_array=False, return_state=False, resume=None):
+    """pfilter(prior, cost, N; ...) -- src/smc.jl:275-340, same keywords (seed = 0; `parallel` accepted and
+    ignored).
+    Context.cancel() or Ctrl-C stops the run at an iteration boundary: Cancelled (its `.result` holds the
+    population after the k iterations that completed, the result of `max_iters = k - 1`; k = 0: the
+    initial draw) or KeyboardInterrupt.
+    `return_state=True` (kabc_pfilter_run_from): info["state"] is the PfilterState the run ended in -- also
+    on Cancelled.result.  `resume=state` continues from it instead of drawing from the prior: `N` and `seed`
+    default to the state's, and `N`, when given, is the EFFECTIVE particle count the state holds
+    (info["nparticles"]); iterations, nreps, cost_evals and `max_iters` count from the start of the run.
+    With the same prior, cost, seed and options the continued run is the uninterrupted one, bit for bit.
+    The stop tests are applied to the state first: a run that ended by rule stays as it is under the same
+    options and goes on under a smaller `epstol` or `eff_tol` or a larger `max_iters`.
+    Returns (P, C) as the reference does (+ info)."""
     fac = as_factored(prior)
     scalar = isinstance(prior, UnivariateDistribution)
     if not isinstance(cost, DeviceCost):
         raise TypeError("`cost` must be a DeviceCost on the MI355X path")
+    if resume is not None:
+        N, seed = _resume_keywords("pfilter", PfilterState, resume, N, "N", len(fac), seed)
+    elif N is None:
+        raise TypeError("pfilter: N is required (or resume=)")
+    seed = 0 if seed is None else seed
     lib = _lib.load()
     ctx = ctx or _lib.default_context()
     o = cd.PfilterOpts()
@@ -1333,11 +1509,29 @@ def pfilter(prior, cost, N, *, q=0.7, eff_tol=0.1, epstol=-math.inf, max_iters=m
     r.theta = theta.ctypes.data_as(cd.c_double_p)
     r.cost = Cst.ctypes.data_as(cd.c_double_p)
     cc = cost.to_c()
-    _lib.check(lib.kabc_pfilter_run(ctx.handle, fac.to_c(), D, C.byref(cc), C.byref(o), C.byref(r)))
-    info = {"eps": r.eps, "eff": r.eff, "iterations": r.iterations, "nreps": r.nreps,
-            "cost_evals": r.cost_evals, "nparticles": n_eff}
-    return PfilterResult(theta if return_array else _bundle(theta, scalar),
-                         Cst if return_array else Particles(Cst), info)
+    to = PfilterState._empty(n_eff, D) if return_state else None
+    st_to = to._to_c() if to is not None else None
+    st_from = resume._to_c() if resume is not None else None
+
+    def result():
+        info = {"eps": r.eps, "eff": r.eff, "iterations": r.iterations, "nreps": r.nreps,
+                "cost_evals": r.cost_evals, "nparticles": n_eff}
+        if to is not None:
+            to._take_scalars(st_to)
+            info["state"] = to
+        return PfilterResult(theta if return_array else _bundle(theta, scalar),
+                             Cst if return_array else Particles(Cst), info)
+
+    with ctx.interruptible():
+        # (a state in or out: kabc_pfilter_run_from; else kabc_pfilter_run, which copies nothing more)
+        if to is None and resume is None:
+            status = lib.kabc_pfilter_run(ctx.handle, fac.to_c(), D, C.byref(cc), C.byref(o), C.byref(r))
+        else:
+            status = lib.kabc_pfilter_run_from(ctx.handle, fac.to_c(), D, C.byref(cc), C.byref(o),
+                                               C.byref(st_from) if st_from is not None else None,
+                                               C.byref(st_to) if st_to is not None else None, C.byref(r))
+        _check_with_result(status, result)
+    return result()
 
 
 class PfilterBatchResult(list):

@@ -16,7 +16,7 @@ struct AbcdeCtrl {
     int32_t cur;         // buffer set holding θs, Δs, logπ
     int32_t done;        // earlystop break (:379-381)
     int32_t error;       // 1: initial sampling never produced a finite (Δ, logπ)
-    int32_t pad;
+    int32_t cancelled;   // 1: `done` was set by kabc_ctx_cancel at a generation boundary, not by the break
     long long iters;
     unsigned long long nsims;
 };
@@ -157,9 +157,15 @@ __global__ void __launch_bounds__(kAbcdeBlock) abcde_init_kernel(const AbcdeArgs
 
 #ifdef KABC_ABCDE_SINGLE_UNIT  // non-template kernels: defined once, in capi_abcde.hip
 // ϵ_l, ϵ_h = extrema(Δs); earlystop break; ϵ_pop (:377-382).  One workgroup.
-__global__ void __launch_bounds__(1024) abcde_extrema_kernel(const AbcdeArgs A) {
+// `cancel`: kabc_ctx_cancel's word (host-coherent memory), or NULL.  As in abcde_small_kernel.hpp thread 0
+// requests it at the top and decides on it at the generation boundary below, so the read of host memory
+// hides behind the reduction.  On a request the generation is neither begun nor counted: a pending flip
+// is still committed, `done` makes every later kernel a no-op, `cancelled` tells the host why.
+__global__ void __launch_bounds__(1024) abcde_extrema_kernel(const AbcdeArgs A, const uint32_t* cancel) {
     __shared__ double smin[16], smax[16];
     if (A.ctrl->done) return;
+    uint32_t cw = 0u;
+    if (threadIdx.x == 0 && cancel) cw = __hip_atomic_load(cancel, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     const int cur = A.ctrl->cur ^ (A.flip_first ? 1 : 0);  // (every thread: nobody writes ctrl before the end)
     const double* dl = A.delta[cur];
     double mn = KABC_INF, mx = -KABC_INF;
@@ -184,6 +190,11 @@ __global__ void __launch_bounds__(1024) abcde_extrema_kernel(const AbcdeArgs A) 
             mx = smax[w] > mx ? smax[w] : mx;
         }
         A.ctrl->cur = cur;
+        if (cw != 0u) {  // stop at this generation boundary (kabc_ctx_cancel)
+            A.ctrl->done = 1;
+            A.ctrl->cancelled = 1;
+            return;
+        }
         A.ctrl->eps_l = mn;
         A.ctrl->eps_h = mx;
         A.ctrl->iters += 1;  // iters += 1 (:373): counted before the earlystop break (:379-381), as the reference does

@@ -1,6 +1,7 @@
 // capi_abcde.hip -- kabc_abcde_run: ABCDE(prior, cost, ϵ_target; ...) of
-// src/smc.jl:347-430.  All generations are enqueued without a host round trip; the
-// earlystop break is taken on the device (kernels after it are no-ops).
+// src/smc.jl:347-430.  The generations are enqueued without a host round trip, 64 at a time; the
+// earlystop break and a kabc_ctx_cancel stop are taken on the device (kernels after either are no-ops).
+// kabc_abcde_run_from: the same run started from a state and / or leaving one.
 // kabc_abcde_run_batch: many independent runs, one workgroup each, as one launch grid
 // (abcde_small_kernel.hpp), or one after another through kabc_abcde_run.
 #include <cmath>
@@ -407,9 +408,42 @@ void kabc_abcde_default_opts(kabc_abcde_opts_t* o) {
     o->seed = 0;
 }
 
-kabc_status_t kabc_abcde_run(kabc_ctx_t* ctx, const kabc_prior_t* prior, int32_t D,
-                             const kabc_cost_t* cost, const kabc_abcde_opts_t* o,
-                             kabc_abcde_result_t* res) {
+}  // extern "C"
+
+namespace kabc {
+namespace {
+
+// generations enqueued between two looks of the host at the cancel word: a call of up to 64 generations
+// (the default is 20) is enqueued in one piece; a longer one keeps one block queued behind the running one
+constexpr int64_t kAbcdeEnqueueBlock = 64;
+
+// kabc_abcde_run_from's states, before anything is launched
+kabc_status_t abcde_check_state(const kabc_abcde_state_t* f, const kabc_abcde_state_t* t, int32_t D,
+                                const kabc_abcde_opts_t* o) {
+    auto bad = [](const char* what) {
+        set_error("kabc_abcde_run_from: %s", what);
+        return KABC_ERR_INVALID_ARG;
+    };
+    if (t && (!t->theta || !t->cost || !t->logprior)) return bad("an array of `to` is NULL");
+    if (!f) return KABC_OK;
+    // (`to` is written while `from` still belongs to the caller as the state the run began in)
+    if (t && (t == f || t->theta == f->theta || t->cost == f->cost || t->logprior == f->logprior))
+        return bad("`to` shares its struct or an array with `from`");
+    if (!f->theta || !f->cost || !f->logprior) return bad("an array of `from` is NULL");
+    if (f->nparticles != o->nparticles) return bad("the state's nparticles differs from opts->nparticles");
+    if (f->D != D) return bad("the state's D differs from the call's");
+    if (f->generation < 0) return bad("the state's generation is negative (a failed run leaves -1)");
+    for (int64_t i = 0; i < f->nparticles; ++i)  // (the invariant the initial draw leaves, :354-366)
+        if (!std::isfinite(f->cost[i]) || !std::isfinite(f->logprior[i]))
+            return bad("the state holds a cost or a log-prior that is not finite");
+    return KABC_OK;
+}
+
+// poll: the call observes kabc_ctx_cancel (kabc_abcde_run, kabc_abcde_run_from); the one-after-another
+// course of kabc_abcde_run_batch looks between two runs itself and runs each of them without
+kabc_status_t abcde_run_impl(kabc_ctx_t* ctx, const kabc_prior_t* prior, int32_t D, const kabc_cost_t* cost,
+                             const kabc_abcde_opts_t* o, const kabc_abcde_state_t* from, kabc_abcde_state_t* to,
+                             kabc_abcde_result_t* res, bool poll) {
     if (!ctx || !prior || !cost || !o || !res) {
         set_error("kabc_abcde_run: NULL argument");
         return KABC_ERR_INVALID_ARG;
@@ -438,6 +472,16 @@ kabc_status_t kabc_abcde_run(kabc_ctx_t* ctx, const kabc_prior_t* prior, int32_t
         set_error("nparticles must be >= 3 (and < 2^31)");
         return KABC_ERR_INVALID_ARG;
     }
+    {
+        const kabc_status_t cs = abcde_check_state(from, to, D, o);
+        if (cs) {  // (a refused `to` that IS `from` stays the caller's state)
+            if (to && static_cast<const kabc_abcde_state_t*>(to) != from) to->generation = -1;
+            return cs;
+        }
+    }
+    // a request made while ctx was idle: nothing is launched, `result` and `to` stay as they are
+    if (poll && cancel_take(ctx)) return KABC_ERR_CANCELLED;
+    if (to) to->generation = -1;  // (until the result is filled)
     std::vector<kabc_prior_t> resolved((size_t)D);  // MvNormal components: device block, D
     if (kabc_status_t st = resolve_priors(ctx, prior, D, resolved.data())) return st;
     prior = resolved.data();
@@ -515,7 +559,21 @@ kabc_status_t kabc_abcde_run(kabc_ctx_t* ctx, const kabc_prior_t* prior, int32_t
     KABC_HIP_CHECK(alloc((void**)&A.ctrl, sizeof(AbcdeCtrl)));
     KABC_HIP_CHECK(alloc((void**)&d_out, sizeof(double) * N * D));
     KABC_HIP_CHECK(alloc((void**)&d_dout, sizeof(double) * N));
-    KABC_HIP_CHECK(hipMemsetAsync(A.ctrl, 0, sizeof(AbcdeCtrl), s));
+    // a fresh run starts from zeros; a continued one from the state's counters, its population in buffer
+    // set 0: `iters` is the generation index of the streams (the kernels take g from ctrl->iters), while
+    // the buffer parity below runs from this call's first generation
+    AbcdeCtrl hc0;
+    std::memset(&hc0, 0, sizeof hc0);
+    if (from) {
+        hc0.iters = (long long)from->generation;
+        hc0.nsims = (unsigned long long)from->nsims;
+        KABC_HIP_CHECK(hipMemcpyAsync(A.ctrl, &hc0, sizeof hc0, hipMemcpyHostToDevice, s));
+        KABC_HIP_CHECK(hipMemcpyAsync(A.theta[0], from->theta, sizeof(double) * N * D, hipMemcpyHostToDevice, s));
+        KABC_HIP_CHECK(hipMemcpyAsync(A.delta[0], from->cost, sizeof(double) * N, hipMemcpyHostToDevice, s));
+        KABC_HIP_CHECK(hipMemcpyAsync(A.lpi[0], from->logprior, sizeof(double) * N, hipMemcpyHostToDevice, s));
+    } else {
+        KABC_HIP_CHECK(hipMemsetAsync(A.ctrl, 0, sizeof(AbcdeCtrl), s));
+    }
     PriorDev* d_prior = nullptr;
     kabc_prior_t* d_raw = nullptr;
     if (dyn) {
@@ -549,7 +607,7 @@ kabc_status_t kabc_abcde_run(kabc_ctx_t* ctx, const kabc_prior_t* prior, int32_t
     A.gamma = o->proposal_width * 2.38 / std::sqrt((double)(2 * D));
     A.dom_init = KABC_DOM_ABCDE_INIT;
     A.dom_init_cost = KABC_DOM_ABCDE_INIT_COST;
-    f_init(A, s);
+    if (!from) f_init(A, s);
     KABC_HIP_CHECK(hipGetLastError());
     // large ensembles: a rank structure per generation replaces the O(N) donor scans
     RankStructure R;
@@ -599,9 +657,35 @@ kabc_status_t kabc_abcde_run(kabc_ctx_t* ctx, const kabc_prior_t* prior, int32_t
         KABC_HIP_CHECK(alloc((void**)&d_bsorted, sizeof(double) * (size_t)db_blocks * kDbBlock));
         A.donor = d_donor;
     }
-    for (int64_t g = 0; g < o->generations; ++g) {  // while iters < generations (:372)
+    // opts->generations bounds the TOTAL: a continued run enqueues what its state leaves to do
+    const int64_t g_first = from ? from->generation : 0;
+    const int64_t n_gen = o->generations > g_first ? o->generations - g_first : 0;
+    const uint32_t* const cancel_word = poll ? ctx->cancel_d : nullptr;
+    // between two blocks of generations the host waits for the block before the last one and looks at the
+    // cancel word: a cancelled call stops enqueueing (what is already queued ends as no-ops, the device
+    // has seen the same word)
+    struct BlockEvents {
+        hipEvent_t ev[2] = {nullptr, nullptr};
+        ~BlockEvents() {
+            for (hipEvent_t e : ev)
+                if (e) (void)hipEventDestroy(e);
+        }
+    } blk;
+    bool host_stopped = false;
+    for (int64_t g = 0; g < n_gen; ++g) {  // while iters < generations (:372)
+        if (g > 0 && g % kAbcdeEnqueueBlock == 0) {
+            const int64_t b = g / kAbcdeEnqueueBlock;  // the block about to be enqueued
+            hipEvent_t& done_prev = blk.ev[(b - 1) & 1];
+            if (!done_prev) KABC_HIP_CHECK(hipEventCreateWithFlags(&done_prev, hipEventDisableTiming));
+            KABC_HIP_CHECK(hipEventRecord(done_prev, s));
+            if (b >= 2) KABC_HIP_CHECK(hipEventSynchronize(blk.ev[b & 1]));  // (block b - 2 has ended)
+            if (poll && cancel_pending(ctx)) {
+                host_stopped = true;
+                break;
+            }
+        }
         A.flip_first = g > 0 ? 1 : 0;  // (the flip after generation g - 1 rides on this launch)
-        hipLaunchKernelGGL(abcde_extrema_kernel, dim3(1), dim3(1024), 0, s, A);
+        hipLaunchKernelGGL(abcde_extrema_kernel, dim3(1), dim3(1024), 0, s, A, cancel_word);
         if (use_blocks) {
             hipLaunchKernelGGL(abcde_blocksort_kernel, dim3(db_blocks), dim3(kDbBlock), 0, s, A, d_bsorted);
             hipLaunchKernelGGL(abcde_donor_blocks_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s, A,
@@ -615,7 +699,7 @@ kabc_status_t kabc_abcde_run(kabc_ctx_t* ctx, const kabc_prior_t* prior, int32_t
         if (R.sorted) KABC_HIP_CHECK(build_rank(R, A.delta[g & 1], N, s));
         f_gen(A, s);
     }
-    if (o->generations > 0) hipLaunchKernelGGL(abcde_flip_kernel, dim3(1), dim3(1), 0, s, A.ctrl);  // the last one
+    if (n_gen > 0) hipLaunchKernelGGL(abcde_flip_kernel, dim3(1), dim3(1), 0, s, A.ctrl);  // the last one
     KABC_HIP_CHECK(hipGetLastError());
     AbcdeFinalArgs F;
     for (int b = 0; b < 2; ++b) {
@@ -652,10 +736,45 @@ kabc_status_t kabc_abcde_run(kabc_ctx_t* ctx, const kabc_prior_t* prior, int32_t
     res->reserved = 0;
     res->generations_run = hc.iters;
     res->nsims = hc.nsims;
+    if (to) {  // the population as the loop holds it (NOT push_p'ed), from the buffer set the run ended in
+        KABC_HIP_CHECK(hipMemcpyAsync(to->theta, A.theta[hc.cur], sizeof(double) * N * D, hipMemcpyDeviceToHost, s));
+        KABC_HIP_CHECK(hipMemcpyAsync(to->logprior, A.lpi[hc.cur], sizeof(double) * N, hipMemcpyDeviceToHost, s));
+        KABC_HIP_CHECK(hipStreamSynchronize(s));
+        std::memcpy(to->cost, hd.data(), sizeof(double) * N);
+        to->nparticles = N;
+        to->D = D;
+        to->reserved = 0;
+        to->seed = o->seed;
+        // the stream counter: the iteration that took the earlystop break was counted (:373) but drew nothing
+        to->generation = hc.iters - ((hc.done && !hc.cancelled) ? 1 : 0);
+        to->nsims = hc.nsims;
+    }
     if (o->verbose)
         fprintf(stderr, "ABCDE End: converged = %d nsim = %llu range_eps = (%g, %g)\n",
                 res->reached_eps, (unsigned long long)hc.nsims, hc.eps_l, hc.eps_h);
+    if (hc.cancelled || host_stopped) {  // stopped after hc.iters generations: the result of generations = hc.iters
+        if (!cancel_take(ctx)) set_error("cancelled");
+        return KABC_ERR_CANCELLED;
+    }
     return KABC_OK;
+}
+
+}  // namespace
+}  // namespace kabc
+
+extern "C" {
+
+kabc_status_t kabc_abcde_run(kabc_ctx_t* ctx, const kabc_prior_t* prior, int32_t D, const kabc_cost_t* cost,
+                             const kabc_abcde_opts_t* o, kabc_abcde_result_t* res) {
+    return abcde_run_impl(ctx, prior, D, cost, o, nullptr, nullptr, res, true);
+}
+
+int64_t kabc_abcde_state_sizeof(void) { return (int64_t)sizeof(kabc_abcde_state_t); }
+
+kabc_status_t kabc_abcde_run_from(kabc_ctx_t* ctx, const kabc_prior_t* prior, int32_t D, const kabc_cost_t* cost,
+                                  const kabc_abcde_opts_t* o, const kabc_abcde_state_t* from, kabc_abcde_state_t* to,
+                                  kabc_abcde_result_t* res) {
+    return abcde_run_impl(ctx, prior, D, cost, o, from, to, res, true);
 }
 
 }  // extern "C"
@@ -846,7 +965,7 @@ kabc_status_t abcde_run_grid(kabc_ctx_t* ctx, const kabc_prior_t* prior, int32_t
 }
 
 // the course of shapes the one-workgroup kernel cannot take: the runs one after another, with a look
-// at the cancel word between two runs (kabc_abcde_run itself does not poll)
+// at the cancel word between two runs (each run itself goes without polling)
 void abcde_batch_sequential(kabc_ctx_t* ctx, const kabc_prior_t* prior, int32_t D, const kabc_cost_t* costs,
                             int64_t nruns, const uint64_t* seeds, const kabc_abcde_opts_t* o,
                             kabc_abcde_result_t* results, kabc_status_t* status, std::string* first_msg) {
@@ -858,7 +977,7 @@ void abcde_batch_sequential(kabc_ctx_t* ctx, const kabc_prior_t* prior, int32_t 
         }
         kabc_abcde_opts_t oq = *o;
         oq.seed = seeds[q];
-        status[q] = kabc_abcde_run(ctx, prior, D, &costs[q], &oq, &results[q]);
+        status[q] = abcde_run_impl(ctx, prior, D, &costs[q], &oq, nullptr, nullptr, &results[q], false);
         tl_abcde_batch_stats[1] = q + 1;
         if (status[q] != KABC_OK && first_msg->empty()) {
             const char* m = get_error();

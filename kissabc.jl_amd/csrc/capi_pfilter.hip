@@ -1,6 +1,7 @@
 // capi_pfilter.hip -- kabc_pfilter_run: pfilter(prior, cost, N; ...) of src/smc.jl:275-340, driven from
 // the host: one iteration = the select kernel (shared with smc, capi_smc.hip) + the replacement of every
 // bad particle by a rejection loop.
+// kabc_pfilter_run_from: the same run started from a state and / or leaving one.
 // kabc_pfilter_run_batch: many independent runs, one workgroup each, as one launch grid
 // (pfilter_small_kernel.hpp), or one after another through kabc_pfilter_run.
 #include <cmath>
@@ -84,23 +85,45 @@ PfBatchLaunchFn pf_pick_batch(int D, std::integer_sequence<int, Ds...>) {
 }
 }  // namespace
 
+// kabc_pfilter_run_from's states (from: the one the run continues from, NULL: the initial draw; to: the one
+// it leaves, NULL: none), and whether the call observes kabc_ctx_cancel: the one-after-another course of
+// kabc_pfilter_run_batch looks between two runs itself and runs each of them without
+struct PfMode {
+    const kabc_pfilter_state_t* from = nullptr;
+    kabc_pfilter_state_t* to = nullptr;
+    bool poll = false;
+};
+
+// the states, before anything is launched
+static kabc_status_t pf_check_state(const PfMode& mode, int32_t D, const kabc_pfilter_opts_t* o) {
+    auto bad = [](const char* what) {
+        set_error("kabc_pfilter_run_from: %s", what);
+        return KABC_ERR_INVALID_ARG;
+    };
+    const kabc_pfilter_state_t *f = mode.from, *t = mode.to;
+    if (t && (!t->theta || !t->cost || !t->logprior)) return bad("an array of `to` is NULL");
+    if (!f) return KABC_OK;
+    // (`to` is written while `from` still belongs to the caller as the state the run began in)
+    if (t && (t == f || t->theta == f->theta || t->cost == f->cost || t->logprior == f->logprior))
+        return bad("`to` shares its struct or an array with `from`");
+    if (!f->theta || !f->cost || !f->logprior) return bad("an array of `from` is NULL");
+    if (f->nparticles != kabc_pfilter_nparticles(o->nparticles, o->q, D))
+        return bad("the state's nparticles differs from the effective N, kabc_pfilter_nparticles(opts->nparticles, q, D)");
+    if (f->D != D) return bad("the state's D differs from the call's");
+    if (f->iteration < 0) return bad("the state's iteration is negative (a failed run leaves -1)");
+    for (int64_t i = 0; i < f->nparticles; ++i)  // (the invariant the initial draw leaves, :283-294)
+        if (!std::isfinite(f->cost[i]) || !std::isfinite(f->logprior[i]))
+            return bad("the state holds a cost or a log-prior that is not finite");
+    return KABC_OK;
+}
+
 // force_coop: the run is repeated with cooperative launches of the select kernel after an ordinary
 // launch did not become co-resident in time (several large runs or another tenant holding the CUs)
 static kabc_status_t pfilter_run_impl(kabc_ctx_t* ctx, const kabc_prior_t* prior, int32_t D,
                                       const kabc_cost_t* cost, const kabc_pfilter_opts_t* o,
-                                      kabc_pfilter_result_t* res, bool force_coop) {
-    if (!ctx || !prior || !cost || !o || !res) {
-        set_error("kabc_pfilter_run: NULL argument");
-        return KABC_ERR_INVALID_ARG;
-    }
-    if (D < 1 || D > KABC_MAX_DIM_DYN) {
-        set_error("length(prior) = %d is outside the device path's range 1..%d", D, KABC_MAX_DIM_DYN);
-        return KABC_ERR_UNSUPPORTED;
-    }
-    if (!(o->q > 0 && o->q <= 1) || o->nparticles < 1) {
-        set_error("pfilter needs 0 < q <= 1 and N >= 1");
-        return KABC_ERR_INVALID_ARG;
-    }
+                                      kabc_pfilter_result_t* res, const PfMode& mode, bool force_coop) {
+    const kabc_pfilter_state_t* const from = mode.from;
+    kabc_pfilter_state_t* const to = mode.to;
     // length(prior) > KABC_MAX_DIM: the run-time-dimension instantiation (D = 0) of the kernels,
     // prior components as device arrays
     std::vector<kabc_prior_t> resolved((size_t)D);  // MvNormal components: device block, D
@@ -202,7 +225,7 @@ static kabc_status_t pfilter_run_impl(kabc_ctx_t* ctx, const kabc_prior_t* prior
     KABC_HIP_CHECK(bufs.alloc(&actrl, 1));
     KABC_HIP_CHECK(hipMemsetAsync(ones, 1, (size_t)N, s));
     KABC_HIP_CHECK(hipMemsetAsync(sel, 0, sizeof(SmcCtrl), s));
-    KABC_HIP_CHECK(hipMemsetAsync(pctrl, 0, sizeof(PfCtrl), s));
+    KABC_HIP_CHECK(hipMemsetAsync(pctrl, 0, sizeof(PfCtrl), s));  // (a continued run: the state's counters, below)
     KABC_HIP_CHECK(hipMemsetAsync(actrl, 0, sizeof(AbcdeCtrl), s));
     PriorDev* d_prior = nullptr;
     kabc_prior_t* d_raw = nullptr;
@@ -222,8 +245,24 @@ static kabc_status_t pfilter_run_impl(kabc_ctx_t* ctx, const kabc_prior_t* prior
         KABC_HIP_CHECK(hipMemcpyAsync(d_data, cost->data, sizeof(double) * cost->ndata,
                                       hipMemcpyHostToDevice, s));
     }
+    // the loop's counters: zeros, or the state's (pf_small_kernel starts from *pctrl, pf_iter_end_kernel and
+    // the attempt kernels count on from it)
+    PfCtrl hp;
+    std::memset(&hp, 0, sizeof hp);
+    if (from) {
+        hp.iters = (long long)from->iteration;
+        hp.eps = from->eps;
+        hp.eff = from->eff;
+        hp.total_reps = (unsigned long long)from->nreps;
+        hp.cost_evals = (unsigned long long)from->cost_evals;
+        KABC_HIP_CHECK(hipMemcpyAsync(pctrl, &hp, sizeof hp, hipMemcpyHostToDevice, s));
+        KABC_HIP_CHECK(hipMemcpyAsync(th, from->theta, sizeof(double) * N * D, hipMemcpyHostToDevice, s));
+        KABC_HIP_CHECK(hipMemcpyAsync(Cc, from->cost, sizeof(double) * N, hipMemcpyHostToDevice, s));
+        KABC_HIP_CHECK(hipMemcpyAsync(lpi, from->logprior, sizeof(double) * N, hipMemcpyHostToDevice, s));
+        KABC_HIP_CHECK(hipStreamSynchronize(s));  // (hp is written again below)
+    }
     // :280-294 (same initial-draw loop as ABCDE, its own stream domains)
-    {
+    if (!from) {
         AbcdeArgs a;
         std::memset(&a, 0, sizeof a);
         a.theta[0] = th;
@@ -291,18 +330,25 @@ static kabc_status_t pfilter_run_impl(kabc_ctx_t* ctx, const kabc_prior_t* prior
     pa.prior = P;
     pa.D_rt = D;
     pa.dprior = d_prior;
-    int64_t iters = 0;
-    double eps = 0.0, eff = 0.0;
+    // (the host's `iters` feeds pa.iteration, the iteration index of the streams: it continues from the state)
+    int64_t iters = from ? from->iteration : 0;
+    double eps = from ? from->eps : INFINITY, eff = from ? from->eff : NAN;  // (iteration 0: Inf, NaN)
     SmcCtrl hsel;
-    PfCtrl hp;
     const char* pf_env = std::getenv("KABC_PF_PASSES");  // =1: one launch per attempt (the former scheme)
     const bool pf_loop = !(pf_env && pf_env[0] == '1');
-    std::memset(&hp, 0, sizeof hp);
+    // a continued run: the stop tests of :330-332 and of "nothing was bad" below, on the state's (eps, eff,
+    // iteration) with this call's options, before the first new iteration (not on the initial draw)
+    bool cancelled = false;
+    bool ended = from && from->iteration > 0 &&
+                 (from->eff < o->eff_tol || from->eps < o->epstol ||
+                  (o->max_iters >= 0 && from->iteration > o->max_iters) || from->eff != from->eff);
+    // kabc_ctx_cancel during the initial draw: the result is that draw, the state has iteration 0
+    if (!ended && mode.poll && cancel_pending(ctx)) cancelled = ended = true;
     // Default: every bad particle's rejection loop inside one launch, the stop tests on the device,
     // FOUR iterations enqueued per host round trip (kernels of iterations after the last are
     // no-ops); verbose runs look after every iteration, to print it.
-    bool batched_done = false;
-    if (small && pf_loop) {
+    bool batched_done = ended;
+    if (!ended && small && pf_loop) {
         PfSmallArgs sm;
         std::memset(&sm, 0, sizeof sm);
         sm.pf = pa;
@@ -314,6 +360,7 @@ static kabc_status_t pfilter_run_impl(kabc_ctx_t* ctx, const kabc_prior_t* prior
         sm.epstol = o->epstol;
         sm.max_iters = o->max_iters;
         sm.iters_this_launch = o->verbose ? 1 : 0;
+        sm.cancel = mode.poll ? ctx->cancel_d : nullptr;
         const PfSmallLaunchFn f_small = dyn ? &pf_l_small<0> : pf_pick_small(D, std::make_integer_sequence<int, KABC_MAX_DIM>{});
         while (true) {
             f_small(sm, s);
@@ -332,6 +379,7 @@ static kabc_status_t pfilter_run_impl(kabc_ctx_t* ctx, const kabc_prior_t* prior
                 fprintf(stderr, "(iters, ϵ, eff) = (%lld, %.17g, %.17g)\n", (long long)hp.iters, hp.eps, hp.eff);
             if (hp.done) break;
         }
+        cancelled = hp.done == 2;  // (stopped at an iteration boundary by kabc_ctx_cancel)
         iters = hp.iters;
         eps = hp.eps;
         eff = hp.eff;
@@ -357,7 +405,7 @@ static kabc_status_t pfilter_run_impl(kabc_ctx_t* ctx, const kabc_prior_t* prior
         if (!select_cooperative(force_coop) && hp.error == 0 && std::getenv("KABC_SMC_SELECT_TIME_OUT")) hp.error = 3;  // (test hook)
         if (hp.error == 3) {
             if (!select_cooperative(force_coop)) {  // an ordinary launch that did not become co-resident in time: the same run, cooperatively
-                return pfilter_run_impl(ctx, prior, D, cost, o, res, true);
+                return pfilter_run_impl(ctx, prior, D, cost, o, res, mode, true);
             }
             set_error("pfilter: a device-wide barrier of a cooperative launch timed out after 5 s (the device is wedged)");
             return KABC_ERR_DEVICE;
@@ -372,7 +420,9 @@ static kabc_status_t pfilter_run_impl(kabc_ctx_t* ctx, const kabc_prior_t* prior
         }
         if (o->verbose)
             fprintf(stderr, "(iters, ϵ, eff) = (%lld, %.17g, %.17g)\n", (long long)hp.iters, hp.eps, hp.eff);
-        if (hp.done) {
+        // (the host waits here anyway: kabc_ctx_cancel is looked at on the boundary of the batch's last iteration)
+        cancelled = !hp.done && mode.poll && cancel_pending(ctx);
+        if (hp.done || cancelled) {
             iters = hp.iters;
             eps = hp.eps;
             eff = hp.eff;
@@ -399,7 +449,7 @@ static kabc_status_t pfilter_run_impl(kabc_ctx_t* ctx, const kabc_prior_t* prior
             KABC_HIP_CHECK(hipStreamSynchronize(s));
             if (hsel.error == 3) {
                 if (!select_cooperative(force_coop)) {  // an ordinary launch that did not become co-resident in time: the same run, cooperatively
-                    return pfilter_run_impl(ctx, prior, D, cost, o, res, true);
+                    return pfilter_run_impl(ctx, prior, D, cost, o, res, mode, true);
                 }
                 set_error("pfilter: a device-wide barrier of a cooperative launch timed out after 5 s (the device is wedged)");
                 return KABC_ERR_DEVICE;
@@ -424,6 +474,10 @@ static kabc_status_t pfilter_run_impl(kabc_ctx_t* ctx, const kabc_prior_t* prior
         if (eps < o->epstol) break;
         if (o->max_iters >= 0 && iters > o->max_iters) break;  // src/smc.jl:332; < 0 = Inf
         if (!(hp.nreps > 0)) break;  // nothing left to refresh: eff is NaN forever
+        if (mode.poll && cancel_pending(ctx)) {  // (kabc_ctx_cancel takes effect at the iteration's end)
+            cancelled = true;
+            break;
+        }
     }
     SmcFinalArgs fa;
     fa.theta[0] = fa.theta[1] = th;
@@ -442,20 +496,83 @@ static kabc_status_t pfilter_run_impl(kabc_ctx_t* ctx, const kabc_prior_t* prior
                                       hipMemcpyDeviceToHost, s));
     if (res->cost)
         KABC_HIP_CHECK(hipMemcpyAsync(res->cost, d_cout, sizeof(double) * N, hipMemcpyDeviceToHost, s));
+    if (to) {  // the population as the loop holds it (NOT push_p'ed)
+        KABC_HIP_CHECK(hipMemcpyAsync(to->theta, th, sizeof(double) * N * D, hipMemcpyDeviceToHost, s));
+        KABC_HIP_CHECK(hipMemcpyAsync(to->cost, Cc, sizeof(double) * N, hipMemcpyDeviceToHost, s));
+        KABC_HIP_CHECK(hipMemcpyAsync(to->logprior, lpi, sizeof(double) * N, hipMemcpyDeviceToHost, s));
+    }
     KABC_HIP_CHECK(hipStreamSynchronize(s));
     res->eps = eps;
     res->eff = eff;
     res->iterations = iters;
     res->nreps = hp.total_reps;
     res->cost_evals = hp.cost_evals;
+    if (to) {
+        to->nparticles = N;
+        to->D = D;
+        to->reserved = 0;
+        to->seed = o->seed;
+        to->iteration = iters;
+        to->eps = eps;
+        to->eff = eff;
+        to->nreps = hp.total_reps;
+        to->cost_evals = hp.cost_evals;
+    }
+    if (cancelled) {  // stopped after `iters` iterations: the result of max_iters = iters - 1
+        if (!cancel_take(ctx)) set_error("cancelled");
+        return KABC_ERR_CANCELLED;
+    }
     return KABC_OK;
 }
 
-extern "C" kabc_status_t kabc_pfilter_run(kabc_ctx_t* ctx, const kabc_prior_t* prior, int32_t D,
-                                          const kabc_cost_t* cost, const kabc_pfilter_opts_t* o,
-                                          kabc_pfilter_result_t* res) {
-    return pfilter_run_impl(ctx, prior, D, cost, o, res, false);
+// the checks that need neither the context nor the device, the states, a cancel request pending at entry
+static kabc_status_t pfilter_run_entry(kabc_ctx_t* ctx, const kabc_prior_t* prior, int32_t D,
+                                       const kabc_cost_t* cost, const kabc_pfilter_opts_t* o,
+                                       kabc_pfilter_result_t* res, const PfMode& mode) {
+    if (!ctx || !prior || !cost || !o || !res) {
+        set_error("kabc_pfilter_run: NULL argument");
+        return KABC_ERR_INVALID_ARG;
+    }
+    if (D < 1 || D > KABC_MAX_DIM_DYN) {
+        set_error("length(prior) = %d is outside the device path's range 1..%d", D, KABC_MAX_DIM_DYN);
+        return KABC_ERR_UNSUPPORTED;
+    }
+    if (!(o->q > 0 && o->q <= 1) || o->nparticles < 1) {
+        set_error("pfilter needs 0 < q <= 1 and N >= 1");
+        return KABC_ERR_INVALID_ARG;
+    }
+    if (const kabc_status_t cs = pf_check_state(mode, D, o)) {  // (a refused `to` that IS `from` stays the caller's state)
+        if (mode.to && static_cast<const kabc_pfilter_state_t*>(mode.to) != mode.from) mode.to->iteration = -1;
+        return cs;
+    }
+    // a request made while ctx was idle: nothing is launched, `result` and `to` stay as they are
+    if (mode.poll && cancel_take(ctx)) return KABC_ERR_CANCELLED;
+    if (mode.to) mode.to->iteration = -1;  // (until the result is filled)
+    return pfilter_run_impl(ctx, prior, D, cost, o, res, mode, false);
 }
+
+extern "C" {
+
+kabc_status_t kabc_pfilter_run(kabc_ctx_t* ctx, const kabc_prior_t* prior, int32_t D, const kabc_cost_t* cost,
+                               const kabc_pfilter_opts_t* o, kabc_pfilter_result_t* res) {
+    PfMode mode;
+    mode.poll = true;
+    return pfilter_run_entry(ctx, prior, D, cost, o, res, mode);
+}
+
+int64_t kabc_pfilter_state_sizeof(void) { return (int64_t)sizeof(kabc_pfilter_state_t); }
+
+kabc_status_t kabc_pfilter_run_from(kabc_ctx_t* ctx, const kabc_prior_t* prior, int32_t D, const kabc_cost_t* cost,
+                                    const kabc_pfilter_opts_t* o, const kabc_pfilter_state_t* from,
+                                    kabc_pfilter_state_t* to, kabc_pfilter_result_t* res) {
+    PfMode mode;
+    mode.from = from;
+    mode.to = to;
+    mode.poll = true;
+    return pfilter_run_entry(ctx, prior, D, cost, o, res, mode);
+}
+
+}  // extern "C"
 
 // ---- kabc_pfilter_run_batch ---------------------------------------------------------------------
 namespace kabc {
@@ -659,7 +776,7 @@ kabc_status_t pf_run_grid(kabc_ctx_t* ctx, const kabc_prior_t* prior, int32_t D,
 }
 
 // the course of shapes the one-workgroup kernel cannot take: the runs one after another, with a look
-// at the cancel word between two runs (kabc_pfilter_run itself does not poll)
+// at the cancel word between two runs (each run itself goes without polling)
 void pf_batch_sequential(kabc_ctx_t* ctx, const kabc_prior_t* prior, int32_t D, const kabc_cost_t* costs,
                          int64_t nruns, const uint64_t* seeds, const kabc_pfilter_opts_t* o,
                          kabc_pfilter_result_t* results, kabc_status_t* status, std::string* first_msg) {
@@ -671,7 +788,7 @@ void pf_batch_sequential(kabc_ctx_t* ctx, const kabc_prior_t* prior, int32_t D, 
         }
         kabc_pfilter_opts_t oq = *o;
         oq.seed = seeds[r];
-        status[r] = kabc_pfilter_run(ctx, prior, D, &costs[r], &oq, &results[r]);
+        status[r] = pfilter_run_entry(ctx, prior, D, &costs[r], &oq, &results[r], PfMode{});
         tl_pf_batch_stats[1] = r + 1;
         if (status[r] != KABC_OK && first_msg->empty()) {
             const char* m = get_error();

@@ -23,7 +23,7 @@ struct PfCtrl {
     // decision of :328-333, an error (the select kernel's code, or 9 = a particle left unreplaced)
     long long iters;
     double eps, eff;
-    int32_t done, error;
+    int32_t done, error;  // done = 2: stopped at an iteration boundary by kabc_ctx_cancel (pf_small_kernel)
 };
 
 struct PfArgs {
@@ -191,6 +191,7 @@ struct PfSmallArgs {
     double q, eff_tol, epstol;
     int64_t max_iters;
     int32_t iters_this_launch;  // > 0: return after that many iterations (verbose runs: one)
+    const uint32_t* cancel;     // kabc_ctx_cancel's word (host-coherent memory), or NULL
 };
 
 template <int DT>
@@ -200,12 +201,22 @@ __global__ void __launch_bounds__(kPfSmallBlock) pf_small_kernel(const PfSmallAr
     __shared__ unsigned s_cnt[kPfSmallBlock / kWave];
     __shared__ unsigned long long s_red[3][kPfSmallBlock / kWave];
     __shared__ double s_ab[2];
+    __shared__ int s_stop;
     PfArgs A = S.pf;
     const int tid = threadIdx.x, lane = tid & (kWave - 1), wid = tid >> 6;
     const int N = (int)A.N;
     const bool in = tid < N;
     PfCtrl c = *A.ctrl;  // (every thread: uniform values)
     if (c.done) return;
+    // kabc_ctx_cancel's word is read by the LAST thread, after the iteration's first barrier, and decided on at
+    // the iteration's boundary; never inside the rejection phase.  The read of host memory takes ~1.3 us and a
+    // wave's loads return in order, so WHERE it is issued matters: issued at the loop's back edge it met the
+    // loop header's wait for the pre-loop load of Ci and held all four waves at the first barrier, every
+    // iteration.  Issued behind that barrier, the poller's wave (which owns no particle up to 192 of them)
+    // waits for the word alone, in front of the barrier that ends the rejection phase, while the other waves
+    // run their rejection loops.
+    const bool poller = tid == kPfSmallBlock - 1;
+    uint32_t cw = 0u;
     double Ci = in ? A.C[tid] : 0.0;
     const unsigned long long below = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
     for (int launched = 0; S.iters_this_launch <= 0 || launched < S.iters_this_launch; ++launched) {
@@ -215,6 +226,7 @@ __global__ void __launch_bounds__(kPfSmallBlock) pf_small_kernel(const PfSmallAr
         const unsigned long long ki = in ? key_of(Ci) : ~0ull;
         s_key[tid] = ki;
         __syncthreads();
+        if (poller && S.cancel) cw = __hip_atomic_load(S.cancel, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         unsigned nn = 0;
 #pragma unroll
         for (int w = 0; w < kPfSmallBlock / kWave; ++w) nn += s_cnt[w];
@@ -263,6 +275,7 @@ __global__ void __launch_bounds__(kPfSmallBlock) pf_small_kernel(const PfSmallAr
             s_red[1][wid] = se;
             s_red[2][wid] = sd;
         }
+        if (poller) s_stop = cw != 0u ? 1 : 0;
         __syncthreads();  // (and: every row written above is visible to the workgroup's next reads)
         unsigned long long nreps = 0, nev = 0, ndone = 0;
 #pragma unroll
@@ -287,6 +300,10 @@ __global__ void __launch_bounds__(kPfSmallBlock) pf_small_kernel(const PfSmallAr
         c.eff = (double)nbad / (double)nreps;  // :327 (0/0 = NaN when nothing was bad, as in Julia)
         if (c.eff < S.eff_tol || eps < S.epstol || (S.max_iters >= 0 && c.iters > S.max_iters) || !(nreps > 0ull)) {
             c.done = 1;
+            break;
+        }
+        if (s_stop) {  // (uniform) stop at this iteration boundary (kabc_ctx_cancel)
+            c.done = 2;
             break;
         }
     }
