@@ -674,6 +674,50 @@ kabc_status_t kabc_ais_end_generation(kabc_ais_t* h, int32_t ntransitions);
 kabc_status_t kabc_ais_advance(kabc_ais_t* h, int64_t ngenerations, int32_t ntransitions,
                                double* out_samples, kabc_stats_t* stats);
 
+/* ---- posterior summaries on the device: moments of the trace without the trace ----------------
+ *
+ * What a caller of sample() looks at is mean +- std per parameter and the covariance between
+ * parameters; the trace that carries them is [ngenerations][N][D] doubles over PCIe.  A summary
+ * consumes the trace where the kernels write it, in device memory, and returns the moments.
+ *
+ * The definition is a fixed order of fp64 operations (no contraction), so the result is the same bits
+ * on every driver, for every chunk size, and whether the generations come in one call or in several.
+ * For one chain let r[g][i][k] be the row kabc_ais_advance would have put at out_samples[g][i][k], over
+ * the G generations of every kabc_ais_advance_summary call since kabc_ais_summary_begin, in order:
+ *   pivot      p[k] = r[0][0][k]
+ *   deviation  d[g][i][k] = r[g][i][k] - p[k]
+ *   per row i, from +0.0, sequentially in g:  S1[i][k] += d[g][i][k];  S2[i][k][l] += d[g][i][k] * d[g][i][l]
+ *              (l <= k; the product is rounded, then added);  mn[i][k] = r < mn ? r : mn;  mx likewise
+ *   row tree   for w = 1, 2, 4, ... < N: for every i that is a multiple of 2w with i + w < N:
+ *              A[i] += A[i + w] (min / max for mn / mx);  T = A[0]
+ *   n = G * N;  mean[k] = p[k] + T1[k] / n;  cov[k][l] = (T2[k][l] - (T1[k] * T1[l]) / n) / (n - 1)
+ * cov_mode KABC_SUMMARY_FULL keeps S2 for every l <= k (length(prior) <= KABC_MAX_DIM; beyond it
+ * KABC_ERR_UNSUPPORTED), KABC_SUMMARY_DIAG keeps l = k only (any length(prior)), KABC_SUMMARY_AUTO is FULL
+ * up to KABC_MAX_DIM parameters and DIAG beyond.  tests/ais_summary_oracle.py restates this in numpy. */
+#define KABC_SUMMARY_AUTO 0
+#define KABC_SUMMARY_FULL 1
+#define KABC_SUMMARY_DIAG 2
+/* Opens a summary on an initialised single-process handle (batch handles: one summary per chain): the
+ * accumulators come from the context's buffer pool and are zeroed.  On a handle whose summary is open it
+ * starts the summary over.  Sharded handles (kabc_ais_create_sharded with world > 1, kabc_ais_create_dist)
+ * have no streamed trace: KABC_ERR_INVALID_ARG. */
+kabc_status_t kabc_ais_summary_begin(kabc_ais_t* h, int32_t cov_mode);
+/* kabc_ais_advance with the trace folded into the open summary on the device: the same courses, counters,
+ * stats and cancel rules, no host buffer.  KABC_ERR_CANCELLED: the summary holds exactly the generations that
+ * completed.  Without an open summary: KABC_ERR_INVALID_STATE.  kabc_ais_advance itself keeps working while a
+ * summary is open and does not feed it. */
+kabc_status_t kabc_ais_advance_summary(kabc_ais_t* h, int64_t ngenerations, int32_t ntransitions,
+                                       kabc_stats_t* stats);
+/* Reads the summary (the accumulators stay: the summary can go on afterwards).  Every pointer may be NULL.
+ * *n = G * N; pivot, sum1 (T1), mean, mn, mx: [chain][D]; sum2 (T2) and cov: [chain][D][D], symmetric, for
+ * FULL and [chain][D] (the diagonal) for DIAG.  With no generation summarised yet: KABC_ERR_INVALID_STATE and
+ * every output is left untouched. */
+kabc_status_t kabc_ais_summary_get(kabc_ais_t* h, int64_t* n, double* pivot, double* sum1, double* sum2,
+                                   double* mean, double* cov, double* mn, double* mx);
+/* Closes the summary and hands its buffers back to the pool (kabc_ais_destroy does so too); no summary
+ * open: KABC_OK. */
+kabc_status_t kabc_ais_summary_end(kabc_ais_t* h);
+
 /* AISState (src/KissABC.jl:25-33) <-> host.  x: [N][D] unrounded positions in
  * walker-id order (owned rows only when sharded: [n_owned][D], half 0 rows
  * first); logprior, loglik: [N]; t = transitions done per walker. */

@@ -9,7 +9,7 @@ from ._cdefs import KABC_MAX_DIM
 from ._lib import Cancelled, Context, KabcError, LIB_PATH, default_context
 from .api import (ABCDE, ABCDE_batch, AIS, AisEnsemble, ApproxKernelizedPosterior, ApproxPosterior, CommonLogDensity,
                   MCMCThreads, abc_reject, abc_reject_batch, compile_model, pfilter, pfilter_batch, prior_predictive, set_specialize,
-                  AbcdeState, Particles, PfilterState, SmcState, sample, sample_batch, smc, smc_batch)
+                  AbcdeState, ChainSummaries, Particles, PfilterState, PosteriorSummary, SmcState, sample, sample_batch, smc, smc_batch)
 from . import comm
 from .comm import Comm, EnsembleGroup
 from .costs import DeviceCost
@@ -21,7 +21,7 @@ from .distributions import (Ar1Normal, Beta, Dirichlet, DiscreteUniform, Exponen
 __all__ = [
     "ABCDE", "ABCDE_batch", "AIS", "AisEnsemble", "ApproxKernelizedPosterior", "ApproxPosterior", "CommonLogDensity",
     "MCMCThreads", "abc_reject", "abc_reject_batch", "pfilter", "pfilter_batch", "prior_predictive",
-    "AbcdeState", "Particles", "PfilterState", "SmcState", "sample", "sample_batch", "smc", "smc_batch", "DeviceCost", "costs", "Factored", "Uniform", "Normal",
+    "AbcdeState", "ChainSummaries", "Particles", "PosteriorSummary", "PfilterState", "SmcState", "sample", "sample_batch", "smc", "smc_batch", "DeviceCost", "costs", "Factored", "Uniform", "Normal",
     "Truncated", "truncated", "TruncatedNormal", "Beta", "DiscreteUniform", "NegativeBinomial",
     "Exponential", "Gamma", "LogNormal", "Product", "MvNormal", "MultivariateNormal", "Context", "KabcError", "Cancelled", "default_context", "LIB_PATH",
     "KABC_MAX_DIM", "comm", "Comm", "EnsembleGroup", "UserInit", "InitFromSnippet",

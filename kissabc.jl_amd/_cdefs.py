@@ -26,6 +26,7 @@ PRIOR_USER = 100         # kinds >= this: families compiled at run time (kabc_co
 FAMILY_AIS, FAMILY_SMC, FAMILY_ABCDE, FAMILY_PFILTER, FAMILY_AIS_SMALL = 1, 2, 4, 8, 16
 
 POSTERIOR_KERNELIZED, POSTERIOR_THRESHOLD, POSTERIOR_COMMON = 1, 2, 3
+SUMMARY_AUTO, SUMMARY_FULL, SUMMARY_DIAG = 0, 1, 2   # kabc_ais_summary_begin's cov_mode
 
 # DeviceCost ids (include/kabc_costs.h)
 COST_GAUSS_DIST, COST_ROSENBROCK, COST_HIER_GAUSS_SIM, COST_NORMAL_MEANSTD_SIM, COST_DIRAC_SQ, \
@@ -205,6 +206,11 @@ PROTOTYPES = {
     "kabc_ais_half_generation": (C.c_int, [VP, C.c_int32, C.c_int32, VP]),
     "kabc_ais_end_generation": (C.c_int, [VP, C.c_int32]),
     "kabc_ais_advance": (C.c_int, [VP, C.c_int64, C.c_int32, c_double_p, C.POINTER(Stats)]),
+    "kabc_ais_summary_begin": (C.c_int, [VP, C.c_int32]),
+    "kabc_ais_advance_summary": (C.c_int, [VP, C.c_int64, C.c_int32, C.POINTER(Stats)]),
+    "kabc_ais_summary_get": (C.c_int, [VP, C.POINTER(C.c_int64), c_double_p, c_double_p, c_double_p,
+                                       c_double_p, c_double_p, c_double_p, c_double_p]),
+    "kabc_ais_summary_end": (C.c_int, [VP]),
     "kabc_ais_get_state": (C.c_int, [VP, c_double_p, c_double_p, c_double_p,
                                      C.POINTER(C.c_uint64)]),
     "kabc_ais_set_state": (C.c_int, [VP, c_double_p, c_double_p, c_double_p, C.c_uint64]),

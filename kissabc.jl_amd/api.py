@@ -61,6 +61,92 @@ class Particles:
         return f"{self.mean():.4g} ± {self.std():.2g}"
 
 
+class PosteriorSummary:
+    """Moments of an AIS trace, accumulated on the device instead of the trace (AisEnsemble.summary,
+    sample(..., summary=True); include/kabc.h gives the definition, operation by operation):
+
+        n                number of samples, generations x nparticles
+        mean, std        per parameter [D]
+        cov              [D][D] ("full"), or the variances [D] ("diag", beyond KABC_MAX_DIM parameters)
+        min, max         per parameter
+        pivot, sum1, sum2   the raw sums behind them: sums of (x - pivot) and of its products
+
+    On a batch handle every array has a leading chain axis and chain(c) gives chain c's own summary."""
+
+    def __init__(self, n, mean, cov, min, max, pivot=None, sum1=None, sum2=None, diag=False):
+        self.n, self.mean, self.cov, self.min, self.max = int(n), mean, cov, min, max
+        self.pivot, self.sum1, self.sum2, self.diag = pivot, sum1, sum2, bool(diag)
+
+    @property
+    def var(self):
+        return self.cov if self.diag else np.diagonal(self.cov, axis1=-2, axis2=-1)
+
+    @property
+    def std(self):
+        return np.sqrt(self.var)
+
+    @property
+    def nchains(self):
+        """chains on the leading axis, None for a single summary"""
+        return self.mean.shape[0] if self.mean.ndim == 2 else None
+
+    def chain(self, c):
+        if self.nchains is None:
+            raise ValueError("this summary holds one chain")
+        pick = lambda a: None if a is None else a[c]   # noqa: E731
+        return PosteriorSummary(self.n, self.mean[c], self.cov[c], self.min[c], self.max[c], pick(self.pivot),
+                                pick(self.sum1), pick(self.sum2), self.diag)
+
+    def isapprox(self, c, nsigma=2.0):
+        """Particles.isapprox per parameter: |mean - c| < nsigma * std, an array of bool"""
+        return np.abs(self.mean - np.asarray(c, dtype=np.float64)) < nsigma * self.std
+
+    def __repr__(self):
+        if self.nchains is not None:
+            return "[" + ",\n ".join(repr(self.chain(c)) for c in range(self.nchains)) + "]"
+        return "[" + ", ".join(f"{m:.4g} ± {sd:.2g}" for m, sd in zip(self.mean, self.std)) + "]"
+
+
+class ChainSummaries(list):
+    """sample(model, AIS(N), MCMCThreads(), Ns, Nc, summary=True): one PosteriorSummary per chain, `.pooled`
+    (the chains merged on the host, in chain order, from their n, mean and cov) and `.rhat` (Gelman-Rubin's
+    potential scale reduction per parameter, from the per-chain means and variances)."""
+
+    def __init__(self, chains):
+        super().__init__(chains)
+        self.pooled = _pool_summaries(self)
+        self.rhat = _rhat(self)
+
+
+def _pool_summaries(chains):
+    """the pairwise update of Chan, Golub & LeVeque, chain after chain: n, mean and the centred sum of
+    products M2 = cov * (n - 1)"""
+    c0 = chains[0]
+    n, mean, m2 = c0.n, np.array(c0.mean, dtype=np.float64), np.array(c0.cov, dtype=np.float64) * (c0.n - 1)
+    mn, mx = np.array(c0.min), np.array(c0.max)
+    for c in chains[1:]:
+        tot = n + c.n
+        delta = c.mean - mean
+        cross = delta * delta if c0.diag else np.outer(delta, delta)
+        m2 = m2 + c.cov * (c.n - 1) + cross * (n * c.n / tot)
+        mean = mean + delta * (c.n / tot)
+        n = tot
+        mn, mx = np.minimum(mn, c.min), np.maximum(mx, c.max)
+    return PosteriorSummary(n, mean, m2 / (n - 1), mn, mx, diag=c0.diag)
+
+
+def _rhat(chains):
+    """sqrt(((n - 1) / n * W + B / n) / W): W the mean of the chains' variances, B / n the variance of their
+    means; NaN with one chain"""
+    n = chains[0].n
+    means = np.stack([c.mean for c in chains])
+    W = np.mean(np.stack([c.var for c in chains]), axis=0)
+    if len(chains) < 2:
+        return np.full(means.shape[1], np.nan)
+    b_over_n = np.var(means, axis=0, ddof=1)
+    return np.sqrt(((n - 1) / n * W + b_over_n) / W)
+
+
 class _ApproxModel:
     posterior = 0
 
@@ -222,11 +308,23 @@ class AisEnsemble:
         return self
 
     # step(rng, model, spl, state; ntransitions) x N x ngenerations -- src/KissABC.jl:66-80
-    def advance(self, ngenerations, ntransitions=1, collect=False, out=None):
+    def advance(self, ngenerations, ntransitions=1, collect=False, out=None, summary=False):
         """`collect=True` returns the sample trace [generation][walker][D]
         ([generation][chain][walker][D] for a batch handle); `out` may supply its buffer
-        (C-contiguous float64, e.g. from _lib.pinned_empty)."""
+        (C-contiguous float64, e.g. from _lib.pinned_empty).  `summary=True` folds the trace into the
+        summary opened with summary_begin() on the device instead (kabc_ais_advance_summary): nothing is
+        returned, summary() reads the moments; it excludes `collect` and `out`."""
         lib = _lib.load()
+        if summary:
+            if collect or out is not None:
+                raise ValueError("advance: summary=True consumes the trace on the device; it excludes collect / out")
+            st = cd.Stats()
+            with self.ctx.interruptible():
+                status = lib.kabc_ais_advance_summary(self._h, int(ngenerations), int(ntransitions), C.byref(st))
+                self.last_stats = {"proposals": st.proposals, "cost_evals": st.cost_evals,
+                                   "accepted": st.accepted}
+                _lib.check(status)
+            return None
         ptr = None
         if collect or out is not None:
             shape = ((int(ngenerations), self.nchains, self.N, self.D) if self.batched
@@ -246,6 +344,34 @@ class AisEnsemble:
                                "accepted": st.accepted}
             _lib.check(status)
         return out
+
+    COV_MODES = {None: cd.SUMMARY_AUTO, "full": cd.SUMMARY_FULL, "diag": cd.SUMMARY_DIAG}
+
+    def summary_begin(self, cov=None):
+        """Opens (or starts over) the posterior summary of this handle: advance(..., summary=True) then
+        accumulates, summary() reads.  cov: "full" (the covariance matrix, up to KABC_MAX_DIM parameters),
+        "diag" (the variances, any length(prior)), None (full where it exists, else diag)."""
+        if cov not in self.COV_MODES:
+            raise ValueError(f'summary_begin: cov must be "full", "diag" or None, not {cov!r}')
+        _lib.check(_lib.load().kabc_ais_summary_begin(self._h, self.COV_MODES[cov]))
+        self._summary_diag = cov == "diag" or (cov is None and self.D > cd.KABC_MAX_DIM)
+        return self
+
+    def summary(self):
+        """The PosteriorSummary of the generations advanced with summary=True since summary_begin()."""
+        diag = getattr(self, "_summary_diag", False)
+        lead = (self.nchains,) if self.batched else ()
+        vec = lambda: np.empty(lead + (self.D,))                                  # noqa: E731
+        mat = lambda: np.empty(lead + ((self.D,) if diag else (self.D, self.D)))   # noqa: E731
+        n = C.c_int64()
+        pivot, sum1, mean, mn, mx, sum2, cov = vec(), vec(), vec(), vec(), vec(), mat(), mat()
+        p = lambda a: a.ctypes.data_as(cd.c_double_p)                             # noqa: E731
+        _lib.check(_lib.load().kabc_ais_summary_get(self._h, C.byref(n), p(pivot), p(sum1), p(sum2), p(mean),
+                                                    p(cov), p(mn), p(mx)))
+        return PosteriorSummary(n.value, mean, cov, mn, mx, pivot, sum1, sum2, diag)
+
+    def summary_end(self):
+        _lib.check(_lib.load().kabc_ais_summary_end(self._h))
 
     def half_generation(self, half, ntransitions, trace_ptr=None):
         _lib.check(_lib.load().kabc_ais_half_generation(
@@ -364,14 +490,21 @@ def _bundle(samples, scalar):
     return P[0] if (len(P) == 1 or scalar) else P
 
 
-def _sample_chains(model, N, Ns, seeds, costs, ntransitions, discard_initial, retry_sampling, ctx, ens=None):
+def _sample_chains(model, N, Ns, seeds, costs, ntransitions, discard_initial, retry_sampling, ctx, ens=None,
+                   summary=False):
     """len(seeds) independent chains of AIS(N) in ONE batch handle (costs: one DeviceCost per chain, or
     None; ens: that handle where the caller has created it, closed here): the first Ns samples of each,
-    [Nc][Ns][D], and the handle's driver"""
+    [Nc][Ns][D], and the handle's driver; summary: the chains' PosteriorSummary (leading chain axis) in place
+    of the samples"""
     Nc, D = len(seeds), len(model)
     if ens is None:
         ens = AisEnsemble(model, N, ctx=ctx, seeds=seeds, costs=costs)
     gk = max(1, -(-Ns // N))
+    if summary:
+        try:
+            return _summarise(ens, gk, N, ntransitions, discard_initial, retry_sampling), ens.driver
+        finally:
+            ens.close()
     big = gk * Nc * N * D * 8 > (1 << 20)   # (a small trace is not worth a helper thread: see sample)
     pool = concurrent.futures.ThreadPoolExecutor(1) if big else None
     buf = pool.submit(_lib.pinned_empty, (gk, Nc, N, D)) if big else None
@@ -391,17 +524,36 @@ def _sample_chains(model, N, Ns, seeds, costs, ntransitions, discard_initial, re
     return chains, driver
 
 
+def _summarise(ens, gk, N, ntransitions, discard_initial, retry_sampling):
+    """sample()'s course on `ens` with the kept generations summarised on the device"""
+    ens.init(retry_sampling)
+    gd = -(-int(discard_initial) // N)
+    if gd:
+        ens.advance(gd, ntransitions)
+    ens.summary_begin()
+    ens.advance(gk, ntransitions, summary=True)
+    return ens.summary()
+
+
 def sample(model, spl, *args, ntransitions=1, discard_initial=0, retry_sampling=100, seed=0,
-           progress=False, ctx=None, return_array=False, **kwargs):
+           progress=False, ctx=None, return_array=False, summary=False, **kwargs):
     """sample(model, AIS(N), Ns; ...) and sample(model, AIS(N), MCMCThreads(), Ns, Nc; ...).
 
     The device advances a whole generation (every walker `ntransitions` times) per
     launch pair and a generation yields the N samples the reference's N
     consecutive step() calls would emit (src/KissABC.jl:66-80), so
     ceil(discard_initial/N) generations are discarded and ceil(Ns/N) are kept.
+
+    `summary=True` returns a PosteriorSummary (mean, std, cov, min, max per parameter) accumulated on the
+    device in place of the samples: no trace crosses to the host.  It covers the ceil(Ns/N) kept generations
+    WHOLE, so its n = ceil(Ns/N) * N, which exceeds Ns where N does not divide it (the samples form keeps the
+    first Ns).  With MCMCThreads it returns a ChainSummaries: one PosteriorSummary per chain, `.pooled` and
+    `.rhat`.  It excludes return_array.
     """
     if not isinstance(spl, AIS):
         raise TypeError("sampler must be AIS(nparticles)")
+    if summary and return_array:
+        raise ValueError("sample: summary=True returns moments, not samples; it excludes return_array")
     if args and isinstance(args[0], MCMCThreads):
         # chains are a grid dimension of ONE device handle: every launch advances all Nc
         # ensembles (kabc_ais_create_batch); chain c is bit-identical to a single-chain run
@@ -418,6 +570,14 @@ def sample(model, spl, *args, ntransitions=1, discard_initial=0, retry_sampling=
             if e.status != cd.KABC_ERR_UNSUPPORTED:
                 raise
             ens = None
+        if summary:
+            if ens is not None:
+                both, _ = _sample_chains(model, spl.nparticles, Ns, seeds, None, ntransitions,
+                                         discard_initial, retry_sampling, ctx, ens=ens, summary=True)
+                return ChainSummaries(both.chain(c) for c in range(Nc))
+            return ChainSummaries(sample(model, spl, Ns, ntransitions=ntransitions, discard_initial=discard_initial,
+                                         retry_sampling=retry_sampling, seed=sd, ctx=ctx, summary=True)
+                                  for sd in seeds)
         if ens is not None:
             chains, _ = _sample_chains(model, spl.nparticles, Ns, seeds, None, ntransitions,
                                        discard_initial, retry_sampling, ctx, ens=ens)
@@ -432,6 +592,11 @@ def sample(model, spl, *args, ntransitions=1, discard_initial=0, retry_sampling=
     N = spl.nparticles
     ens = AisEnsemble(model, N, seed=seed, ctx=ctx)
     gk = max(1, -(-Ns // N))
+    if summary:
+        try:
+            return _summarise(ens, gk, N, ntransitions, discard_initial, retry_sampling)
+        finally:
+            ens.close()
     shape = (gk, N, len(model))
     # the page-locked trace buffer is allocated on a helper thread (pinning costs
     # ~40 us per MiB) while init and the discarded generations run on the device; a small
@@ -475,7 +640,7 @@ def _model_difference(m, m0):
 
 
 def sample_batch(model, spl, Ns, nruns=None, *, seeds=None, seed=0, ntransitions=1, discard_initial=0,
-                 retry_sampling=100, ctx=None, return_array=False, course=None):
+                 retry_sampling=100, ctx=None, return_array=False, course=None, summary=False):
     """One model fitted to many datasets, or one dataset under many seeds, in one call: run r is
     sample(model_r, spl, Ns, seed=seeds[r], <the same keywords>), bit for bit.
 
@@ -489,12 +654,15 @@ def sample_batch(model, spl, Ns, nruns=None, *, seeds=None, seed=0, ntransitions
     length(prior) -- beyond KABC_MAX_DIM it exists for built-in costs and prior families whose ensemble
     fits one workgroup's LDS (csrc/ais_dyn_small_kernel.hpp) -- and raises KabcError where the shape is
     refused; "sequential" forces the loop of sample() calls.  Same bits on either course.  Returns a list with one entry per run; its `.info` holds the course, the driver,
-    nruns and the wall time.  A failed initial draw raises KabcError("run r: <the reference's message>");
+    nruns and the wall time.  `summary=True` gives one PosteriorSummary per run in place of its samples, on
+    either course (sample's own summary=True: n = ceil(Ns/N) * N per run).  A failed initial draw raises KabcError("run r: <the reference's message>");
     Context.cancel() / Ctrl-C behave as they do for sample()."""
     if not isinstance(spl, AIS):
         raise TypeError("sampler must be AIS(nparticles)")
     if course not in (None, "grid", "sequential"):
         raise ValueError(f'sample_batch: course must be None, "grid" or "sequential", not {course!r}')
+    if summary and return_array:
+        raise ValueError("sample_batch: summary=True returns moments, not samples; it excludes return_array")
     if isinstance(model, _ApproxModel):
         if nruns is None:
             raise ValueError("sample_batch: nruns is required with a single model")
@@ -520,11 +688,12 @@ def sample_batch(model, spl, Ns, nruns=None, *, seeds=None, seed=0, ntransitions
         raise ValueError(f"sample_batch: len(seeds) = {len(seeds)} != nruns = {nruns}")
     Ns, N, D = int(Ns), spl.nparticles, len(m0)
     kw = dict(ntransitions=ntransitions, discard_initial=discard_initial, retry_sampling=retry_sampling)
+    skw = {"summary": True} if summary else {}
     t0 = time.perf_counter()
     chains, driver = None, None
     if course == "grid" or (course is None and D <= cd.KABC_MAX_DIM):
         try:
-            chains, driver = _sample_chains(m0, N, Ns, seeds, [m.cost for m in models], ctx=ctx, **kw)
+            chains, driver = _sample_chains(m0, N, Ns, seeds, [m.cost for m in models], ctx=ctx, **kw, **skw)
         except _lib.Cancelled:
             raise
         except _lib.KabcError as e:
@@ -534,14 +703,17 @@ def sample_batch(model, spl, Ns, nruns=None, *, seeds=None, seed=0, ntransitions
             if e.status != cd.KABC_ERR_UNSUPPORTED or course == "grid":
                 raise
             # (a shape the batch handle refuses: the runs one after another, each with sample()'s own checks)
-    if chains is not None:
+    if chains is not None and summary:
+        out = AisBatchResult(chains.chain(r) for r in range(nruns))
+        course = "grid"
+    elif chains is not None:
         out = AisBatchResult(c if return_array else _bundle(c, m0.scalar) for c in chains)
         course = "grid"
     else:
         out = AisBatchResult()
         for r, m in enumerate(models):
             try:
-                out.append(sample(m, spl, Ns, seed=seeds[r], ctx=ctx, return_array=return_array, **kw))
+                out.append(sample(m, spl, Ns, seed=seeds[r], ctx=ctx, return_array=return_array, **kw, **skw))
             except _lib.Cancelled:
                 raise
             except _lib.KabcError as e:

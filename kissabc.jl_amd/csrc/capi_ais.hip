@@ -14,6 +14,7 @@
 #include "ais_dyn_kernels.hpp"
 #include "ais_dyn_small_kernel.hpp"
 #include "ais_small_kernel.hpp"
+#include "ais_summary_kernel.hpp"
 #include "host_common.hpp"
 #include "plugin_registry.hpp"
 
@@ -237,6 +238,18 @@ struct kabc_ais {
     size_t aux_cap = 0;  // bytes
     // cancellation: the two block / interval events of a bounded queue (created at first need)
     hipEvent_t ev_blk[2] = {};
+    // posterior summary (kabc_ais_summary_begin, ais_summary_kernel.hpp): per-row accumulators
+    // [chain][slot][N], the pivot [chain][D], the row tree's two scratch levels and its result
+    // [chain][slot]; from the context's pool, zeroed by begin
+    DevBufs sum_bufs;
+    int32_t sum_mode = 0;           // 0: no summary open, else KABC_SUMMARY_FULL / KABC_SUMMARY_DIAG
+    int32_t sum_slots = 0;
+    int64_t sum_gens = 0;           // generations folded since begin
+    bool sum_pivot = false;         // the pivot has been taken
+    double* d_sum_acc = nullptr;
+    double* d_sum_pivot = nullptr;
+    double* d_sum_out = nullptr;
+    double* d_sum_lvl[2] = {};
     // debug records (tests)
     int32_t* d_dbg = nullptr;
     int64_t dbg_cap = 0;  // in int32 units
@@ -1336,9 +1349,37 @@ static kabc_status_t ensure_blk_events(kabc_ais_t* h) {
     return KABC_OK;
 }
 
-static kabc_status_t ais_small_run(kabc_ais_t* h, int64_t ngenerations, int32_t ntransitions, double* out_samples,
-                                   int64_t* last_gc, bool* cancelled) {
+// folds `gc` generations of a device trace block ([g][chain][N][D]) into the handle's open summary, behind
+// the kernels that wrote them on the handle's stream; `done`: device count of the generations that ran, or
+// NULL.  The first block since begin supplies the pivot: row 0 of its first generation, per chain.
+static kabc_status_t summary_fold(kabc_ais_t* h, const double* trace, int64_t gc, const int64_t* done) {
     hipStream_t s = h->ctx->stream;
+    if (!h->sum_pivot) {
+        KABC_HIP_CHECK(hipMemcpy2DAsync(h->d_sum_pivot, sizeof(double) * h->D, trace, sizeof(double) * h->N * h->D,
+                                        sizeof(double) * h->D, (size_t)h->nchains, hipMemcpyDeviceToDevice, s));
+        h->sum_pivot = true;
+    }
+    AisSummaryArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.trace = trace;
+    a.acc = h->d_sum_acc;
+    a.pivot = h->d_sum_pivot;
+    a.done = done;
+    a.N = h->N;
+    a.gc = gc;
+    a.D = h->D;
+    a.nchains = h->nchains;
+    a.nslots = h->sum_slots;
+    launch_ais_summary_accumulate(a, h->sum_mode == KABC_SUMMARY_FULL, s);
+    KABC_HIP_CHECK(hipGetLastError());
+    return KABC_OK;
+}
+
+// `summarise`: the trace block is folded into the handle's summary on the device (kabc_ais_advance_summary)
+static kabc_status_t ais_small_run(kabc_ais_t* h, int64_t ngenerations, int32_t ntransitions, double* out_samples,
+                                   int64_t* last_gc, bool* cancelled, bool summarise = false) {
+    hipStream_t s = h->ctx->stream;
+    const bool tracing = out_samples || summarise;
     const int64_t gen_elems = h->N * h->D * h->nchains;  // [chain][N][D] per generation
     const size_t gen_bytes = sizeof(double) * (size_t)gen_elems;
     const int64_t upg = ais_small_units_per_gen(h, ntransitions);
@@ -1352,7 +1393,7 @@ static kabc_status_t ais_small_run(kabc_ais_t* h, int64_t ngenerations, int32_t 
     if (poll_every < 1) poll_every = 1;
     if (poll_every > (1 << 30)) poll_every = 1 << 30;
     *last_gc = 0;
-    if (out_samples) {  // (KABC_TRACE_CHUNK_MIB: tuning / tests, force several blocks)
+    if (tracing) {  // (KABC_TRACE_CHUNK_MIB: tuning / tests, force several blocks)
         const size_t target = env_bytes("KABC_TRACE_CHUNK_MIB", 1 << 20, (size_t)64 << 20);
         const int64_t fit = (int64_t)(target / gen_bytes);
         if (fit < block) block = fit;
@@ -1370,7 +1411,7 @@ static kabc_status_t ais_small_run(kabc_ais_t* h, int64_t ngenerations, int32_t 
     if (block > ngenerations) block = ngenerations;
     if (auxW)
         if (kabc_status_t st = grow(h, &h->d_aux, &h->aux_cap, aux_gen_bytes * (size_t)block)) return st;
-    if (out_samples)
+    if (tracing)
         if (kabc_status_t st = grow(h, &h->d_strace, &h->strace_cap, gen_bytes * (size_t)block)) return st;
     const bool blocks = ngenerations > block;
     if (blocks && !dev_poll)
@@ -1405,7 +1446,7 @@ static kabc_status_t ais_small_run(kabc_ais_t* h, int64_t ngenerations, int32_t 
                 q.rows[hf] = (int32_t)h->rows[hf];
                 q.id_base[hf] = h->id_base[hf];
             }
-            q.trace = out_samples ? h->d_strace : nullptr;
+            q.trace = tracing ? h->d_strace : nullptr;
             // debug records: [N][nt][6] in walker order (those of the block's last generation remain)
             q.dbg = (h->d_dbg && h->N * (int64_t)ntransitions * 6 <= h->dbg_cap) ? h->d_dbg : nullptr;
             q.t0 = h->t;
@@ -1436,6 +1477,9 @@ static kabc_status_t ais_small_run(kabc_ais_t* h, int64_t ngenerations, int32_t 
         if (out_samples)
             KABC_HIP_CHECK(hipMemcpyAsync(out_samples + g0 * gen_elems, h->d_strace, gen_bytes * (size_t)gc,
                                           hipMemcpyDeviceToHost, s));
+        if (summarise)  // (a block the kernel left early on a cancel: exactly the generations it ran)
+            if (kabc_status_t st = summary_fold(h, h->d_strace, gc, dev_poll ? &h->d_counters->small_done : nullptr))
+                return st;
         if (blocks && !dev_poll) KABC_HIP_CHECK(hipEventRecord(h->ev_blk[nblk & 1], s));
         h->t += (uint64_t)gc * (uint64_t)ntransitions;
         *last_gc = dev_poll ? gc : 0;
@@ -1710,6 +1754,46 @@ static kabc_status_t ais_stream_run(kabc_ais_t* h, int64_t ngenerations, int32_t
     return KABC_OK;
 }
 
+// The half-generation course of kabc_ais_advance_summary: the kernels write a chunk of generations into one
+// device buffer (as the streamed-trace course does) and launch_ais_summary_accumulate folds it behind them on
+// the same stream -- no copy, no drain thread, no rotation: the next chunk's kernels are ordered after the fold.
+// A fold reads and writes every accumulator once, nslots / D generations' worth of trace each way (7.5 at
+// D = 8 "full"); the default chunk of 32 generations, within 4..256 MiB of trace, keeps that below half a
+// generation's trace traffic per generation there.  tools/ais_summary_probe.py measures the course.
+static kabc_status_t ais_summary_half_run(kabc_ais_t* h, int64_t ngenerations, int32_t ntransitions,
+                                          bool* cancelled) {
+    hipStream_t s = h->ctx->stream;
+    const int64_t gen_elems = h->N * h->D * h->nchains;  // [chain][N][D] per generation
+    const size_t gen_bytes = sizeof(double) * (size_t)gen_elems;
+    InflightBound ib(h, ntransitions);
+    size_t target = gen_bytes * 32;
+    if (target < (4ull << 20)) target = 4ull << 20;
+    if (target > (256ull << 20)) target = 256ull << 20;
+    target = env_bytes("KABC_TRACE_CHUNK_MIB", 1 << 20, target);  // tuning / tests
+    int64_t chunk = (int64_t)(target / gen_bytes);
+    if (chunk < 1) chunk = 1;
+    if (chunk > ngenerations) chunk = ngenerations;
+    if (kabc_status_t st = grow(h, &h->d_trace[0], &h->trace_cap[0], gen_bytes * (size_t)chunk)) return st;
+    for (int64_t g0 = 0; g0 < ngenerations && !*cancelled; g0 += chunk) {
+        const int64_t gc = ngenerations - g0 < chunk ? ngenerations - g0 : chunk;
+        int64_t g = 0;
+        for (; g < gc; ++g) {
+            if (cancel_pending(h->ctx)) {  // (h->t counts the generations enqueued)
+                *cancelled = true;
+                break;
+            }
+            double* tr0 = h->d_trace[0] + g * gen_elems;
+            if (kabc_status_t st = kabc_ais_half_generation(h, 0, ntransitions, tr0)) return st;
+            if (kabc_status_t st = kabc_ais_half_generation(h, 1, ntransitions, tr0 + h->rows[0] * h->D)) return st;
+            h->t += (uint64_t)ntransitions;
+            if (kabc_status_t st = ib.generation_enqueued(s)) return st;
+        }
+        if (g > 0)
+            if (kabc_status_t st = summary_fold(h, h->d_trace[0], g, nullptr)) return st;
+    }
+    return KABC_OK;
+}
+
 // What every course of kabc_ais_advance ends with, and kabc_ais_advance_multi for each of its handles: the
 // counters read back and checked, the generations the one-workgroup kernel did not run (it saw a cancel:
 // small_gc > small_done) taken back, the stats of the call, the cancel verdict.
@@ -1782,6 +1866,164 @@ kabc_status_t kabc_ais_advance(kabc_ais_t* h, int64_t ngenerations, int32_t ntra
         st = ais_half_run(h, ngenerations, ntransitions, &cancelled);
     if (st) return st;
     return ais_advance_end(h, ntransitions, small_gc, cancelled, stats);
+}
+
+// ---- posterior summaries on the device (ais_summary_kernel.hpp) --------------------------------------
+
+// what every summary entry point asks of its handle; `open`: a summary must have been begun
+static kabc_status_t summary_check(const kabc_ais_t* h, const char* who, bool open) {
+    if (check_handle(h)) return KABC_ERR_INVALID_ARG;
+    if (h->world != 1 || h->comm) {
+        set_error("%s: a sharded ensemble has no streamed trace, and so no summary of one", who);
+        return KABC_ERR_INVALID_ARG;
+    }
+    if (!h->initialised) {
+        set_error("%s: kabc_ais_init / kabc_ais_set_state has not been called", who);
+        return KABC_ERR_INVALID_STATE;
+    }
+    if (open && !h->sum_mode) {
+        set_error("%s: no summary is open on this handle (kabc_ais_summary_begin)", who);
+        return KABC_ERR_INVALID_STATE;
+    }
+    return KABC_OK;
+}
+
+static void summary_release(kabc_ais_t* h) {
+    h->sum_bufs.release();
+    h->d_sum_acc = h->d_sum_pivot = h->d_sum_out = h->d_sum_lvl[0] = h->d_sum_lvl[1] = nullptr;
+    h->sum_mode = h->sum_slots = 0;
+    h->sum_gens = 0;
+    h->sum_pivot = false;
+}
+
+kabc_status_t kabc_ais_summary_begin(kabc_ais_t* h, int32_t cov_mode) {
+    if (kabc_status_t st = summary_check(h, "kabc_ais_summary_begin", false)) return st;
+    if (cov_mode != KABC_SUMMARY_AUTO && cov_mode != KABC_SUMMARY_FULL && cov_mode != KABC_SUMMARY_DIAG) {
+        set_error("kabc_ais_summary_begin: cov_mode %d is none of KABC_SUMMARY_AUTO, _FULL, _DIAG", cov_mode);
+        return KABC_ERR_INVALID_ARG;
+    }
+    if (cov_mode == KABC_SUMMARY_FULL && h->D > KABC_MAX_DIM) {
+        set_error("kabc_ais_summary_begin: the \"full\" covariance is kept up to %d parameters; length(prior) = %d "
+                  "takes \"diag\" (the variances)", KABC_MAX_DIM, h->D);
+        return KABC_ERR_UNSUPPORTED;
+    }
+    const int32_t mode = cov_mode != KABC_SUMMARY_AUTO ? cov_mode
+                         : h->D <= KABC_MAX_DIM        ? KABC_SUMMARY_FULL
+                                                       : KABC_SUMMARY_DIAG;
+    const int nslots = ais_summary_slots(h->D, mode == KABC_SUMMARY_FULL);
+    const int64_t nseries = (int64_t)h->nchains * nslots;
+    const int64_t t1 = (h->N + kSumTile - 1) / kSumTile, t2 = (t1 + kSumTile - 1) / kSumTile;
+    if (nseries * t1 >= (1ll << 31)) {  // (the row tree's grid)
+        set_error("kabc_ais_summary_begin: %d chains x %d accumulators x %lld walkers is beyond the summary's "
+                  "launch grid", h->nchains, nslots, (long long)h->N);
+        return KABC_ERR_UNSUPPORTED;
+    }
+    KABC_HIP_CHECK(hipSetDevice(h->ctx->device));
+    hipStream_t s = h->ctx->stream;
+    if (h->sum_mode) {  // (begin again: the summary starts over; its buffers may still be read by queued work)
+        KABC_HIP_CHECK(hipStreamSynchronize(s));
+        summary_release(h);
+    }
+    h->sum_bufs.ctx = h->ctx;
+    hipError_t e = h->sum_bufs.alloc(&h->d_sum_acc, (size_t)nseries * (size_t)h->N);
+    if (e == hipSuccess) e = h->sum_bufs.alloc(&h->d_sum_pivot, (size_t)h->nchains * (size_t)h->D);
+    if (e == hipSuccess) e = h->sum_bufs.alloc(&h->d_sum_out, (size_t)nseries);
+    if (e == hipSuccess) e = h->sum_bufs.alloc(&h->d_sum_lvl[0], (size_t)(nseries * t1));
+    if (e == hipSuccess) e = h->sum_bufs.alloc(&h->d_sum_lvl[1], (size_t)(nseries * t2));
+    if (e != hipSuccess) {
+        summary_release(h);
+        KABC_HIP_CHECK(e);
+    }
+    launch_ais_summary_init(h->d_sum_acc, h->N, h->D, nslots, h->nchains, s);
+    KABC_HIP_CHECK(hipGetLastError());
+    h->sum_mode = mode;
+    h->sum_slots = nslots;
+    return KABC_OK;
+}
+
+kabc_status_t kabc_ais_advance_summary(kabc_ais_t* h, int64_t ngenerations, int32_t ntransitions,
+                                       kabc_stats_t* stats) {
+    if (kabc_status_t st = summary_check(h, "kabc_ais_advance_summary", true)) return st;
+    if (ngenerations < 0 || ntransitions < 1) {
+        set_error("ngenerations must be >= 0 and ntransitions >= 1");
+        return KABC_ERR_INVALID_ARG;
+    }
+    // (a pending cancel request ends the call before it launches anything, as in kabc_ais_advance)
+    if (cancel_take(h->ctx)) return KABC_ERR_CANCELLED;
+    KABC_HIP_CHECK(hipSetDevice(h->ctx->device));
+    // the courses of kabc_ais_advance with a trace, the trace consumed on the device
+    bool cancelled = false;
+    int64_t small_gc = 0;
+    const uint64_t t0 = h->t;
+    kabc_status_t st = KABC_OK;
+    if (h->small_ok && ngenerations > 0 && ais_small_units_per_gen(h, ntransitions) <= (1ll << 30))
+        st = ais_small_run(h, ngenerations, ntransitions, nullptr, &small_gc, &cancelled, true);
+    else if (ngenerations > 0)
+        st = ais_summary_half_run(h, ngenerations, ntransitions, &cancelled);
+    if (st == KABC_OK) st = ais_advance_end(h, ntransitions, small_gc, cancelled, stats);
+    // (h->t is that of the generations that ran, a cancelled call's included: the ones the summary holds)
+    h->sum_gens += (int64_t)((h->t - t0) / (uint64_t)ntransitions);
+    return st;
+}
+
+kabc_status_t kabc_ais_summary_get(kabc_ais_t* h, int64_t* n, double* pivot, double* sum1, double* sum2,
+                                   double* mean, double* cov, double* mn, double* mx) {
+    if (kabc_status_t st = summary_check(h, "kabc_ais_summary_get", true)) return st;
+    if (h->sum_gens == 0) {
+        set_error("kabc_ais_summary_get: the summary holds no generation yet (n = 0)");
+        return KABC_ERR_INVALID_STATE;
+    }
+    KABC_HIP_CHECK(hipSetDevice(h->ctx->device));
+    hipStream_t s = h->ctx->stream;
+    const int D = h->D, ns = h->sum_slots;
+    const bool full = h->sum_mode == KABC_SUMMARY_FULL;
+    const size_t nch = (size_t)h->nchains;
+    launch_ais_summary_reduce(h->d_sum_acc, h->d_sum_out, h->d_sum_lvl[0], h->d_sum_lvl[1], h->N, D, ns,
+                              (int64_t)nch * ns, s);
+    KABC_HIP_CHECK(hipGetLastError());
+    std::vector<double> T(nch * (size_t)ns), P(nch * (size_t)D);
+    KABC_HIP_CHECK(hipMemcpyAsync(T.data(), h->d_sum_out, sizeof(double) * T.size(), hipMemcpyDeviceToHost, s));
+    KABC_HIP_CHECK(hipMemcpyAsync(P.data(), h->d_sum_pivot, sizeof(double) * P.size(), hipMemcpyDeviceToHost, s));
+    KABC_HIP_CHECK(hipStreamSynchronize(s));
+    const int64_t cnt = h->sum_gens * h->N;
+    const double dn = (double)cnt, dn1 = (double)(cnt - 1);
+    if (n) *n = cnt;
+    const size_t w2 = full ? (size_t)D * D : (size_t)D;  // doubles of sum2 / cov per chain
+    for (size_t c = 0; c < nch; ++c) {
+        const double* t = T.data() + c * (size_t)ns;
+        const double* t2 = t + 3 * D;
+        for (int k = 0; k < D; ++k) {
+            if (pivot) pivot[c * D + k] = P[c * D + k];
+            if (sum1) sum1[c * D + k] = t[k];
+            if (mn) mn[c * D + k] = t[D + k];
+            if (mx) mx[c * D + k] = t[2 * D + k];
+            if (mean) {
+                const double q = t[k] / dn;
+                mean[c * D + k] = P[c * D + k] + q;
+            }
+            for (int l = 0; l <= (full ? k : 0); ++l) {
+                const int ll = full ? l : k;
+                const double s2 = full ? t2[k * (k + 1) / 2 + l] : t2[k];
+                const double pr = t[k] * t[ll];
+                const double q = pr / dn;
+                const double v = (s2 - q) / dn1;
+                const size_t i0 = full ? c * w2 + (size_t)k * D + l : c * w2 + k;
+                const size_t i1 = full ? c * w2 + (size_t)l * D + k : i0;
+                if (sum2) sum2[i0] = sum2[i1] = s2;
+                if (cov) cov[i0] = cov[i1] = v;
+            }
+        }
+    }
+    return KABC_OK;
+}
+
+kabc_status_t kabc_ais_summary_end(kabc_ais_t* h) {
+    if (check_handle(h)) return KABC_ERR_INVALID_ARG;
+    if (!h->sum_mode) return KABC_OK;
+    KABC_HIP_CHECK(hipSetDevice(h->ctx->device));
+    KABC_HIP_CHECK(hipStreamSynchronize(h->ctx->stream));  // (queued folds still read the buffers)
+    summary_release(h);
+    return KABC_OK;
 }
 
 kabc_status_t kabc_ais_advance_multi(kabc_ais_t** hs, int32_t n, int64_t ngenerations,
@@ -2122,6 +2364,7 @@ kabc_status_t kabc_ais_destroy(kabc_ais_t* h) {
     if (h->d_dbg) (void)hipFree(h->d_dbg);
     if (h->d_aux) (void)hipFree(h->d_aux);
     if (h->d_strace) (void)hipFree(h->d_strace);
+    summary_release(h);  // (back to the context's pool)
     timing_release(h);
     delete h;
     return KABC_OK;
