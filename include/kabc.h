@@ -718,9 +718,26 @@ kabc_status_t kabc_ais_summary_get(kabc_ais_t* h, int64_t* n, double* pivot, dou
  * open: KABC_OK. */
 kabc_status_t kabc_ais_summary_end(kabc_ais_t* h);
 
+/* ---- the range of the stream counters -----------------------------------------------------------
+ * Every draw is keyed by a 64-bit counter (include/kabc_philox.h) of which the stream address holds the
+ * low 56 bits: 32 in counter word 1, 24 next to the domain byte in word 3.  A counter of 2^56 + c would
+ * replay the streams of c, so every entry point that takes a counter, or would count past the limit,
+ * answers KABC_ERR_INVALID_ARG before anything is launched:
+ *   AIS     the transition counter t: kabc_ais_set_state with t >= KABC_COUNTER_LIMIT; kabc_ais_advance,
+ *           kabc_ais_advance_summary, kabc_ais_advance_multi and kabc_ais_end_generation when
+ *           t + ngenerations * ntransitions would exceed KABC_COUNTER_LIMIT
+ *   smc     kabc_smc_state_t.pass >= KABC_COUNTER_LIMIT, and a call whose remaining iterations
+ *           (max_iterations - from->iteration, each of up to 1 + mcmc_retrys passes) could count past it
+ *   ABCDE   kabc_abcde_state_t.generation >= KABC_COUNTER_LIMIT, and opts->generations > KABC_COUNTER_LIMIT
+ *   pfilter the counter is (iteration << 24) | attempt: kabc_pfilter_state_t.iteration >=
+ *           KABC_PFILTER_ITERATION_LIMIT.  A run is not refused for where it could end: max_iters may be
+ *           infinite; 2^32 iterations are out of any run's reach. */
+#define KABC_COUNTER_LIMIT (1ull << 56)
+#define KABC_PFILTER_ITERATION_LIMIT (1ull << 32)
+
 /* AISState (src/KissABC.jl:25-33) <-> host.  x: [N][D] unrounded positions in
  * walker-id order (owned rows only when sharded: [n_owned][D], half 0 rows
- * first); logprior, loglik: [N]; t = transitions done per walker. */
+ * first); logprior, loglik: [N]; t = transitions done per walker, below KABC_COUNTER_LIMIT. */
 kabc_status_t kabc_ais_get_state(kabc_ais_t* h, double* x, double* logprior, double* loglik,
                                  uint64_t* t);
 kabc_status_t kabc_ais_set_state(kabc_ais_t* h, const double* x, const double* logprior,
@@ -918,7 +935,8 @@ typedef struct kabc_smc_state {
     int32_t reserved;
     uint64_t seed;       /* of the run that left the state (informative)                       */
     int64_t iteration;   /* iterations completed; -1: the run that was to fill the state failed */
-    uint64_t pass;       /* global pass counter = transition counter of the streams            */
+    uint64_t pass;       /* global pass counter = transition counter of the streams, below     */
+                         /* KABC_COUNTER_LIMIT (2^56)                                           */
     double eps;          /* ϵ after the last completed iteration (Inf at iteration 0)          */
     double eps_prev;     /* ϵv                                                                  */
     uint64_t accepted;   /* accepted[] of the last completed iteration                          */
@@ -949,7 +967,7 @@ int64_t kabc_smc_state_sizeof(void);
  *           goes on, and a run stopped by max_iterations or a cancel goes on.
  * KABC_ERR_INVALID_ARG, before anything is launched: a NULL array in a state, from->nparticles !=
  * opts->nparticles, from->D != D, from->iteration < 0, from->n_alive != the number of nonzero
- * alive[i], `to` sharing its struct or an array with `from`.  Single GPU only: kabc_smc_run_dist, kabc_smc_run_dist_mode and kabc_smc_run_batch
+ * alive[i], from->pass at or (with the passes this call may run) beyond KABC_COUNTER_LIMIT, `to` sharing its struct or an array with `from`.  Single GPU only: kabc_smc_run_dist, kabc_smc_run_dist_mode and kabc_smc_run_batch
  * take no state. */
 kabc_status_t kabc_smc_run_from(kabc_ctx_t* ctx, const kabc_prior_t* prior, int32_t D,
                                 const kabc_cost_t* cost, const kabc_smc_opts_t* opts,
@@ -1089,7 +1107,8 @@ typedef struct kabc_abcde_state {
     int32_t D;
     int32_t reserved;
     uint64_t seed;       /* of the run that left the state (informative)                              */
-    int64_t generation;  /* generations whose moves have run = the generation counter of the streams; */
+    int64_t generation;  /* generations whose moves have run = the generation counter of the streams, */
+                         /* below KABC_COUNTER_LIMIT (2^56);                                           */
                          /* -1: the run that was to fill the state failed.  A run that ended in the    */
                          /* earlystop break reports generations_run = generation + 1: the reference    */
                          /* counts the breaking iteration (:373 before :379), which draws nothing     */
@@ -1110,7 +1129,8 @@ int64_t kabc_abcde_state_sizeof(void);
  *           result).  A run that ended in the earlystop break, continued with the same options, takes
  *           the break again and reports the same generations_run; with a smaller eps_target it goes on.
  * KABC_ERR_INVALID_ARG, before anything is launched: a NULL array in a state, from->nparticles !=
- * opts->nparticles, from->D != D, from->generation < 0, a cost[i] or logprior[i] that is not finite (the
+ * opts->nparticles, from->D != D, from->generation < 0 or >= KABC_COUNTER_LIMIT, opts->generations >
+ * KABC_COUNTER_LIMIT, a cost[i] or logprior[i] that is not finite (the
  * invariant of :354-366), `to` sharing its struct or an array with `from`.  Single GPU, single run:
  * kabc_abcde_run_batch takes no state. */
 kabc_status_t kabc_abcde_run_from(kabc_ctx_t* ctx, const kabc_prior_t* prior, int32_t D,
@@ -1195,7 +1215,8 @@ typedef struct kabc_pfilter_state {
     int32_t reserved;
     uint64_t seed;       /* of the run that left the state (informative)                              */
     int64_t iteration;   /* iterations completed; 0: the initial draw; -1: the run that was to fill   */
-                         /* the state failed                                                           */
+                         /* the state failed.  Below KABC_PFILTER_ITERATION_LIMIT (2^32): the stream   */
+                         /* counter is (iteration << 24) | attempt                                     */
     double eps;          /* ϵ of the last completed iteration (Inf at iteration 0)                    */
     double eff;          /* eff of the last completed iteration (NaN at iteration 0)                  */
     uint64_t nreps;      /* cumulative                                                                 */
@@ -1217,7 +1238,7 @@ int64_t kabc_pfilter_state_sizeof(void);
  *           continued with the same options stays as it is; with a smaller epstol or eff_tol, or a
  *           larger max_iters, it goes on.
  * KABC_ERR_INVALID_ARG, before anything is launched: a NULL array in a state, from->nparticles != the
- * effective N, from->D != D, from->iteration < 0, a cost[i] or logprior[i] that is not finite (the
+ * effective N, from->D != D, from->iteration < 0 or >= KABC_PFILTER_ITERATION_LIMIT, a cost[i] or logprior[i] that is not finite (the
  * invariant of :283-294), `to` sharing its struct or an array with `from`.  Single GPU, single run:
  * kabc_pfilter_run_batch takes no state. */
 kabc_status_t kabc_pfilter_run_from(kabc_ctx_t* ctx, const kabc_prior_t* prior, int32_t D,

@@ -14,6 +14,11 @@
  *
  *   key     = (seed lo32, seed hi32)
  *   counter = (walker id, transition counter t lo32, slot, domain | t hi24 << 8)
+ *
+ * The address holds the low 56 bits of t: bits 56..63 fall off the end of word 3, so t and t + 2^56
+ * name the same stream.  The entry points that take or advance a counter refuse one at or beyond
+ * KABC_COUNTER_LIMIT = 2^56 (include/kabc.h, "the range of the stream counters"); pfilter's
+ * t = (iteration << 24) | attempt stays below it for iteration < 2^32.
  */
 #ifndef KABC_PHILOX_H
 #define KABC_PHILOX_H

@@ -433,6 +433,9 @@ kabc_status_t abcde_check_state(const kabc_abcde_state_t* f, const kabc_abcde_st
     if (f->nparticles != o->nparticles) return bad("the state's nparticles differs from opts->nparticles");
     if (f->D != D) return bad("the state's D differs from the call's");
     if (f->generation < 0) return bad("the state's generation is negative (a failed run leaves -1)");
+    // the generation counter is the transition counter of the streams, whose address holds 56 bits of it (kabc.h)
+    if ((uint64_t)f->generation >= KABC_COUNTER_LIMIT) return bad("the state's generation must be below 2^56 (the random streams hold 56 bits of it)");
+    if (o->generations > 0 && (uint64_t)o->generations > KABC_COUNTER_LIMIT) return bad("generations must be at most 2^56 (the random streams hold 56 bits of the generation counter)");
     for (int64_t i = 0; i < f->nparticles; ++i)  // (the invariant the initial draw leaves, :354-366)
         if (!std::isfinite(f->cost[i]) || !std::isfinite(f->logprior[i]))
             return bad("the state holds a cost or a log-prior that is not finite");

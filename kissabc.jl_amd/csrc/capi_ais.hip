@@ -787,6 +787,17 @@ static int64_t enqueue_aux(kabc_ais_t* h, int half, int64_t row_first, int64_t r
     return x.stride_aux;
 }
 
+// the transition counter stays below KABC_COUNTER_LIMIT (include/kabc.h): the stream address holds 56 bits of it
+static kabc_status_t counter_room(const kabc_ais_t* h, int64_t ngenerations, int32_t ntransitions, const char* who) {
+    const uint64_t room = KABC_COUNTER_LIMIT - h->t;  // (h->t < the limit: kabc_ais_set_state, and this test)
+    if (ngenerations > 0 && ntransitions > 0 && (uint64_t)ngenerations > room / (uint64_t)ntransitions) {
+        set_error("%s: the transition counter t = %llu would pass 2^56 (the random streams hold 56 bits of it)", who,
+                  (unsigned long long)h->t);
+        return KABC_ERR_INVALID_ARG;
+    }
+    return KABC_OK;
+}
+
 extern "C" {
 
 kabc_status_t kabc_ais_create(kabc_ctx_t* ctx, const kabc_model_t* model, int64_t nparticles,
@@ -1303,6 +1314,7 @@ kabc_status_t kabc_ais_half_generation(kabc_ais_t* h, int32_t half, int32_t ntra
         set_error("half must be 0/1 and ntransitions >= 1");
         return KABC_ERR_INVALID_ARG;
     }
+    if (kabc_status_t st = counter_room(h, 1, ntransitions, "kabc_ais_half_generation")) return st;
     for (const kabc_ais::Seg& sg : h->seg[half])
         if (kabc_status_t st = launch_half_seg(h, half, sg, ntransitions, (double*)dev_trace_rows))
             return st;
@@ -1311,6 +1323,7 @@ kabc_status_t kabc_ais_half_generation(kabc_ais_t* h, int32_t half, int32_t ntra
 
 kabc_status_t kabc_ais_end_generation(kabc_ais_t* h, int32_t ntransitions) {
     if (check_handle(h)) return KABC_ERR_INVALID_ARG;
+    if (kabc_status_t st = counter_room(h, 1, ntransitions, "kabc_ais_end_generation")) return st;
     h->t += (uint64_t)ntransitions;
     return KABC_OK;
 }
@@ -1849,6 +1862,7 @@ kabc_status_t kabc_ais_advance(kabc_ais_t* h, int64_t ngenerations, int32_t ntra
         set_error("kabc_ais_init / kabc_ais_set_state has not been called");
         return KABC_ERR_INVALID_STATE;
     }
+    if (kabc_status_t st = counter_room(h, ngenerations, ntransitions, "kabc_ais_advance")) return st;
     // kabc_ctx_cancel (single-process handles; a sharded handle does not poll: kabc.h): a pending request
     // ends the call before it launches anything
     if (!h->comm && cancel_take(h->ctx)) return KABC_ERR_CANCELLED;
@@ -1948,6 +1962,7 @@ kabc_status_t kabc_ais_advance_summary(kabc_ais_t* h, int64_t ngenerations, int3
         set_error("ngenerations must be >= 0 and ntransitions >= 1");
         return KABC_ERR_INVALID_ARG;
     }
+    if (kabc_status_t st = counter_room(h, ngenerations, ntransitions, "kabc_ais_advance_summary")) return st;
     // (a pending cancel request ends the call before it launches anything, as in kabc_ais_advance)
     if (cancel_take(h->ctx)) return KABC_ERR_CANCELLED;
     KABC_HIP_CHECK(hipSetDevice(h->ctx->device));
@@ -2038,6 +2053,7 @@ kabc_status_t kabc_ais_advance_multi(kabc_ais_t** hs, int32_t n, int64_t ngenera
             set_error("kabc_ais_init_multi has not been called");
             return KABC_ERR_INVALID_STATE;
         }
+        if (kabc_status_t st = counter_room(hs[i], ngenerations, ntransitions, "kabc_ais_advance_multi")) return st;
     }
     const int xk = hs[0]->xk;
     kabc_comm_t* comms[KABC_COMM_MAX_WORLD];
@@ -2149,6 +2165,11 @@ kabc_status_t kabc_ais_set_state(kabc_ais_t* h, const double* x, const double* l
     if (check_handle(h)) return KABC_ERR_INVALID_ARG;
     if (!x || !logprior || !loglik) {
         set_error("kabc_ais_set_state: NULL buffer");
+        return KABC_ERR_INVALID_ARG;
+    }
+    if (t >= KABC_COUNTER_LIMIT) {
+        set_error("kabc_ais_set_state: t = %llu, the transition counter must be below 2^56 (the random streams hold "
+                  "56 bits of it)", (unsigned long long)t);
         return KABC_ERR_INVALID_ARG;
     }
     KABC_HIP_CHECK(hipSetDevice(h->ctx->device));

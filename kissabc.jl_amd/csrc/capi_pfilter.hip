@@ -111,6 +111,8 @@ static kabc_status_t pf_check_state(const PfMode& mode, int32_t D, const kabc_pf
         return bad("the state's nparticles differs from the effective N, kabc_pfilter_nparticles(opts->nparticles, q, D)");
     if (f->D != D) return bad("the state's D differs from the call's");
     if (f->iteration < 0) return bad("the state's iteration is negative (a failed run leaves -1)");
+    // the streams' counter is (iteration << 24) | attempt, and their address holds 56 bits of it (kabc.h)
+    if ((uint64_t)f->iteration >= KABC_PFILTER_ITERATION_LIMIT) return bad("the state's iteration must be below 2^32 (the random streams hold 32 bits of it)");
     for (int64_t i = 0; i < f->nparticles; ++i)  // (the invariant the initial draw leaves, :283-294)
         if (!std::isfinite(f->cost[i]) || !std::isfinite(f->logprior[i]))
             return bad("the state holds a cost or a log-prior that is not finite");

@@ -1476,6 +1476,15 @@ kabc_status_t check_state(const SmcMode& mode, int32_t D, const kabc_smc_opts_t*
     int64_t n = 0;
     for (int64_t i = 0; i < f->nparticles; ++i) n += f->alive[i] != 0;
     if (n != f->n_alive) return bad("the state's n_alive is not the number of alive particles");
+    // the pass counter is the transition counter of the streams, whose address holds 56 bits of it (kabc.h)
+    if (f->pass >= KABC_COUNTER_LIMIT) return bad("the state's pass counter must be below 2^56 (the random streams hold 56 bits of it)");
+    {
+        const int64_t max_it = o->max_iterations > 0 ? o->max_iterations : 100000;
+        const uint64_t left = f->iteration < max_it ? (uint64_t)(max_it - f->iteration) : 0;
+        const uint64_t per_it = 1 + (uint64_t)(o->mcmc_retrys > 0 ? o->mcmc_retrys : 0);
+        if (left > (KABC_COUNTER_LIMIT - f->pass) / per_it)
+            return bad("the pass counter could pass 2^56 within max_iterations (the random streams hold 56 bits of it)");
+    }
     return KABC_OK;
 }
 

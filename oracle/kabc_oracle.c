@@ -75,6 +75,12 @@ static blk_t stream(uint64_t seed, uint32_t walker, uint64_t t, uint32_t slot, u
     return b;
 }
 
+/* the oracle's own stream address, for tests/test_math_contract.py */
+void orc_stream_block(uint64_t seed, uint32_t walker, uint64_t t, uint32_t slot, uint32_t domain, uint32_t out[4]) {
+    blk_t b = stream(seed, walker, t, slot, domain);
+    memcpy(out, b.w, sizeof b.w);
+}
+
 /* ------------------------------------------------------------------------- */
 /* math probes                                                                */
 /* ------------------------------------------------------------------------- */
@@ -790,6 +796,18 @@ static int32_t transition_error(int rc) {
     return fail(KABC_ERR_INVALID_STATE, "starting sample invalid.");
 }
 
+/* the transition counter stays below KABC_COUNTER_LIMIT (include/kabc.h), with the library's message */
+static int32_t counter_room(const orc_ais_t* h, int64_t ngen, int32_t nt, const char* who) {
+    const uint64_t room = KABC_COUNTER_LIMIT - h->t;
+    if (ngen > 0 && nt > 0 && (uint64_t)ngen > room / (uint64_t)nt) {
+        snprintf(g_err, sizeof g_err,
+                 "%s: the transition counter t = %llu would pass 2^56 (the random streams hold 56 bits of it)", who,
+                 (unsigned long long)h->t);
+        return KABC_ERR_INVALID_ARG;
+    }
+    return KABC_OK;
+}
+
 /* step(rng, model, spl, state; ntransitions) repeated nsteps times -- src/KissABC.jl:66-80 */
 int32_t orc_ais_steps_serial(orc_ais_t* h, int64_t nsteps, int32_t ntransitions, double* out) {
     if (!h->initialised) return fail(KABC_ERR_INVALID_STATE, "orc_ais_init not called");
@@ -813,6 +831,7 @@ int32_t orc_ais_half_generation(orc_ais_t* h, int32_t half, int32_t ntransitions
     const int64_t first = half ? h->N0 : 0;
     const int64_t rows = half ? h->N - h->N0 : h->N0;
     if (row_begin < 0 || row_end > rows) return fail(KABC_ERR_INVALID_ARG, "row range");
+    if (counter_room(h, 1, ntransitions, "kabc_ais_half_generation")) return KABC_ERR_INVALID_ARG;
     partner_set_t ps;
     ps.base = half ? 0 : h->N0;
     ps.n = half ? h->N0 : h->N - h->N0;
@@ -828,6 +847,7 @@ int32_t orc_ais_half_generation(orc_ais_t* h, int32_t half, int32_t ntransitions
 }
 
 int32_t orc_ais_end_generation(orc_ais_t* h, int32_t ntransitions) {
+    if (counter_room(h, 1, ntransitions, "kabc_ais_end_generation")) return KABC_ERR_INVALID_ARG;
     h->t += (uint64_t)ntransitions;
     for (int64_t i = 0; i < h->N; ++i) h->tc[i] = h->t;
     return KABC_OK;
@@ -836,6 +856,7 @@ int32_t orc_ais_end_generation(orc_ais_t* h, int32_t ntransitions) {
 int32_t orc_ais_generations_sync(orc_ais_t* h, int64_t ngen, int32_t ntransitions, double* out,
                                  orc_trace_rec_t* trace) {
     if (!h->initialised) return fail(KABC_ERR_INVALID_STATE, "orc_ais_init not called");
+    if (counter_room(h, ngen, ntransitions, "kabc_ais_advance")) return KABC_ERR_INVALID_ARG;
     const int D = h->D;
     for (int64_t g = 0; g < ngen; ++g) {
         for (int half = 0; half < 2; ++half) {
@@ -873,6 +894,12 @@ int32_t orc_ais_get_state(orc_ais_t* h, double* x, double* lp, double* ll, uint6
 
 int32_t orc_ais_set_state(orc_ais_t* h, const double* x, const double* lp, const double* ll,
                           uint64_t t) {
+    if (t >= KABC_COUNTER_LIMIT) {
+        snprintf(g_err, sizeof g_err,
+                 "kabc_ais_set_state: t = %llu, the transition counter must be below 2^56 (the random streams hold "
+                 "56 bits of it)", (unsigned long long)t);
+        return KABC_ERR_INVALID_ARG;
+    }
     memcpy(h->x, x, sizeof(double) * h->N * h->D);
     memcpy(h->lp, lp, sizeof(double) * h->N);
     memcpy(h->ll, ll, sizeof(double) * h->N);
@@ -936,6 +963,43 @@ int32_t orc_quantile(const double* v, int64_t n, double p, double* out) {
 
 int32_t orc_smc_run(const kabc_prior_t* prior, int32_t D, const kabc_cost_t* cost,
                     const kabc_smc_opts_t* o, kabc_smc_result_t* res) {
+    return orc_smc_run_from(prior, D, cost, o, NULL, NULL, res);
+}
+
+static int32_t bad_state(const char* who, const char* what) {
+    snprintf(g_err, sizeof g_err, "%s: %s", who, what);
+    return KABC_ERR_INVALID_ARG;
+}
+
+/* kabc_smc_run_from (include/kabc.h): the run from `from` (NULL: the initial draw), its end state in `to`
+ * (NULL: none).  The refusals and their messages are the library's. */
+int32_t orc_smc_run_from(const kabc_prior_t* prior, int32_t D, const kabc_cost_t* cost,
+                         const kabc_smc_opts_t* o, const kabc_smc_state_t* from, kabc_smc_state_t* to,
+                         kabc_smc_result_t* res) {
+    static const char who[] = "kabc_smc_run_from";
+    if (to && (!to->theta || !to->cost || !to->logprior || !to->alive)) return bad_state(who, "an array of `to` is NULL");
+    if (from) {
+        const kabc_smc_state_t* f = from;
+        if (to && (to == f || to->theta == f->theta || to->cost == f->cost || to->logprior == f->logprior ||
+                   to->alive == f->alive))
+            return bad_state(who, "`to` shares its struct or an array with `from`");
+        if (!f->theta || !f->cost || !f->logprior || !f->alive) return bad_state(who, "an array of `from` is NULL");
+        if (f->nparticles != o->nparticles) return bad_state(who, "the state's nparticles differs from opts->nparticles");
+        if (f->D != D) return bad_state(who, "the state's D differs from the call's");
+        if (f->iteration < 0) return bad_state(who, "the state's iteration is negative (a failed run leaves -1)");
+        if (f->nparticles < 1) return bad_state(who, "the state's nparticles must be >= 1");
+        int64_t n = 0;
+        for (int64_t i = 0; i < f->nparticles; ++i) n += f->alive[i] != 0;
+        if (n != f->n_alive) return bad_state(who, "the state's n_alive is not the number of alive particles");
+        if (f->pass >= KABC_COUNTER_LIMIT)
+            return bad_state(who, "the state's pass counter must be below 2^56 (the random streams hold 56 bits of it)");
+        const int64_t mx = o->max_iterations > 0 ? o->max_iterations : 100000;
+        const uint64_t left = f->iteration < mx ? (uint64_t)(mx - f->iteration) : 0;
+        const uint64_t per_it = 1 + (uint64_t)(o->mcmc_retrys > 0 ? o->mcmc_retrys : 0);
+        if (left > (KABC_COUNTER_LIMIT - f->pass) / per_it)
+            return bad_state(who, "the pass counter could pass 2^56 within max_iterations (the random streams hold 56 bits of it)");
+    }
+    if (to) to->iteration = -1; /* until the result is filled */
     const int64_t N = o->nparticles;
     const double alpha = o->alpha;
     const double r_epstol = kabc_isnan(o->r_epstol) ? pow(1.0 - alpha, 1.5) / 50.0 : o->r_epstol;
@@ -976,7 +1040,7 @@ int32_t orc_smc_run(const kabc_prior_t* prior, int32_t D, const kabc_cost_t* cos
     int32_t rc = KABC_OK;
 
     /* :119-125 */
-    for (int64_t i = 0; i < N; ++i) {
+    for (int64_t i = 0; i < N && !from; ++i) {
         factored_rand(prior, D, seed, (uint32_t)i, 0, KABC_DOM_SMC_INIT, th + i * D);
         push_p(q, D, th + i * D, xp);
         Xs[i] = orc_cost_eval(cost, D, xp, seed, (uint32_t)i, 0, KABC_DOM_SMC_INIT_COST);
@@ -984,14 +1048,33 @@ int32_t orc_smc_run(const kabc_prior_t* prior, int32_t D, const kabc_cost_t* cos
         lpi[i] = factored_logpdf(q, D, xp);
         alive[i] = 1;
     }
-    double eps = KABC_INF;
-    int64_t iteration = 0;
+    double eps = KABC_INF, epsv = KABC_INF;
+    int64_t iteration = 0, accepted = 0;
     uint64_t pass = 0;
     const int64_t max_it = o->max_iterations > 0 ? o->max_iterations : 100000;
     const double sqrtD = kabc_sqrt((double)D);
-    while (1) {
+    int stopped = 0;
+    if (from) {
+        memcpy(th, from->theta, sizeof(double) * N * D);
+        memcpy(Xs, from->cost, sizeof(double) * N);
+        memcpy(lpi, from->logprior, sizeof(double) * N);
+        for (int64_t i = 0; i < N; ++i) alive[i] = from->alive[i] != 0;
+        eps = from->eps;
+        epsv = from->eps_prev;
+        iteration = from->iteration;
+        accepted = (int64_t)from->accepted;
+        pass = from->pass;
+        cost_evals = from->cost_evals;
+        proposals = from->proposals;
+        /* the stop tests of :194-198 and the iteration bound, on the state, with this call's options */
+        stopped = iteration > 0 &&
+                  (2.0 * fabs(epsv - eps) < r_epstol * (fabs(epsv) + fabs(eps)) || eps <= o->epstol ||
+                   (double)accepted < o->mcmc_tol * (double)N || iteration >= max_it);
+    }
+    const int64_t first_iteration = iteration;
+    while (!stopped) {
         ++iteration;
-        double epsv = eps;
+        epsv = eps;
         /* Step 1 :134-143 */
         int64_t na = 0;
         double mn = KABC_INF;
@@ -1049,7 +1132,7 @@ int32_t orc_smc_run(const kabc_prior_t* prior, int32_t D, const kabc_cost_t* cos
             resampled = 1;
         }
         /* Step 3 :156-193 */
-        int64_t accepted = 0;
+        accepted = 0;
         int passes = 0;
         for (int r = 1; r <= 1 + o->mcmc_retrys; ++r) {
             ++pass;
@@ -1098,8 +1181,9 @@ int32_t orc_smc_run(const kabc_prior_t* prior, int32_t D, const kabc_cost_t* cos
             }
             if ((double)accepted >= o->mcmc_tol * (double)N) break; /* :192 */
         }
-        if (res->iter_log && iteration <= res->iter_log_cap) {
-            kabc_smc_iter_t* L = &res->iter_log[iteration - 1];
+        /* (a continued run's log starts at its first own iteration) */
+        if (res->iter_log && iteration - first_iteration <= res->iter_log_cap) {
+            kabc_smc_iter_t* L = &res->iter_log[iteration - first_iteration - 1];
             L->eps = eps;
             L->ess = ess_logged;
             L->accepted = accepted;
@@ -1126,6 +1210,24 @@ int32_t orc_smc_run(const kabc_prior_t* prior, int32_t D, const kabc_cost_t* cos
     res->iterations = iteration;
     res->cost_evals = cost_evals;
     res->proposals = proposals;
+    if (to) { /* the walkers as the loop holds them: no push_p */
+        memcpy(to->theta, th, sizeof(double) * N * D);
+        memcpy(to->cost, Xs, sizeof(double) * N);
+        memcpy(to->logprior, lpi, sizeof(double) * N);
+        memcpy(to->alive, alive, (size_t)N);
+        to->nparticles = N;
+        to->D = D;
+        to->reserved = 0;
+        to->seed = seed;
+        to->iteration = iteration;
+        to->pass = pass;
+        to->eps = eps;
+        to->eps_prev = epsv;
+        to->accepted = (uint64_t)accepted;
+        to->cost_evals = cost_evals;
+        to->proposals = proposals;
+        to->n_alive = res->n_alive;
+    }
 done:
     free(th); free(th2); free(Xs); free(X2); free(lpi); free(lp2); free(tmp);
     free(alive); free(idx); free(prop); free(lprob);
@@ -1137,9 +1239,37 @@ done:
 /* ------------------------------------------------------------------------- */
 int32_t orc_abcde_run(const kabc_prior_t* prior, int32_t D, const kabc_cost_t* cost,
                       const kabc_abcde_opts_t* o, kabc_abcde_result_t* res) {
+    return orc_abcde_run_from(prior, D, cost, o, NULL, NULL, res);
+}
+
+/* kabc_abcde_run_from (include/kabc.h); the refusals and their messages are the library's */
+int32_t orc_abcde_run_from(const kabc_prior_t* prior, int32_t D, const kabc_cost_t* cost,
+                           const kabc_abcde_opts_t* o, const kabc_abcde_state_t* from, kabc_abcde_state_t* to,
+                           kabc_abcde_result_t* res) {
     if (!(o->alpha >= 0 && o->alpha < 1)) return fail(KABC_ERR_INVALID_ARG, "α must be in 0 <= α < 1.");
     const int64_t N = o->nparticles;
     if (N < 3) return fail(KABC_ERR_INVALID_ARG, "nparticles must be >= 3 (and < 2^31)");
+    {
+        static const char who[] = "kabc_abcde_run_from";
+        const kabc_abcde_state_t *f = from, *t = to;
+        if (t && (!t->theta || !t->cost || !t->logprior)) return bad_state(who, "an array of `to` is NULL");
+        if (f) {
+            if (t && (t == f || t->theta == f->theta || t->cost == f->cost || t->logprior == f->logprior))
+                return bad_state(who, "`to` shares its struct or an array with `from`");
+            if (!f->theta || !f->cost || !f->logprior) return bad_state(who, "an array of `from` is NULL");
+            if (f->nparticles != o->nparticles) return bad_state(who, "the state's nparticles differs from opts->nparticles");
+            if (f->D != D) return bad_state(who, "the state's D differs from the call's");
+            if (f->generation < 0) return bad_state(who, "the state's generation is negative (a failed run leaves -1)");
+            if ((uint64_t)f->generation >= KABC_COUNTER_LIMIT)
+                return bad_state(who, "the state's generation must be below 2^56 (the random streams hold 56 bits of it)");
+            if (o->generations > 0 && (uint64_t)o->generations > KABC_COUNTER_LIMIT)
+                return bad_state(who, "generations must be at most 2^56 (the random streams hold 56 bits of the generation counter)");
+            for (int64_t i = 0; i < f->nparticles; ++i)
+                if (!kabc_isfinite(f->cost[i]) || !kabc_isfinite(f->logprior[i]))
+                    return bad_state(who, "the state holds a cost or a log-prior that is not finite");
+        }
+        if (to) to->generation = -1; /* until the result is filled */
+    }
     prep_t q[ORC_MAX_DIM];
     if (!prep_all(prior, D, q)) return fail(KABC_ERR_INVALID_ARG, "invalid prior");
     if (!cost_dim_ok_any(cost->id, D)) return fail(KABC_ERR_UNSUPPORTED, "cost id / dimension not supported");
@@ -1153,8 +1283,14 @@ int32_t orc_abcde_run(const kabc_prior_t* prior, int32_t D, const kabc_cost_t* c
     double xp[ORC_MAX_DIM], tp[ORC_MAX_DIM];
     uint64_t nsims = 0;
     int32_t rc = KABC_OK;
+    if (from) {
+        memcpy(th, from->theta, sizeof(double) * N * D);
+        memcpy(dl, from->cost, sizeof(double) * N);
+        memcpy(lp, from->logprior, sizeof(double) * N);
+        nsims = from->nsims;
+    }
     /* :349-366 */
-    for (int64_t i = 0; i < N; ++i) {
+    for (int64_t i = 0; i < N && !from; ++i) {
         for (unsigned attempt = 0;; ++attempt) {
             factored_rand(prior, D, seed, (uint32_t)i, attempt, KABC_DOM_ABCDE_INIT, th + i * D);
             push_p(q, D, th + i * D, xp);
@@ -1171,7 +1307,8 @@ int32_t orc_abcde_run(const kabc_prior_t* prior, int32_t D, const kabc_cost_t* c
         }
     }
     const double gamma = o->proposal_width * 2.38 / sqrt((double)(2 * D)); /* :370 */
-    int64_t iters = 0;
+    int64_t iters = from ? from->generation : 0;
+    int broke = 0;
     while (iters < o->generations) { /* :372 */
         double el = KABC_INF, eh = -KABC_INF;
         for (int64_t i = 0; i < N; ++i) {
@@ -1179,7 +1316,10 @@ int32_t orc_abcde_run(const kabc_prior_t* prior, int32_t D, const kabc_cost_t* c
             if (dl[i] > eh) eh = dl[i];
         }
         iters += 1;                                     /* :373: the reference counts the generation first ... */
-        if (o->earlystop && eh <= o->eps_target) break; /* :379-381 ... and then leaves (iters includes it) */
+        if (o->earlystop && eh <= o->eps_target) { /* :379-381 ... and then leaves (iters includes it) */
+            broke = 1;
+            break;
+        }
         memcpy(nth, th, sizeof(double) * N * D);
         memcpy(ndl, dl, sizeof(double) * N);
         memcpy(nlp, lp, sizeof(double) * N);
@@ -1239,6 +1379,17 @@ int32_t orc_abcde_run(const kabc_prior_t* prior, int32_t D, const kabc_cost_t* c
         res->generations_run = iters;
         res->nsims = nsims;
     }
+    if (to) { /* the particles as the loop holds them: no push_p */
+        memcpy(to->theta, th, sizeof(double) * N * D);
+        memcpy(to->cost, dl, sizeof(double) * N);
+        memcpy(to->logprior, lp, sizeof(double) * N);
+        to->nparticles = N;
+        to->D = D;
+        to->reserved = 0;
+        to->seed = seed;
+        to->generation = iters - broke; /* the stream counter: the breaking iteration drew nothing */
+        to->nsims = nsims;
+    }
 done:
     free(th); free(nth); free(dl); free(ndl); free(lp); free(nlp);
     return rc;
@@ -1255,12 +1406,39 @@ int64_t orc_pfilter_nparticles(int64_t N, double q, int32_t D) {
 
 int32_t orc_pfilter_run(const kabc_prior_t* prior, int32_t D, const kabc_cost_t* cost,
                         const kabc_pfilter_opts_t* o, kabc_pfilter_result_t* res) {
+    return orc_pfilter_run_from(prior, D, cost, o, NULL, NULL, res);
+}
+
+/* kabc_pfilter_run_from (include/kabc.h); the refusals and their messages are the library's */
+int32_t orc_pfilter_run_from(const kabc_prior_t* prior, int32_t D, const kabc_cost_t* cost,
+                             const kabc_pfilter_opts_t* o, const kabc_pfilter_state_t* from,
+                             kabc_pfilter_state_t* to, kabc_pfilter_result_t* res) {
     prep_t q[ORC_MAX_DIM];
     if (!prep_all(prior, D, q)) return fail(KABC_ERR_INVALID_ARG, "invalid prior");
     if (!cost_dim_ok_any(cost->id, D)) return fail(KABC_ERR_UNSUPPORTED, "cost id / dimension not supported");
     if (!(o->q > 0 && o->q <= 1) || o->nparticles < 1)
         return fail(KABC_ERR_INVALID_ARG, "pfilter needs 0 < q <= 1 and N >= 1");
     const int64_t N = orc_pfilter_nparticles(o->nparticles, o->q, D);
+    {
+        static const char who[] = "kabc_pfilter_run_from";
+        const kabc_pfilter_state_t *f = from, *t = to;
+        if (t && (!t->theta || !t->cost || !t->logprior)) return bad_state(who, "an array of `to` is NULL");
+        if (f) {
+            if (t && (t == f || t->theta == f->theta || t->cost == f->cost || t->logprior == f->logprior))
+                return bad_state(who, "`to` shares its struct or an array with `from`");
+            if (!f->theta || !f->cost || !f->logprior) return bad_state(who, "an array of `from` is NULL");
+            if (f->nparticles != N)
+                return bad_state(who, "the state's nparticles differs from the effective N, kabc_pfilter_nparticles(opts->nparticles, q, D)");
+            if (f->D != D) return bad_state(who, "the state's D differs from the call's");
+            if (f->iteration < 0) return bad_state(who, "the state's iteration is negative (a failed run leaves -1)");
+            if ((uint64_t)f->iteration >= KABC_PFILTER_ITERATION_LIMIT)
+                return bad_state(who, "the state's iteration must be below 2^32 (the random streams hold 32 bits of it)");
+            for (int64_t i = 0; i < f->nparticles; ++i)
+                if (!kabc_isfinite(f->cost[i]) || !kabc_isfinite(f->logprior[i]))
+                    return bad_state(who, "the state holds a cost or a log-prior that is not finite");
+        }
+        if (to) to->iteration = -1; /* until the result is filled */
+    }
     const uint64_t seed = o->seed;
     double* th = (double*)malloc(sizeof(double) * N * D);
     double* Cc = (double*)malloc(sizeof(double) * N);
@@ -1271,7 +1449,7 @@ int32_t orc_pfilter_run(const kabc_prior_t* prior, int32_t D, const kabc_cost_t*
     double xp[ORC_MAX_DIM], p[ORC_MAX_DIM];
     uint64_t total_reps = 0, cost_evals = 0;
     int32_t rc = KABC_OK;
-    for (int64_t i = 0; i < N; ++i) { /* :280-294 */
+    for (int64_t i = 0; i < N && !from; ++i) { /* :280-294 */
         for (unsigned attempt = 0;; ++attempt) {
             factored_rand(prior, D, seed, (uint32_t)i, attempt, KABC_DOM_PF_INIT, th + i * D);
             push_p(q, D, th + i * D, xp);
@@ -1287,8 +1465,22 @@ int32_t orc_pfilter_run(const kabc_prior_t* prior, int32_t D, const kabc_cost_t*
         }
     }
     int64_t iters = 0;
-    double eps = 0.0, eff = 0.0;
-    while (1) {
+    double eps = KABC_INF, eff = KABC_NAN; /* (iteration 0: Inf, NaN) */
+    int ended = 0;
+    if (from) {
+        memcpy(th, from->theta, sizeof(double) * N * D);
+        memcpy(Cc, from->cost, sizeof(double) * N);
+        memcpy(lp, from->logprior, sizeof(double) * N);
+        iters = from->iteration;
+        eps = from->eps;
+        eff = from->eff;
+        total_reps = from->nreps;
+        cost_evals = from->cost_evals;
+        /* the stop tests of :330-332, and "nothing was bad: eff is NaN", on the state with this call's options */
+        ended = iters > 0 && (eff < o->eff_tol || eps < o->epstol || (o->max_iters >= 0 && iters > o->max_iters) ||
+                              eff != eff);
+    }
+    while (!ended) {
         iters += 1;
         memcpy(tmp, Cc, sizeof(double) * N);
         qsort(tmp, N, sizeof(double), cmp_double);
@@ -1349,6 +1541,20 @@ int32_t orc_pfilter_run(const kabc_prior_t* prior, int32_t D, const kabc_cost_t*
     res->iterations = iters;
     res->nreps = total_reps;
     res->cost_evals = cost_evals;
+    if (to) { /* the particles as the loop holds them: no push_p */
+        memcpy(to->theta, th, sizeof(double) * N * D);
+        memcpy(to->cost, Cc, sizeof(double) * N);
+        memcpy(to->logprior, lp, sizeof(double) * N);
+        to->nparticles = N;
+        to->D = D;
+        to->reserved = 0;
+        to->seed = seed;
+        to->iteration = iters;
+        to->eps = eps;
+        to->eff = eff;
+        to->nreps = total_reps;
+        to->cost_evals = cost_evals;
+    }
 done:
     free(th); free(Cc); free(lp); free(tmp); free(idxok); free(bad);
     return rc;

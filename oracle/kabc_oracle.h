@@ -49,6 +49,8 @@ const char* orc_last_error(void);
 void orc_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
 void orc_philox4x32_r(const uint32_t ctr[4], const uint32_t key[2], int32_t rounds, uint32_t out[4]);
 int32_t orc_philox_rounds(void);
+/* one block of the oracle's own stream (seed, walker, t, slot, domain) */
+void orc_stream_block(uint64_t seed, uint32_t walker, uint64_t t, uint32_t slot, uint32_t domain, uint32_t out[4]);
 
 /* math-contract probes (vectorised wrappers over include/kabc_math.h) */
 void orc_math_vec(int32_t fn, int64_t n, const double* x, double* out);
@@ -101,6 +103,19 @@ void orc_ais_destroy(orc_ais_t* h);
 /* smc(prior, cost; ...) -- src/smc.jl:92-206 */
 int32_t orc_smc_run(const kabc_prior_t* prior, int32_t D, const kabc_cost_t* cost,
                     const kabc_smc_opts_t* opts, kabc_smc_result_t* result);
+/* the three population runs from a state and into one, as kabc_smc_run_from, kabc_abcde_run_from and
+ * kabc_pfilter_run_from (include/kabc.h) define it: `from` NULL = the initial draw, `to` NULL = no end
+ * state; the stop tests are applied to the state first, the counts are totals, and the refusals carry the
+ * library's messages */
+int32_t orc_smc_run_from(const kabc_prior_t* prior, int32_t D, const kabc_cost_t* cost,
+                         const kabc_smc_opts_t* opts, const kabc_smc_state_t* from, kabc_smc_state_t* to,
+                         kabc_smc_result_t* result);
+int32_t orc_abcde_run_from(const kabc_prior_t* prior, int32_t D, const kabc_cost_t* cost,
+                           const kabc_abcde_opts_t* opts, const kabc_abcde_state_t* from,
+                           kabc_abcde_state_t* to, kabc_abcde_result_t* result);
+int32_t orc_pfilter_run_from(const kabc_prior_t* prior, int32_t D, const kabc_cost_t* cost,
+                             const kabc_pfilter_opts_t* opts, const kabc_pfilter_state_t* from,
+                             kabc_pfilter_state_t* to, kabc_pfilter_result_t* result);
 /* ABCDE(prior, cost, ϵ_target; ...) -- src/smc.jl:347-430 */
 int32_t orc_abcde_run(const kabc_prior_t* prior, int32_t D, const kabc_cost_t* cost,
                       const kabc_abcde_opts_t* opts, kabc_abcde_result_t* result);

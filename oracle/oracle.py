@@ -50,6 +50,8 @@ def load():
             "orc_philox4x32_r": (None, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_int32,
                                         C.POINTER(C.c_uint32)]),
             "orc_philox_rounds": (C.c_int32, []),
+            "orc_stream_block": (None, [C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32,
+                                        C.POINTER(C.c_uint32)]),
             "orc_math_vec": (None, [C.c_int32, C.c_int64, dp, dp]),
             "orc_normal_pairs": (None, [C.c_int64, C.POINTER(C.c_uint64), dp]),
             "orc_div_rc_vec": (None, [C.c_int64, dp, dp, dp]),
@@ -82,6 +84,15 @@ def load():
             "orc_ais_destroy": (None, [VP]),
             "orc_smc_run": (C.c_int32, [C.POINTER(cd.Prior), C.c_int32, C.POINTER(cd.Cost),
                                         C.POINTER(cd.SmcOpts), C.POINTER(cd.SmcResult)]),
+            "orc_smc_run_from": (C.c_int32, [C.POINTER(cd.Prior), C.c_int32, C.POINTER(cd.Cost),
+                                             C.POINTER(cd.SmcOpts), C.POINTER(cd.SmcState),
+                                             C.POINTER(cd.SmcState), C.POINTER(cd.SmcResult)]),
+            "orc_abcde_run_from": (C.c_int32, [C.POINTER(cd.Prior), C.c_int32, C.POINTER(cd.Cost),
+                                               C.POINTER(cd.AbcdeOpts), C.POINTER(cd.AbcdeState),
+                                               C.POINTER(cd.AbcdeState), C.POINTER(cd.AbcdeResult)]),
+            "orc_pfilter_run_from": (C.c_int32, [C.POINTER(cd.Prior), C.c_int32, C.POINTER(cd.Cost),
+                                                 C.POINTER(cd.PfilterOpts), C.POINTER(cd.PfilterState),
+                                                 C.POINTER(cd.PfilterState), C.POINTER(cd.PfilterResult)]),
             "orc_quantile": (C.c_int32, [dp, C.c_int64, C.c_double, dp]),
             "orc_pfilter_nparticles": (C.c_int64, [C.c_int64, C.c_double, C.c_int32]),
             "orc_pfilter_run": (C.c_int32, [C.POINTER(cd.Prior), C.c_int32, C.POINTER(cd.Cost),
@@ -251,6 +262,13 @@ def philox(ctr, key, rounds=10):
     return list(o)
 
 
+def stream_block(seed, walker, t, slot, domain):
+    """one block of the oracle's own stream (seed, walker, t, slot, domain): four 32-bit words"""
+    o = (C.c_uint32 * 4)()
+    load().orc_stream_block(seed, walker, t, slot, domain, o)
+    return list(o)
+
+
 def philox_rounds():
     return load().orc_philox_rounds()
 
@@ -415,10 +433,19 @@ class OracleAIS:
 
 
 def smc(prior, cost, *, nparticles=100, alpha=0.95, mcmc_retrys=0, mcmc_tol=0.015, epstol=0.0,
-        r_epstol=None, min_r_ess=None, max_stretch=2.0, verbose=False, seed=0, max_iterations=None):
+        r_epstol=None, min_r_ess=None, max_stretch=2.0, verbose=False, seed=None, max_iterations=None,
+        resume=None, return_state=False):
     """CPU restatement of smc() (src/smc.jl:92-206); returns dict.  `max_iterations` bounds the
-    outer loop as kissabc_jl_amd.smc's does (None: the 100 000 of kabc_smc_opts_t)."""
+    outer loop as kissabc_jl_amd.smc's does (None: the 100 000 of kabc_smc_opts_t).
+    `resume` (a kissabc_jl_amd SmcState) starts the run from that state instead of the initial draw, by the
+    rules of kabc_smc_run_from: `nparticles` is the state's, the counts are totals, "log" holds this call's
+    records; `return_state=True` adds "state", the SmcState the run ended in (its log: the state's own
+    followed by this call's, as kissabc_jl_amd.smc returns it)."""
+    from kissabc_jl_amd import api
     fac = as_factored(prior)
+    if resume is not None:
+        nparticles = resume.nparticles
+    seed = (resume.seed if resume is not None else 0) if seed is None else seed
     o = cd.SmcOpts()
     o.nparticles, o.alpha, o.mcmc_retrys, o.verbose = int(nparticles), alpha, mcmc_retrys, int(verbose)
     o.mcmc_tol, o.epstol, o.max_stretch, o.seed = mcmc_tol, epstol, max_stretch, seed
@@ -435,9 +462,24 @@ def smc(prior, cost, *, nparticles=100, alpha=0.95, mcmc_retrys=0, mcmc_tol=0.01
     r.alive = alive.ctypes.data_as(C.POINTER(C.c_uint8))
     r.iter_log, r.iter_log_cap = log, 4096
     cc = cost.to_c()
-    _check(load().orc_smc_run(_prior_c(fac), D, C.byref(cc), C.byref(o), C.byref(r)))
-    nit = min(r.iterations, 4096)
-    return {
+    to = st_to = None
+    if return_state:
+        to = api.SmcState(np.empty((max(N, 1), D)), np.empty(max(N, 1)), np.empty(max(N, 1)),
+                          np.zeros(max(N, 1), np.uint8), seed=0, iteration=-1, pass_count=0, eps=math.inf,
+                          eps_prev=math.inf, accepted=0, cost_evals=0, proposals=0, n_alive=0)
+        st_to = to._to_c()
+    st_from = resume._to_c() if resume is not None else None
+    _check(load().orc_smc_run_from(_prior_c(fac), D, C.byref(cc), C.byref(o),
+                                   C.byref(st_from) if st_from is not None else None,
+                                   C.byref(st_to) if st_to is not None else None, C.byref(r)))
+    first = resume.iteration if resume is not None else 0
+    nit = min(r.iterations - first, 4096)
+    if to is not None:
+        for name, field in (("seed", "seed"), ("iteration", "iteration"), ("pass_count", "pass_"), ("eps", "eps"),
+                            ("eps_prev", "eps_prev"), ("accepted", "accepted"), ("cost_evals", "cost_evals"),
+                            ("proposals", "proposals"), ("n_alive", "n_alive")):
+            setattr(to, name, getattr(st_to, field))
+    out = {
         "theta_all": theta, "C": Cst, "alive": alive.astype(bool), "eps": r.eps,
         "P": theta[alive.astype(bool)], "iterations": r.iterations, "n_alive": r.n_alive,
         "cost_evals": r.cost_evals, "proposals": r.proposals,
@@ -445,12 +487,22 @@ def smc(prior, cost, *, nparticles=100, alpha=0.95, mcmc_retrys=0, mcmc_tol=0.01
                      resampled=log[i].resampled, flag=log[i].flag, passes=log[i].mcmc_passes)
                 for i in range(nit)],
     }
+    if to is not None:
+        to.log = ([dict(rec) for rec in resume.log] if resume is not None else []) + [dict(rec) for rec in out["log"]]
+        out["state"] = to
+    return out
 
 
 def abcde(prior, cost, eps_target, *, nparticles=50, generations=20, alpha=0.0, earlystop=False,
-          proposal_width=1.0, seed=0):
-    """CPU restatement of ABCDE (src/smc.jl:347-430); returns dict."""
+          proposal_width=1.0, seed=None, resume=None, return_state=False):
+    """CPU restatement of ABCDE (src/smc.jl:347-430); returns dict.  `resume` (a kissabc_jl_amd AbcdeState)
+    and `return_state` ("state": the AbcdeState the run ended in) by the rules of kabc_abcde_run_from:
+    `nparticles` is the state's, `generations` bounds the total, the counts are totals."""
+    from kissabc_jl_amd import api
     fac = as_factored(prior)
+    if resume is not None:
+        nparticles = resume.nparticles
+    seed = (resume.seed if resume is not None else 0) if seed is None else seed
     o = cd.AbcdeOpts()
     o.nparticles, o.generations, o.eps_target, o.alpha = int(nparticles), int(generations), eps_target, alpha
     o.proposal_width, o.earlystop, o.verbose, o.seed = proposal_width, int(earlystop), 0, seed
@@ -460,15 +512,31 @@ def abcde(prior, cost, eps_target, *, nparticles=50, generations=20, alpha=0.0, 
     r = cd.AbcdeResult()
     r.theta, r.cost = _dp(theta), _dp(Cst)
     cc = cost.to_c()
-    _check(load().orc_abcde_run(_prior_c(fac), D, C.byref(cc), C.byref(o), C.byref(r)))
-    return {"P": theta, "C": Cst, "reached_eps": bool(r.reached_eps),
-            "generations_run": r.generations_run, "nsims": r.nsims}
+    to = api.AbcdeState._empty(N, D) if return_state else None
+    st_to = to._to_c() if to is not None else None
+    st_from = resume._to_c() if resume is not None else None
+    _check(load().orc_abcde_run_from(_prior_c(fac), D, C.byref(cc), C.byref(o),
+                                     C.byref(st_from) if st_from is not None else None,
+                                     C.byref(st_to) if st_to is not None else None, C.byref(r)))
+    out = {"P": theta, "C": Cst, "reached_eps": bool(r.reached_eps),
+           "generations_run": r.generations_run, "nsims": r.nsims}
+    if to is not None:
+        to._take_scalars(st_to)
+        out["state"] = to
+    return out
 
 
-def pfilter(prior, cost, N, *, q=0.7, eff_tol=0.1, epstol=-math.inf, max_iters=math.inf,
-            proposal_width=0.75, seed=0):
-    """CPU restatement of pfilter (src/smc.jl:275-340); returns dict."""
+def pfilter(prior, cost, N=None, *, q=0.7, eff_tol=0.1, epstol=-math.inf, max_iters=math.inf,
+            proposal_width=0.75, seed=None, resume=None, return_state=False):
+    """CPU restatement of pfilter (src/smc.jl:275-340); returns dict.  `resume` (a kissabc_jl_amd
+    PfilterState; `N` is then the effective particle count it holds, or None) and `return_state` ("state":
+    the PfilterState the run ended in) by the rules of kabc_pfilter_run_from: the stop tests are applied to
+    the state first, `max_iters` bounds the total, the counts are totals."""
+    from kissabc_jl_amd import api
     fac = as_factored(prior)
+    if resume is not None:
+        N = resume.nparticles
+    seed = (resume.seed if resume is not None else 0) if seed is None else seed
     o = cd.PfilterOpts()
     o.nparticles, o.q, o.eff_tol, o.epstol = int(N), q, eff_tol, epstol
     o.proposal_width, o.verbose, o.seed = proposal_width, 0, seed
@@ -480,6 +548,15 @@ def pfilter(prior, cost, N, *, q=0.7, eff_tol=0.1, epstol=-math.inf, max_iters=m
     r = cd.PfilterResult()
     r.theta, r.cost = _dp(theta), _dp(Cst)
     cc = cost.to_c()
-    _check(load().orc_pfilter_run(_prior_c(fac), D, C.byref(cc), C.byref(o), C.byref(r)))
-    return {"P": theta, "C": Cst, "eps": r.eps, "eff": r.eff, "iterations": r.iterations,
-            "nreps": r.nreps, "cost_evals": r.cost_evals}
+    to = api.PfilterState._empty(n_eff, D) if return_state else None
+    st_to = to._to_c() if to is not None else None
+    st_from = resume._to_c() if resume is not None else None
+    _check(load().orc_pfilter_run_from(_prior_c(fac), D, C.byref(cc), C.byref(o),
+                                       C.byref(st_from) if st_from is not None else None,
+                                       C.byref(st_to) if st_to is not None else None, C.byref(r)))
+    out = {"P": theta, "C": Cst, "eps": r.eps, "eff": r.eff, "iterations": r.iterations,
+           "nreps": r.nreps, "cost_evals": r.cost_evals}
+    if to is not None:
+        to._take_scalars(st_to)
+        out["state"] = to
+    return out

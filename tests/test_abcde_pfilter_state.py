@@ -276,3 +276,67 @@ def test_pfilter_state_is_checked_against_the_effective_n(k):
     assert status == cd.KABC_ERR_INVALID_ARG and "effective N" in msg
     status, msg = call(13)
     assert status == cd.KABC_ERR_INVALID_ARG and "iteration is negative" in msg
+
+
+@pytest.mark.parametrize("drv", DRIVERS)
+def test_library_and_oracle_refuse_a_counter_beyond_the_streams(k, orc, drv):
+    """the stream address holds 56 bits of the counter (include/kabc_philox.h): ABCDE's generation counter must
+    stay below 2^56 (and opts->generations, the total, at or below it); pfilter's counter is
+    (iteration << 24) | attempt, so its iteration must stay below 2^32.  KABC_ERR_INVALID_ARG before anything is
+    launched, in the library and, with the same message, in the oracle"""
+    from kissabc_jl_amd import _cdefs as cd, _lib
+    lib = _lib.load()
+    D, N = 2, 50
+    prior = k.Factored(*[k.Uniform(-5, 5)] * D)
+    cost = k.costs.GaussDist([0.5, -0.3])
+    cc = cost.to_c()
+    opts, _, result = _types(cd, drv)
+
+    def state(counter):
+        rng = np.random.default_rng(0)
+        arrays = rng.normal(size=(N, D)), rng.normal(size=N), rng.normal(size=N)
+        if drv == "abcde":
+            return k.AbcdeState(*arrays, seed=1, generation=counter, nsims=100)
+        return k.PfilterState(*arrays, seed=1, iteration=counter, eps=1.0, eff=0.5, nreps=100, cost_evals=90)
+
+    def library(st, total):
+        o = opts()
+        getattr(lib, f"kabc_{drv}_default_opts")(C.byref(o))
+        o.nparticles = N
+        if drv == "abcde":
+            o.generations = total
+        else:
+            o.max_iters, o.eff_tol = total, 0.0
+        c, r = st._to_c(), result()
+        # (the context is never used: every call here is refused)
+        status = getattr(lib, f"kabc_{drv}_run_from")(C.c_void_p(8), prior.to_c(), D, C.byref(cc), C.byref(o),
+                                                      C.byref(c), None, C.byref(r))
+        return status, lib.kabc_last_error().decode()
+
+    def oracle(st, total):
+        try:
+            if drv == "abcde":
+                orc.abcde(prior, cost, 0.01, resume=st, generations=total)
+            else:
+                orc.pfilter(prior, cost, resume=st, max_iters=total, eff_tol=0.0)
+        except orc.OracleError as e:
+            return e.status, str(e)
+        return 0, ""
+
+    limit, word = (2 ** 56, "generation must be below 2^56") if drv == "abcde" else (2 ** 32, "iteration must be below 2^32")
+    for c in (limit, limit + 5, 2 ** 62):
+        status, msg = library(state(c), c + 8)
+        assert status == cd.KABC_ERR_INVALID_ARG and word in msg, c
+        assert oracle(state(c), c + 8) == (status, msg)
+    if drv == "abcde":      # the total a call may be asked for
+        status, msg = library(state(limit - 3), limit + 1)
+        assert status == cd.KABC_ERR_INVALID_ARG and "generations must be at most 2^56" in msg
+        assert oracle(state(limit - 3), limit + 1) == (status, msg)
+    # the last admissible counters are not refused (the oracle; the library from such states:
+    # tests/test_gpu_stream_counter.py)
+    if drv == "abcde":
+        out = orc.abcde(prior, cost, 0.01, resume=state(limit - 3), generations=limit, return_state=True)
+        assert out["generations_run"] == limit and out["state"].generation == limit
+    else:
+        out = orc.pfilter(prior, cost, resume=state(limit - 3), max_iters=limit - 3, eff_tol=0.0, return_state=True)
+        assert out["iterations"] == limit - 2 == out["state"].iteration

@@ -92,3 +92,32 @@ def test_sample_batch_courses_without_a_batch_handle(k, fake):
         out = k.sample_batch(_model(k, D), k.AIS(60), 60, nruns=2, return_array=True)
         assert out.info["course"] == "sequential"
         assert [c[0] for c in fake.created] == (["batch"] if D <= cd.KABC_MAX_DIM else []) + ["single", "single"]
+
+
+def test_oracle_refuses_a_transition_counter_beyond_the_streams(k, orc):
+    """the stream address holds 56 bits of the transition counter (include/kabc_philox.h): the oracle refuses
+    set_state at or beyond 2^56, and an advance that would count past it, as kabc_ais_set_state and
+    kabc_ais_advance do (the library's refusals need a handle: tests/test_gpu_stream_counter.py)"""
+    from kissabc_jl_amd import _cdefs as cd
+    model = k.ApproxKernelizedPosterior(k.Factored(k.Uniform(-5, 5), k.Uniform(-5, 5)), k.costs.Rosenbrock(), 1.0)
+    o = orc.OracleAIS(model, 12, seed=1).init()
+    x, lp, ll, t = o.state()
+    assert t == 0
+    for bad in (2 ** 56, 2 ** 56 + 5, 2 ** 64 - 1):
+        with pytest.raises(orc.OracleError, match=r"kabc_ais_set_state: t = %d, the transition counter must be below 2\^56" % bad) as e:
+            o.set_state(x, lp, ll, bad)
+        assert e.value.status == cd.KABC_ERR_INVALID_ARG
+    assert o.state()[3] == 0                       # (a refused state changes nothing)
+    o.set_state(x, lp, ll, 2 ** 56 - 16)
+    with pytest.raises(orc.OracleError, match=r"kabc_ais_advance: the transition counter t = %d would pass 2\^56" % (2 ** 56 - 16)):
+        o.generations_sync(3, 8)
+    assert o.state()[3] == 2 ** 56 - 16 and np.array_equal(o.state()[0], x)
+    o.generations_sync(2, 8)                       # the last two admissible generations
+    assert o.state()[3] == 2 ** 56
+    with pytest.raises(orc.OracleError, match="would pass"):
+        o.generations_sync(1, 1)
+    with pytest.raises(orc.OracleError, match="kabc_ais_half_generation"):
+        o.half_generation(0, 1, 0, 6)
+    with pytest.raises(orc.OracleError, match="kabc_ais_end_generation"):
+        o.end_generation(1)
+    o.generations_sync(0, 8)                       # (nothing to count)

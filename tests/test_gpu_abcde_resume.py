@@ -120,6 +120,26 @@ def test_split_on_every_course(k, orc, gpu_ctx, monkeypatch, case):
     _against_oracle(orc, full, pri, cost, eps, 11, kw)
 
 
+@pytest.mark.parametrize("case", ["scan_100", "sorted_blocks_1537"])
+def test_continued_run_equals_the_oracle_continued_from_the_same_state(k, orc, gpu_ctx, monkeypatch, case):
+    """an independent reference for a continued run: the device's state after 2 generations, continued to 5 by the
+    device and by the oracle (orc.abcde(resume=), tests/test_oracle_resume.py)"""
+    for name in ("KABC_ABCDE_RANK", "KABC_ABCDE_DONOR", "KABC_ABCDE_BLOCKS_FROM"):
+        monkeypatch.delenv(name, raising=False)
+    pri = k.Factored(k.DiscreteUniform(-10, 10), k.Normal(0, 3))
+    cost = k.costs.GaussDist([3.0, -2.0])
+    N = int(case.rsplit("_", 1)[1])
+    first = k.ABCDE(pri, cost, 0.5, seed=11, nparticles=N, generations=2, proposal_width=0.9, return_state=True)
+    st = first.info["state"]
+    assert st.generation == 2
+    got = k.ABCDE(pri, cost, 0.5, resume=st, generations=5, proposal_width=0.9, return_array=True, return_state=True)
+    ref = orc.abcde(pri, cost, 0.5, resume=st, generations=5, proposal_width=0.9, return_state=True)
+    assert np.array_equal(_u64(got.P), _u64(ref["P"])) and np.array_equal(_u64(got.C), _u64(ref["C"]))
+    assert got.reached_eps == ref["reached_eps"]
+    assert got.info["generations_run"] == ref["generations_run"] == 5 and got.info["nsims"] == ref["nsims"] > st.nsims
+    _same_state(got.info["state"], ref["state"], case)
+
+
 def test_split_discrete_prior_state_is_not_rounded(k, orc, gpu_ctx):
     """DiscreteUniform + NoisyQuadDU: P is push_p'ed (integral), the state's theta is what the loop holds"""
     pri = k.Factored(k.Normal(1, 0.5), k.DiscreteUniform(1, 10))

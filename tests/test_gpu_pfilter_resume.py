@@ -92,6 +92,25 @@ def test_split_after_every_iteration(k, orc, gpu_ctx, monkeypatch, case):
     assert ref["iterations"] == 6
 
 
+@pytest.mark.parametrize("case", ["one_workgroup_100", "default_loop_300"])
+def test_continued_run_equals_the_oracle_continued_from_the_same_state(k, orc, gpu_ctx, monkeypatch, case):
+    """an independent reference for a continued run: the device's state after 3 iterations, continued to 6 by the
+    device and by the oracle (orc.pfilter(resume=), tests/test_oracle_resume.py)"""
+    for name in ("KABC_PF_SMALL", "KABC_PF_PASSES"):
+        monkeypatch.delenv(name, raising=False)
+    N = int(case.rsplit("_", 1)[1])
+    pri, cost = _gauss(k)
+    st = _run(k, pri, cost, N, 4, eff_tol=0.0, max_iters=2).info["state"]
+    assert st.iteration == 3
+    got = k.pfilter(pri, cost, resume=st, return_array=True, return_state=True, eff_tol=0.0, max_iters=5)
+    ref = orc.pfilter(pri, cost, resume=st, return_state=True, eff_tol=0.0, max_iters=5)
+    assert np.array_equal(_u64(got.P), _u64(ref["P"])) and np.array_equal(_u64(got.C), _u64(ref["C"]))
+    for key in ("eps", "eff", "iterations", "nreps", "cost_evals"):
+        assert _u64(got.info[key]) == _u64(ref[key]), key
+    assert ref["iterations"] == 6 and ref["nreps"] > st.nreps
+    _same_state(got.info["state"], ref["state"], case)
+
+
 @pytest.mark.parametrize("case", ["verbose", "d17", "discrete", "raised_13"])
 def test_split_other_shapes(k, orc, gpu_ctx, capfd, case):
     pri, cost = _gauss(k)

@@ -330,3 +330,25 @@ def test_default_path_unchanged(k, orc, gpu_ctx, monkeypatch, course):
         assert np.array_equal(_bits(out["C"]), _bits(ref["C"])), name
         assert (out["cost_evals"], out["proposals"]) == (ref["cost_evals"], ref["proposals"]), name
     assert raw["launches"] == got.info["mcmc_launches"]
+
+
+@pytest.mark.parametrize("course", FOUR)
+def test_continued_run_equals_the_oracle_continued_from_the_same_state(k, orc, gpu_ctx, monkeypatch, course):
+    """an independent reference for a continued run: the device's state after 4 iterations (the first resample),
+    continued to 9 by the device and by the oracle (orc.smc(resume=), tests/test_oracle_resume.py)"""
+    N = _env(monkeypatch, course)
+    prior, cost = _base(k)
+    first = k.smc(prior, cost, nparticles=N, return_array=True, return_state=True, **dict(BASE_KW, max_iterations=4))
+    st = first.info["state"]
+    assert st.iteration == 4 and st.n_alive == N and first.info["log"][3]["resampled"]
+    rest = {a: b for a, b in BASE_KW.items() if a != "seed"}
+    got = k.smc(prior, cost, resume=st, return_array=True, return_state=True, max_iterations=M, **rest)
+    ref = orc.smc(prior, cost, resume=st, return_state=True, max_iterations=M, **rest)
+    assert got.info["iterations"] == ref["iterations"] == M
+    assert got.info["log"][4:] == ref["log"] and len(ref["log"]) == M - 4
+    assert _bits(got.eps) == _bits(ref["eps"])
+    assert np.array_equal(got.info["alive"], ref["alive"])
+    assert np.array_equal(_bits(got.info["theta_all"]), _bits(ref["theta_all"]))
+    assert np.array_equal(_bits(got.C), _bits(ref["C"]))
+    assert (got.info["cost_evals"], got.info["proposals"]) == (ref["cost_evals"], ref["proposals"])
+    _assert_same_state(got.info["state"], ref["state"], course)

@@ -217,3 +217,57 @@ def test_library_refuses_bad_states_before_it_launches(k):
     to.alive = c.alive
     status, msg = call(c, to)
     assert status == cd.KABC_ERR_INVALID_ARG and "shares" in msg and c.iteration == 2
+
+
+def test_library_and_oracle_refuse_a_pass_counter_beyond_the_streams(k, orc):
+    """the stream address holds 56 bits of the pass counter (include/kabc_philox.h): a state at or beyond 2^56,
+    or one from which max_iterations x (1 + mcmc_retrys) passes could count past it, is KABC_ERR_INVALID_ARG
+    before anything is launched -- in the library and, with the same message, in the oracle"""
+    from kissabc_jl_amd import _cdefs as cd, _lib
+    lib = _lib.load()
+    D, N = 2, 50
+    prior = k.Factored(*[k.Uniform(-5, 5)] * D)
+    cost = k.costs.GaussDist([0.5, -0.3])
+    cc = cost.to_c()
+
+    def state(pass_count, iteration=3):
+        rng = np.random.default_rng(0)
+        return k.SmcState(rng.normal(size=(N, D)), rng.normal(size=N), rng.normal(size=N), np.ones(N, np.uint8), seed=1,
+                          iteration=iteration, pass_count=pass_count, eps=1.0, eps_prev=2.0, accepted=5,
+                          cost_evals=100, proposals=100, n_alive=N)
+
+    def library(st, max_iterations, mcmc_retrys=0):
+        o = cd.SmcOpts()
+        lib.kabc_smc_default_opts(C.byref(o))
+        o.nparticles, o.max_iterations, o.mcmc_retrys = N, max_iterations, mcmc_retrys
+        c, r = st._to_c(), cd.SmcResult()
+        status = lib.kabc_smc_run_from(C.c_void_p(8), prior.to_c(), D, C.byref(cc), C.byref(o), C.byref(c), None,
+                                       C.byref(r))      # (the context is never used: every call here is refused)
+        return status, lib.kabc_last_error().decode()
+
+    def oracle(st, max_iterations, mcmc_retrys=0):
+        try:
+            orc.smc(prior, cost, resume=st, max_iterations=max_iterations, mcmc_retrys=mcmc_retrys)
+        except orc.OracleError as e:
+            return e.status, str(e)
+        return 0, ""
+
+    for p in (2 ** 56, 2 ** 56 + 5, 2 ** 63, 2 ** 64 - 1):
+        status, msg = library(state(p), 9)
+        assert status == cd.KABC_ERR_INVALID_ARG and "pass counter must be below 2^56" in msg, p
+        assert oracle(state(p), 9) == (status, msg)
+    # a call that could run past the limit: 6 iterations left, of one pass each, from 2^56 - 5
+    status, msg = library(state(2 ** 56 - 5), 9)
+    assert status == cd.KABC_ERR_INVALID_ARG and "could pass 2^56" in msg
+    assert oracle(state(2 ** 56 - 5), 9) == (status, msg)
+    # ... and of up to four passes each from 2^56 - 23; from 2^56 - 24 they fit
+    status, msg = library(state(2 ** 56 - 23), 9, mcmc_retrys=3)
+    assert status == cd.KABC_ERR_INVALID_ARG and "could pass 2^56" in msg
+    assert oracle(state(2 ** 56 - 23), 9, mcmc_retrys=3) == (status, msg)
+    # the default max_iterations (100 000) from the last admissible counters
+    status, msg = library(state(2 ** 56 - 64), 0)
+    assert status == cd.KABC_ERR_INVALID_ARG and "could pass 2^56" in msg
+    # what fits is not refused (the oracle; the library from such states: tests/test_gpu_stream_counter.py)
+    out = orc.smc(prior, cost, resume=state(2 ** 56 - 6), max_iterations=9, r_epstol=0.0, mcmc_tol=0.0, epstol=-1e308,
+                  return_state=True)
+    assert out["iterations"] == 9 and out["state"].pass_count == 2 ** 56
