@@ -431,6 +431,18 @@ void kabc_reject_batch_stats(int64_t out[4]);
 kabc_status_t kabc_math_probe(kabc_ctx_t* ctx, int32_t fn, int64_t n, const double* x,
                               double* out);
 
+/* ---- task table of the wide AIS half-generation kernel (verification only) ----
+ * The kernel's workgroup is `waves` wavefronts (8 or 12): waves 0 and 1 consume, the others fill
+ * the 2 * chunk tasks of a chunk of `chunk` sub-steps x 2 batches, dealt by the SIMD the hardware
+ * placed each wave on (csrc/ais_kernels.hpp wide_deal_mask, the function the kernel itself runs).
+ * kabc_ais_wide_deal needs no device: simd[waves] are SIMD ids 0..15, nc the tasks per chunk of a
+ * consumer's SIMD (< 0: equal shares); masks[waves - 2] receives each producer's tasks, bit
+ * 2 si + b = sub-step si of batch b.  kabc_ais_wide_shipped: geom[3] = {waves, chunk, nc} of the
+ * kernel the library ships. */
+kabc_status_t kabc_ais_wide_deal(const int32_t* simd, int32_t waves, int32_t chunk, int32_t nc,
+                                 uint32_t* masks);
+void kabc_ais_wide_shipped(int32_t geom[3]);
+
 /* ---- working-memory probe (verification only) ----------------------------------
  * KABC_POISON_ALLOC (read once per process: unset, empty or 0 off; 1 byte 0xA5; 0xNN that byte) fills
  * every working buffer of the library with one byte before use.  The hook is silent, so tests prove it

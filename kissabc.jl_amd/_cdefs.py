@@ -159,6 +159,9 @@ PROTOTYPES = {
     "kabc_math_probe": (C.c_int, [VP, C.c_int32, C.c_int64, c_double_p, c_double_p]),
     "kabc_poison_probe": (C.c_int, [VP, C.c_int64, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8),
                                     C.POINTER(C.c_uint8), C.POINTER(C.c_int32)]),
+    "kabc_ais_wide_deal": (C.c_int, [C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32,
+                                     C.POINTER(C.c_uint32)]),
+    "kabc_ais_wide_shipped": (None, [C.POINTER(C.c_int32)]),
     "kabc_host_alloc": (C.c_int, [C.c_size_t, C.POINTER(VP)]),
     "kabc_host_free": (C.c_int, [VP]),
     "kabc_factored_logpdf": (C.c_int, [VP, C.POINTER(Prior), C.c_int32, C.c_int64, c_double_p,

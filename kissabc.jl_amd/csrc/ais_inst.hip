@@ -22,12 +22,12 @@ static void launch_half(const AisArgs& a, hipStream_t s, unsigned nchains) {
     hipLaunchKernelGGL((ais_half_kernel<D, COST, PC, PK>), dim3(grid, nchains), dim3(kAisBlock), 0, s, a);
 }
 
-// the wide geometry (ais_kernels.hpp WideGeom): 512 threads, two batches per workgroup
-template <int D, int COST, int PC, int PK, int K, int NC>
+// the wide geometry (ais_kernels.hpp WideGeom): W waves, two batches per workgroup
+template <int D, int COST, int PC, int PK, int K, int NC, int W>
 static void launch_half_wide(const AisArgs& a, hipStream_t s, unsigned nchains) {
     const dim3 grid = ais_wide_geom(a, nchains);
     if (grid.x == 0) return;
-    hipLaunchKernelGGL((ais_half_wide_kernel<D, COST, PC, PK, K, NC>), grid, dim3(kWideBlock), 0, s, a);
+    hipLaunchKernelGGL((ais_half_wide_kernel<D, COST, PC, PK, K, NC, W>), grid, dim3(W * 64), 0, s, a);
 }
 
 // (one translation unit instantiates the dimensions KABC_INST_DLO .. KABC_INST_DHI of some prior
@@ -60,7 +60,9 @@ static AisLaunchFn pick_wide() {
     constexpr bool pc_ok = KABC_INST_PCSEL == 0 || (KABC_INST_PCSEL == 1) == is_normal;
     if constexpr (pc_ok && D >= KABC_INST_DLO && D <= KABC_INST_DHI && cost_dim_ok_c(COST, D) &&
                   ais_wide_ok_c(COST, D))
-        return &launch_half_wide<D, COST, PCX % kPriorClasses, PCX / kPriorClasses + 1, kWideK, kWideNC>;
+        return &launch_half_wide<D, COST, PCX % kPriorClasses, PCX / kPriorClasses + 1,
+                                 ais_wide_chunk_c(D, PCX % kPriorClasses), ais_wide_nc_c(D, PCX % kPriorClasses),
+                                 ais_wide_waves_c(D, PCX % kPriorClasses)>;
     else return nullptr;
 }
 

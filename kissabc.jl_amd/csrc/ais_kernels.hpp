@@ -124,26 +124,95 @@ constexpr int kChunk = 3;    // sub-steps per record buffer = number of producer
 
 // A workgroup's geometry as a type: the kernel body (ais_half_body) is written once over it.
 //   HalfGeom            the geometry above: producer wave q fills sub-step q - 1 of every chunk.
-//   WideGeom<K, NC>     512 threads = 8 wavefronts = TWO batches: waves 0, 1 consume batches 0, 1
-//                       of the workgroup, waves 2..7 produce.  A chunk is K sub-steps x 2 batches
-//                       = 2K tasks, dealt to the producers by where the hardware PLACED them: a
-//                       producer that shares its SIMD with a consumer takes NC tasks per chunk, the
-//                       others split the rest (NC < 0: equal shares whatever the placement).  The
-//                       table is derived once per launch from the SIMD ids the waves publish in
-//                       LDS; a placement it does not expect gets equal shares.  A record is a pure
+//   WideGeom<K, NC, W>  W wavefronts (8 or 12: 512 or 768 threads) = TWO batches: waves 0, 1
+//                       consume batches 0, 1 of the workgroup, waves 2..W-1 produce.  A chunk is K
+//                       sub-steps x 2 batches = 2K tasks, dealt to the producers by where the
+//                       hardware PLACED them (wide_deal_mask below): the producers on a consumer's
+//                       SIMD take NC tasks per chunk between them, the producer-only waves split
+//                       the rest (NC < 0: equal shares whatever the placement).  The table is
+//                       derived once per launch from the SIMD ids the waves publish in LDS; a
+//                       placement it does not expect gets equal shares.  A record is a pure
 //                       function of (seed, walker, t, slot): which wave writes it, and when, cannot
-//                       change a value.
+//                       change a value.  W = 12 is three waves per SIMD: its kernel is bound to 168
+//                       registers per lane, so its consumer keeps ONE set of partner-row registers
+//                       (kOneRowSet; the path of D > kLateFrom).
 struct HalfGeom {
-    static constexpr bool kWide = false;
+    static constexpr bool kWide = false, kOneRowSet = false;
     static constexpr int kBlock = kAisBlock, kBatches = 1, kCh = kChunk, kNC = -1;
 };
-template <int K, int NC>
+constexpr int kWideBatches = 2, kWideMaxWaves = 12;
+template <int K, int NC, int W = 8, bool ONE = (W > 8)>
 struct WideGeom {
     static_assert(K >= 1 && K <= 8 && NC <= K, "the consumer spells out up to 8 sub-steps");
-    static constexpr bool kWide = true;
-    static constexpr int kBlock = 512, kBatches = 2, kCh = K, kNC = NC;
+    static_assert(W == 8 || W == 12, "two or three waves on each of the four SIMDs");
+    static_assert(W == 8 || ONE, "three waves per SIMD have registers for one set of partner rows");
+    static constexpr bool kWide = true, kOneRowSet = ONE;
+    static constexpr int kWaves = W, kBlock = W * 64, kBatches = kWideBatches, kCh = K, kNC = NC;
 };
-constexpr int kWideBlock = 512, kWideBatches = 2;
+
+// The wide geometry's task table.  sd: the SIMD id of wave w in bits 4w .. 4w + 3 (waves 0, 1 the
+// consumers, 2 .. W - 1 the producers); returns the tasks of a chunk that producer `me` (0 .. W - 3)
+// fills, bit 2 si + b = sub-step si of batch b.  The placement the shares are made for: the two
+// consumers on two SIMDs, W / 4 - 1 producers beside each.  Then each consumer's SIMD gets nc
+// tasks per chunk -- handed out one at a time to its first producer, then its second -- and the
+// producer-only waves split the other 2K - 2 nc, the first ones taking the remainder.  Any other
+// placement, or nc < 0: equal shares.  The tasks then go round the producers that still have
+// room, so that each batch's earliest sub-steps are filled first and every task has ONE owner.
+// Scalar code, once per launch; shares packed four bits apiece.
+// (the kernel passes compile-time W, K, nc: its loops unroll; the host entry's need not)
+#ifdef __HIP_DEVICE_COMPILE__
+#define KABC_DEAL_UNROLL _Pragma("unroll")
+#else
+#define KABC_DEAL_UNROLL
+#endif
+__host__ __device__ __forceinline__ uint32_t wide_deal_mask(uint64_t sd, int W, int K, int nc, int me) {
+    const int NPROD = W - kWideBatches, NT = 2 * K, beside = W / 4 - 1;
+    const uint32_t sc0 = (uint32_t)sd & 15u, sc1 = (uint32_t)(sd >> 4) & 15u;
+    uint32_t cot = 0;  // bit p: producer p shares its SIMD with a consumer
+    int n0 = 0, n1 = 0;
+    KABC_DEAL_UNROLL
+    for (int p = 0; p < NPROD; ++p) {
+        const uint32_t sp = (uint32_t)(sd >> (4 * (kWideBatches + p))) & 15u;
+        n0 += sp == sc0 ? 1 : 0;
+        n1 += sp == sc1 ? 1 : 0;
+        cot |= (sp == sc0 || sp == sc1) ? 1u << p : 0u;
+    }
+    const bool by_place = nc >= 0 && sc0 != sc1 && n0 == beside && n1 == beside;
+    uint64_t cap = 0;
+    if (by_place) {
+        const int rest = NT - 2 * nc, others = NPROD - 2 * beside;
+        int seen = 0, seen0 = 0, seen1 = 0;
+    KABC_DEAL_UNROLL
+        for (int p = 0; p < NPROD; ++p) {
+            int n;
+            if ((cot >> p) & 1u) {
+                const bool on0 = ((uint32_t)(sd >> (4 * (kWideBatches + p))) & 15u) == sc0;
+                const int k = on0 ? seen0 : seen1;  // (this one is the k-th producer beside its consumer)
+                n = nc / beside + (k < nc % beside ? 1 : 0);
+                seen0 += on0 ? 1 : 0;
+                seen1 += on0 ? 0 : 1;
+            } else {
+                n = rest / others + (seen < rest % others ? 1 : 0);
+                ++seen;
+            }
+            cap |= (uint64_t)n << (4 * p);
+        }
+    } else {
+    KABC_DEAL_UNROLL
+        for (int p = 0; p < NPROD; ++p) cap |= (uint64_t)(NT / NPROD + (p < NT % NPROD ? 1 : 0)) << (4 * p);
+    }
+    // (the shares add up to NT: the search for a producer with room ends)
+    uint32_t mine = 0;
+    int p = 0;
+    for (int task = 0; task < NT; ++task) {
+        while (((cap >> (4 * p)) & 15u) == 0u) p = p + 1 < NPROD ? p + 1 : 0;
+        if (p == me) mine |= 1u << task;
+        cap -= (uint64_t)1 << (4 * p);
+        p = p + 1 < NPROD ? p + 1 : 0;
+    }
+    return mine;
+}
+#undef KABC_DEAL_UNROLL
 
 template <int D>
 struct RecGeom {
@@ -696,9 +765,11 @@ __device__ __forceinline__ void ais_half_body(const AisArgs& A0) {
     }
 
     // the table's loads are issued here and land in LDS right before the barrier below
-    static_assert(KABC_MATH_TAB_WORDS == 2 * kAisBlock && (G::kBlock == kAisBlock || G::kBlock == 2 * kAisBlock),
-                  "two table words per thread, or one");
-    const double tab0 = kabc_log_tab[threadIdx.x];
+    // (768 threads: one word per thread of the first 512 -- wave-uniform)
+    static_assert(KABC_MATH_TAB_WORDS == 2 * kAisBlock && (G::kBlock == kAisBlock || G::kBlock >= 2 * kAisBlock),
+                  "two table words per thread, or one for each of the first 512");
+    const bool tab_thread = G::kBlock <= KABC_MATH_TAB_WORDS || threadIdx.x < (unsigned)KABC_MATH_TAB_WORDS;
+    const double tab0 = tab_thread ? kabc_log_tab[threadIdx.x] : 0.0;
     [[maybe_unused]] double tab1 = 0.0;
     if constexpr (G::kBlock == kAisBlock) tab1 = kabc_log_tab[threadIdx.x + kAisBlock];
     if (threadIdx.x < D * (int)(sizeof(PriorDev) / 8))
@@ -737,7 +808,7 @@ __device__ __forceinline__ void ais_half_body(const AisArgs& A0) {
         }
     }
     // the log table is staged by every wave and read by the producers right away
-    slogtab[threadIdx.x] = tab0;
+    if (tab_thread) slogtab[threadIdx.x] = tab0;
     if constexpr (G::kBlock == kAisBlock) slogtab[threadIdx.x + kAisBlock] = tab1;
     if constexpr (G::kWide) {
         uint32_t hw;
@@ -808,7 +879,7 @@ __device__ __forceinline__ void ais_half_body(const AisArgs& A0) {
     // drawn them) was measured too and COSTS 1.6 % at 100: in steady state the SIMD's other waves
     // fill that round trip, and the flag test + register-set copy are consumer instructions.
     // The rows come from the frozen half: WHEN they are read cannot matter.
-    constexpr bool kLate = D > kLateFrom;
+    constexpr bool kLate = D > kLateFrom || G::kOneRowSet;
     double r0a[D], r0b[D], r1a[kLate ? 1 : D], r1b[kLate ? 1 : D];
     // (wave-uniform and, outside the probes build, a compile-time constant)
     const bool pro_rows = !G::kWide && !(KABL & 5);
@@ -817,50 +888,12 @@ __device__ __forceinline__ void ais_half_body(const AisArgs& A0) {
     // LDS words -- scalar code, once per launch; shares and SIMD ids packed four bits apiece.
     [[maybe_unused]] uint32_t my_tasks = 0;
     if constexpr (G::kWide) {
-        constexpr int NT = 2 * CH;
-        uint32_t sd = 0;
+        static_assert(4 * (NBAT + NPROD) <= 64, "the SIMD ids of a workgroup's waves, four bits apiece");
+        uint64_t sd = 0;
 #pragma unroll
         for (int w = 0; w < NBAT + NPROD; ++w)
-            sd |= (uint32_t)__builtin_amdgcn_readfirstlane((int)ssimd[w]) << (4 * w);
-        const uint32_t sc0 = sd & 15u, sc1 = (sd >> 4) & 15u;
-        uint32_t cot = 0;  // bit p: producer p shares its SIMD with a consumer
-        int n0 = 0, n1 = 0;
-#pragma unroll
-        for (int p = 0; p < NPROD; ++p) {
-            const uint32_t sp = (sd >> (4 * (NBAT + p))) & 15u;
-            n0 += sp == sc0 ? 1 : 0;
-            n1 += sp == sc1 ? 1 : 0;
-            cot |= (sp == sc0 || sp == sc1) ? 1u << p : 0u;
-        }
-        // the placement the shares are made for: the consumers on two SIMDs, one producer beside
-        // each.  Anything else (both consumers on one SIMD, three waves on one ...): equal shares.
-        const bool by_place = G::kNC >= 0 && sc0 != sc1 && n0 == 1 && n1 == 1;
-        uint32_t cap = 0;
-        if (by_place) {
-            constexpr int nc = G::kNC >= 0 ? G::kNC : 0;
-            constexpr int rest = NT - 2 * nc, others = NPROD - 2;
-            int seen = 0;
-#pragma unroll
-            for (int p = 0; p < NPROD; ++p) {
-                int n = nc;
-                if (!((cot >> p) & 1u)) {
-                    n = rest / others + (seen < rest % others ? 1 : 0);
-                    ++seen;
-                }
-                cap |= (uint32_t)n << (4 * p);
-            }
-        } else {
-#pragma unroll
-            for (int p = 0; p < NPROD; ++p) cap |= (uint32_t)(NT / NPROD + (p < NT % NPROD ? 1 : 0)) << (4 * p);
-        }
-        // (the shares add up to NT: the search for a producer with room ends)
-        int p = 0;
-        for (int task = 0; task < NT; ++task) {
-            while (((cap >> (4 * p)) & 15u) == 0u) p = p + 1 < NPROD ? p + 1 : 0;
-            if (p == wave - NBAT) my_tasks |= 1u << task;
-            cap -= 1u << (4 * p);
-            p = p + 1 < NPROD ? p + 1 : 0;
-        }
+            sd |= (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)ssimd[w]) << (4 * w);
+        my_tasks = wide_deal_mask(sd, NBAT + NPROD, CH, G::kNC, wave - NBAT);
     }
     // PRODUCER: sub-step si (transition s of the launch) of batch b into record buffer `buf`, by
     // producer wave pw
@@ -983,7 +1016,7 @@ __device__ __forceinline__ void ais_half_body(const AisArgs& A0) {
 #pragma unroll
                     for (int j = 0; j < D + 1; ++j) zs[j] = R.zs[si][j][lane];
                     // (2) prefetch.  D <= kLateFrom: into the second register set, right away.
-                    //     Larger D (two more rows would not fit 256 VGPRs: D = 16 spilled 480 B
+                    //     Larger D, and every D of a geometry with one set (two more rows would not fit 256 VGPRs: D = 16 spilled 480 B
                     //     and ran 4.3x slower than D = 8): into the SAME registers, as soon as
                     //     the proposal below has consumed the current rows.
                     if constexpr (!kLate) {
@@ -1181,11 +1214,12 @@ ais_half_kernel(const AisArgs A0) {
     ais_half_body<D, COST, PC, PK, HalfGeom>(A0);
 }
 
-// the wide geometry (WideGeom above): same registers per wave, one workgroup per CU
-template <int D, int COST, int PC, int PK, int K, int NC>
-__global__ void __launch_bounds__(kWideBlock) __attribute__((amdgpu_waves_per_eu(2, 2)))
+// the wide geometry (WideGeom above): one workgroup per CU; W / 4 waves per SIMD, so 256 registers
+// per lane at W = 8 and 168 at W = 12
+template <int D, int COST, int PC, int PK, int K, int NC, int W = 8, bool ONE = (W > 8)>
+__global__ void __launch_bounds__(W * 64) __attribute__((amdgpu_waves_per_eu(W / 4, W / 4)))
 ais_half_wide_kernel(const AisArgs A0) {
-    ais_half_body<D, COST, PC, PK, WideGeom<K, NC>>(A0);
+    ais_half_body<D, COST, PC, PK, WideGeom<K, NC, W, ONE>>(A0);
 }
 
 // step(rng, model, spl::AIS; retry_sampling): one thread per owned walker; the
@@ -1267,21 +1301,40 @@ inline dim3 ais_init_geom(const InitArgs& a, unsigned nchains) {
 }
 // pcx = prior class + kPriorClasses * (posterior kind - 1)
 AisLaunch find_ais_kernel(int cost_id, int D, int pcx);
-// The wide geometry as shipped: (K, n_c) chosen by measurement (profiles/ais_wide.md: C3 110.2 ->
-// 105.4 us per launch in the final A/B; K = 5 and K = 3 with the same n_c LOSE 6 % and 1.5 %).  With n_c = 1 the two
-// producers beside a consumer fill one sub-step per chunk each, the other four 2, 2, 1, 1.
-constexpr int kWideK = 4, kWideNC = 1;
-// first cut: the dimensions measured (D = 8) and below -- the box bounds in registers, two sets of
-// partner rows; larger D keeps the existing geometry
+// The wide geometry as shipped: (W, K, n_c) chosen by measurement (profiles/ais_wide3.md: C3 105.6 ->
+// 98.5 us per launch; profiles/ais_wide.md for the eight-wave kernel it replaces).  W = 12: three waves
+// per SIMD, the consumer on one set of partner-row registers.  K = 6, n_c = 2: the two producers
+// beside a consumer fill one sub-step per chunk each, the six producer-only waves 2, 2, 1, 1, 1, 1 --
+// four tasks per producer-only SIMD and chunk of six consumer sub-steps.
+constexpr int kWideK = 6, kWideNC = 2, kWideW = 12;
+constexpr int kWideBlock = kWideW * 64;
+// Three waves per SIMD leave a lane 168 registers.  Where the kernel does not compile into them
+// without spilling (the register table of profiles/ais_wide3.md: by prior class, from these
+// dimensions on) the library keeps the eight-wave kernel it shipped before -- two waves per SIMD,
+// two sets of partner rows, K = 4, n_c = 1 -- with the registers it had.
+constexpr int kWideW8 = 8, kWideK8 = 4, kWideNC8 = 1;
+constexpr int ais_wide_waves_c(int D, int pc) {
+    const int dmax = pc == kPriorBox ? 8 : pc == kPriorNormal ? 6 : pc == kPriorSimple ? 4 : 2;
+    return D <= dmax ? kWideW : kWideW8;
+}
+constexpr int ais_wide_chunk_c(int D, int pc) { return ais_wide_waves_c(D, pc) == kWideW ? kWideK : kWideK8; }
+constexpr int ais_wide_nc_c(int D, int pc) { return ais_wide_waves_c(D, pc) == kWideW ? kWideNC : kWideNC8; }
+// first cut: the dimensions measured (D = 8) and below; larger D keeps the existing geometry
 constexpr int kWideMaxDim = 8;
-// what the wide kernel is instantiated for: prebuilt costs whose producers only fill records (no
-// prepared cost words, no cost normals), and the dimensions whose 4 K record buffers fit the
-// 160 KB of LDS beside the tables (12 KB covers the GENERAL class's)
-constexpr bool ais_wide_ok_c(int cost, int D) {
+// LDS of a wide workgroup: 4 K record buffers, the producers' work lists (64 B per producer wave)
+// and the tables (6 KB: the log table, the prior's components; 12 KB with the GENERAL class's)
+constexpr int ais_wide_lds_c(int D, int pc) {
     const int nz = (D + 2 > 4) ? (D + 2) : 4;
+    return 4 * ais_wide_chunk_c(D, pc) * kBatch * (20 + 8 * nz) + (ais_wide_waves_c(D, pc) - kWideBatches) * kBatch +
+           ((pc == kPriorGeneral ? 12 : 6) << 10);
+}
+// what the wide kernel is instantiated for: prebuilt costs whose producers only fill records (no
+// prepared cost words, no cost normals), and the dimensions whose buffers fit the 160 KB of LDS
+constexpr bool ais_wide_ok_c(int cost, int D) {
     if (D > kWideMaxDim) return false;
     return cost < KABC_COST_USER && cost_aux_c(cost) == 0 && ais_pre_blocks(cost, D) == 0 &&
-           4 * kWideK * kBatch * (20 + 8 * nz) + (12 << 10) <= (160 << 10);
+           ais_wide_lds_c(D, kPriorBox) <= (160 << 10) && ais_wide_lds_c(D, kPriorSimple) <= (160 << 10) &&
+           ais_wide_lds_c(D, kPriorGeneral) <= (160 << 10) && ais_wide_lds_c(D, kPriorNormal) <= (160 << 10);
 }
 inline dim3 ais_wide_geom(const AisArgs& a, unsigned nchains) {
     return dim3((unsigned)((a.rows_owned + kWideBatches * kBatch - 1) / (kWideBatches * kBatch)), nchains);

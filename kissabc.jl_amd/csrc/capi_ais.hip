@@ -1173,14 +1173,15 @@ static void ais_poll_spec(kabc_ais_t* h) {
 // Which geometry a launch of `nt` sub-steps over `rows` owned rows takes.  The wide kernel exists for
 // the prebuilt costs whose records fit the LDS (ais_wide_ok_c) and needs two full batches; single-chain,
 // unsharded handles only (ais_can_wide).  By default it is taken where it was measured to win
-// (profiles/ais_wide.md): from kAisWideFrom sub-steps on (its prologue is longer), and only where the
+// (profiles/ais_wide3.md; ais_wide.md for the eight-wave kernel): from kAisWideFrom sub-steps on (its
+// prologue is longer: 26.0 against 24.9 us at 16 sub-steps, 32.2 against 32.8 at 24), and only where the
 // existing geometry would put two workgroups on every compute unit, i.e. at least two batches per
 // unit -- below that a batch of the existing geometry has its unit to itself, the wide one packs two
 // on half as many units, and nobody has measured that.  KABC_AIS_WIDE=0 keeps the existing geometry,
 // =1 takes the wide one wherever it can run, =2 does the same and makes a launch that cannot take
 // it an error, raised before anything is enqueued (read per launch: the tests flip it).  Same bits
 // either way.
-constexpr int32_t kAisWideFrom = 32;
+constexpr int32_t kAisWideFrom = 24;
 static bool ais_can_wide(const kabc_ais_t* h, int64_t rows) {
     return h->launch_wide && h->nchains == 1 && h->world == 1 && !h->comm && rows >= kWideBatches * kBatch;
 }
@@ -1301,6 +1302,30 @@ static kabc_status_t launch_half_seg(kabc_ais_t* h, int32_t half, const kabc_ais
         if (kabc_status_t st = timing_close_pair(h)) return st;
     KABC_HIP_CHECK(hipGetLastError());
     return KABC_OK;
+}
+
+// the wide kernel's task table on the host (no device needed): the function the kernel runs
+kabc_status_t kabc_ais_wide_deal(const int32_t* simd, int32_t waves, int32_t chunk, int32_t nc,
+                                 uint32_t* masks) {
+    if (!simd || !masks || (waves != 8 && waves != 12) || chunk < 1 || chunk > 8 || nc > chunk) {
+        set_error("kabc_ais_wide_deal: bad argument (waves 8 or 12, chunk 1..8, nc <= chunk)");
+        return KABC_ERR_INVALID_ARG;
+    }
+    uint64_t sd = 0;
+    for (int w = 0; w < waves; ++w) {
+        if (simd[w] < 0 || simd[w] > 15) {
+            set_error("kabc_ais_wide_deal: SIMD id %d of wave %d is not in 0..15", (int)simd[w], w);
+            return KABC_ERR_INVALID_ARG;
+        }
+        sd |= (uint64_t)simd[w] << (4 * w);
+    }
+    for (int p = 0; p < waves - kWideBatches; ++p) masks[p] = wide_deal_mask(sd, waves, chunk, nc, p);
+    return KABC_OK;
+}
+void kabc_ais_wide_shipped(int32_t geom[3]) {
+    geom[0] = kWideW;
+    geom[1] = kWideK;
+    geom[2] = kWideNC;
 }
 
 kabc_status_t kabc_ais_half_generation(kabc_ais_t* h, int32_t half, int32_t ntransitions,
