@@ -730,6 +730,52 @@ kabc_status_t kabc_ais_summary_get(kabc_ais_t* h, int64_t* n, double* pivot, dou
  * open: KABC_OK. */
 kabc_status_t kabc_ais_summary_end(kabc_ais_t* h);
 
+/* ---- autocorrelation time and effective sample size of a summarised trace ----------------------
+ *
+ * Successive generations of an ensemble sampler are correlated: a mean over n = G * N samples has a Monte
+ * Carlo error of std * sqrt(tau / n), tau the integrated autocorrelation time.  An open summary can carry
+ * the lagged products that tau needs, on the device, next to its moments -- defined, like them, operation
+ * by operation in fp64 (every product is rounded before it is added), so that they are the same bits on
+ * every driver, for every chunk size and however the generations are split over calls.
+ *
+ * In the summary's notation (one chain; d = r - p), with L = maxlag, 1 <= L <= KABC_AUTOCORR_MAX_LAG:
+ *   per element (i, k), sequentially in g, from +0.0:
+ *     lagged products  for t = 1 ... min(g, L):  P[i][k][t] += d[g][i][k] * d[g - t][i][k]
+ *                      (lag 0 is the summary's own S2[k][k], which both cov modes keep)
+ *     first window     F[g][i][k] = d[g][i][k]  for g < L
+ *     last window      a ring R[g mod L][i][k] = d[g][i][k];  when read, Last[j] (j = 1 ... min(L, G)) is
+ *                      the deviation of generation G - j
+ *   when read, the summary's row tree (plain add) over i of every P[.][k][t], F[g][.][k] and Last[j][.][k]
+ *   gives TP[k][t], TF[k][g] and TL[k][j]; TP[k][0] = T2[k][k].
+ *   finalisation, per parameter k, in this order:
+ *     Lm = min(L, G - 1);  n = G * N;  m = T1[k] / n
+ *     head[0] = tail[0] = 0;  head[t] = head[t - 1] + TF[k][t - 1];  tail[t] = tail[t - 1] + TL[k][t]
+ *     for t = 0 ... Lm:  A = T1[k] - tail[t];  B = T1[k] - head[t];  u = A + B;  v = m * u;  w = TP[k][t] - v;
+ *                        q = m * m;  c = (double)(N * (G - t));  x = c * q;  y = w + x;  acov[k][t] = y / n
+ *       (the autocovariance about the chain-wide mean with the biased normalisation, summed over walkers)
+ *     rho[k][t] = acov[k][t] / acov[k][0]
+ *     Sokal's automatic window with c = 5:  s_0 = 0;  s_M = s_{M-1} + rho[k][M];  tau_M = 1 + 2 * s_M;
+ *       window[k] = the smallest M in 0 ... Lm with (double)M >= 5 * tau_M and converged[k] = 1; if there is
+ *       none, window[k] = Lm and converged[k] = 0.  tau[k] = tau_window;  ess[k] = n / tau[k]
+ *     acov[k][0] == 0 (a constant column) or G < 2:  rho, tau and ess are NaN, window = 0, converged = 0
+ * tests/ais_autocorr_oracle.py restates this in numpy. */
+#define KABC_AUTOCORR_MAX_LAG 256
+/* Adds the lagged products to the open summary of `h`, into which nothing has been folded yet (else
+ * KABC_ERR_INVALID_STATE); maxlag outside 1 ... KABC_AUTOCORR_MAX_LAG: KABC_ERR_INVALID_ARG.  The accumulators
+ * are 3 * maxlag * N * D doubles per chain from the context's pool; beyond the launch grid of their row tree:
+ * KABC_ERR_UNSUPPORTED.  kabc_ais_summary_begin (which starts over WITHOUT them), kabc_ais_summary_end and
+ * kabc_ais_destroy release them.  A summary without this call allocates, launches and returns what it
+ * always did. */
+kabc_status_t kabc_ais_autocorr_begin(kabc_ais_t* h, int32_t maxlag);
+/* Reads them (the accumulators stay).  Every pointer may be NULL.  *nlags = Lm + 1; lagsum (TP), acov, rho:
+ * [chain][D][maxlag + 1], entries 0 ... Lm written; first (TF): [chain][maxlag][D], rows g < min(maxlag, G)
+ * written; last (TL): [chain][maxlag][D], row j - 1 holds Last[j], rows j <= min(maxlag, G) written; tau, ess,
+ * window, converged: [chain][D].  Everything else is left untouched.  No autocorrelation open on the
+ * summary, or no generation folded yet: KABC_ERR_INVALID_STATE and every output is left untouched. */
+kabc_status_t kabc_ais_autocorr_get(kabc_ais_t* h, int32_t* nlags, double* lagsum, double* first, double* last,
+                                    double* acov, double* rho, double* tau, double* ess, int32_t* window,
+                                    int32_t* converged);
+
 /* ---- the range of the stream counters -----------------------------------------------------------
  * Every draw is keyed by a 64-bit counter (include/kabc_philox.h) of which the stream address holds the
  * low 56 bits: 32 in counter word 1, 24 next to the domain byte in word 3.  A counter of 2^56 + c would

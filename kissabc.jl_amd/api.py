@@ -71,11 +71,29 @@ class PosteriorSummary:
         min, max         per parameter
         pivot, sum1, sum2   the raw sums behind them: sums of (x - pivot) and of its products
 
+    With summary_begin(autocorr=...) / sample(..., autocorr=...), else None:
+
+        tau, ess         integrated autocorrelation time in generations and n / tau, per parameter [D]
+        mcse             Monte Carlo standard error of the mean: std * sqrt(tau / n)
+        acf, acov        autocorrelation and autocovariance [D][nlags] at lags 0 ... nlags - 1
+        window           Sokal's automatic window (c = 5) per parameter; tau_converged: it lies inside maxlag
+        maxlag           the largest lag kept
+
     On a batch handle every array has a leading chain axis and chain(c) gives chain c's own summary."""
 
-    def __init__(self, n, mean, cov, min, max, pivot=None, sum1=None, sum2=None, diag=False):
+    def __init__(self, n, mean, cov, min, max, pivot=None, sum1=None, sum2=None, diag=False, autocorr=None):
         self.n, self.mean, self.cov, self.min, self.max = int(n), mean, cov, min, max
         self.pivot, self.sum1, self.sum2, self.diag = pivot, sum1, sum2, bool(diag)
+        # autocorr: dict of tau, ess, acf, acov, window, tau_converged, maxlag (and the raw lagsum, first, last)
+        self.autocorr = autocorr
+        for f in self.AUTOCORR_FIELDS:
+            setattr(self, f, None if autocorr is None else autocorr.get(f))
+
+    AUTOCORR_FIELDS = ("tau", "ess", "acf", "acov", "window", "tau_converged", "maxlag", "lagsum", "first", "last")
+
+    @property
+    def mcse(self):
+        return None if self.tau is None else self.std * np.sqrt(self.tau / self.n)
 
     @property
     def var(self):
@@ -94,8 +112,11 @@ class PosteriorSummary:
         if self.nchains is None:
             raise ValueError("this summary holds one chain")
         pick = lambda a: None if a is None else a[c]   # noqa: E731
+        ac = self.autocorr
+        if ac is not None:
+            ac = {f: (v if f == "maxlag" else pick(v)) for f, v in ac.items()}
         return PosteriorSummary(self.n, self.mean[c], self.cov[c], self.min[c], self.max[c], pick(self.pivot),
-                                pick(self.sum1), pick(self.sum2), self.diag)
+                                pick(self.sum1), pick(self.sum2), self.diag, ac)
 
     def isapprox(self, c, nsigma=2.0):
         """Particles.isapprox per parameter: |mean - c| < nsigma * std, an array of bool"""
@@ -116,6 +137,8 @@ class ChainSummaries(list):
         super().__init__(chains)
         self.pooled = _pool_summaries(self)
         self.rhat = _rhat(self)
+        # with autocorr: the chains are independent, so their effective sample sizes add (pooled.tau stays None)
+        self.ess = None if self[0].ess is None else np.sum(np.stack([c.ess for c in self]), axis=0)
 
 
 def _pool_summaries(chains):
@@ -252,6 +275,21 @@ class MCMCThreads:
     distinct seeds advanced TOGETHER: chain is a grid dimension of every launch."""
 
 
+AUTOCORR_DEFAULT_LAG = 64
+
+
+def _autocorr_maxlag(autocorr, who):
+    """autocorr: None / False (off: 0), True (AUTOCORR_DEFAULT_LAG) or an int in 1 ... KABC_AUTOCORR_MAX_LAG"""
+    if autocorr is None or autocorr is False:
+        return 0
+    if autocorr is True:
+        return AUTOCORR_DEFAULT_LAG
+    if isinstance(autocorr, (int, np.integer)) and 1 <= int(autocorr) <= cd.KABC_AUTOCORR_MAX_LAG:
+        return int(autocorr)
+    raise ValueError(f"{who}: autocorr must be None, a bool or a maximum lag in 1 ... "
+                     f"{cd.KABC_AUTOCORR_MAX_LAG}, not {autocorr!r}")
+
+
 class AisEnsemble:
     """kabc_ais_t: the device-resident AISState (src/KissABC.jl:25-33)."""
 
@@ -347,14 +385,21 @@ class AisEnsemble:
 
     COV_MODES = {None: cd.SUMMARY_AUTO, "full": cd.SUMMARY_FULL, "diag": cd.SUMMARY_DIAG}
 
-    def summary_begin(self, cov=None):
+    def summary_begin(self, cov=None, autocorr=None):
         """Opens (or starts over) the posterior summary of this handle: advance(..., summary=True) then
         accumulates, summary() reads.  cov: "full" (the covariance matrix, up to KABC_MAX_DIM parameters),
-        "diag" (the variances, any length(prior)), None (full where it exists, else diag)."""
+        "diag" (the variances, any length(prior)), None (full where it exists, else diag).  autocorr: True
+        (maxlag = 64) or a maximum lag adds the lagged products on the device (kabc_ais_autocorr_begin):
+        summary() then reports tau, ess and mcse per parameter."""
         if cov not in self.COV_MODES:
             raise ValueError(f'summary_begin: cov must be "full", "diag" or None, not {cov!r}')
+        maxlag = _autocorr_maxlag(autocorr, "summary_begin")
         _lib.check(_lib.load().kabc_ais_summary_begin(self._h, self.COV_MODES[cov]))
         self._summary_diag = cov == "diag" or (cov is None and self.D > cd.KABC_MAX_DIM)
+        self._summary_maxlag = 0
+        if maxlag:
+            _lib.check(_lib.load().kabc_ais_autocorr_begin(self._h, maxlag))
+            self._summary_maxlag = maxlag
         return self
 
     def summary(self):
@@ -368,7 +413,28 @@ class AisEnsemble:
         p = lambda a: a.ctypes.data_as(cd.c_double_p)                             # noqa: E731
         _lib.check(_lib.load().kabc_ais_summary_get(self._h, C.byref(n), p(pivot), p(sum1), p(sum2), p(mean),
                                                     p(cov), p(mn), p(mx)))
-        return PosteriorSummary(n.value, mean, cov, mn, mx, pivot, sum1, sum2, diag)
+        return PosteriorSummary(n.value, mean, cov, mn, mx, pivot, sum1, sum2, diag, self._autocorr(lead))
+
+    def _autocorr(self, lead):
+        """kabc_ais_autocorr_get of the open summary as PosteriorSummary's dict, None without autocorr"""
+        L = getattr(self, "_summary_maxlag", 0)
+        if not L:
+            return None
+        D = self.D
+        nl = C.c_int32()
+        lagsum, acov, rho = (np.full(lead + (D, L + 1), np.nan) for _ in range(3))
+        first, last = (np.full(lead + (L, D), np.nan) for _ in range(2))
+        tau, ess = np.empty(lead + (D,)), np.empty(lead + (D,))
+        window, conv = np.zeros(lead + (D,), dtype=np.int32), np.zeros(lead + (D,), dtype=np.int32)
+        p = lambda a: a.ctypes.data_as(cd.c_double_p)                             # noqa: E731
+        pi = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))                     # noqa: E731
+        _lib.check(_lib.load().kabc_ais_autocorr_get(self._h, C.byref(nl), p(lagsum), p(first), p(last), p(acov),
+                                                     p(rho), p(tau), p(ess), pi(window), pi(conv)))
+        nl = nl.value
+        nw = min(L, nl)                                      # rows of the two windows: min(maxlag, G)
+        return {"tau": tau, "ess": ess, "acf": rho[..., :nl], "acov": acov[..., :nl], "window": window,
+                "tau_converged": conv.astype(bool), "maxlag": L, "lagsum": lagsum[..., :nl],
+                "first": first[..., :nw, :], "last": last[..., :nw, :]}
 
     def summary_end(self):
         _lib.check(_lib.load().kabc_ais_summary_end(self._h))
@@ -491,7 +557,7 @@ def _bundle(samples, scalar):
 
 
 def _sample_chains(model, N, Ns, seeds, costs, ntransitions, discard_initial, retry_sampling, ctx, ens=None,
-                   summary=False):
+                   summary=False, autocorr=None):
     """len(seeds) independent chains of AIS(N) in ONE batch handle (costs: one DeviceCost per chain, or
     None; ens: that handle where the caller has created it, closed here): the first Ns samples of each,
     [Nc][Ns][D], and the handle's driver; summary: the chains' PosteriorSummary (leading chain axis) in place
@@ -502,7 +568,7 @@ def _sample_chains(model, N, Ns, seeds, costs, ntransitions, discard_initial, re
     gk = max(1, -(-Ns // N))
     if summary:
         try:
-            return _summarise(ens, gk, N, ntransitions, discard_initial, retry_sampling), ens.driver
+            return _summarise(ens, gk, N, ntransitions, discard_initial, retry_sampling, autocorr), ens.driver
         finally:
             ens.close()
     big = gk * Nc * N * D * 8 > (1 << 20)   # (a small trace is not worth a helper thread: see sample)
@@ -524,19 +590,22 @@ def _sample_chains(model, N, Ns, seeds, costs, ntransitions, discard_initial, re
     return chains, driver
 
 
-def _summarise(ens, gk, N, ntransitions, discard_initial, retry_sampling):
+def _summarise(ens, gk, N, ntransitions, discard_initial, retry_sampling, autocorr=None):
     """sample()'s course on `ens` with the kept generations summarised on the device"""
     ens.init(retry_sampling)
     gd = -(-int(discard_initial) // N)
     if gd:
         ens.advance(gd, ntransitions)
-    ens.summary_begin()
+    if autocorr:
+        ens.summary_begin(autocorr=autocorr)
+    else:
+        ens.summary_begin()
     ens.advance(gk, ntransitions, summary=True)
     return ens.summary()
 
 
 def sample(model, spl, *args, ntransitions=1, discard_initial=0, retry_sampling=100, seed=0,
-           progress=False, ctx=None, return_array=False, summary=False, **kwargs):
+           progress=False, ctx=None, return_array=False, summary=False, autocorr=None, **kwargs):
     """sample(model, AIS(N), Ns; ...) and sample(model, AIS(N), MCMCThreads(), Ns, Nc; ...).
 
     The device advances a whole generation (every walker `ntransitions` times) per
@@ -548,12 +617,17 @@ def sample(model, spl, *args, ntransitions=1, discard_initial=0, retry_sampling=
     device in place of the samples: no trace crosses to the host.  It covers the ceil(Ns/N) kept generations
     WHOLE, so its n = ceil(Ns/N) * N, which exceeds Ns where N does not divide it (the samples form keeps the
     first Ns).  With MCMCThreads it returns a ChainSummaries: one PosteriorSummary per chain, `.pooled` and
-    `.rhat`.  It excludes return_array.
+    `.rhat`.  It excludes return_array.  `autocorr=True` (maxlag = 64) or a maximum lag adds tau, ess and mcse
+    per parameter to the summary (per chain with MCMCThreads, whose `.ess` is the chains' sum); it needs
+    summary=True.
     """
     if not isinstance(spl, AIS):
         raise TypeError("sampler must be AIS(nparticles)")
     if summary and return_array:
         raise ValueError("sample: summary=True returns moments, not samples; it excludes return_array")
+    if _autocorr_maxlag(autocorr, "sample") and not summary:
+        raise ValueError("sample: autocorr is part of the device summary; it needs summary=True")
+    akw = {"autocorr": autocorr} if _autocorr_maxlag(autocorr, "sample") else {}
     if args and isinstance(args[0], MCMCThreads):
         # chains are a grid dimension of ONE device handle: every launch advances all Nc
         # ensembles (kabc_ais_create_batch); chain c is bit-identical to a single-chain run
@@ -573,10 +647,10 @@ def sample(model, spl, *args, ntransitions=1, discard_initial=0, retry_sampling=
         if summary:
             if ens is not None:
                 both, _ = _sample_chains(model, spl.nparticles, Ns, seeds, None, ntransitions,
-                                         discard_initial, retry_sampling, ctx, ens=ens, summary=True)
+                                         discard_initial, retry_sampling, ctx, ens=ens, summary=True, **akw)
                 return ChainSummaries(both.chain(c) for c in range(Nc))
             return ChainSummaries(sample(model, spl, Ns, ntransitions=ntransitions, discard_initial=discard_initial,
-                                         retry_sampling=retry_sampling, seed=sd, ctx=ctx, summary=True)
+                                         retry_sampling=retry_sampling, seed=sd, ctx=ctx, summary=True, **akw)
                                   for sd in seeds)
         if ens is not None:
             chains, _ = _sample_chains(model, spl.nparticles, Ns, seeds, None, ntransitions,
@@ -594,7 +668,7 @@ def sample(model, spl, *args, ntransitions=1, discard_initial=0, retry_sampling=
     gk = max(1, -(-Ns // N))
     if summary:
         try:
-            return _summarise(ens, gk, N, ntransitions, discard_initial, retry_sampling)
+            return _summarise(ens, gk, N, ntransitions, discard_initial, retry_sampling, akw.get("autocorr"))
         finally:
             ens.close()
     shape = (gk, N, len(model))
@@ -640,7 +714,7 @@ def _model_difference(m, m0):
 
 
 def sample_batch(model, spl, Ns, nruns=None, *, seeds=None, seed=0, ntransitions=1, discard_initial=0,
-                 retry_sampling=100, ctx=None, return_array=False, course=None, summary=False):
+                 retry_sampling=100, ctx=None, return_array=False, course=None, summary=False, autocorr=None):
     """One model fitted to many datasets, or one dataset under many seeds, in one call: run r is
     sample(model_r, spl, Ns, seed=seeds[r], <the same keywords>), bit for bit.
 
@@ -655,7 +729,7 @@ def sample_batch(model, spl, Ns, nruns=None, *, seeds=None, seed=0, ntransitions
     fits one workgroup's LDS (csrc/ais_dyn_small_kernel.hpp) -- and raises KabcError where the shape is
     refused; "sequential" forces the loop of sample() calls.  Same bits on either course.  Returns a list with one entry per run; its `.info` holds the course, the driver,
     nruns and the wall time.  `summary=True` gives one PosteriorSummary per run in place of its samples, on
-    either course (sample's own summary=True: n = ceil(Ns/N) * N per run).  A failed initial draw raises KabcError("run r: <the reference's message>");
+    either course (sample's own summary=True: n = ceil(Ns/N) * N per run; `autocorr` as in sample).  A failed initial draw raises KabcError("run r: <the reference's message>");
     Context.cancel() / Ctrl-C behave as they do for sample()."""
     if not isinstance(spl, AIS):
         raise TypeError("sampler must be AIS(nparticles)")
@@ -663,6 +737,8 @@ def sample_batch(model, spl, Ns, nruns=None, *, seeds=None, seed=0, ntransitions
         raise ValueError(f'sample_batch: course must be None, "grid" or "sequential", not {course!r}')
     if summary and return_array:
         raise ValueError("sample_batch: summary=True returns moments, not samples; it excludes return_array")
+    if _autocorr_maxlag(autocorr, "sample_batch") and not summary:
+        raise ValueError("sample_batch: autocorr is part of the device summary; it needs summary=True")
     if isinstance(model, _ApproxModel):
         if nruns is None:
             raise ValueError("sample_batch: nruns is required with a single model")
@@ -689,6 +765,8 @@ def sample_batch(model, spl, Ns, nruns=None, *, seeds=None, seed=0, ntransitions
     Ns, N, D = int(Ns), spl.nparticles, len(m0)
     kw = dict(ntransitions=ntransitions, discard_initial=discard_initial, retry_sampling=retry_sampling)
     skw = {"summary": True} if summary else {}
+    if summary and _autocorr_maxlag(autocorr, "sample_batch"):
+        skw["autocorr"] = autocorr
     t0 = time.perf_counter()
     chains, driver = None, None
     if course == "grid" or (course is None and D <= cd.KABC_MAX_DIM):

@@ -8,6 +8,7 @@
 #include <mutex>
 #include <thread>
 #include <type_traits>
+#include <limits>
 #include <vector>
 
 #include "ais_aux_kernels.hpp"
@@ -15,6 +16,7 @@
 #include "ais_dyn_small_kernel.hpp"
 #include "ais_small_kernel.hpp"
 #include "ais_summary_kernel.hpp"
+#include "ais_autocorr_kernel.hpp"
 #include "host_common.hpp"
 #include "plugin_registry.hpp"
 
@@ -250,6 +252,15 @@ struct kabc_ais {
     double* d_sum_pivot = nullptr;
     double* d_sum_out = nullptr;
     double* d_sum_lvl[2] = {};
+    // ... and its autocorrelation (kabc_ais_autocorr_begin, ais_autocorr_kernel.hpp): the lagged products,
+    // the first window and the ring [3][chain][L][N * D], the device count of the generations folded, the
+    // row tree's result [3][chain][L][D] and its two scratch levels; from the context's pool
+    DevBufs ac_bufs;
+    int32_t ac_L = 0;               // maxlag, 0: none open
+    double* d_ac_acc = nullptr;
+    int64_t* d_ac_gens = nullptr;
+    double* d_ac_out = nullptr;
+    double* d_ac_lvl[2] = {};
     // debug records (tests)
     int32_t* d_dbg = nullptr;
     int64_t dbg_cap = 0;  // in int32 units
@@ -1410,6 +1421,22 @@ static kabc_status_t summary_fold(kabc_ais_t* h, const double* trace, int64_t gc
     a.nslots = h->sum_slots;
     launch_ais_summary_accumulate(a, h->sum_mode == KABC_SUMMARY_FULL, s);
     KABC_HIP_CHECK(hipGetLastError());
+    if (h->ac_L) {  // the same block into the lagged products, behind the moments
+        AisAutocorrArgs c;
+        std::memset(&c, 0, sizeof c);
+        c.trace = trace;
+        c.acc = h->d_ac_acc;
+        c.pivot = h->d_sum_pivot;
+        c.done = done;
+        c.gens = h->d_ac_gens;
+        c.N = h->N;
+        c.gc = gc;
+        c.D = h->D;
+        c.nchains = h->nchains;
+        c.L = h->ac_L;
+        launch_ais_autocorr_accumulate(c, h->d_ac_gens, s);
+        KABC_HIP_CHECK(hipGetLastError());
+    }
     return KABC_OK;
 }
 
@@ -1927,7 +1954,15 @@ static kabc_status_t summary_check(const kabc_ais_t* h, const char* who, bool op
     return KABC_OK;
 }
 
+static void autocorr_release(kabc_ais_t* h) {
+    h->ac_bufs.release();
+    h->d_ac_acc = h->d_ac_out = h->d_ac_lvl[0] = h->d_ac_lvl[1] = nullptr;
+    h->d_ac_gens = nullptr;
+    h->ac_L = 0;
+}
+
 static void summary_release(kabc_ais_t* h) {
+    autocorr_release(h);
     h->sum_bufs.release();
     h->d_sum_acc = h->d_sum_pivot = h->d_sum_out = h->d_sum_lvl[0] = h->d_sum_lvl[1] = nullptr;
     h->sum_mode = h->sum_slots = 0;
@@ -2063,6 +2098,149 @@ kabc_status_t kabc_ais_summary_end(kabc_ais_t* h) {
     KABC_HIP_CHECK(hipSetDevice(h->ctx->device));
     KABC_HIP_CHECK(hipStreamSynchronize(h->ctx->stream));  // (queued folds still read the buffers)
     summary_release(h);
+    return KABC_OK;
+}
+
+// ---- autocorrelation of the summarised trace (ais_autocorr_kernel.hpp) --------------------------------
+
+kabc_status_t kabc_ais_autocorr_begin(kabc_ais_t* h, int32_t maxlag) {
+    if (kabc_status_t st = summary_check(h, "kabc_ais_autocorr_begin", true)) return st;
+    if (maxlag < 1 || maxlag > KABC_AUTOCORR_MAX_LAG) {
+        set_error("kabc_ais_autocorr_begin: maxlag %d is outside 1 ... %d", maxlag, KABC_AUTOCORR_MAX_LAG);
+        return KABC_ERR_INVALID_ARG;
+    }
+    if (h->sum_gens != 0 || h->sum_pivot) {
+        set_error("kabc_ais_autocorr_begin: the open summary already holds generations; the lagged products "
+                  "start with the summary (kabc_ais_summary_begin, then this call)");
+        return KABC_ERR_INVALID_STATE;
+    }
+    const int64_t L = maxlag;
+    const int64_t nouter = 3 * (int64_t)h->nchains * L, nseries = nouter * h->D;
+    const int64_t t1 = (h->N + kAcTile - 1) / kAcTile, t2 = (t1 + kAcTile - 1) / kAcTile;
+    if (nseries * t1 >= (1ll << 31)) {  // (the row tree's grid, as for the summary's own accumulators)
+        set_error("kabc_ais_autocorr_begin: %d chains x 3 x maxlag %d x %d parameters x %lld walkers (%.1f GiB of "
+                  "accumulators) is beyond the row tree's launch grid", h->nchains, maxlag, h->D, (long long)h->N,
+                  (double)nseries * (double)h->N * 8.0 / (double)(1ll << 30));
+        return KABC_ERR_UNSUPPORTED;
+    }
+    KABC_HIP_CHECK(hipSetDevice(h->ctx->device));
+    hipStream_t s = h->ctx->stream;
+    if (h->ac_L) {  // (begin again: its buffers may still be read by queued work)
+        KABC_HIP_CHECK(hipStreamSynchronize(s));
+        autocorr_release(h);
+    }
+    const size_t plane = (size_t)h->nchains * (size_t)L * (size_t)h->N * (size_t)h->D;
+    h->ac_bufs.ctx = h->ctx;
+    hipError_t e = h->ac_bufs.alloc(&h->d_ac_acc, 3 * plane);
+    if (e == hipSuccess) e = h->ac_bufs.alloc(&h->d_ac_gens, (size_t)1);
+    if (e == hipSuccess) e = h->ac_bufs.alloc(&h->d_ac_out, (size_t)nseries);
+    if (e == hipSuccess) e = h->ac_bufs.alloc(&h->d_ac_lvl[0], (size_t)(nseries * t1));
+    if (e == hipSuccess) e = h->ac_bufs.alloc(&h->d_ac_lvl[1], (size_t)(nseries * t2));
+    // the lagged products start at +0.0; the windows are written before they are read
+    if (e == hipSuccess) e = hipMemsetAsync(h->d_ac_acc, 0, sizeof(double) * plane, s);
+    if (e == hipSuccess) e = hipMemsetAsync(h->d_ac_gens, 0, sizeof(int64_t), s);
+    if (e != hipSuccess) {
+        autocorr_release(h);
+        KABC_HIP_CHECK(e);
+    }
+    h->ac_L = maxlag;
+    return KABC_OK;
+}
+
+kabc_status_t kabc_ais_autocorr_get(kabc_ais_t* h, int32_t* nlags, double* lagsum, double* first, double* last,
+                                    double* acov, double* rho, double* tau, double* ess, int32_t* window,
+                                    int32_t* converged) {
+    if (kabc_status_t st = summary_check(h, "kabc_ais_autocorr_get", true)) return st;
+    if (!h->ac_L) {
+        set_error("kabc_ais_autocorr_get: the open summary keeps no lagged products (kabc_ais_autocorr_begin)");
+        return KABC_ERR_INVALID_STATE;
+    }
+    if (h->sum_gens == 0) {
+        set_error("kabc_ais_autocorr_get: the summary holds no generation yet (n = 0)");
+        return KABC_ERR_INVALID_STATE;
+    }
+    KABC_HIP_CHECK(hipSetDevice(h->ctx->device));
+    hipStream_t s = h->ctx->stream;
+    const int D = h->D, ns = h->sum_slots, L = h->ac_L;
+    const bool full = h->sum_mode == KABC_SUMMARY_FULL;
+    const size_t nch = (size_t)h->nchains;
+    launch_ais_summary_reduce(h->d_sum_acc, h->d_sum_out, h->d_sum_lvl[0], h->d_sum_lvl[1], h->N, D, ns,
+                              (int64_t)nch * ns, s);
+    KABC_HIP_CHECK(hipGetLastError());
+    launch_ais_autocorr_reduce(h->d_ac_acc, h->d_ac_out, h->d_ac_lvl[0], h->d_ac_lvl[1], h->N, D,
+                               3 * (int64_t)nch * L, s);
+    KABC_HIP_CHECK(hipGetLastError());
+    const size_t pl = nch * (size_t)L * (size_t)D;  // one plane of the tree's result: [chain][L][D]
+    std::vector<double> T(nch * (size_t)ns), Q(3 * pl);
+    KABC_HIP_CHECK(hipMemcpyAsync(T.data(), h->d_sum_out, sizeof(double) * T.size(), hipMemcpyDeviceToHost, s));
+    KABC_HIP_CHECK(hipMemcpyAsync(Q.data(), h->d_ac_out, sizeof(double) * Q.size(), hipMemcpyDeviceToHost, s));
+    KABC_HIP_CHECK(hipStreamSynchronize(s));
+    const int64_t G = h->sum_gens, N = h->N;
+    const int Lm = (int)(G - 1 < L ? G - 1 : L), Lw = (int)(G < L ? G : L);  // lags; rows of the windows
+    const double dn = (double)(G * N);
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    if (nlags) *nlags = Lm + 1;
+    std::vector<double> ac((size_t)Lm + 1), rh((size_t)Lm + 1);
+    for (size_t c = 0; c < nch; ++c) {
+        const double* t = T.data() + c * (size_t)ns;
+        const double* TP = Q.data() + c * (size_t)L * D;  // [t - 1][k]
+        const double* TF = TP + pl;                       // [g][k]
+        const double* TR = TF + pl;                       // [slot][k]
+        for (int g = 0; g < Lw; ++g)
+            for (int k = 0; k < D; ++k) {
+                if (first) first[(c * L + g) * D + k] = TF[(size_t)g * D + k];
+                // Last[j], j = g + 1: generation G - j, at ring slot (G - j) mod L
+                if (last) last[(c * L + g) * D + k] = TR[(size_t)((G - 1 - g) % L) * D + k];
+            }
+        for (int k = 0; k < D; ++k) {
+            const double t1 = t[k];
+            const double t2 = full ? t[3 * D + k * (k + 1) / 2 + k] : t[3 * D + k];
+            const double m = t1 / dn;
+            double head = 0.0, tail = 0.0;
+            for (int lag = 0; lag <= Lm; ++lag) {
+                if (lag > 0) {
+                    head = head + TF[(size_t)(lag - 1) * D + k];
+                    tail = tail + TR[(size_t)((G - lag) % L) * D + k];
+                }
+                const double tp = lag == 0 ? t2 : TP[(size_t)(lag - 1) * D + k];
+                const double a = t1 - tail, b = t1 - head;
+                const double u = a + b;
+                const double v = m * u;
+                const double w = tp - v;
+                const double q = m * m;
+                const double cnt = (double)(N * (G - lag));
+                const double x = cnt * q;
+                const double y = w + x;
+                ac[lag] = y / dn;
+                if (lagsum) lagsum[(c * D + k) * (size_t)(L + 1) + lag] = tp;
+                if (acov) acov[(c * D + k) * (size_t)(L + 1) + lag] = ac[lag];
+            }
+            const bool flat = ac[0] == 0.0 || G < 2;
+            int win = 0, conv = 0;
+            double tw = nan;
+            if (!flat) {
+                double sm = 0.0;
+                win = Lm;
+                for (int M = 0; M <= Lm; ++M) {
+                    rh[M] = ac[M] / ac[0];
+                    if (M > 0) sm = sm + rh[M];
+                    const double tm = 1.0 + 2.0 * sm;
+                    if (!conv && (double)M >= 5.0 * tm) {
+                        win = M;
+                        conv = 1;
+                        tw = tm;
+                    }
+                    if (!conv && M == Lm) tw = tm;
+                }
+            }
+            for (int lag = 0; lag <= Lm; ++lag)
+                if (rho) rho[(c * D + k) * (size_t)(L + 1) + lag] = flat ? nan : rh[lag];
+            if (tau) tau[c * D + k] = tw;
+            if (ess) ess[c * D + k] = flat ? nan : dn / tw;
+            if (window) window[c * D + k] = win;
+            if (converged) converged[c * D + k] = conv;
+        }
+    }
     return KABC_OK;
 }
 
