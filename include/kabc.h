@@ -776,6 +776,60 @@ kabc_status_t kabc_ais_autocorr_get(kabc_ais_t* h, int32_t* nlags, double* lagsu
                                     double* acov, double* rho, double* tau, double* ess, int32_t* window,
                                     int32_t* converged);
 
+/* ---- marginal histograms and quantiles of a summarised trace -----------------------------------
+ *
+ * mean +- std says little about a skewed or bounded posterior.  An open summary can count, on the device
+ * and next to its moments, a histogram per parameter over a range the caller gives; a median or a credible
+ * interval is then read from the counts by a fixed rule on the host.  Counts are integers, so they do not
+ * depend on the order in which the device adds them, nor on the driver, the chunk or the split over calls.
+ *
+ * In the summary's notation (one chain; r = r[g][i][k]), with B = nbins, 1 <= B <= KABC_HIST_MAX_BINS, and
+ * per parameter lo[k] < hi[k], both finite:
+ *   scale[k] = (double)B / (hi[k] - lo[k]), computed once on the host when the histogram is opened; it must
+ *              be finite and greater than 0
+ *   counters c[k][0 ... B + 1] of uint64_t, from 0; c[k][0] is the underflow, c[k][B + 1] the overflow.
+ *   Per element:
+ *     r < lo[k]:       ++c[k][0]
+ *     !(r < hi[k]):    ++c[k][B + 1]                      (a NaN lands here)
+ *     else             d = r - lo[k];  u = d * scale[k]   (the difference rounded, then the product: no
+ *                      contraction);  b = (int)u;  b = b > B - 1 ? B - 1 : b;  ++c[k][1 + b]
+ *   so that for every chain and parameter the sum over j of c[k][j] is G * N after G folded generations.
+ *
+ * The quantile rule (kabc_hist_quantile; one parameter, counts c[0 ... B + 1], mn and mx the summary's min
+ * and max, n = the sum of c, w = (hi - lo) / (double)B), for q in [0, 1]:
+ *   h = q * (double)n
+ *   walk j = 0 ... B + 1 with an integer running total cum of the counts before j; the located j is the
+ *   first with c[j] > 0 and h <= (double)(cum + c[j])
+ *   j == 0: mn.   j == B + 1: mx.
+ *   else f = (h - (double)cum) / (double)c[j];  v = lo + ((double)(j - 1) + f) * w;  the result is
+ *   min(max(v, mn), mx)
+ * Hence q = 0 gives mn and q = 1 gives mx exactly, and where the order statistic x_(max(ceil(h), 1)) lies in
+ * [lo, hi) the result is within one bin width w of it.  (One exception, by the rule itself: when EVERY sample
+ * lies below lo the underflow is located for every q and the answer is mn, q = 1 included; when every sample
+ * lies at or above hi it is mx.  Such a range says nothing beyond [mn, mx].)  tests/ais_hist_oracle.py
+ * restates both in numpy. */
+#define KABC_HIST_MAX_BINS 1024
+/* Adds histograms of `nbins` bins over [lo, hi) ([chain][D] each) to the open summary of `h`, into which
+ * nothing has been folded yet (else KABC_ERR_INVALID_STATE).  nbins outside 1 ... KABC_HIST_MAX_BINS, a NULL
+ * range, a bound that is not finite, lo >= hi or a scale that is not finite and positive:
+ * KABC_ERR_INVALID_ARG, the message names the chain and the parameter.  The counts are nchains * D *
+ * (nbins + 2) uint64_t from the context's pool; 2^31 counters or more: KABC_ERR_UNSUPPORTED.  Independent of
+ * kabc_ais_autocorr_begin: either, both, in either order.  kabc_ais_summary_begin (which starts over
+ * WITHOUT them), kabc_ais_summary_end and kabc_ais_destroy release them.  A summary without this call
+ * allocates, launches and returns what it always did. */
+kabc_status_t kabc_ais_hist_begin(kabc_ais_t* h, int32_t nbins, const double* lo, const double* hi);
+/* Reads them (the counts stay).  Every pointer may be NULL.  counts: [chain][D][nbins + 2]; lo, hi:
+ * [chain][D], as given.  After KABC_ERR_CANCELLED the counts are those of the generations that completed,
+ * the ones the summary's n reports.  No histogram open on the summary, or no generation folded yet:
+ * KABC_ERR_INVALID_STATE and every output is left untouched. */
+kabc_status_t kabc_ais_hist_get(kabc_ais_t* h, int32_t* nbins, uint64_t* counts, double* lo, double* hi);
+/* The quantile rule above for nq values of q from the nbins + 2 counts of one parameter.  Host arithmetic
+ * only: it needs no context and no device.  A NULL pointer, nbins outside 1 ... KABC_HIST_MAX_BINS, bounds
+ * that are not finite or not lo < hi, nq < 0, a q outside [0, 1] or NaN: KABC_ERR_INVALID_ARG; counts that
+ * sum to 0: KABC_ERR_INVALID_STATE; `out` is left untouched on every error. */
+kabc_status_t kabc_hist_quantile(const uint64_t* counts, int32_t nbins, double lo, double hi, double mn, double mx,
+                                 const double* q, int32_t nq, double* out);
+
 /* ---- the range of the stream counters -----------------------------------------------------------
  * Every draw is keyed by a 64-bit counter (include/kabc_philox.h) of which the stream address holds the
  * low 56 bits: 32 in counter word 1, 24 next to the domain byte in word 3.  A counter of 2^56 + c would

@@ -28,6 +28,7 @@ FAMILY_AIS, FAMILY_SMC, FAMILY_ABCDE, FAMILY_PFILTER, FAMILY_AIS_SMALL = 1, 2, 4
 POSTERIOR_KERNELIZED, POSTERIOR_THRESHOLD, POSTERIOR_COMMON = 1, 2, 3
 SUMMARY_AUTO, SUMMARY_FULL, SUMMARY_DIAG = 0, 1, 2   # kabc_ais_summary_begin's cov_mode
 KABC_AUTOCORR_MAX_LAG = 256                          # kabc_ais_autocorr_begin's largest maxlag
+KABC_HIST_MAX_BINS = 1024                            # kabc_ais_hist_begin's largest nbins
 
 # DeviceCost ids (include/kabc_costs.h)
 COST_GAUSS_DIST, COST_ROSENBROCK, COST_HIER_GAUSS_SIM, COST_NORMAL_MEANSTD_SIM, COST_DIRAC_SQ, \
@@ -219,6 +220,10 @@ PROTOTYPES = {
     "kabc_ais_autocorr_get": (C.c_int, [VP, C.POINTER(C.c_int32), c_double_p, c_double_p, c_double_p, c_double_p,
                                         c_double_p, c_double_p, c_double_p, C.POINTER(C.c_int32),
                                         C.POINTER(C.c_int32)]),
+    "kabc_ais_hist_begin": (C.c_int, [VP, C.c_int32, c_double_p, c_double_p]),
+    "kabc_ais_hist_get": (C.c_int, [VP, C.POINTER(C.c_int32), C.POINTER(C.c_uint64), c_double_p, c_double_p]),
+    "kabc_hist_quantile": (C.c_int, [C.POINTER(C.c_uint64), C.c_int32, C.c_double, C.c_double, C.c_double,
+                                     C.c_double, c_double_p, C.c_int32, c_double_p]),
     "kabc_ais_get_state": (C.c_int, [VP, c_double_p, c_double_p, c_double_p,
                                      C.POINTER(C.c_uint64)]),
     "kabc_ais_set_state": (C.c_int, [VP, c_double_p, c_double_p, c_double_p, C.c_uint64]),

@@ -79,17 +79,85 @@ class PosteriorSummary:
         window           Sokal's automatic window (c = 5) per parameter; tau_converged: it lies inside maxlag
         maxlag           the largest lag kept
 
+    With summary_begin(hist=...) / sample(..., hist=...), else None (and quantile() raises):
+
+        hist             marginal histogram per parameter [D][nbins], uint64 counts
+        edges            its bin edges [D][nbins + 1]: lo + j * (hi - lo) / nbins, the last one hi itself
+        underflow, overflow   samples below lo / not below hi (a NaN counts as overflow), per parameter [D]
+        quantile(q), median, interval(level)   read from the counts by kabc_hist_quantile's rule
+                         (include/kabc.h): exact at q = 0 and 1 (min and max), within one bin width of the
+                         sample's order statistic where that lies inside [lo, hi)
+
     On a batch handle every array has a leading chain axis and chain(c) gives chain c's own summary."""
 
-    def __init__(self, n, mean, cov, min, max, pivot=None, sum1=None, sum2=None, diag=False, autocorr=None):
+    def __init__(self, n, mean, cov, min, max, pivot=None, sum1=None, sum2=None, diag=False, autocorr=None,
+                 hist=None):
         self.n, self.mean, self.cov, self.min, self.max = int(n), mean, cov, min, max
         self.pivot, self.sum1, self.sum2, self.diag = pivot, sum1, sum2, bool(diag)
         # autocorr: dict of tau, ess, acf, acov, window, tau_converged, maxlag (and the raw lagsum, first, last)
         self.autocorr = autocorr
         for f in self.AUTOCORR_FIELDS:
             setattr(self, f, None if autocorr is None else autocorr.get(f))
+        # hist: dict of counts [...][D][nbins + 2] (uint64: underflow, the bins, overflow), lo, hi [...][D]
+        self.histogram = hist
 
     AUTOCORR_FIELDS = ("tau", "ess", "acf", "acov", "window", "tau_converged", "maxlag", "lagsum", "first", "last")
+
+    @property
+    def hist(self):
+        return None if self.histogram is None else self.histogram["counts"][..., 1:-1]
+
+    @property
+    def underflow(self):
+        return None if self.histogram is None else self.histogram["counts"][..., 0]
+
+    @property
+    def overflow(self):
+        return None if self.histogram is None else self.histogram["counts"][..., -1]
+
+    @property
+    def nbins(self):
+        return None if self.histogram is None else self.histogram["counts"].shape[-1] - 2
+
+    @property
+    def edges(self):
+        if self.histogram is None:
+            return None
+        lo, hi, B = self.histogram["lo"][..., None], self.histogram["hi"][..., None], self.nbins
+        e = lo + np.arange(B + 1) * ((hi - lo) / B)
+        e[..., -1] = hi[..., 0]
+        return e
+
+    def quantile(self, q):
+        """The q-quantile (q in [0, 1], a scalar or a sequence) of every parameter from its histogram:
+        [D] for a scalar q, else [D][len(q)]; a leading chain axis on a batch summary."""
+        if self.histogram is None:
+            raise ValueError(self.NO_HIST)
+        qs = np.ascontiguousarray(np.atleast_1d(np.asarray(q, dtype=np.float64)))
+        if qs.ndim != 1:
+            raise ValueError("quantile: q must be a scalar or a sequence")
+        counts = np.ascontiguousarray(self.histogram["counts"], dtype=np.uint64)
+        B = counts.shape[-1] - 2
+        lo, hi = self.histogram["lo"], self.histogram["hi"]
+        out = np.empty(lo.shape + (qs.size,))
+        lib = _lib.load()
+        for idx in np.ndindex(*lo.shape):
+            c, o = counts[idx], out[idx]
+            _lib.check(lib.kabc_hist_quantile(c.ctypes.data_as(C.POINTER(C.c_uint64)), B, float(lo[idx]),
+                                              float(hi[idx]), float(self.min[idx]), float(self.max[idx]),
+                                              qs.ctypes.data_as(cd.c_double_p), qs.size,
+                                              o.ctypes.data_as(cd.c_double_p)))
+        return out[..., 0] if np.ndim(q) == 0 else out
+
+    NO_HIST = "this summary carries no histogram: open it with summary_begin(hist=...) / sample(..., hist=...)"
+
+    @property
+    def median(self):
+        return None if self.histogram is None else self.quantile(0.5)
+
+    def interval(self, level=0.95):
+        """The central credible interval: the quantiles at (1 - level) / 2 and (1 + level) / 2, [D][2]"""
+        return self.quantile([(1.0 - level) / 2.0, (1.0 + level) / 2.0])
 
     @property
     def mcse(self):
@@ -115,8 +183,11 @@ class PosteriorSummary:
         ac = self.autocorr
         if ac is not None:
             ac = {f: (v if f == "maxlag" else pick(v)) for f, v in ac.items()}
+        hs = self.histogram
+        if hs is not None:
+            hs = {f: pick(v) for f, v in hs.items()}
         return PosteriorSummary(self.n, self.mean[c], self.cov[c], self.min[c], self.max[c], pick(self.pivot),
-                                pick(self.sum1), pick(self.sum2), self.diag, ac)
+                                pick(self.sum1), pick(self.sum2), self.diag, ac, hs)
 
     def isapprox(self, c, nsigma=2.0):
         """Particles.isapprox per parameter: |mean - c| < nsigma * std, an array of bool"""
@@ -131,7 +202,9 @@ class PosteriorSummary:
 class ChainSummaries(list):
     """sample(model, AIS(N), MCMCThreads(), Ns, Nc, summary=True): one PosteriorSummary per chain, `.pooled`
     (the chains merged on the host, in chain order, from their n, mean and cov) and `.rhat` (Gelman-Rubin's
-    potential scale reduction per parameter, from the per-chain means and variances)."""
+    potential scale reduction per parameter, from the per-chain means and variances).  With `hist`, `.pooled`
+    carries the sum of the chains' counts where every chain has the same bins bit for bit -- a range the
+    caller gave, hist=(lo, hi); the automatic range is each chain's own, and `.pooled.hist` is then None."""
 
     def __init__(self, chains):
         super().__init__(chains)
@@ -155,7 +228,25 @@ def _pool_summaries(chains):
         mean = mean + delta * (c.n / tot)
         n = tot
         mn, mx = np.minimum(mn, c.min), np.maximum(mx, c.max)
-    return PosteriorSummary(n, mean, m2 / (n - 1), mn, mx, diag=c0.diag)
+    pooled = PosteriorSummary(n, mean, m2 / (n - 1), mn, mx, diag=c0.diag, hist=_pool_histograms(chains))
+    if c0.histogram is not None and pooled.histogram is None:
+        pooled.NO_HIST = ("the chains' histograms have different ranges (the automatic range is each chain's own): "
+                          "pass hist=(lo, hi) to pool their counts")
+    return pooled
+
+
+def _pool_histograms(chains):
+    """the sum of the chains' counts where all have the same lo, hi and nbins bit for bit, else None"""
+    hs = [c.histogram for c in chains]
+    if any(h is None for h in hs):
+        return None
+    h0 = hs[0]
+    same = lambda a, b: a.shape == b.shape and a.tobytes() == b.tobytes()   # noqa: E731
+    for h in hs[1:]:
+        if h["counts"].shape != h0["counts"].shape or not same(h["lo"], h0["lo"]) or not same(h["hi"], h0["hi"]):
+            return None
+    return {"counts": np.sum(np.stack([h["counts"] for h in hs]), axis=0, dtype=np.uint64),
+            "lo": np.array(h0["lo"]), "hi": np.array(h0["hi"])}
 
 
 def _rhat(chains):
@@ -290,6 +381,65 @@ def _autocorr_maxlag(autocorr, who):
                      f"{cd.KABC_AUTOCORR_MAX_LAG}, not {autocorr!r}")
 
 
+HIST_DEFAULT_BINS = 128
+
+
+def _hist_spec(hist, who):
+    """hist: None / False (off: None), True (HIST_DEFAULT_BINS bins, automatic range), an int (that many bins,
+    automatic range), (lo, hi) or (lo, hi, nbins)  ->  (nbins, lo, hi); lo and hi are None for the automatic
+    range, else float64 arrays still to be broadcast to the handle's [chain][D] (_hist_range)"""
+    if hist is None or hist is False:
+        return None
+    bad = ValueError(f"{who}: hist must be None, a bool, a number of bins in 1 ... {cd.KABC_HIST_MAX_BINS}, "
+                     f"(lo, hi) or (lo, hi, nbins), not {hist!r}")
+    is_bins = lambda b: (isinstance(b, (int, np.integer)) and not isinstance(b, bool)   # noqa: E731
+                         and 1 <= int(b) <= cd.KABC_HIST_MAX_BINS)
+    if hist is True:
+        return HIST_DEFAULT_BINS, None, None
+    if isinstance(hist, (int, np.integer)):
+        if not is_bins(hist):
+            raise bad
+        return int(hist), None, None
+    if not isinstance(hist, (tuple, list)) or len(hist) not in (2, 3):
+        raise bad
+    nbins = HIST_DEFAULT_BINS
+    if len(hist) == 3:
+        if not is_bins(hist[2]):
+            raise bad
+        nbins = int(hist[2])
+    try:
+        lo, hi = (np.asarray(v, dtype=np.float64) for v in hist[:2])
+    except (TypeError, ValueError):
+        raise bad from None
+    if not (np.all(np.isfinite(lo)) and np.all(np.isfinite(hi))):
+        raise ValueError(f"{who}: hist: lo and hi must be finite")
+    return nbins, lo, hi
+
+
+def _hist_range(lo, hi, nchains, D, who):
+    """lo, hi (scalars, [D] or [chain][D]) as C-contiguous [nchains][D] with lo < hi everywhere"""
+    out = []
+    for name, v in (("lo", lo), ("hi", hi)):
+        if v.shape not in ((), (D,), (nchains, D)):
+            raise ValueError(f"{who}: hist: {name} must be a scalar, [D] = [{D}] or [chain][D] = [{nchains}][{D}], "
+                             f"not of shape {list(v.shape)}")
+        out.append(np.ascontiguousarray(np.broadcast_to(v, (nchains, D))))
+    if not np.all(out[0] < out[1]):
+        c, k = np.argwhere(~(out[0] < out[1]))[0]
+        raise ValueError(f"{who}: hist: chain {c}, parameter {k}: lo = {out[0][c, k]!r} is not below "
+                         f"hi = {out[1][c, k]!r}")
+    return out
+
+
+def _hist_auto_range(x):
+    """the automatic range from the walkers x [...][N][D]: with mn, mx over the walkers and s = mx - mn,
+    lo = mn - s and hi = mx + s; a parameter on which all walkers agree (s == 0) gets mn - 0.5, mx + 0.5"""
+    mn, mx = np.min(x, axis=-2), np.max(x, axis=-2)
+    s = mx - mn
+    flat = s == 0
+    return np.where(flat, mn - 0.5, mn - s), np.where(flat, mx + 0.5, mx + s)
+
+
 class AisEnsemble:
     """kabc_ais_t: the device-resident AISState (src/KissABC.jl:25-33)."""
 
@@ -385,21 +535,43 @@ class AisEnsemble:
 
     COV_MODES = {None: cd.SUMMARY_AUTO, "full": cd.SUMMARY_FULL, "diag": cd.SUMMARY_DIAG}
 
-    def summary_begin(self, cov=None, autocorr=None):
+    def summary_begin(self, cov=None, autocorr=None, hist=None):
         """Opens (or starts over) the posterior summary of this handle: advance(..., summary=True) then
         accumulates, summary() reads.  cov: "full" (the covariance matrix, up to KABC_MAX_DIM parameters),
         "diag" (the variances, any length(prior)), None (full where it exists, else diag).  autocorr: True
         (maxlag = 64) or a maximum lag adds the lagged products on the device (kabc_ais_autocorr_begin):
-        summary() then reports tau, ess and mcse per parameter."""
+        summary() then reports tau, ess and mcse per parameter.
+
+        hist adds a marginal histogram per parameter, counted on the device (kabc_ais_hist_begin): summary()
+        then reports hist, edges, underflow, overflow, quantile(q), median and interval(level).  True: 128
+        bins over the automatic range; an int: that many bins (up to KABC_HIST_MAX_BINS); (lo, hi) or
+        (lo, hi, nbins): the range [lo, hi), each a scalar, [D] or [chain][D].  The automatic range is taken
+        per chain and parameter from the walkers as they stand now: with mn, mx over them and s = mx - mn,
+        lo = mn - s and hi = mx + s (mn - 0.5, mx + 0.5 where s == 0).  It is a convention, not a guarantee:
+        a chain that has not yet spread, or drifts, leaves it, and `underflow` / `overflow` report how many
+        samples it missed.  A discrete parameter wants an explicit integer-aligned range, one bin per value:
+        (-0.5, K + 0.5, K + 1) for values 0 ... K."""
         if cov not in self.COV_MODES:
             raise ValueError(f'summary_begin: cov must be "full", "diag" or None, not {cov!r}')
         maxlag = _autocorr_maxlag(autocorr, "summary_begin")
+        spec = _hist_spec(hist, "summary_begin")
+        if spec is not None and spec[1] is not None:
+            spec = (spec[0], *_hist_range(spec[1], spec[2], self.nchains, self.D, "summary_begin"))
         _lib.check(_lib.load().kabc_ais_summary_begin(self._h, self.COV_MODES[cov]))
         self._summary_diag = cov == "diag" or (cov is None and self.D > cd.KABC_MAX_DIM)
         self._summary_maxlag = 0
+        self._summary_hist = 0
         if maxlag:
             _lib.check(_lib.load().kabc_ais_autocorr_begin(self._h, maxlag))
             self._summary_maxlag = maxlag
+        if spec is not None:
+            nbins, lo, hi = spec
+            if lo is None:
+                x = self.state()[0]
+                lo, hi = (np.ascontiguousarray(v.reshape(self.nchains, self.D)) for v in _hist_auto_range(x))
+            _lib.check(_lib.load().kabc_ais_hist_begin(self._h, nbins, lo.ctypes.data_as(cd.c_double_p),
+                                                       hi.ctypes.data_as(cd.c_double_p)))
+            self._summary_hist = nbins
         return self
 
     def summary(self):
@@ -413,7 +585,21 @@ class AisEnsemble:
         p = lambda a: a.ctypes.data_as(cd.c_double_p)                             # noqa: E731
         _lib.check(_lib.load().kabc_ais_summary_get(self._h, C.byref(n), p(pivot), p(sum1), p(sum2), p(mean),
                                                     p(cov), p(mn), p(mx)))
-        return PosteriorSummary(n.value, mean, cov, mn, mx, pivot, sum1, sum2, diag, self._autocorr(lead))
+        return PosteriorSummary(n.value, mean, cov, mn, mx, pivot, sum1, sum2, diag, self._autocorr(lead),
+                                self._histogram(lead))
+
+    def _histogram(self, lead):
+        """kabc_ais_hist_get of the open summary as PosteriorSummary's dict, None without hist"""
+        B = getattr(self, "_summary_hist", 0)
+        if not B:
+            return None
+        nb = C.c_int32()
+        counts = np.zeros(lead + (self.D, B + 2), dtype=np.uint64)
+        lo, hi = np.empty(lead + (self.D,)), np.empty(lead + (self.D,))
+        _lib.check(_lib.load().kabc_ais_hist_get(self._h, C.byref(nb), counts.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                 lo.ctypes.data_as(cd.c_double_p), hi.ctypes.data_as(cd.c_double_p)))
+        assert nb.value == B, (nb.value, B)
+        return {"counts": counts, "lo": lo, "hi": hi}
 
     def _autocorr(self, lead):
         """kabc_ais_autocorr_get of the open summary as PosteriorSummary's dict, None without autocorr"""
@@ -557,7 +743,7 @@ def _bundle(samples, scalar):
 
 
 def _sample_chains(model, N, Ns, seeds, costs, ntransitions, discard_initial, retry_sampling, ctx, ens=None,
-                   summary=False, autocorr=None):
+                   summary=False, autocorr=None, hist=None):
     """len(seeds) independent chains of AIS(N) in ONE batch handle (costs: one DeviceCost per chain, or
     None; ens: that handle where the caller has created it, closed here): the first Ns samples of each,
     [Nc][Ns][D], and the handle's driver; summary: the chains' PosteriorSummary (leading chain axis) in place
@@ -568,7 +754,7 @@ def _sample_chains(model, N, Ns, seeds, costs, ntransitions, discard_initial, re
     gk = max(1, -(-Ns // N))
     if summary:
         try:
-            return _summarise(ens, gk, N, ntransitions, discard_initial, retry_sampling, autocorr), ens.driver
+            return _summarise(ens, gk, N, ntransitions, discard_initial, retry_sampling, autocorr, hist), ens.driver
         finally:
             ens.close()
     big = gk * Nc * N * D * 8 > (1 << 20)   # (a small trace is not worth a helper thread: see sample)
@@ -590,22 +776,31 @@ def _sample_chains(model, N, Ns, seeds, costs, ntransitions, discard_initial, re
     return chains, driver
 
 
-def _summarise(ens, gk, N, ntransitions, discard_initial, retry_sampling, autocorr=None):
+def _summarise(ens, gk, N, ntransitions, discard_initial, retry_sampling, autocorr=None, hist=None):
     """sample()'s course on `ens` with the kept generations summarised on the device"""
     ens.init(retry_sampling)
     gd = -(-int(discard_initial) // N)
     if gd:
         ens.advance(gd, ntransitions)
-    if autocorr:
-        ens.summary_begin(autocorr=autocorr)
-    else:
-        ens.summary_begin()
+    bkw = {"autocorr": autocorr} if autocorr else {}
+    if hist is not None and hist is not False:
+        bkw["hist"] = hist
+    ens.summary_begin(**bkw)
     ens.advance(gk, ntransitions, summary=True)
     return ens.summary()
 
 
+def _chain_kw(kw, c, nchains, D):
+    """sample()'s summary keywords for chain c alone: a [chain][D] range of `hist` gives its row c"""
+    spec = _hist_spec(kw.get("hist"), "sample")
+    if spec is None or spec[1] is None:
+        return kw
+    row = lambda v: v[c] if v.shape == (nchains, D) else v   # noqa: E731
+    return dict(kw, hist=(row(spec[1]), row(spec[2]), spec[0]))
+
+
 def sample(model, spl, *args, ntransitions=1, discard_initial=0, retry_sampling=100, seed=0,
-           progress=False, ctx=None, return_array=False, summary=False, autocorr=None, **kwargs):
+           progress=False, ctx=None, return_array=False, summary=False, autocorr=None, hist=None, **kwargs):
     """sample(model, AIS(N), Ns; ...) and sample(model, AIS(N), MCMCThreads(), Ns, Nc; ...).
 
     The device advances a whole generation (every walker `ntransitions` times) per
@@ -619,7 +814,12 @@ def sample(model, spl, *args, ntransitions=1, discard_initial=0, retry_sampling=
     first Ns).  With MCMCThreads it returns a ChainSummaries: one PosteriorSummary per chain, `.pooled` and
     `.rhat`.  It excludes return_array.  `autocorr=True` (maxlag = 64) or a maximum lag adds tau, ess and mcse
     per parameter to the summary (per chain with MCMCThreads, whose `.ess` is the chains' sum); it needs
-    summary=True.
+    summary=True.  `hist` (True: 128 bins, an int, (lo, hi) or (lo, hi, nbins): AisEnsemble.summary_begin) adds
+    a marginal histogram per parameter and with it quantile(q), median and interval(level); it needs
+    summary=True too.  Its automatic range is taken from the walkers after discard_initial -- a convention,
+    not a guarantee: `underflow` and `overflow` report what it missed, and a discrete parameter wants an
+    explicit integer-aligned range such as (-0.5, K + 0.5, K + 1).  With MCMCThreads every chain has its own
+    range, and `.pooled` carries a histogram only for a range the caller gave.
     """
     if not isinstance(spl, AIS):
         raise TypeError("sampler must be AIS(nparticles)")
@@ -627,7 +827,11 @@ def sample(model, spl, *args, ntransitions=1, discard_initial=0, retry_sampling=
         raise ValueError("sample: summary=True returns moments, not samples; it excludes return_array")
     if _autocorr_maxlag(autocorr, "sample") and not summary:
         raise ValueError("sample: autocorr is part of the device summary; it needs summary=True")
+    if _hist_spec(hist, "sample") is not None and not summary:
+        raise ValueError("sample: hist is part of the device summary; it needs summary=True")
     akw = {"autocorr": autocorr} if _autocorr_maxlag(autocorr, "sample") else {}
+    if _hist_spec(hist, "sample") is not None:
+        akw["hist"] = hist
     if args and isinstance(args[0], MCMCThreads):
         # chains are a grid dimension of ONE device handle: every launch advances all Nc
         # ensembles (kabc_ais_create_batch); chain c is bit-identical to a single-chain run
@@ -650,8 +854,9 @@ def sample(model, spl, *args, ntransitions=1, discard_initial=0, retry_sampling=
                                          discard_initial, retry_sampling, ctx, ens=ens, summary=True, **akw)
                 return ChainSummaries(both.chain(c) for c in range(Nc))
             return ChainSummaries(sample(model, spl, Ns, ntransitions=ntransitions, discard_initial=discard_initial,
-                                         retry_sampling=retry_sampling, seed=sd, ctx=ctx, summary=True, **akw)
-                                  for sd in seeds)
+                                         retry_sampling=retry_sampling, seed=sd, ctx=ctx, summary=True,
+                                         **_chain_kw(akw, c, Nc, D))
+                                  for c, sd in enumerate(seeds))
         if ens is not None:
             chains, _ = _sample_chains(model, spl.nparticles, Ns, seeds, None, ntransitions,
                                        discard_initial, retry_sampling, ctx, ens=ens)
@@ -668,7 +873,8 @@ def sample(model, spl, *args, ntransitions=1, discard_initial=0, retry_sampling=
     gk = max(1, -(-Ns // N))
     if summary:
         try:
-            return _summarise(ens, gk, N, ntransitions, discard_initial, retry_sampling, akw.get("autocorr"))
+            return _summarise(ens, gk, N, ntransitions, discard_initial, retry_sampling, akw.get("autocorr"),
+                              akw.get("hist"))
         finally:
             ens.close()
     shape = (gk, N, len(model))
@@ -714,7 +920,8 @@ def _model_difference(m, m0):
 
 
 def sample_batch(model, spl, Ns, nruns=None, *, seeds=None, seed=0, ntransitions=1, discard_initial=0,
-                 retry_sampling=100, ctx=None, return_array=False, course=None, summary=False, autocorr=None):
+                 retry_sampling=100, ctx=None, return_array=False, course=None, summary=False, autocorr=None,
+                 hist=None):
     """One model fitted to many datasets, or one dataset under many seeds, in one call: run r is
     sample(model_r, spl, Ns, seed=seeds[r], <the same keywords>), bit for bit.
 
@@ -729,7 +936,7 @@ def sample_batch(model, spl, Ns, nruns=None, *, seeds=None, seed=0, ntransitions
     fits one workgroup's LDS (csrc/ais_dyn_small_kernel.hpp) -- and raises KabcError where the shape is
     refused; "sequential" forces the loop of sample() calls.  Same bits on either course.  Returns a list with one entry per run; its `.info` holds the course, the driver,
     nruns and the wall time.  `summary=True` gives one PosteriorSummary per run in place of its samples, on
-    either course (sample's own summary=True: n = ceil(Ns/N) * N per run; `autocorr` as in sample).  A failed initial draw raises KabcError("run r: <the reference's message>");
+    either course (sample's own summary=True: n = ceil(Ns/N) * N per run; `autocorr` and `hist` as in sample, a [run][D] range of `hist` giving run r its row).  A failed initial draw raises KabcError("run r: <the reference's message>");
     Context.cancel() / Ctrl-C behave as they do for sample()."""
     if not isinstance(spl, AIS):
         raise TypeError("sampler must be AIS(nparticles)")
@@ -739,6 +946,8 @@ def sample_batch(model, spl, Ns, nruns=None, *, seeds=None, seed=0, ntransitions
         raise ValueError("sample_batch: summary=True returns moments, not samples; it excludes return_array")
     if _autocorr_maxlag(autocorr, "sample_batch") and not summary:
         raise ValueError("sample_batch: autocorr is part of the device summary; it needs summary=True")
+    if _hist_spec(hist, "sample_batch") is not None and not summary:
+        raise ValueError("sample_batch: hist is part of the device summary; it needs summary=True")
     if isinstance(model, _ApproxModel):
         if nruns is None:
             raise ValueError("sample_batch: nruns is required with a single model")
@@ -767,6 +976,8 @@ def sample_batch(model, spl, Ns, nruns=None, *, seeds=None, seed=0, ntransitions
     skw = {"summary": True} if summary else {}
     if summary and _autocorr_maxlag(autocorr, "sample_batch"):
         skw["autocorr"] = autocorr
+    if summary and _hist_spec(hist, "sample_batch") is not None:
+        skw["hist"] = hist
     t0 = time.perf_counter()
     chains, driver = None, None
     if course == "grid" or (course is None and D <= cd.KABC_MAX_DIM):
@@ -791,7 +1002,8 @@ def sample_batch(model, spl, Ns, nruns=None, *, seeds=None, seed=0, ntransitions
         out = AisBatchResult()
         for r, m in enumerate(models):
             try:
-                out.append(sample(m, spl, Ns, seed=seeds[r], ctx=ctx, return_array=return_array, **kw, **skw))
+                out.append(sample(m, spl, Ns, seed=seeds[r], ctx=ctx, return_array=return_array, **kw,
+                                  **_chain_kw(skw, r, nruns, D)))
             except _lib.Cancelled:
                 raise
             except _lib.KabcError as e:

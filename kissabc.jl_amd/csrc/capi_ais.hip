@@ -17,6 +17,7 @@
 #include "ais_small_kernel.hpp"
 #include "ais_summary_kernel.hpp"
 #include "ais_autocorr_kernel.hpp"
+#include "ais_hist_kernel.hpp"
 #include "host_common.hpp"
 #include "plugin_registry.hpp"
 
@@ -261,6 +262,13 @@ struct kabc_ais {
     int64_t* d_ac_gens = nullptr;
     double* d_ac_out = nullptr;
     double* d_ac_lvl[2] = {};
+    // ... and its histograms (kabc_ais_hist_begin, ais_hist_kernel.hpp): the counts [chain][D][B + 2] and the
+    // range [3][chain][D] (lo, hi, scale) on the device, from the context's pool; the range as given, on the host
+    DevBufs hist_bufs;
+    int32_t hist_B = 0;             // nbins, 0: none open
+    unsigned long long* d_hist_counts = nullptr;
+    double* d_hist_range = nullptr;
+    std::vector<double> hist_range;  // [3][chain][D]
     // debug records (tests)
     int32_t* d_dbg = nullptr;
     int64_t dbg_cap = 0;  // in int32 units
@@ -1398,6 +1406,15 @@ static kabc_status_t ensure_blk_events(kabc_ais_t* h) {
     return KABC_OK;
 }
 
+// which of the two counting kernels takes this handle's blocks: ais_hist_direct()'s shape rule, or what
+// KABC_HIST_PATH=lds / direct says (the counts are the same: tools/ais_hist_probe.py times both)
+static bool hist_direct(const kabc_ais_t* h) {
+    const char* e = std::getenv("KABC_HIST_PATH");
+    if (e && !std::strcmp(e, "lds")) return false;
+    if (e && !std::strcmp(e, "direct")) return true;
+    return ais_hist_direct(h->N, h->D);
+}
+
 // folds `gc` generations of a device trace block ([g][chain][N][D]) into the handle's open summary, behind
 // the kernels that wrote them on the handle's stream; `done`: device count of the generations that ran, or
 // NULL.  The first block since begin supplies the pivot: row 0 of its first generation, per chain.
@@ -1435,6 +1452,21 @@ static kabc_status_t summary_fold(kabc_ais_t* h, const double* trace, int64_t gc
         c.nchains = h->nchains;
         c.L = h->ac_L;
         launch_ais_autocorr_accumulate(c, h->d_ac_gens, s);
+        KABC_HIP_CHECK(hipGetLastError());
+    }
+    if (h->hist_B) {  // ... and into the histograms
+        AisHistArgs c;
+        std::memset(&c, 0, sizeof c);
+        c.trace = trace;
+        c.counts = h->d_hist_counts;
+        c.range = h->d_hist_range;
+        c.done = done;
+        c.N = h->N;
+        c.gc = gc;
+        c.D = h->D;
+        c.nchains = h->nchains;
+        c.B = h->hist_B;
+        launch_ais_hist_accumulate(c, hist_direct(h), s);
         KABC_HIP_CHECK(hipGetLastError());
     }
     return KABC_OK;
@@ -1961,8 +1993,17 @@ static void autocorr_release(kabc_ais_t* h) {
     h->ac_L = 0;
 }
 
+static void hist_release(kabc_ais_t* h) {
+    h->hist_bufs.release();
+    h->d_hist_counts = nullptr;
+    h->d_hist_range = nullptr;
+    h->hist_range.clear();
+    h->hist_B = 0;
+}
+
 static void summary_release(kabc_ais_t* h) {
     autocorr_release(h);
+    hist_release(h);
     h->sum_bufs.release();
     h->d_sum_acc = h->d_sum_pivot = h->d_sum_out = h->d_sum_lvl[0] = h->d_sum_lvl[1] = nullptr;
     h->sum_mode = h->sum_slots = 0;
@@ -2240,6 +2281,154 @@ kabc_status_t kabc_ais_autocorr_get(kabc_ais_t* h, int32_t* nlags, double* lagsu
             if (window) window[c * D + k] = win;
             if (converged) converged[c * D + k] = conv;
         }
+    }
+    return KABC_OK;
+}
+
+// ---- histograms of the summarised trace (ais_hist_kernel.hpp) -----------------------------------------
+
+kabc_status_t kabc_ais_hist_begin(kabc_ais_t* h, int32_t nbins, const double* lo, const double* hi) {
+    if (kabc_status_t st = summary_check(h, "kabc_ais_hist_begin", true)) return st;
+    if (nbins < 1 || nbins > KABC_HIST_MAX_BINS) {
+        set_error("kabc_ais_hist_begin: nbins %d is outside 1 ... %d", nbins, KABC_HIST_MAX_BINS);
+        return KABC_ERR_INVALID_ARG;
+    }
+    if (!lo || !hi) {
+        set_error("kabc_ais_hist_begin: lo and hi must be non-NULL ([chain][D] each)");
+        return KABC_ERR_INVALID_ARG;
+    }
+    const size_t nchD = (size_t)h->nchains * (size_t)h->D;
+    std::vector<double> range(3 * nchD);
+    for (size_t i = 0; i < nchD; ++i) {
+        const int c = (int)(i / (size_t)h->D), k = (int)(i % (size_t)h->D);
+        const double width = hi[i] - lo[i];
+        const double scale = (double)nbins / width;
+        if (!std::isfinite(lo[i]) || !std::isfinite(hi[i]) || !(lo[i] < hi[i])) {
+            set_error("kabc_ais_hist_begin: chain %d, parameter %d: the range [%g, %g) needs finite bounds with "
+                      "lo < hi", c, k, lo[i], hi[i]);
+            return KABC_ERR_INVALID_ARG;
+        }
+        if (!std::isfinite(scale) || !(scale > 0.0)) {
+            set_error("kabc_ais_hist_begin: chain %d, parameter %d: nbins / (hi - lo) = %d / (%g - %g) = %g is not "
+                      "finite and positive", c, k, nbins, hi[i], lo[i], scale);
+            return KABC_ERR_INVALID_ARG;
+        }
+        range[i] = lo[i];
+        range[nchD + i] = hi[i];
+        range[2 * nchD + i] = scale;
+    }
+    if (h->sum_gens != 0 || h->sum_pivot) {
+        set_error("kabc_ais_hist_begin: the open summary already holds generations; the histograms start with "
+                  "the summary (kabc_ais_summary_begin, then this call)");
+        return KABC_ERR_INVALID_STATE;
+    }
+    const int64_t nwords = (int64_t)nchD * (nbins + 2);
+    if (nwords >= (1ll << 31)) {
+        set_error("kabc_ais_hist_begin: %d chains x %d parameters x (%d + 2) counters (%.1f GiB of counts) is "
+                  "beyond what one launch grid and the pool serve", h->nchains, h->D, nbins,
+                  (double)nwords * 8.0 / (double)(1ll << 30));
+        return KABC_ERR_UNSUPPORTED;
+    }
+    KABC_HIP_CHECK(hipSetDevice(h->ctx->device));
+    hipStream_t s = h->ctx->stream;
+    if (h->hist_B) {  // (begin again: its buffers may still be read by queued work)
+        KABC_HIP_CHECK(hipStreamSynchronize(s));
+        hist_release(h);
+    }
+    h->hist_bufs.ctx = h->ctx;
+    h->hist_range.swap(range);  // (the source of the copy below lives as long as the histogram)
+    hipError_t e = h->hist_bufs.alloc(&h->d_hist_counts, (size_t)nwords);
+    if (e == hipSuccess) e = h->hist_bufs.alloc(&h->d_hist_range, 3 * nchD);
+    // pool buffers come back dirty: the counts start at 0
+    if (e == hipSuccess) e = hipMemsetAsync(h->d_hist_counts, 0, sizeof(unsigned long long) * (size_t)nwords, s);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(h->d_hist_range, h->hist_range.data(), sizeof(double) * 3 * nchD, hipMemcpyHostToDevice, s);
+    if (e != hipSuccess) {
+        hist_release(h);
+        KABC_HIP_CHECK(e);
+    }
+    h->hist_B = nbins;
+    return KABC_OK;
+}
+
+kabc_status_t kabc_ais_hist_get(kabc_ais_t* h, int32_t* nbins, uint64_t* counts, double* lo, double* hi) {
+    if (kabc_status_t st = summary_check(h, "kabc_ais_hist_get", true)) return st;
+    if (!h->hist_B) {
+        set_error("kabc_ais_hist_get: the open summary keeps no histograms (kabc_ais_hist_begin)");
+        return KABC_ERR_INVALID_STATE;
+    }
+    if (h->sum_gens == 0) {
+        set_error("kabc_ais_hist_get: the summary holds no generation yet (n = 0)");
+        return KABC_ERR_INVALID_STATE;
+    }
+    const size_t nchD = (size_t)h->nchains * (size_t)h->D;
+    if (counts) {
+        static_assert(sizeof(uint64_t) == sizeof(unsigned long long), "the counts are 64-bit words");
+        KABC_HIP_CHECK(hipSetDevice(h->ctx->device));
+        hipStream_t s = h->ctx->stream;
+        KABC_HIP_CHECK(hipMemcpyAsync(counts, h->d_hist_counts, sizeof(uint64_t) * nchD * (size_t)(h->hist_B + 2),
+                                      hipMemcpyDeviceToHost, s));
+        KABC_HIP_CHECK(hipStreamSynchronize(s));
+    }
+    if (nbins) *nbins = h->hist_B;
+    if (lo) std::memcpy(lo, h->hist_range.data(), sizeof(double) * nchD);
+    if (hi) std::memcpy(hi, h->hist_range.data() + nchD, sizeof(double) * nchD);
+    return KABC_OK;
+}
+
+kabc_status_t kabc_hist_quantile(const uint64_t* counts, int32_t nbins, double lo, double hi, double mn, double mx,
+                                 const double* q, int32_t nq, double* out) {
+    if (!counts || (nq > 0 && (!q || !out))) {
+        set_error("kabc_hist_quantile: counts, q and out must be non-NULL");
+        return KABC_ERR_INVALID_ARG;
+    }
+    if (nbins < 1 || nbins > KABC_HIST_MAX_BINS) {
+        set_error("kabc_hist_quantile: nbins %d is outside 1 ... %d", nbins, KABC_HIST_MAX_BINS);
+        return KABC_ERR_INVALID_ARG;
+    }
+    if (!std::isfinite(lo) || !std::isfinite(hi) || !(lo < hi)) {
+        set_error("kabc_hist_quantile: the range [%g, %g) needs finite bounds with lo < hi", lo, hi);
+        return KABC_ERR_INVALID_ARG;
+    }
+    if (nq < 0) {
+        set_error("kabc_hist_quantile: nq = %d is negative", nq);
+        return KABC_ERR_INVALID_ARG;
+    }
+    for (int32_t i = 0; i < nq; ++i)
+        if (!(q[i] >= 0.0 && q[i] <= 1.0)) {
+            set_error("kabc_hist_quantile: q[%d] = %g is outside [0, 1]", i, q[i]);
+            return KABC_ERR_INVALID_ARG;
+        }
+    const int B = nbins;
+    uint64_t n = 0;
+    for (int j = 0; j < B + 2; ++j) n += counts[j];
+    if (n == 0) {
+        set_error("kabc_hist_quantile: the counts sum to 0 (n = 0)");
+        return KABC_ERR_INVALID_STATE;
+    }
+    const double span = hi - lo;
+    const double w = span / (double)B;
+    for (int32_t i = 0; i < nq; ++i) {
+        const double hq = q[i] * (double)n;
+        uint64_t cum = 0;
+        int j = 0;
+        for (; j < B + 1; ++j) {  // (h <= n: the last non-empty counter is located at the latest)
+            if (counts[j] > 0 && hq <= (double)(cum + counts[j])) break;
+            cum += counts[j];
+        }
+        double v;
+        if (j == 0) v = mn;
+        else if (j == B + 1) v = mx;
+        else {
+            const double num = hq - (double)cum;
+            const double f = num / (double)counts[j];
+            const double pos = (double)(j - 1) + f;
+            const double off = pos * w;
+            v = lo + off;
+            v = v > mn ? v : mn;
+            v = v < mx ? v : mx;
+        }
+        out[i] = v;
     }
     return KABC_OK;
 }
