@@ -830,6 +830,72 @@ kabc_status_t kabc_ais_hist_get(kabc_ais_t* h, int32_t* nbins, uint64_t* counts,
 kabc_status_t kabc_hist_quantile(const uint64_t* counts, int32_t nbins, double lo, double hi, double mn, double mx,
                                  const double* q, int32_t nq, double* out);
 
+/* ---- user-defined derived quantities g(theta) of a summarised trace ----------------------------
+ *
+ * The reference returns Particles, and Particles are pushed through functions: P[1] / P[2], P[1] > P[2],
+ * sqrt(P[1]^2 + P[2]^2).  The moments, lagged products and histograms above answer for the coordinates only;
+ * the covariance gives linear functions of them and the marginals give none.  An open summary can carry a
+ * SECOND set of accumulators over G values computed from every trace row by a C snippet of the caller:
+ *
+ *   KABC_HD void kabc_user_derived(const double* x, int D, const double* params, int nparams,
+ *                                  double* g, int G);
+ *
+ *   x       one row of the trace: exactly the D values kabc_ais_advance would have put at
+ *           out_samples[g][i][0 ... D - 1] for that walker and generation
+ *   params  the nparams doubles given with the snippet's use (kabc_derived_eval, kabc_ais_derived_begin)
+ *   g       the function writes ALL G entries, 1 <= G <= KABC_MAX_DIM_DYN; it may read back what it wrote
+ * The function has no random stream: posterior-predictive draws are not its business.  It is compiled like
+ * a cost snippet -- -ffp-contract=off, no fast-math, kabc_math.h available -- so a snippet made of + - * /,
+ * kabc_sqrt and comparisons has ONE fp64 result, whichever kernel form, launch or sub-block computes the row.
+ *
+ * The derived set is the summary's own definition applied to the rows g[gen][i][0 ... G - 1] in place of
+ * r[gen][i][0 ... D - 1]: the same pivot rule (row 0 of the first folded generation, mapped), the same
+ * sequential per-row sums, row tree, lagged products, counters and finalisations, with G for D, and the same
+ * n.  "Full" covariance follows the parameters' rule: up to KABC_MAX_DIM derived values, variances beyond.
+ * A value that is not finite goes where those definitions already send one: a NaN propagates into that
+ * quantity's sums (S1, S2 and the lagged products; `r < mn` and `r > mx` are false for it, so min and max
+ * pass it over), and a NaN pivot -- a NaN in row 0 of the first generation -- makes every deviation of that
+ * quantity NaN; +inf and -inf give inf - inf = NaN in the sums once both a pivot and a value are infinite.
+ * In the histogram a NaN and +inf are counted in the overflow (!(r < hi)), -inf in the underflow (r < lo),
+ * so the counts still sum to n.  tests/ais_derived_oracle.py composes the three numpy oracles with a
+ * restatement of the test snippets. */
+/* Registers a snippet.  It is checked at once, with the function called the way the kernel calls it: a
+ * missing kabc_user_derived or a syntax error gives KABC_ERR_INVALID_ARG with the compiler's message in
+ * kabc_last_error (no hipRTC: KABC_ERR_DEVICE).  The same text registered again gives the same id.  Needs
+ * no device; the map kernel is compiled at its first use on one. */
+kabc_status_t kabc_compile_derived(const char* src, int32_t* out_id);
+/* Compiles the map kernel of a registered snippet now, on the current device (1-3 s, else at its first use).
+ * Without a device the code object is still produced and only its load fails: KABC_ERR_DEVICE with a message
+ * that says the kernels compiled.  An id that is not registered: KABC_ERR_INVALID_ARG. */
+kabc_status_t kabc_derived_precompile(int32_t id);
+/* The map over n rows the caller gives: out[i][0 ... G - 1] = g(theta[i][0 ... D - 1]) (host arrays), in
+ * launches of KABC_EVAL_ROWS rows; the same bits whatever the launch size.  A cancel request between
+ * launches: KABC_ERR_CANCELLED, `out` unspecified. */
+kabc_status_t kabc_derived_eval(kabc_ctx_t* ctx, int32_t id, int32_t D, int32_t G, int64_t n, const double* theta,
+                                const double* params, int32_t nparams, double* out);
+/* Adds the derived set to the open summary of `h`, into which nothing has been folded yet (else
+ * KABC_ERR_INVALID_STATE; no summary open: KABC_ERR_INVALID_STATE too).  cov_mode as in
+ * kabc_ais_summary_begin, with G for length(prior).  maxlag = 0: no lagged products, else as
+ * kabc_ais_autocorr_begin; nbins = 0: no histograms, else as kabc_ais_hist_begin with lo, hi [chain][G]
+ * (NULL with nbins > 0: KABC_ERR_INVALID_ARG).  G outside 1 ... KABC_MAX_DIM_DYN, an id that is not
+ * registered, a NULL params with nparams > 0: KABC_ERR_INVALID_ARG.  params is copied.  Every
+ * kabc_ais_advance_summary then maps each trace block on the device into a pooled buffer of at most 32 MiB
+ * (or one generation, if that is more; a longer block goes through it in sub-blocks of whole generations,
+ * which changes no bit) and folds it into the second set behind the first.  kabc_ais_summary_begin (which
+ * starts over WITHOUT it), kabc_ais_summary_end and kabc_ais_destroy release it.  A summary without this
+ * call allocates, launches and returns what it always did.  Sharded handles: as kabc_ais_summary_begin. */
+kabc_status_t kabc_ais_derived_begin(kabc_ais_t* h, int32_t id, int32_t G, const double* params, int32_t nparams,
+                                     int32_t cov_mode, int32_t maxlag, int32_t nbins, const double* lo,
+                                     const double* hi);
+/* kabc_ais_summary_get, kabc_ais_autocorr_get and kabc_ais_hist_get of the derived set: the same arrays with
+ * G for D, the same n.  No derived set open: KABC_ERR_INVALID_STATE and every output is left untouched. */
+kabc_status_t kabc_ais_derived_summary_get(kabc_ais_t* h, int64_t* n, double* pivot, double* sum1, double* sum2,
+                                           double* mean, double* cov, double* mn, double* mx);
+kabc_status_t kabc_ais_derived_autocorr_get(kabc_ais_t* h, int32_t* nlags, double* lagsum, double* first,
+                                            double* last, double* acov, double* rho, double* tau, double* ess,
+                                            int32_t* window, int32_t* converged);
+kabc_status_t kabc_ais_derived_hist_get(kabc_ais_t* h, int32_t* nbins, uint64_t* counts, double* lo, double* hi);
+
 /* ---- the range of the stream counters -----------------------------------------------------------
  * Every draw is keyed by a 64-bit counter (include/kabc_philox.h) of which the stream address holds the
  * low 56 bits: 32 in counter word 1, 24 next to the domain byte in word 3.  A counter of 2^56 + c would

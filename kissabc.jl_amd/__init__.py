@@ -13,6 +13,7 @@ from .api import (ABCDE, ABCDE_batch, AIS, AisEnsemble, ApproxKernelizedPosterio
 from . import comm
 from .comm import Comm, EnsembleGroup
 from .costs import DeviceCost
+from .derived import Derived
 from .distributions import (Ar1Normal, Beta, Dirichlet, DiscreteUniform, Exponential, Factored, Gamma, InitFromSnippet,
                             LogNormal, MultivariateNormal, MvNormal, NegativeBinomial, Normal, Product,
                             Laplace, Poisson, Truncated, TruncatedGamma, TruncatedNormal, Uniform, UserInit,
@@ -21,7 +22,7 @@ from .distributions import (Ar1Normal, Beta, Dirichlet, DiscreteUniform, Exponen
 __all__ = [
     "ABCDE", "ABCDE_batch", "AIS", "AisEnsemble", "ApproxKernelizedPosterior", "ApproxPosterior", "CommonLogDensity",
     "MCMCThreads", "abc_reject", "abc_reject_batch", "pfilter", "pfilter_batch", "prior_predictive",
-    "AbcdeState", "ChainSummaries", "Particles", "PosteriorSummary", "PfilterState", "SmcState", "sample", "sample_batch", "smc", "smc_batch", "DeviceCost", "costs", "Factored", "Uniform", "Normal",
+    "AbcdeState", "ChainSummaries", "Particles", "PosteriorSummary", "PfilterState", "SmcState", "sample", "sample_batch", "smc", "smc_batch", "DeviceCost", "Derived", "costs", "Factored", "Uniform", "Normal",
     "Truncated", "truncated", "TruncatedNormal", "Beta", "DiscreteUniform", "NegativeBinomial",
     "Exponential", "Gamma", "LogNormal", "Product", "MvNormal", "MultivariateNormal", "Context", "KabcError", "Cancelled", "default_context", "LIB_PATH",
     "KABC_MAX_DIM", "comm", "Comm", "EnsembleGroup", "UserInit", "InitFromSnippet",

@@ -224,6 +224,19 @@ PROTOTYPES = {
     "kabc_ais_hist_get": (C.c_int, [VP, C.POINTER(C.c_int32), C.POINTER(C.c_uint64), c_double_p, c_double_p]),
     "kabc_hist_quantile": (C.c_int, [C.POINTER(C.c_uint64), C.c_int32, C.c_double, C.c_double, C.c_double,
                                      C.c_double, c_double_p, C.c_int32, c_double_p]),
+    "kabc_compile_derived": (C.c_int, [C.c_char_p, C.POINTER(C.c_int32)]),
+    "kabc_derived_precompile": (C.c_int, [C.c_int32]),
+    "kabc_derived_eval": (C.c_int, [VP, C.c_int32, C.c_int32, C.c_int32, C.c_int64, c_double_p, c_double_p,
+                                    C.c_int32, c_double_p]),
+    "kabc_ais_derived_begin": (C.c_int, [VP, C.c_int32, C.c_int32, c_double_p, C.c_int32, C.c_int32, C.c_int32,
+                                         C.c_int32, c_double_p, c_double_p]),
+    "kabc_ais_derived_summary_get": (C.c_int, [VP, C.POINTER(C.c_int64), c_double_p, c_double_p, c_double_p,
+                                               c_double_p, c_double_p, c_double_p, c_double_p]),
+    "kabc_ais_derived_autocorr_get": (C.c_int, [VP, C.POINTER(C.c_int32), c_double_p, c_double_p, c_double_p,
+                                                c_double_p, c_double_p, c_double_p, c_double_p,
+                                                C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "kabc_ais_derived_hist_get": (C.c_int, [VP, C.POINTER(C.c_int32), C.POINTER(C.c_uint64), c_double_p,
+                                            c_double_p]),
     "kabc_ais_get_state": (C.c_int, [VP, c_double_p, c_double_p, c_double_p,
                                      C.POINTER(C.c_uint64)]),
     "kabc_ais_set_state": (C.c_int, [VP, c_double_p, c_double_p, c_double_p, C.c_uint64]),

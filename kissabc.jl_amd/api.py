@@ -79,6 +79,11 @@ class PosteriorSummary:
         window           Sokal's automatic window (c = 5) per parameter; tau_converged: it lies inside maxlag
         maxlag           the largest lag kept
 
+    With summary_begin(derived=d) / sample(..., derived=d), else None:
+
+        derived          a PosteriorSummary of its own over d's G quantities of every trace row, with every field
+                         and method listed here and `.names`, d's labels (`names` is None on the parameters' own)
+
     With summary_begin(hist=...) / sample(..., hist=...), else None (and quantile() raises):
 
         hist             marginal histogram per parameter [D][nbins], uint64 counts
@@ -100,6 +105,10 @@ class PosteriorSummary:
             setattr(self, f, None if autocorr is None else autocorr.get(f))
         # hist: dict of counts [...][D][nbins + 2] (uint64: underflow, the bins, overflow), lo, hi [...][D]
         self.histogram = hist
+        # derived: the PosteriorSummary over a Derived's G quantities (summary_begin(derived=...)), its labels
+        # in its `.names`; None on a summary without one
+        self.derived = None
+        self.names = None
 
     AUTOCORR_FIELDS = ("tau", "ess", "acf", "acov", "window", "tau_converged", "maxlag", "lagsum", "first", "last")
 
@@ -186,8 +195,12 @@ class PosteriorSummary:
         hs = self.histogram
         if hs is not None:
             hs = {f: pick(v) for f, v in hs.items()}
-        return PosteriorSummary(self.n, self.mean[c], self.cov[c], self.min[c], self.max[c], pick(self.pivot),
-                                pick(self.sum1), pick(self.sum2), self.diag, ac, hs)
+        out = PosteriorSummary(self.n, self.mean[c], self.cov[c], self.min[c], self.max[c], pick(self.pivot),
+                               pick(self.sum1), pick(self.sum2), self.diag, ac, hs)
+        out.names = self.names
+        if self.derived is not None:
+            out.derived = self.derived.chain(c)
+        return out
 
     def isapprox(self, c, nsigma=2.0):
         """Particles.isapprox per parameter: |mean - c| < nsigma * std, an array of bool"""
@@ -212,6 +225,13 @@ class ChainSummaries(list):
         self.rhat = _rhat(self)
         # with autocorr: the chains are independent, so their effective sample sizes add (pooled.tau stays None)
         self.ess = None if self[0].ess is None else np.sum(np.stack([c.ess for c in self]), axis=0)
+        # with derived: the chains' derived summaries pooled by this same code -- `.derived` is their
+        # ChainSummaries (its .pooled, .rhat and .ess), and `.pooled.derived` its pooled summary
+        self.derived = None
+        if all(c.derived is not None for c in self):
+            self.derived = ChainSummaries(c.derived for c in self)
+            self.derived.pooled.names = self[0].derived.names
+            self.pooled.derived = self.derived.pooled
 
 
 def _pool_summaries(chains):
@@ -431,6 +451,21 @@ def _hist_range(lo, hi, nchains, D, who):
     return out
 
 
+def _derived_check(derived, who, summary=True, sharded=False):
+    """the refusals of `derived=` that need no library"""
+    if derived is None:
+        return
+    from .derived import Derived
+    if not isinstance(derived, Derived):
+        raise TypeError(f"{who}: derived must be a Derived, not {type(derived).__name__}")
+    if not summary:
+        raise ValueError(f"{who}: derived quantities are accumulated by the device summary; derived= needs "
+                         "summary=True (on a returned trace, call derived(trace) instead)")
+    if sharded:
+        raise ValueError(f"{who}: a sharded ensemble has no streamed trace, and so no summary of one: derived= "
+                         "needs a single-process ensemble")
+
+
 def _hist_auto_range(x):
     """the automatic range from the walkers x [...][N][D]: with mn, mx over the walkers and s = mx - mn,
     lo = mn - s and hi = mx + s; a parameter on which all walkers agree (s == 0) gets mn - 0.5, mx + 0.5"""
@@ -459,6 +494,7 @@ class AisEnsemble:
                 raise ValueError(f"AisEnsemble: {len(costs)} costs for {len(seeds)} seeds")
         self.model = model
         self.comm = comm
+        self._is_sharded = comm is not None or (sharded is not None and sharded[1] > 1)
         self.nchains = 1 if seeds is None else len(seeds)
         self.batched = seeds is not None
         self.ctx = comm.ctx if comm is not None else (ctx or _lib.default_context())
@@ -535,7 +571,7 @@ class AisEnsemble:
 
     COV_MODES = {None: cd.SUMMARY_AUTO, "full": cd.SUMMARY_FULL, "diag": cd.SUMMARY_DIAG}
 
-    def summary_begin(self, cov=None, autocorr=None, hist=None):
+    def summary_begin(self, cov=None, autocorr=None, hist=None, derived=None):
         """Opens (or starts over) the posterior summary of this handle: advance(..., summary=True) then
         accumulates, summary() reads.  cov: "full" (the covariance matrix, up to KABC_MAX_DIM parameters),
         "diag" (the variances, any length(prior)), None (full where it exists, else diag).  autocorr: True
@@ -550,17 +586,40 @@ class AisEnsemble:
         lo = mn - s and hi = mx + s (mn - 0.5, mx + 0.5 where s == 0).  It is a convention, not a guarantee:
         a chain that has not yet spread, or drifts, leaves it, and `underflow` / `overflow` report how many
         samples it missed.  A discrete parameter wants an explicit integer-aligned range, one bin per value:
-        (-0.5, K + 0.5, K + 1) for values 0 ... K."""
+        (-0.5, K + 0.5, K + 1) for values 0 ... K.
+
+        derived (a Derived) adds a second set of accumulators over its G quantities of every trace row, mapped
+        on the device (kabc_ais_derived_begin): summary().derived is then a PosteriorSummary over them, with
+        `.names`.  autocorr and hist (its number of bins) apply to both sets; the derived histograms range over
+        derived.hist_range, else over the automatic convention applied to derived(walkers as they stand now).
+        "full" covariance up to KABC_MAX_DIM derived values, variances beyond."""
         if cov not in self.COV_MODES:
             raise ValueError(f'summary_begin: cov must be "full", "diag" or None, not {cov!r}')
         maxlag = _autocorr_maxlag(autocorr, "summary_begin")
         spec = _hist_spec(hist, "summary_begin")
         if spec is not None and spec[1] is not None:
             spec = (spec[0], *_hist_range(spec[1], spec[2], self.nchains, self.D, "summary_begin"))
+        _derived_check(derived, "summary_begin", sharded=self._is_sharded)
         _lib.check(_lib.load().kabc_ais_summary_begin(self._h, self.COV_MODES[cov]))
         self._summary_diag = cov == "diag" or (cov is None and self.D > cd.KABC_MAX_DIM)
         self._summary_maxlag = 0
         self._summary_hist = 0
+        self._summary_derived = None
+        if derived is not None:
+            # the second set: autocorr and hist (its bin count) apply to it too; its range is derived.hist_range,
+            # else the automatic convention applied to derived(walkers as they stand now), per chain
+            d, nb, lo, hi = derived, 0, None, None
+            if spec is not None:
+                nb = spec[0]
+                if d.hist_range is not None:
+                    lo, hi = (np.ascontiguousarray(np.broadcast_to(v, (self.nchains, d.G))) for v in d.hist_range)
+                else:
+                    g = d(self.state()[0], ctx=self.ctx)
+                    lo, hi = (np.ascontiguousarray(v.reshape(self.nchains, d.G)) for v in _hist_auto_range(g))
+            ptr = lambda v: None if v is None else v.ctypes.data_as(cd.c_double_p)   # noqa: E731
+            _lib.check(_lib.load().kabc_ais_derived_begin(self._h, d.id, d.G, d._params_ptr(), d.params.size,
+                                                          cd.SUMMARY_AUTO, maxlag, nb, ptr(lo), ptr(hi)))
+            self._summary_derived = d
         if maxlag:
             _lib.check(_lib.load().kabc_ais_autocorr_begin(self._h, maxlag))
             self._summary_maxlag = maxlag
@@ -575,38 +634,49 @@ class AisEnsemble:
         return self
 
     def summary(self):
-        """The PosteriorSummary of the generations advanced with summary=True since summary_begin()."""
-        diag = getattr(self, "_summary_diag", False)
+        """The PosteriorSummary of the generations advanced with summary=True since summary_begin(); with
+        summary_begin(derived=d) its `.derived` is the PosteriorSummary of d's G quantities."""
+        out = self._read_set(self.D, getattr(self, "_summary_diag", False), getattr(self, "_summary_maxlag", 0),
+                             getattr(self, "_summary_hist", 0), "kabc_ais_summary_get", "kabc_ais_autocorr_get",
+                             "kabc_ais_hist_get")
+        d = getattr(self, "_summary_derived", None)
+        if d is not None:
+            out.derived = self._read_set(d.G, d.G > cd.KABC_MAX_DIM, self._summary_maxlag, self._summary_hist,
+                                         "kabc_ais_derived_summary_get", "kabc_ais_derived_autocorr_get",
+                                         "kabc_ais_derived_hist_get")
+            out.derived.names = d.names
+        return out
+
+    def _read_set(self, D, diag, maxlag, nbins, get, get_autocorr, get_hist):
+        """one set of the open summary (the parameters' or the derived values') through its three getters"""
+        lib = _lib.load()
         lead = (self.nchains,) if self.batched else ()
-        vec = lambda: np.empty(lead + (self.D,))                                  # noqa: E731
-        mat = lambda: np.empty(lead + ((self.D,) if diag else (self.D, self.D)))   # noqa: E731
+        vec = lambda: np.empty(lead + (D,))                              # noqa: E731
+        mat = lambda: np.empty(lead + ((D,) if diag else (D, D)))         # noqa: E731
         n = C.c_int64()
         pivot, sum1, mean, mn, mx, sum2, cov = vec(), vec(), vec(), vec(), vec(), mat(), mat()
         p = lambda a: a.ctypes.data_as(cd.c_double_p)                             # noqa: E731
-        _lib.check(_lib.load().kabc_ais_summary_get(self._h, C.byref(n), p(pivot), p(sum1), p(sum2), p(mean),
-                                                    p(cov), p(mn), p(mx)))
-        return PosteriorSummary(n.value, mean, cov, mn, mx, pivot, sum1, sum2, diag, self._autocorr(lead),
-                                self._histogram(lead))
+        _lib.check(getattr(lib, get)(self._h, C.byref(n), p(pivot), p(sum1), p(sum2), p(mean), p(cov), p(mn), p(mx)))
+        return PosteriorSummary(n.value, mean, cov, mn, mx, pivot, sum1, sum2, diag,
+                                self._autocorr(lead, D, maxlag, getattr(lib, get_autocorr)),
+                                self._histogram(lead, D, nbins, getattr(lib, get_hist)))
 
-    def _histogram(self, lead):
+    def _histogram(self, lead, D, B, get):
         """kabc_ais_hist_get of the open summary as PosteriorSummary's dict, None without hist"""
-        B = getattr(self, "_summary_hist", 0)
         if not B:
             return None
         nb = C.c_int32()
-        counts = np.zeros(lead + (self.D, B + 2), dtype=np.uint64)
-        lo, hi = np.empty(lead + (self.D,)), np.empty(lead + (self.D,))
-        _lib.check(_lib.load().kabc_ais_hist_get(self._h, C.byref(nb), counts.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                                 lo.ctypes.data_as(cd.c_double_p), hi.ctypes.data_as(cd.c_double_p)))
+        counts = np.zeros(lead + (D, B + 2), dtype=np.uint64)
+        lo, hi = np.empty(lead + (D,)), np.empty(lead + (D,))
+        _lib.check(get(self._h, C.byref(nb), counts.ctypes.data_as(C.POINTER(C.c_uint64)),
+                       lo.ctypes.data_as(cd.c_double_p), hi.ctypes.data_as(cd.c_double_p)))
         assert nb.value == B, (nb.value, B)
         return {"counts": counts, "lo": lo, "hi": hi}
 
-    def _autocorr(self, lead):
+    def _autocorr(self, lead, D, L, get):
         """kabc_ais_autocorr_get of the open summary as PosteriorSummary's dict, None without autocorr"""
-        L = getattr(self, "_summary_maxlag", 0)
         if not L:
             return None
-        D = self.D
         nl = C.c_int32()
         lagsum, acov, rho = (np.full(lead + (D, L + 1), np.nan) for _ in range(3))
         first, last = (np.full(lead + (L, D), np.nan) for _ in range(2))
@@ -614,8 +684,8 @@ class AisEnsemble:
         window, conv = np.zeros(lead + (D,), dtype=np.int32), np.zeros(lead + (D,), dtype=np.int32)
         p = lambda a: a.ctypes.data_as(cd.c_double_p)                             # noqa: E731
         pi = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))                     # noqa: E731
-        _lib.check(_lib.load().kabc_ais_autocorr_get(self._h, C.byref(nl), p(lagsum), p(first), p(last), p(acov),
-                                                     p(rho), p(tau), p(ess), pi(window), pi(conv)))
+        _lib.check(get(self._h, C.byref(nl), p(lagsum), p(first), p(last), p(acov), p(rho), p(tau), p(ess),
+                       pi(window), pi(conv)))
         nl = nl.value
         nw = min(L, nl)                                      # rows of the two windows: min(maxlag, G)
         return {"tau": tau, "ess": ess, "acf": rho[..., :nl], "acov": acov[..., :nl], "window": window,
@@ -743,7 +813,7 @@ def _bundle(samples, scalar):
 
 
 def _sample_chains(model, N, Ns, seeds, costs, ntransitions, discard_initial, retry_sampling, ctx, ens=None,
-                   summary=False, autocorr=None, hist=None):
+                   summary=False, autocorr=None, hist=None, derived=None):
     """len(seeds) independent chains of AIS(N) in ONE batch handle (costs: one DeviceCost per chain, or
     None; ens: that handle where the caller has created it, closed here): the first Ns samples of each,
     [Nc][Ns][D], and the handle's driver; summary: the chains' PosteriorSummary (leading chain axis) in place
@@ -754,7 +824,8 @@ def _sample_chains(model, N, Ns, seeds, costs, ntransitions, discard_initial, re
     gk = max(1, -(-Ns // N))
     if summary:
         try:
-            return _summarise(ens, gk, N, ntransitions, discard_initial, retry_sampling, autocorr, hist), ens.driver
+            return _summarise(ens, gk, N, ntransitions, discard_initial, retry_sampling, autocorr, hist,
+                              derived), ens.driver
         finally:
             ens.close()
     big = gk * Nc * N * D * 8 > (1 << 20)   # (a small trace is not worth a helper thread: see sample)
@@ -776,7 +847,7 @@ def _sample_chains(model, N, Ns, seeds, costs, ntransitions, discard_initial, re
     return chains, driver
 
 
-def _summarise(ens, gk, N, ntransitions, discard_initial, retry_sampling, autocorr=None, hist=None):
+def _summarise(ens, gk, N, ntransitions, discard_initial, retry_sampling, autocorr=None, hist=None, derived=None):
     """sample()'s course on `ens` with the kept generations summarised on the device"""
     ens.init(retry_sampling)
     gd = -(-int(discard_initial) // N)
@@ -785,6 +856,8 @@ def _summarise(ens, gk, N, ntransitions, discard_initial, retry_sampling, autoco
     bkw = {"autocorr": autocorr} if autocorr else {}
     if hist is not None and hist is not False:
         bkw["hist"] = hist
+    if derived is not None:
+        bkw["derived"] = derived
     ens.summary_begin(**bkw)
     ens.advance(gk, ntransitions, summary=True)
     return ens.summary()
@@ -800,7 +873,8 @@ def _chain_kw(kw, c, nchains, D):
 
 
 def sample(model, spl, *args, ntransitions=1, discard_initial=0, retry_sampling=100, seed=0,
-           progress=False, ctx=None, return_array=False, summary=False, autocorr=None, hist=None, **kwargs):
+           progress=False, ctx=None, return_array=False, summary=False, autocorr=None, hist=None, derived=None,
+           **kwargs):
     """sample(model, AIS(N), Ns; ...) and sample(model, AIS(N), MCMCThreads(), Ns, Nc; ...).
 
     The device advances a whole generation (every walker `ntransitions` times) per
@@ -819,7 +893,11 @@ def sample(model, spl, *args, ntransitions=1, discard_initial=0, retry_sampling=
     summary=True too.  Its automatic range is taken from the walkers after discard_initial -- a convention,
     not a guarantee: `underflow` and `overflow` report what it missed, and a discrete parameter wants an
     explicit integer-aligned range such as (-0.5, K + 0.5, K + 1).  With MCMCThreads every chain has its own
-    range, and `.pooled` carries a histogram only for a range the caller gave.
+    range, and `.pooled` carries a histogram only for a range the caller gave.  `derived` (a Derived: a C
+    snippet mapping a trace row to G quantities) adds `.derived`, a PosteriorSummary of those quantities
+    accumulated on the device beside the parameters' (AisEnsemble.summary_begin); it needs summary=True and a
+    single-process ensemble.  With MCMCThreads `.derived` is the ChainSummaries of the chains' derived sets and
+    `.pooled.derived` its pooled summary.
     """
     if not isinstance(spl, AIS):
         raise TypeError("sampler must be AIS(nparticles)")
@@ -832,6 +910,9 @@ def sample(model, spl, *args, ntransitions=1, discard_initial=0, retry_sampling=
     akw = {"autocorr": autocorr} if _autocorr_maxlag(autocorr, "sample") else {}
     if _hist_spec(hist, "sample") is not None:
         akw["hist"] = hist
+    _derived_check(derived, "sample", summary=summary)
+    if derived is not None:
+        akw["derived"] = derived
     if args and isinstance(args[0], MCMCThreads):
         # chains are a grid dimension of ONE device handle: every launch advances all Nc
         # ensembles (kabc_ais_create_batch); chain c is bit-identical to a single-chain run
@@ -874,7 +955,7 @@ def sample(model, spl, *args, ntransitions=1, discard_initial=0, retry_sampling=
     if summary:
         try:
             return _summarise(ens, gk, N, ntransitions, discard_initial, retry_sampling, akw.get("autocorr"),
-                              akw.get("hist"))
+                              akw.get("hist"), akw.get("derived"))
         finally:
             ens.close()
     shape = (gk, N, len(model))
@@ -921,7 +1002,7 @@ def _model_difference(m, m0):
 
 def sample_batch(model, spl, Ns, nruns=None, *, seeds=None, seed=0, ntransitions=1, discard_initial=0,
                  retry_sampling=100, ctx=None, return_array=False, course=None, summary=False, autocorr=None,
-                 hist=None):
+                 hist=None, derived=None):
     """One model fitted to many datasets, or one dataset under many seeds, in one call: run r is
     sample(model_r, spl, Ns, seed=seeds[r], <the same keywords>), bit for bit.
 
@@ -936,7 +1017,7 @@ def sample_batch(model, spl, Ns, nruns=None, *, seeds=None, seed=0, ntransitions
     fits one workgroup's LDS (csrc/ais_dyn_small_kernel.hpp) -- and raises KabcError where the shape is
     refused; "sequential" forces the loop of sample() calls.  Same bits on either course.  Returns a list with one entry per run; its `.info` holds the course, the driver,
     nruns and the wall time.  `summary=True` gives one PosteriorSummary per run in place of its samples, on
-    either course (sample's own summary=True: n = ceil(Ns/N) * N per run; `autocorr` and `hist` as in sample, a [run][D] range of `hist` giving run r its row).  A failed initial draw raises KabcError("run r: <the reference's message>");
+    either course (sample's own summary=True: n = ceil(Ns/N) * N per run; `autocorr`, `hist` and `derived` as in sample, a [run][D] range of `hist` giving run r its row).  A failed initial draw raises KabcError("run r: <the reference's message>");
     Context.cancel() / Ctrl-C behave as they do for sample()."""
     if not isinstance(spl, AIS):
         raise TypeError("sampler must be AIS(nparticles)")
@@ -948,6 +1029,7 @@ def sample_batch(model, spl, Ns, nruns=None, *, seeds=None, seed=0, ntransitions
         raise ValueError("sample_batch: autocorr is part of the device summary; it needs summary=True")
     if _hist_spec(hist, "sample_batch") is not None and not summary:
         raise ValueError("sample_batch: hist is part of the device summary; it needs summary=True")
+    _derived_check(derived, "sample_batch", summary=summary)
     if isinstance(model, _ApproxModel):
         if nruns is None:
             raise ValueError("sample_batch: nruns is required with a single model")
@@ -978,6 +1060,8 @@ def sample_batch(model, spl, Ns, nruns=None, *, seeds=None, seed=0, ntransitions
         skw["autocorr"] = autocorr
     if summary and _hist_spec(hist, "sample_batch") is not None:
         skw["hist"] = hist
+    if derived is not None:
+        skw["derived"] = derived
     t0 = time.perf_counter()
     chains, driver = None, None
     if course == "grid" or (course is None and D <= cd.KABC_MAX_DIM):

@@ -1332,6 +1332,35 @@ hipError_t rtc_launch_cooperative(void* fn, unsigned G, unsigned block, const vo
     return hipModuleLaunchCooperativeKernel((hipFunction_t)fn, G, 1, 1, block, 1, 1, 0, s, params);
 }
 
+// ---- derived quantities (kabc_compile_derived, ais_derived_kernel.hpp) --------------------------
+struct DerivedPlugin : RtcCache {
+    std::string src;  // the user's snippet: kabc_user_derived
+};
+static std::vector<DerivedPlugin*> g_derived;  // id = index + 1 (g_mu)
+
+static std::string derived_head(const DerivedPlugin* P) {
+    return "#include \"kabc_math.h\"\n" + P->src + "\n#define KABC_USER_DERIVED_DEFINED 1\n";
+}
+
+bool derived_registered(int id) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    return id >= 1 && id <= (int)g_derived.size();
+}
+
+void* derived_kernel(int id, bool staged) {
+    DerivedPlugin* P = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(g_mu);
+        if (id >= 1 && id <= (int)g_derived.size()) P = g_derived[(size_t)id - 1];
+    }
+    if (!P) {
+        set_error("%d is not a registered derived-quantity snippet (kabc_compile_derived)", id);
+        return nullptr;
+    }
+    const std::vector<std::string> n = {"kabc::ais_derived_kernel", "kabc::ais_derived_lds_kernel"};
+    return rtc_kernel(P, derived_head(P), "ais_derived_kernel.hpp", false, n, n[staged ? 1 : 0]);
+}
+
 }  // namespace kabc
 
 using namespace kabc;
@@ -1502,6 +1531,47 @@ extern "C" kabc_status_t kabc_compile_prior_plugin(const char* src, int32_t disc
     }
     *out_kind = P->kind;
     return KABC_OK;
+}
+
+extern "C" kabc_status_t kabc_compile_derived(const char* src, int32_t* out_id) {
+    if (!src || !out_id) {
+        set_error("kabc_compile_derived: NULL argument");
+        return KABC_ERR_INVALID_ARG;
+    }
+    {
+        std::lock_guard<std::mutex> lk(g_mu);
+        for (size_t i = 0; i < g_derived.size(); ++i)  // (the same snippet registered again is the same map)
+            if (g_derived[i]->src == src) {
+                *out_id = (int32_t)i + 1;
+                return KABC_OK;
+            }
+    }
+    DerivedPlugin* P = new DerivedPlugin();
+    P->src = src;
+    // the snippet alone first, with the function called the way the kernel calls it: a missing
+    // kabc_user_derived or a syntax error comes back now, with the compiler's message
+    const std::string check = derived_head(P) +
+        "extern \"C\" __global__ void kabc_derived_check(const double* x, const double* p, double* g) {\n"
+        "    kabc_user_derived(x, 2, p, 1, g, 3);\n}\n";
+    if (kabc_status_t st = rtc_compile(check, nullptr, false, {}, nullptr, nullptr)) {
+        delete P;
+        return st;
+    }
+    std::lock_guard<std::mutex> lk(g_mu);
+    g_derived.push_back(P);
+    *out_id = (int32_t)g_derived.size();
+    return KABC_OK;
+}
+
+extern "C" kabc_status_t kabc_derived_precompile(int32_t id) {
+    if (!derived_registered(id)) {
+        set_error("kabc_derived_precompile: %d is not a registered derived-quantity snippet", id);
+        return KABC_ERR_INVALID_ARG;
+    }
+    set_error("%s", "");
+    if (derived_kernel(id, false)) return KABC_OK;
+    if (!get_error()[0]) set_error("kabc_derived_precompile: the map kernel of snippet %d could not be built", id);
+    return KABC_ERR_DEVICE;
 }
 
 // the kernel families (and their variants) a model's entry points will ask its specialised unit for

@@ -93,4 +93,10 @@ bool unit_required(const ModelUnit* u);
 // launch boundary.  Everything returned computes the same bits.
 PluginKernel unit_kernel(ModelUnit* u, int family, int D, int variant, int* spec_state = nullptr);
 
+// ---- derived quantities (kabc_compile_derived; ais_derived_kernel.hpp) -----------------------
+bool derived_registered(int id);
+// the map kernel of snippet `id` on the CURRENT device, compiled at first use; staged: the form that stages
+// the rows through LDS.  nullptr with the message set: an unknown id, a failed compilation or load
+void* derived_kernel(int id, bool staged);
+
 }  // namespace kabc
