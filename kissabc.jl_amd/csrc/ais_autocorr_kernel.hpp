@@ -7,17 +7,19 @@
 // L = maxlag; all fp64, no contraction):
 //   per element, sequentially in g, from +0.0:   P[t][e] += d[g][e] * d[g - t][e]   for t = 1 ... min(g, L)
 //   first window   F[g][e] = d[g][e] for g < L;      last window   a ring R[g mod L][e] = d[g][e]
-// and the summary's row tree over i when they are read.
+// and the summary's row tree over i when they are read (ais_row_tree_kernel, plain add over entries D apart).
 //
 // Accumulator layout: [3][chain][L][N * D] doubles -- plane 0: P (lag t at row t - 1), plane 1: F, plane 2:
 // R -- with the element index fastest in all three, as it is in the trace: neighbouring lanes coalesce.
 // The running generation count G that addresses the ring lives in device memory (the generations of a
-// block may be known on the device alone: AisAutocorrArgs::done); every workgroup reads it at entry and a
+// block may be known on the device alone: AisFoldBlock::done); every workgroup reads it at entry and a
 // one-thread launch behind the accumulate kernel advances it.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+
+#include "ais_fold_block.hpp"
 
 namespace kabc {
 
@@ -25,28 +27,16 @@ constexpr int kAcBlock = 256;                     // threads of every kernel her
 constexpr int kAcElems = 32;                      // elements a workgroup owns
 constexpr int kAcGroups = kAcBlock / kAcElems;    // lag groups: lane = (element, lag group)
 constexpr int kAcSub = 32;                        // generations staged into LDS at a time
-constexpr int kAcTile = 2 * kAcBlock;             // entries one workgroup of the row tree combines
 
 struct AisAutocorrArgs {
-    const double* trace;   // [g][chain][N][D]
+    AisFoldBlock blk;
     double* acc;           // [3][chain][L][N * D]
     const double* pivot;   // [chain][D]
-    const int64_t* done;   // device count of the block's generations that ran, or NULL: all `gc`
     const int64_t* gens;   // generations folded before this block (device)
-    int64_t N;
-    int64_t gc;
-    int32_t D, nchains, L, pad;
+    int32_t L;
 };
 
 #ifdef KABC_AIS_AUTOCORR_INSTANTIATE
-__device__ inline int64_t autocorr_generations(const int64_t* done, int64_t gc) {
-    if (done) {
-        const int64_t d = *done;
-        gc = d < gc ? (d < 0 ? 0 : d) : gc;
-    }
-    return gc;
-}
-
 // A workgroup owns kAcElems consecutive elements of one chain, and with them those elements' ring, first
 // window and P: no other workgroup touches them.  Lane (el, lg) holds the lags t = 1 + lg + j * kAcGroups
 // (j < TL: up to kAcGroups * TL lags) of element el in registers for the whole block, so P is read and
@@ -58,15 +48,15 @@ template <int TL>
 __global__ __launch_bounds__(kAcBlock) void ais_autocorr_kernel(AisAutocorrArgs A) {
     constexpr int E = kAcElems, LG = kAcGroups, W = LG * TL + kAcSub;
     __shared__ double s_w[W * E];
-    const int tid = threadIdx.x, chain = blockIdx.y, L = A.L, D = A.D;
+    const int tid = threadIdx.x, chain = blockIdx.y, L = A.L, D = A.blk.D;
     const int el = tid % E, lg = tid / E;
-    const size_t ND = (size_t)A.N * (size_t)D;
+    const size_t ND = (size_t)A.blk.N * (size_t)D;
     const size_t e0 = (size_t)blockIdx.x * E;
     const bool live = e0 + el < ND;
-    const int64_t gcount = autocorr_generations(A.done, A.gc);
+    const int64_t gcount = fold_generations(A.blk);
     const int64_t G0 = *A.gens;
     if (gcount <= 0) return;  // (the whole grid alike)
-    const size_t plane = (size_t)A.nchains * (size_t)L * ND;
+    const size_t plane = (size_t)A.blk.nchains * (size_t)L * ND;
     double* P = A.acc + (size_t)chain * (size_t)L * ND + e0 + el;
     double* F = P + plane;
     double* R = F + plane;
@@ -88,8 +78,8 @@ __global__ __launch_bounds__(kAcBlock) void ais_autocorr_kernel(AisAutocorrArgs 
     }
     // (every ring slot has been read before any is overwritten)
     __syncthreads();
-    const size_t gstride = (size_t)A.nchains * ND;
-    const double* src = A.trace + (size_t)chain * ND + e0 + el;
+    const size_t gstride = (size_t)A.blk.nchains * ND;
+    const double* src = A.blk.trace + (size_t)chain * ND + e0 + el;
     for (int64_t b = 0; b < gcount; b += kAcSub) {
         const int sb = (int)(gcount - b < kAcSub ? gcount - b : kAcSub);
         for (int s = lg; s < sb; s += LG) {
@@ -137,43 +127,13 @@ __global__ __launch_bounds__(kAcBlock) void ais_autocorr_kernel(AisAutocorrArgs 
 }
 
 // behind the accumulate kernel on the same stream: the block's generations join the count
-__global__ void ais_autocorr_advance_kernel(int64_t* gens, const int64_t* done, int64_t gc) {
-    if (blockIdx.x == 0 && threadIdx.x == 0) *gens += autocorr_generations(done, gc);
-}
-
-// One level of the summary's row tree (ais_summary_reduce_kernel's order, plain add) over entries that lie
-// `inner` doubles apart: series (outer, k) of `in` ([outer][n][inner]) has its entry j at
-// in[(outer * n + j) * inner + k]; workgroup (series, tile) combines the aligned run of kAcTile entries and
-// writes out[series][tile] -- contiguous, so the next level runs with inner = 1.
-__global__ __launch_bounds__(kAcBlock) void ais_autocorr_reduce_kernel(const double* in, double* out, int64_t n,
-                                                                       int64_t ntiles, int32_t inner) {
-    __shared__ double s[kAcBlock];
-    const int tid = threadIdx.x;
-    const int64_t series = (int64_t)blockIdx.x / ntiles, tile = (int64_t)blockIdx.x - series * ntiles;
-    const int64_t outer = series / inner;
-    const int k = (int)(series - outer * inner);
-    const int64_t base = tile * kAcTile;
-    const int cnt = (int)(n - base < kAcTile ? n - base : kAcTile);  // entries of this run, >= 1
-    const double* src = in + ((size_t)outer * (size_t)n + (size_t)base) * (size_t)inner + k;
-    const size_t st = (size_t)inner;
-    // w = 1: pairs (2t, 2t + 1)
-    if (2 * tid < cnt) s[tid] = (2 * tid + 1 < cnt) ? src[2 * tid * st] + src[(2 * tid + 1) * st] : src[2 * tid * st];
-    const int half = (cnt + 1) / 2;  // values left, at s[0 .. half)
-    __syncthreads();
-    for (int w = 1; w < half; w <<= 1) {
-        if ((tid % (2 * w)) == 0 && tid + w < half) s[tid] = s[tid] + s[tid + w];
-        __syncthreads();
-    }
-    if (tid == 0) out[(size_t)series * (size_t)ntiles + (size_t)tile] = s[0];
+__global__ void ais_autocorr_advance_kernel(int64_t* gens, AisFoldBlock blk) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) *gens += fold_generations(blk);
 }
 #endif  // KABC_AIS_AUTOCORR_INSTANTIATE
 
 // launches of ais_autocorr.hip
 // the accumulate kernel and, behind it, the advance of *gens (`gens` is written: pass it non-const)
 void launch_ais_autocorr_accumulate(const AisAutocorrArgs& a, int64_t* gens, hipStream_t s);
-// the row tree over i of every series (outer, k) of `acc` ([nouter][N][D]) into out[nouter][D]; lvl0 / lvl1:
-// scratch levels of nouter * D * ceil(N / kAcTile) and nouter * D * ceil(ceil(N / kAcTile) / kAcTile) doubles
-void launch_ais_autocorr_reduce(const double* acc, double* out, double* lvl0, double* lvl1, int64_t N, int D,
-                                int64_t nouter, hipStream_t s);
 
 }  // namespace kabc

@@ -1,5 +1,5 @@
 // ais_derived.hip -- the host side of the derived-quantity map (ais_derived_kernel.hpp): its launch, shared by
-// the summary fold of capi_ais.hip, and kabc_derived_eval, the same map over rows the caller gives.  The kernel
+// the summary fold of capi_ais_summary.hip, and kabc_derived_eval, the same map over rows the caller gives.  The kernel
 // itself is compiled at run time with the user's snippet (capi_plugin.hip: kabc_compile_derived).
 #include <algorithm>
 #include <cstring>
@@ -22,7 +22,7 @@ kabc_status_t launch_ais_derived(int id, AisDerivedArgs a, hipStream_t s) {
     if (!fn) return KABC_ERR_DEVICE;  // (message set by the compilation / load)
     if (staged) {
         const AisDerivedLdsGeom g = ais_derived_lds_geom(a.nrows, a.D, a.G);
-        a.pad = g.rpb;
+        a.rpb = g.rpb;
         KABC_HIP_CHECK(rtc_launch_lds(fn, dim3(g.grid), dim3(g.block), &a, s, g.lds));
     } else {
         Launcher<AisDerivedArgs>(fn, &ais_derived_geom, kDerivedBlock)(a, s);

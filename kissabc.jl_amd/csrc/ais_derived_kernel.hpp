@@ -45,18 +45,23 @@ struct AisDerivedArgs {
     int64_t nrows;         // rows of this launch: ngen * rows_per_gen
     int64_t rows_per_gen;  // nchains * N
     int64_t gen0, ngen;    // the launch's generations within the trace block
-    int32_t D, G, nparams, pad;
+    int32_t D, G, nparams;
+    int32_t rpb;           // rows per workgroup of the staged form: set by the launcher, ignored by the direct form
 };
 
 #ifdef KABC_USER_DERIVED_DEFINED
+// the rows of the launch to map: all of them, or with `done` those of its generations that ran, whose number
+// thread 0 of the grid writes to *sub_done
+__device__ inline int64_t derived_rows(const AisDerivedArgs& A) {
+    if (!A.done) return A.nrows;
+    int64_t d = *A.done - A.gen0;
+    d = d < 0 ? 0 : (d < A.ngen ? d : A.ngen);
+    if (blockIdx.x == 0 && threadIdx.x == 0) *A.sub_done = d;
+    return d * A.rows_per_gen;
+}
+
 __global__ void __launch_bounds__(kDerivedBlock) ais_derived_kernel(const AisDerivedArgs A) {
-    int64_t nrows = A.nrows;
-    if (A.done) {
-        int64_t d = *A.done - A.gen0;
-        d = d < 0 ? 0 : (d < A.ngen ? d : A.ngen);
-        nrows = d * A.rows_per_gen;
-        if (blockIdx.x == 0 && threadIdx.x == 0) *A.sub_done = d;
-    }
+    const int64_t nrows = derived_rows(A);
     const int64_t row = (int64_t)blockIdx.x * kDerivedBlock + threadIdx.x;
     if (row >= nrows) return;
     kabc_user_derived(A.x + row * A.D, A.D, A.params, A.nparams, A.g + row * A.G, A.G);
@@ -67,15 +72,9 @@ __global__ void __launch_bounds__(kDerivedBlock) ais_derived_kernel(const AisDer
 // words in order
 __global__ void __launch_bounds__(kDerivedBlock) ais_derived_lds_kernel(const AisDerivedArgs A) {
     extern __shared__ __attribute__((aligned(16))) double der_rows[];
-    const int tid = threadIdx.x, nthreads = blockDim.x, rpb = A.pad;
+    const int tid = threadIdx.x, nthreads = blockDim.x, rpb = A.rpb;
     const int D = A.D, G = A.G, Dp = D | 1, Gp = G | 1;
-    int64_t nrows = A.nrows;
-    if (A.done) {
-        int64_t d = *A.done - A.gen0;
-        d = d < 0 ? 0 : (d < A.ngen ? d : A.ngen);
-        nrows = d * A.rows_per_gen;
-        if (blockIdx.x == 0 && tid == 0) *A.sub_done = d;
-    }
+    const int64_t nrows = derived_rows(A);
     const int64_t row0 = (int64_t)blockIdx.x * rpb;
     if (row0 >= nrows) return;  // (the whole workgroup)
     const int nr = (int)(nrows - row0 < rpb ? nrows - row0 : rpb);

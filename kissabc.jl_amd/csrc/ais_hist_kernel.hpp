@@ -16,6 +16,8 @@
 
 #include <cstdint>
 
+#include "ais_fold_block.hpp"
+
 namespace kabc {
 
 constexpr int kHistBlock = 256;                       // threads of both kernels
@@ -30,28 +32,14 @@ constexpr int kHistWordsLarge = kHistSlab * (1024 + 2);  // 16 x (KABC_HIST_MAX_
 constexpr int64_t kHistMaxGens = (int64_t)1 << 22;
 
 struct AisHistArgs {
-    const double* trace;          // [g][chain][N][D]
+    AisFoldBlock blk;
     unsigned long long* counts;   // [chain][D][B + 2]
     const double* range;          // [3][chain][D]: lo, hi, scale
-    const int64_t* done;          // device count of the block's generations that ran, or NULL: all `gc`
-    int64_t N;
-    int64_t gc;                   // generations of the block
-    int64_t g0, gn;               // this launch counts generations g0 ... g0 + gn - 1 of them
-    int32_t D, nchains, B, pad;
+    int64_t g0, gn;               // this launch counts generations g0 ... g0 + gn - 1 of the block
+    int32_t B;
 };
 
 #ifdef KABC_AIS_HIST_INSTANTIATE
-// the launch's generations [g0, gend) that ran
-__device__ inline int64_t hist_generations_end(const AisHistArgs& A) {
-    int64_t gc = A.gc;
-    if (A.done) {
-        const int64_t d = *A.done;
-        gc = d < gc ? (d < 0 ? 0 : d) : gc;
-    }
-    const int64_t end = A.g0 + A.gn;
-    return end < gc ? end : gc;
-}
-
 // the counter of r: 0 ... B + 1
 __device__ inline int hist_bin(double r, double lo, double hi, double scale, int B) {
     if (r < lo) return 0;
@@ -73,21 +61,22 @@ __device__ inline int hist_bin(double r, double lo, double hi, double scale, int
 template <int WORDS>
 __global__ __launch_bounds__(kHistBlock) void ais_hist_lds_kernel(AisHistArgs A) {
     __shared__ uint32_t s_c[WORDS];
-    const int tid = threadIdx.x, chain = blockIdx.y, D = A.D, B = A.B, nb = B + 2;
+    const int tid = threadIdx.x, chain = blockIdx.y, D = A.blk.D, B = A.B, nb = B + 2;
     const int k0 = (int)blockIdx.z * kHistSlab;
     const int ks = D - k0 < kHistSlab ? D - k0 : kHistSlab;
     const int words = ks * nb;  // <= WORDS (the launcher's choice of instantiation)
-    const int64_t g0 = A.g0, gend = hist_generations_end(A);
+    const int64_t g0 = A.g0, gran = fold_generations(A.blk);
+    const int64_t gend = g0 + A.gn < gran ? g0 + A.gn : gran;  // the launch's generations [g0, gend) that ran
     if (gend <= g0) return;  // (the whole grid alike)
     for (int w = tid; w < words; w += kHistBlock) s_c[w] = 0u;
-    const size_t ND = (size_t)A.N * (size_t)D;
+    const size_t ND = (size_t)A.blk.N * (size_t)D;
     const size_t e0 = (size_t)blockIdx.x * kHistTile + tid;
-    const size_t nchD = (size_t)A.nchains * (size_t)D;
+    const size_t nchD = (size_t)A.blk.nchains * (size_t)D;
     bool ok[kHistPer];
     int base[kHistPer];
     double lo[kHistPer], hi[kHistPer], sc[kHistPer], nxt[kHistPer];
-    const size_t gstride = (size_t)A.nchains * ND;
-    const double* src = A.trace + (size_t)chain * ND + e0;
+    const size_t gstride = (size_t)A.blk.nchains * ND;
+    const double* src = A.blk.trace + (size_t)chain * ND + e0;
 #pragma unroll
     for (int j = 0; j < kHistPer; ++j) {
         const size_t e = e0 + (size_t)j * kHistBlock;
@@ -125,20 +114,21 @@ __global__ __launch_bounds__(kHistBlock) void ais_hist_lds_kernel(AisHistArgs A)
 // e of [chain][N][D] and adds straight to the device counts -- one atomic per RUN of generations in which
 // its element stays in one counter (a walker that is not moved, or moves within a bin, adds nothing new).
 __global__ __launch_bounds__(kHistBlock) void ais_hist_direct_kernel(AisHistArgs A) {
-    const int D = A.D, B = A.B, nb = B + 2;
-    const size_t ND = (size_t)A.N * (size_t)D;
-    const size_t total = (size_t)A.nchains * ND;
+    const int D = A.blk.D, B = A.B, nb = B + 2;
+    const size_t ND = (size_t)A.blk.N * (size_t)D;
+    const size_t total = (size_t)A.blk.nchains * ND;
     const size_t e = (size_t)blockIdx.x * kHistBlock + threadIdx.x;
     if (e >= total) return;
-    const int64_t g0 = A.g0, gend = hist_generations_end(A);
+    const int64_t g0 = A.g0, gran = fold_generations(A.blk);
+    const int64_t gend = g0 + A.gn < gran ? g0 + A.gn : gran;  // the launch's generations [g0, gend) that ran
     if (gend <= g0) return;
     const size_t chain = e / ND;
     const int k = (int)((e - chain * ND) % (size_t)D);
-    const size_t nchD = (size_t)A.nchains * (size_t)D;
+    const size_t nchD = (size_t)A.blk.nchains * (size_t)D;
     const double* rg = A.range + chain * D + k;
     const double lo = rg[0], hi = rg[nchD], sc = rg[2 * nchD];
     unsigned long long* dst = A.counts + (chain * D + k) * (size_t)nb;
-    const double* src = A.trace + e;  // ([g][chain][N][D]: element e of generation 0)
+    const double* src = A.blk.trace + e;  // ([g][chain][N][D]: element e of generation 0)
     double nxt = src[(size_t)g0 * total];
     int run_bin = -1;
     unsigned long long run = 0ull;

@@ -8,17 +8,13 @@
 #include <mutex>
 #include <thread>
 #include <type_traits>
-#include <limits>
 #include <vector>
 
 #include "ais_aux_kernels.hpp"
 #include "ais_dyn_kernels.hpp"
 #include "ais_dyn_small_kernel.hpp"
 #include "ais_small_kernel.hpp"
-#include "ais_summary_kernel.hpp"
-#include "ais_autocorr_kernel.hpp"
-#include "ais_hist_kernel.hpp"
-#include "ais_derived_kernel.hpp"
+#include "ais_summary_host.hpp"
 #include "host_common.hpp"
 #include "plugin_registry.hpp"
 
@@ -163,38 +159,6 @@ using namespace kabc;
 
 static constexpr int kTraceBufs = 3;
 
-// One set of summary accumulators over rows of `D` doubles.  A handle holds two: over its parameters, and over
-// the derived values of kabc_ais_derived_begin (D := G); the same kernels and the same host code serve both.
-struct SummarySet {
-    int32_t D = 0;                  // the row length
-    // the moments (ais_summary_kernel.hpp): per-row accumulators [chain][slot][N], the pivot [chain][D], the
-    // row tree's two scratch levels and its result [chain][slot]; from the context's pool, zeroed by begin
-    DevBufs sum_bufs;
-    int32_t sum_mode = 0;           // 0: not open, else KABC_SUMMARY_FULL / KABC_SUMMARY_DIAG
-    int32_t sum_slots = 0;
-    bool sum_pivot = false;         // the pivot has been taken
-    double* d_sum_acc = nullptr;
-    double* d_sum_pivot = nullptr;
-    double* d_sum_out = nullptr;
-    double* d_sum_lvl[2] = {};
-    // ... and its autocorrelation (kabc_ais_autocorr_begin, ais_autocorr_kernel.hpp): the lagged products,
-    // the first window and the ring [3][chain][L][N * D], the device count of the generations folded, the
-    // row tree's result [3][chain][L][D] and its two scratch levels; from the context's pool
-    DevBufs ac_bufs;
-    int32_t ac_L = 0;               // maxlag, 0: none open
-    double* d_ac_acc = nullptr;
-    int64_t* d_ac_gens = nullptr;
-    double* d_ac_out = nullptr;
-    double* d_ac_lvl[2] = {};
-    // ... and its histograms (kabc_ais_hist_begin, ais_hist_kernel.hpp): the counts [chain][D][B + 2] and the
-    // range [3][chain][D] (lo, hi, scale) on the device, from the context's pool; the range as given, on the host
-    DevBufs hist_bufs;
-    int32_t hist_B = 0;             // nbins, 0: none open
-    unsigned long long* d_hist_counts = nullptr;
-    double* d_hist_range = nullptr;
-    std::vector<double> hist_range;  // [3][chain][D]
-};
-
 struct kabc_ais {
     kabc_ctx_t* ctx = nullptr;
     int32_t D = 0, posterior = 0, cost_id = 0;
@@ -274,21 +238,8 @@ struct kabc_ais {
     size_t aux_cap = 0;  // bytes
     // cancellation: the two block / interval events of a bounded queue (created at first need)
     hipEvent_t ev_blk[2] = {};
-    // posterior summary (kabc_ais_summary_begin): the accumulators over the D parameters, and -- with
-    // kabc_ais_derived_begin -- a second set over the G derived values of every trace row
-    SummarySet par, der;
-    int64_t sum_gens = 0;           // generations folded since begin (into both sets)
-    // the derived map (ais_derived_kernel.hpp): the snippet, its parameters on the device, the mapped block
-    // [g][chain][N][G] (a pooled buffer of at most KABC_DERIVED_MIB, default 32 MiB, or one generation: a longer
-    // trace block is mapped and folded in sub-blocks of whole generations) and the device word that tells
-    // the folds how many generations of a sub-block ran
-    int32_t der_id = 0;             // 0: no derived set open
-    int32_t der_nparams = 0;
-    DevBufs der_bufs, der_map_bufs;
-    double* d_der_params = nullptr;
-    int64_t* d_der_done = nullptr;
-    double* d_der_map = nullptr;
-    size_t der_map_cap = 0;         // bytes
+    // posterior summary (kabc_ais_summary_begin; ais_summary_host.hpp, capi_ais_summary.hip)
+    AisSummary sum;
     // debug records (tests)
     int32_t* d_dbg = nullptr;
     int64_t dbg_cap = 0;  // in int32 units
@@ -704,6 +655,7 @@ static kabc_status_t ais_create_common(kabc_ctx_t* ctx, const kabc_model_t* m, i
     h->world = world;
     h->comm = comm;
     h->nchains = nchains;
+    h->sum.ctx = ctx, h->sum.N = n_total, h->sum.nchains = nchains, h->sum.D = mres.D;  // (the trace a summary folds)
     h->seed = seed;
     h->own_halves = ext0 == nullptr;
     h->spec_variant = kPriorGeneral + kPriorClasses * (mres.posterior - 1);
@@ -781,16 +733,6 @@ static void fill_args(A& a, const kabc_ais_t* h) {
     // per-chain costs (the pre-pass reads params only)
     a.params_stride = h->params_stride;
     if constexpr (!aux) a.data_stride = h->data_stride;
-}
-
-// a size knob of the environment (tests, tuning) in `unit` bytes, else `dflt`; read at every call, as
-// the tests change it between handles
-static size_t env_bytes(const char* name, size_t unit, size_t dflt) {
-    if (const char* e = std::getenv(name)) {
-        const long v = std::atol(e);
-        if (v > 0) return (size_t)v * unit;
-    }
-    return dflt;
 }
 
 // grows a device buffer to `bytes` (it never shrinks); the old one may still be read by work queued on
@@ -1426,124 +1368,23 @@ static kabc_status_t ensure_blk_events(kabc_ais_t* h) {
     return KABC_OK;
 }
 
-// which of the two counting kernels takes this handle's blocks: ais_hist_direct()'s shape rule, or what
-// KABC_HIST_PATH=lds / direct says (the counts are the same: tools/ais_hist_probe.py times both)
-static bool hist_direct(const kabc_ais_t* h, int D) {
-    const char* e = std::getenv("KABC_HIST_PATH");
-    if (e && !std::strcmp(e, "lds")) return false;
-    if (e && !std::strcmp(e, "direct")) return true;
-    return ais_hist_direct(h->N, D);
-}
-
-// folds `gc` generations of a device block of rows ([g][chain][N][S.D]) into the set `S`, behind the kernels
-// that wrote them on the handle's stream; `done`: device count of the generations that ran, or NULL.  The
-// first block since begin supplies the pivot: row 0 of its first generation, per chain.
-static kabc_status_t summary_fold_set(kabc_ais_t* h, SummarySet& S, const double* trace, int64_t gc,
-                                      const int64_t* done) {
-    hipStream_t s = h->ctx->stream;
-    if (!S.sum_pivot) {
-        KABC_HIP_CHECK(hipMemcpy2DAsync(S.d_sum_pivot, sizeof(double) * S.D, trace, sizeof(double) * h->N * S.D,
-                                        sizeof(double) * S.D, (size_t)h->nchains, hipMemcpyDeviceToDevice, s));
-        S.sum_pivot = true;
+// From a handle to its summary (ais_summary_host.hpp): what every summary entry point asks of its handle;
+// `open`: a summary must have been begun
+kabc_status_t kabc::ais_summary_of(kabc_ais_t* h, const char* who, bool open, AisSummary** out) {
+    if (check_handle(h)) return KABC_ERR_INVALID_ARG;
+    if (h->world != 1 || h->comm) {
+        set_error("%s: a sharded ensemble has no streamed trace, and so no summary of one", who);
+        return KABC_ERR_INVALID_ARG;
     }
-    AisSummaryArgs a;
-    std::memset(&a, 0, sizeof a);
-    a.trace = trace;
-    a.acc = S.d_sum_acc;
-    a.pivot = S.d_sum_pivot;
-    a.done = done;
-    a.N = h->N;
-    a.gc = gc;
-    a.D = S.D;
-    a.nchains = h->nchains;
-    a.nslots = S.sum_slots;
-    launch_ais_summary_accumulate(a, S.sum_mode == KABC_SUMMARY_FULL, s);
-    KABC_HIP_CHECK(hipGetLastError());
-    if (S.ac_L) {  // the same block into the lagged products, behind the moments
-        AisAutocorrArgs c;
-        std::memset(&c, 0, sizeof c);
-        c.trace = trace;
-        c.acc = S.d_ac_acc;
-        c.pivot = S.d_sum_pivot;
-        c.done = done;
-        c.gens = S.d_ac_gens;
-        c.N = h->N;
-        c.gc = gc;
-        c.D = S.D;
-        c.nchains = h->nchains;
-        c.L = S.ac_L;
-        launch_ais_autocorr_accumulate(c, S.d_ac_gens, s);
-        KABC_HIP_CHECK(hipGetLastError());
+    if (!h->initialised) {
+        set_error("%s: kabc_ais_init / kabc_ais_set_state has not been called", who);
+        return KABC_ERR_INVALID_STATE;
     }
-    if (S.hist_B) {  // ... and into the histograms
-        AisHistArgs c;
-        std::memset(&c, 0, sizeof c);
-        c.trace = trace;
-        c.counts = S.d_hist_counts;
-        c.range = S.d_hist_range;
-        c.done = done;
-        c.N = h->N;
-        c.gc = gc;
-        c.D = S.D;
-        c.nchains = h->nchains;
-        c.B = S.hist_B;
-        launch_ais_hist_accumulate(c, hist_direct(h, S.D), s);
-        KABC_HIP_CHECK(hipGetLastError());
+    if (open && !h->sum.par.sum_mode) {
+        set_error("%s: no summary is open on this handle (kabc_ais_summary_begin)", who);
+        return KABC_ERR_INVALID_STATE;
     }
-    return KABC_OK;
-}
-
-// grows the pooled buffer of the mapped block to `bytes` (it never shrinks); the old one may still be read by
-// work queued on the handle's stream, which is waited for first
-static kabc_status_t derived_map_grow(kabc_ais_t* h, size_t bytes) {
-    if (bytes <= h->der_map_cap) return KABC_OK;
-    if (h->d_der_map) {
-        KABC_HIP_CHECK(hipStreamSynchronize(h->ctx->stream));
-        h->der_map_bufs.release();
-        h->d_der_map = nullptr;
-        h->der_map_cap = 0;
-    }
-    h->der_map_bufs.ctx = h->ctx;
-    KABC_HIP_CHECK(h->der_map_bufs.alloc(&h->d_der_map, bytes / sizeof(double)));
-    h->der_map_cap = bytes;
-    return KABC_OK;
-}
-
-// The block into the handle's open summary: the parameters' set, and with a derived set open the block mapped
-// row by row (ais_derived_kernel.hpp) into the pooled buffer and that folded into the second set.  The buffer
-// is capped (KABC_DERIVED_MIB: tests, tuning), so a long block goes through it in sub-blocks of whole
-// generations -- the accumulators live on the handle, the result does not depend on the cut.
-static kabc_status_t summary_fold(kabc_ais_t* h, const double* trace, int64_t gc, const int64_t* done) {
-    if (kabc_status_t st = summary_fold_set(h, h->par, trace, gc, done)) return st;
-    if (!h->der_id) return KABC_OK;
-    hipStream_t s = h->ctx->stream;
-    const int D = h->D, G = h->der.D;
-    const int64_t rows_per_gen = h->N * h->nchains;
-    const size_t gen_bytes = sizeof(double) * (size_t)rows_per_gen * (size_t)G;
-    const size_t cap = env_bytes("KABC_DERIVED_MIB", 1 << 20, (size_t)32 << 20);
-    int64_t sub = (int64_t)(cap / gen_bytes);
-    if (sub < 1) sub = 1;
-    if (sub > gc) sub = gc;
-    if (kabc_status_t st = derived_map_grow(h, gen_bytes * (size_t)sub)) return st;
-    for (int64_t s0 = 0; s0 < gc; s0 += sub) {
-        const int64_t sn = gc - s0 < sub ? gc - s0 : sub;
-        AisDerivedArgs a;
-        std::memset(&a, 0, sizeof a);
-        a.x = trace + (size_t)s0 * (size_t)rows_per_gen * (size_t)D;
-        a.g = h->d_der_map;
-        a.params = h->d_der_params;
-        a.done = done;
-        a.sub_done = h->d_der_done;
-        a.nrows = sn * rows_per_gen;
-        a.rows_per_gen = rows_per_gen;
-        a.gen0 = s0;
-        a.ngen = sn;
-        a.D = D;
-        a.G = G;
-        a.nparams = h->der_nparams;
-        if (kabc_status_t st = launch_ais_derived(h->der_id, a, s)) return st;
-        if (kabc_status_t st = summary_fold_set(h, h->der, h->d_der_map, sn, done ? h->d_der_done : nullptr)) return st;
-    }
+    *out = &h->sum;
     return KABC_OK;
 }
 
@@ -1650,7 +1491,7 @@ static kabc_status_t ais_small_run(kabc_ais_t* h, int64_t ngenerations, int32_t 
             KABC_HIP_CHECK(hipMemcpyAsync(out_samples + g0 * gen_elems, h->d_strace, gen_bytes * (size_t)gc,
                                           hipMemcpyDeviceToHost, s));
         if (summarise)  // (a block the kernel left early on a cancel: exactly the generations it ran)
-            if (kabc_status_t st = summary_fold(h, h->d_strace, gc, dev_poll ? &h->d_counters->small_done : nullptr))
+            if (kabc_status_t st = summary_fold(h->sum, h->d_strace, gc, dev_poll ? &h->d_counters->small_done : nullptr))
                 return st;
         if (blocks && !dev_poll) KABC_HIP_CHECK(hipEventRecord(h->ev_blk[nblk & 1], s));
         h->t += (uint64_t)gc * (uint64_t)ntransitions;
@@ -1961,7 +1802,7 @@ static kabc_status_t ais_summary_half_run(kabc_ais_t* h, int64_t ngenerations, i
             if (kabc_status_t st = ib.generation_enqueued(s)) return st;
         }
         if (g > 0)
-            if (kabc_status_t st = summary_fold(h, h->d_trace[0], g, nullptr)) return st;
+            if (kabc_status_t st = summary_fold(h->sum, h->d_trace[0], g, nullptr)) return st;
     }
     return KABC_OK;
 }
@@ -2041,131 +1882,10 @@ kabc_status_t kabc_ais_advance(kabc_ais_t* h, int64_t ngenerations, int32_t ntra
     return ais_advance_end(h, ntransitions, small_gc, cancelled, stats);
 }
 
-// ---- posterior summaries on the device (ais_summary_kernel.hpp) --------------------------------------
-
-// what every summary entry point asks of its handle; `open`: a summary must have been begun
-static kabc_status_t summary_check(const kabc_ais_t* h, const char* who, bool open) {
-    if (check_handle(h)) return KABC_ERR_INVALID_ARG;
-    if (h->world != 1 || h->comm) {
-        set_error("%s: a sharded ensemble has no streamed trace, and so no summary of one", who);
-        return KABC_ERR_INVALID_ARG;
-    }
-    if (!h->initialised) {
-        set_error("%s: kabc_ais_init / kabc_ais_set_state has not been called", who);
-        return KABC_ERR_INVALID_STATE;
-    }
-    if (open && !h->par.sum_mode) {
-        set_error("%s: no summary is open on this handle (kabc_ais_summary_begin)", who);
-        return KABC_ERR_INVALID_STATE;
-    }
-    return KABC_OK;
-}
-
-static void autocorr_release(SummarySet& S) {
-    S.ac_bufs.release();
-    S.d_ac_acc = S.d_ac_out = S.d_ac_lvl[0] = S.d_ac_lvl[1] = nullptr;
-    S.d_ac_gens = nullptr;
-    S.ac_L = 0;
-}
-
-static void hist_release(SummarySet& S) {
-    S.hist_bufs.release();
-    S.d_hist_counts = nullptr;
-    S.d_hist_range = nullptr;
-    S.hist_range.clear();
-    S.hist_B = 0;
-}
-
-static void set_release(SummarySet& S) {
-    autocorr_release(S);
-    hist_release(S);
-    S.sum_bufs.release();
-    S.d_sum_acc = S.d_sum_pivot = S.d_sum_out = S.d_sum_lvl[0] = S.d_sum_lvl[1] = nullptr;
-    S.sum_mode = S.sum_slots = 0;
-    S.sum_pivot = false;
-}
-
-static void derived_release(kabc_ais_t* h) {
-    set_release(h->der);
-    h->der_bufs.release();
-    h->der_map_bufs.release();
-    h->d_der_params = h->d_der_map = nullptr;
-    h->d_der_done = nullptr;
-    h->der_map_cap = 0;
-    h->der_id = h->der_nparams = 0;
-}
-
-static void summary_release(kabc_ais_t* h) {
-    derived_release(h);
-    set_release(h->par);
-    h->sum_gens = 0;
-}
-
-// what the moments of a set over rows of D ask (`who`: the entry point); *mode: the resolved cov_mode
-static kabc_status_t set_check(const kabc_ais_t* h, int32_t D, bool der, int32_t cov_mode, const char* who,
-                               int32_t* mode_out) {
-    if (cov_mode != KABC_SUMMARY_AUTO && cov_mode != KABC_SUMMARY_FULL && cov_mode != KABC_SUMMARY_DIAG) {
-        set_error("%s: cov_mode %d is none of KABC_SUMMARY_AUTO, _FULL, _DIAG", who, cov_mode);
-        return KABC_ERR_INVALID_ARG;
-    }
-    if (cov_mode == KABC_SUMMARY_FULL && D > KABC_MAX_DIM) {
-        set_error("%s: the \"full\" covariance is kept up to %d %s; %s = %d takes \"diag\" (the variances)", who,
-                  KABC_MAX_DIM, der ? "derived values" : "parameters", der ? "G" : "length(prior)", D);
-        return KABC_ERR_UNSUPPORTED;
-    }
-    const int32_t mode = cov_mode != KABC_SUMMARY_AUTO ? cov_mode
-                         : D <= KABC_MAX_DIM           ? KABC_SUMMARY_FULL
-                                                       : KABC_SUMMARY_DIAG;
-    const int nslots = ais_summary_slots(D, mode == KABC_SUMMARY_FULL);
-    const int64_t t1 = (h->N + kSumTile - 1) / kSumTile;
-    if ((int64_t)h->nchains * nslots * t1 >= (1ll << 31)) {  // (the row tree's grid)
-        set_error("%s: %d chains x %d accumulators x %lld walkers is beyond the summary's "
-                  "launch grid", who, h->nchains, nslots, (long long)h->N);
-        return KABC_ERR_UNSUPPORTED;
-    }
-    *mode_out = mode;
-    return KABC_OK;
-}
-
-// the moments' accumulators of a set over rows of D, from the pool and at their start values; `mode` from set_check
-static kabc_status_t set_begin(kabc_ais_t* h, SummarySet& S, int32_t D, int32_t mode) {
-    const int nslots = ais_summary_slots(D, mode == KABC_SUMMARY_FULL);
-    const int64_t nseries = (int64_t)h->nchains * nslots;
-    const int64_t t1 = (h->N + kSumTile - 1) / kSumTile, t2 = (t1 + kSumTile - 1) / kSumTile;
-    hipStream_t s = h->ctx->stream;
-    S.D = D;
-    S.sum_bufs.ctx = h->ctx;
-    hipError_t e = S.sum_bufs.alloc(&S.d_sum_acc, (size_t)nseries * (size_t)h->N);
-    if (e == hipSuccess) e = S.sum_bufs.alloc(&S.d_sum_pivot, (size_t)h->nchains * (size_t)D);
-    if (e == hipSuccess) e = S.sum_bufs.alloc(&S.d_sum_out, (size_t)nseries);
-    if (e == hipSuccess) e = S.sum_bufs.alloc(&S.d_sum_lvl[0], (size_t)(nseries * t1));
-    if (e == hipSuccess) e = S.sum_bufs.alloc(&S.d_sum_lvl[1], (size_t)(nseries * t2));
-    if (e != hipSuccess) {
-        set_release(S);
-        KABC_HIP_CHECK(e);
-    }
-    launch_ais_summary_init(S.d_sum_acc, h->N, D, nslots, h->nchains, s);
-    KABC_HIP_CHECK(hipGetLastError());
-    S.sum_mode = mode;
-    S.sum_slots = nslots;
-    return KABC_OK;
-}
-
-kabc_status_t kabc_ais_summary_begin(kabc_ais_t* h, int32_t cov_mode) {
-    if (kabc_status_t st = summary_check(h, "kabc_ais_summary_begin", false)) return st;
-    int32_t mode = 0;
-    if (kabc_status_t st = set_check(h, h->D, false, cov_mode, "kabc_ais_summary_begin", &mode)) return st;
-    KABC_HIP_CHECK(hipSetDevice(h->ctx->device));
-    if (h->par.sum_mode) {  // (begin again: the summary starts over; its buffers may still be read by queued work)
-        KABC_HIP_CHECK(hipStreamSynchronize(h->ctx->stream));
-        summary_release(h);
-    }
-    return set_begin(h, h->par, h->D, mode);
-}
-
 kabc_status_t kabc_ais_advance_summary(kabc_ais_t* h, int64_t ngenerations, int32_t ntransitions,
                                        kabc_stats_t* stats) {
-    if (kabc_status_t st = summary_check(h, "kabc_ais_advance_summary", true)) return st;
+    AisSummary* sum;
+    if (kabc_status_t st = ais_summary_of(h, "kabc_ais_advance_summary", true, &sum)) return st;
     if (ngenerations < 0 || ntransitions < 1) {
         set_error("ngenerations must be >= 0 and ntransitions >= 1");
         return KABC_ERR_INVALID_ARG;
@@ -2185,497 +1905,18 @@ kabc_status_t kabc_ais_advance_summary(kabc_ais_t* h, int64_t ngenerations, int3
         st = ais_summary_half_run(h, ngenerations, ntransitions, &cancelled);
     if (st == KABC_OK) st = ais_advance_end(h, ntransitions, small_gc, cancelled, stats);
     // (h->t is that of the generations that ran, a cancelled call's included: the ones the summary holds)
-    h->sum_gens += (int64_t)((h->t - t0) / (uint64_t)ntransitions);
+    sum->gens += (int64_t)((h->t - t0) / (uint64_t)ntransitions);
     return st;
 }
 
-// what every entry point of the derived set asks beyond summary_check(open)
-static kabc_status_t derived_check(const kabc_ais_t* h, const char* who) {
-    if (!h->der_id) {
-        set_error("%s: no derived set is open on this handle's summary (kabc_ais_derived_begin)", who);
-        return KABC_ERR_INVALID_STATE;
-    }
-    return KABC_OK;
-}
-
-// the getters, on either set of the handle (`who`: the entry point)
-static kabc_status_t summary_get_set(kabc_ais_t* h, SummarySet& S, const char* who, int64_t* n, double* pivot,
-                                     double* sum1, double* sum2, double* mean, double* cov, double* mn, double* mx) {
-    if (h->sum_gens == 0) {
-        set_error("%s: the summary holds no generation yet (n = 0)", who);
-        return KABC_ERR_INVALID_STATE;
-    }
-    KABC_HIP_CHECK(hipSetDevice(h->ctx->device));
-    hipStream_t s = h->ctx->stream;
-    const int D = S.D, ns = S.sum_slots;
-    const bool full = S.sum_mode == KABC_SUMMARY_FULL;
-    const size_t nch = (size_t)h->nchains;
-    launch_ais_summary_reduce(S.d_sum_acc, S.d_sum_out, S.d_sum_lvl[0], S.d_sum_lvl[1], h->N, D, ns,
-                              (int64_t)nch * ns, s);
-    KABC_HIP_CHECK(hipGetLastError());
-    std::vector<double> T(nch * (size_t)ns), P(nch * (size_t)D);
-    KABC_HIP_CHECK(hipMemcpyAsync(T.data(), S.d_sum_out, sizeof(double) * T.size(), hipMemcpyDeviceToHost, s));
-    KABC_HIP_CHECK(hipMemcpyAsync(P.data(), S.d_sum_pivot, sizeof(double) * P.size(), hipMemcpyDeviceToHost, s));
-    KABC_HIP_CHECK(hipStreamSynchronize(s));
-    const int64_t cnt = h->sum_gens * h->N;
-    const double dn = (double)cnt, dn1 = (double)(cnt - 1);
-    if (n) *n = cnt;
-    const size_t w2 = full ? (size_t)D * D : (size_t)D;  // doubles of sum2 / cov per chain
-    for (size_t c = 0; c < nch; ++c) {
-        const double* t = T.data() + c * (size_t)ns;
-        const double* t2 = t + 3 * D;
-        for (int k = 0; k < D; ++k) {
-            if (pivot) pivot[c * D + k] = P[c * D + k];
-            if (sum1) sum1[c * D + k] = t[k];
-            if (mn) mn[c * D + k] = t[D + k];
-            if (mx) mx[c * D + k] = t[2 * D + k];
-            if (mean) {
-                const double q = t[k] / dn;
-                mean[c * D + k] = P[c * D + k] + q;
-            }
-            for (int l = 0; l <= (full ? k : 0); ++l) {
-                const int ll = full ? l : k;
-                const double s2 = full ? t2[k * (k + 1) / 2 + l] : t2[k];
-                const double pr = t[k] * t[ll];
-                const double q = pr / dn;
-                const double v = (s2 - q) / dn1;
-                const size_t i0 = full ? c * w2 + (size_t)k * D + l : c * w2 + k;
-                const size_t i1 = full ? c * w2 + (size_t)l * D + k : i0;
-                if (sum2) sum2[i0] = sum2[i1] = s2;
-                if (cov) cov[i0] = cov[i1] = v;
-            }
-        }
-    }
-    return KABC_OK;
-}
-
-kabc_status_t kabc_ais_summary_get(kabc_ais_t* h, int64_t* n, double* pivot, double* sum1, double* sum2,
-                                   double* mean, double* cov, double* mn, double* mx) {
-    const char* who = "kabc_ais_summary_get";
-    if (kabc_status_t st = summary_check(h, who, true)) return st;
-    return summary_get_set(h, h->par, who, n, pivot, sum1, sum2, mean, cov, mn, mx);
-}
-
+// (here, beside kabc_ais_destroy's release: unlike every other summary entry point it asks nothing of the
+// handle but that it exists -- a handle that is not initialised, or sharded, simply has nothing open)
 kabc_status_t kabc_ais_summary_end(kabc_ais_t* h) {
     if (check_handle(h)) return KABC_ERR_INVALID_ARG;
-    if (!h->par.sum_mode) return KABC_OK;
+    if (!h->sum.par.sum_mode) return KABC_OK;
     KABC_HIP_CHECK(hipSetDevice(h->ctx->device));
     KABC_HIP_CHECK(hipStreamSynchronize(h->ctx->stream));  // (queued folds still read the buffers)
-    summary_release(h);
-    return KABC_OK;
-}
-
-// ---- autocorrelation of the summarised trace (ais_autocorr_kernel.hpp) --------------------------------
-
-// how a set's rows are called in a message
-static const char* set_what(const kabc_ais_t* h, const SummarySet& S) {
-    return &S == &h->der ? "derived values" : "parameters";
-}
-
-static kabc_status_t autocorr_begin_set(kabc_ais_t* h, SummarySet& S, const char* who, int32_t maxlag) {
-    if (maxlag < 1 || maxlag > KABC_AUTOCORR_MAX_LAG) {
-        set_error("%s: maxlag %d is outside 1 ... %d", who, maxlag, KABC_AUTOCORR_MAX_LAG);
-        return KABC_ERR_INVALID_ARG;
-    }
-    if (h->sum_gens != 0 || h->par.sum_pivot) {
-        set_error("%s: the open summary already holds generations; the lagged products "
-                  "start with the summary (kabc_ais_summary_begin, then this call)", who);
-        return KABC_ERR_INVALID_STATE;
-    }
-    const int64_t L = maxlag;
-    const int64_t nouter = 3 * (int64_t)h->nchains * L, nseries = nouter * S.D;
-    const int64_t t1 = (h->N + kAcTile - 1) / kAcTile, t2 = (t1 + kAcTile - 1) / kAcTile;
-    if (nseries * t1 >= (1ll << 31)) {  // (the row tree's grid, as for the summary's own accumulators)
-        set_error("%s: %d chains x 3 x maxlag %d x %d %s x %lld walkers (%.1f GiB of "
-                  "accumulators) is beyond the row tree's launch grid", who, h->nchains, maxlag, S.D, set_what(h, S),
-                  (long long)h->N, (double)nseries * (double)h->N * 8.0 / (double)(1ll << 30));
-        return KABC_ERR_UNSUPPORTED;
-    }
-    KABC_HIP_CHECK(hipSetDevice(h->ctx->device));
-    hipStream_t s = h->ctx->stream;
-    if (S.ac_L) {  // (begin again: its buffers may still be read by queued work)
-        KABC_HIP_CHECK(hipStreamSynchronize(s));
-        autocorr_release(S);
-    }
-    const size_t plane = (size_t)h->nchains * (size_t)L * (size_t)h->N * (size_t)S.D;
-    S.ac_bufs.ctx = h->ctx;
-    hipError_t e = S.ac_bufs.alloc(&S.d_ac_acc, 3 * plane);
-    if (e == hipSuccess) e = S.ac_bufs.alloc(&S.d_ac_gens, (size_t)1);
-    if (e == hipSuccess) e = S.ac_bufs.alloc(&S.d_ac_out, (size_t)nseries);
-    if (e == hipSuccess) e = S.ac_bufs.alloc(&S.d_ac_lvl[0], (size_t)(nseries * t1));
-    if (e == hipSuccess) e = S.ac_bufs.alloc(&S.d_ac_lvl[1], (size_t)(nseries * t2));
-    // the lagged products start at +0.0; the windows are written before they are read
-    if (e == hipSuccess) e = hipMemsetAsync(S.d_ac_acc, 0, sizeof(double) * plane, s);
-    if (e == hipSuccess) e = hipMemsetAsync(S.d_ac_gens, 0, sizeof(int64_t), s);
-    if (e != hipSuccess) {
-        autocorr_release(S);
-        KABC_HIP_CHECK(e);
-    }
-    S.ac_L = maxlag;
-    return KABC_OK;
-}
-
-kabc_status_t kabc_ais_autocorr_begin(kabc_ais_t* h, int32_t maxlag) {
-    const char* who = "kabc_ais_autocorr_begin";
-    if (kabc_status_t st = summary_check(h, who, true)) return st;
-    return autocorr_begin_set(h, h->par, who, maxlag);
-}
-
-static kabc_status_t autocorr_get_set(kabc_ais_t* h, SummarySet& S, const char* who, const char* opener,
-                                      int32_t* nlags, double* lagsum, double* first, double* last, double* acov,
-                                      double* rho, double* tau, double* ess, int32_t* window, int32_t* converged) {
-    if (!S.ac_L) {
-        set_error("%s: the open summary keeps no lagged products (%s)", who, opener);
-        return KABC_ERR_INVALID_STATE;
-    }
-    if (h->sum_gens == 0) {
-        set_error("%s: the summary holds no generation yet (n = 0)", who);
-        return KABC_ERR_INVALID_STATE;
-    }
-    KABC_HIP_CHECK(hipSetDevice(h->ctx->device));
-    hipStream_t s = h->ctx->stream;
-    const int D = S.D, ns = S.sum_slots, L = S.ac_L;
-    const bool full = S.sum_mode == KABC_SUMMARY_FULL;
-    const size_t nch = (size_t)h->nchains;
-    launch_ais_summary_reduce(S.d_sum_acc, S.d_sum_out, S.d_sum_lvl[0], S.d_sum_lvl[1], h->N, D, ns,
-                              (int64_t)nch * ns, s);
-    KABC_HIP_CHECK(hipGetLastError());
-    launch_ais_autocorr_reduce(S.d_ac_acc, S.d_ac_out, S.d_ac_lvl[0], S.d_ac_lvl[1], h->N, D,
-                               3 * (int64_t)nch * L, s);
-    KABC_HIP_CHECK(hipGetLastError());
-    const size_t pl = nch * (size_t)L * (size_t)D;  // one plane of the tree's result: [chain][L][D]
-    std::vector<double> T(nch * (size_t)ns), Q(3 * pl);
-    KABC_HIP_CHECK(hipMemcpyAsync(T.data(), S.d_sum_out, sizeof(double) * T.size(), hipMemcpyDeviceToHost, s));
-    KABC_HIP_CHECK(hipMemcpyAsync(Q.data(), S.d_ac_out, sizeof(double) * Q.size(), hipMemcpyDeviceToHost, s));
-    KABC_HIP_CHECK(hipStreamSynchronize(s));
-    const int64_t G = h->sum_gens, N = h->N;
-    const int Lm = (int)(G - 1 < L ? G - 1 : L), Lw = (int)(G < L ? G : L);  // lags; rows of the windows
-    const double dn = (double)(G * N);
-    const double nan = std::numeric_limits<double>::quiet_NaN();
-    if (nlags) *nlags = Lm + 1;
-    std::vector<double> ac((size_t)Lm + 1), rh((size_t)Lm + 1);
-    for (size_t c = 0; c < nch; ++c) {
-        const double* t = T.data() + c * (size_t)ns;
-        const double* TP = Q.data() + c * (size_t)L * D;  // [t - 1][k]
-        const double* TF = TP + pl;                       // [g][k]
-        const double* TR = TF + pl;                       // [slot][k]
-        for (int g = 0; g < Lw; ++g)
-            for (int k = 0; k < D; ++k) {
-                if (first) first[(c * L + g) * D + k] = TF[(size_t)g * D + k];
-                // Last[j], j = g + 1: generation G - j, at ring slot (G - j) mod L
-                if (last) last[(c * L + g) * D + k] = TR[(size_t)((G - 1 - g) % L) * D + k];
-            }
-        for (int k = 0; k < D; ++k) {
-            const double t1 = t[k];
-            const double t2 = full ? t[3 * D + k * (k + 1) / 2 + k] : t[3 * D + k];
-            const double m = t1 / dn;
-            double head = 0.0, tail = 0.0;
-            for (int lag = 0; lag <= Lm; ++lag) {
-                if (lag > 0) {
-                    head = head + TF[(size_t)(lag - 1) * D + k];
-                    tail = tail + TR[(size_t)((G - lag) % L) * D + k];
-                }
-                const double tp = lag == 0 ? t2 : TP[(size_t)(lag - 1) * D + k];
-                const double a = t1 - tail, b = t1 - head;
-                const double u = a + b;
-                const double v = m * u;
-                const double w = tp - v;
-                const double q = m * m;
-                const double cnt = (double)(N * (G - lag));
-                const double x = cnt * q;
-                const double y = w + x;
-                ac[lag] = y / dn;
-                if (lagsum) lagsum[(c * D + k) * (size_t)(L + 1) + lag] = tp;
-                if (acov) acov[(c * D + k) * (size_t)(L + 1) + lag] = ac[lag];
-            }
-            const bool flat = ac[0] == 0.0 || G < 2;
-            int win = 0, conv = 0;
-            double tw = nan;
-            if (!flat) {
-                double sm = 0.0;
-                win = Lm;
-                for (int M = 0; M <= Lm; ++M) {
-                    rh[M] = ac[M] / ac[0];
-                    if (M > 0) sm = sm + rh[M];
-                    const double tm = 1.0 + 2.0 * sm;
-                    if (!conv && (double)M >= 5.0 * tm) {
-                        win = M;
-                        conv = 1;
-                        tw = tm;
-                    }
-                    if (!conv && M == Lm) tw = tm;
-                }
-            }
-            for (int lag = 0; lag <= Lm; ++lag)
-                if (rho) rho[(c * D + k) * (size_t)(L + 1) + lag] = flat ? nan : rh[lag];
-            if (tau) tau[c * D + k] = tw;
-            if (ess) ess[c * D + k] = flat ? nan : dn / tw;
-            if (window) window[c * D + k] = win;
-            if (converged) converged[c * D + k] = conv;
-        }
-    }
-    return KABC_OK;
-}
-
-kabc_status_t kabc_ais_autocorr_get(kabc_ais_t* h, int32_t* nlags, double* lagsum, double* first, double* last,
-                                    double* acov, double* rho, double* tau, double* ess, int32_t* window,
-                                    int32_t* converged) {
-    const char* who = "kabc_ais_autocorr_get";
-    if (kabc_status_t st = summary_check(h, who, true)) return st;
-    return autocorr_get_set(h, h->par, who, "kabc_ais_autocorr_begin", nlags, lagsum, first, last, acov, rho, tau,
-                            ess, window, converged);
-}
-
-// ---- histograms of the summarised trace (ais_hist_kernel.hpp) -----------------------------------------
-
-static kabc_status_t hist_begin_set(kabc_ais_t* h, SummarySet& S, const char* who, int32_t nbins, const double* lo,
-                                    const double* hi) {
-    const bool der = &S == &h->der;
-    const char* one = der ? "derived value" : "parameter";
-    if (nbins < 1 || nbins > KABC_HIST_MAX_BINS) {
-        set_error("%s: nbins %d is outside 1 ... %d", who, nbins, KABC_HIST_MAX_BINS);
-        return KABC_ERR_INVALID_ARG;
-    }
-    if (!lo || !hi) {
-        set_error("%s: lo and hi must be non-NULL ([chain][%s] each)", who, der ? "G" : "D");
-        return KABC_ERR_INVALID_ARG;
-    }
-    const size_t nchD = (size_t)h->nchains * (size_t)S.D;
-    std::vector<double> range(3 * nchD);
-    for (size_t i = 0; i < nchD; ++i) {
-        const int c = (int)(i / (size_t)S.D), k = (int)(i % (size_t)S.D);
-        const double width = hi[i] - lo[i];
-        const double scale = (double)nbins / width;
-        if (!std::isfinite(lo[i]) || !std::isfinite(hi[i]) || !(lo[i] < hi[i])) {
-            set_error("%s: chain %d, %s %d: the range [%g, %g) needs finite bounds with "
-                      "lo < hi", who, c, one, k, lo[i], hi[i]);
-            return KABC_ERR_INVALID_ARG;
-        }
-        if (!std::isfinite(scale) || !(scale > 0.0)) {
-            set_error("%s: chain %d, %s %d: nbins / (hi - lo) = %d / (%g - %g) = %g is not "
-                      "finite and positive", who, c, one, k, nbins, hi[i], lo[i], scale);
-            return KABC_ERR_INVALID_ARG;
-        }
-        range[i] = lo[i];
-        range[nchD + i] = hi[i];
-        range[2 * nchD + i] = scale;
-    }
-    if (h->sum_gens != 0 || h->par.sum_pivot) {
-        set_error("%s: the open summary already holds generations; the histograms start with "
-                  "the summary (kabc_ais_summary_begin, then this call)", who);
-        return KABC_ERR_INVALID_STATE;
-    }
-    const int64_t nwords = (int64_t)nchD * (nbins + 2);
-    if (nwords >= (1ll << 31)) {
-        set_error("%s: %d chains x %d %s x (%d + 2) counters (%.1f GiB of counts) is "
-                  "beyond what one launch grid and the pool serve", who, h->nchains, S.D, set_what(h, S), nbins,
-                  (double)nwords * 8.0 / (double)(1ll << 30));
-        return KABC_ERR_UNSUPPORTED;
-    }
-    KABC_HIP_CHECK(hipSetDevice(h->ctx->device));
-    hipStream_t s = h->ctx->stream;
-    if (S.hist_B) {  // (begin again: its buffers may still be read by queued work)
-        KABC_HIP_CHECK(hipStreamSynchronize(s));
-        hist_release(S);
-    }
-    S.hist_bufs.ctx = h->ctx;
-    S.hist_range.swap(range);  // (the source of the copy below lives as long as the histogram)
-    hipError_t e = S.hist_bufs.alloc(&S.d_hist_counts, (size_t)nwords);
-    if (e == hipSuccess) e = S.hist_bufs.alloc(&S.d_hist_range, 3 * nchD);
-    // pool buffers come back dirty: the counts start at 0
-    if (e == hipSuccess) e = hipMemsetAsync(S.d_hist_counts, 0, sizeof(unsigned long long) * (size_t)nwords, s);
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(S.d_hist_range, S.hist_range.data(), sizeof(double) * 3 * nchD, hipMemcpyHostToDevice, s);
-    if (e != hipSuccess) {
-        hist_release(S);
-        KABC_HIP_CHECK(e);
-    }
-    S.hist_B = nbins;
-    return KABC_OK;
-}
-
-kabc_status_t kabc_ais_hist_begin(kabc_ais_t* h, int32_t nbins, const double* lo, const double* hi) {
-    const char* who = "kabc_ais_hist_begin";
-    if (kabc_status_t st = summary_check(h, who, true)) return st;
-    return hist_begin_set(h, h->par, who, nbins, lo, hi);
-}
-
-static kabc_status_t hist_get_set(kabc_ais_t* h, SummarySet& S, const char* who, const char* opener, int32_t* nbins,
-                                  uint64_t* counts, double* lo, double* hi) {
-    if (!S.hist_B) {
-        set_error("%s: the open summary keeps no histograms (%s)", who, opener);
-        return KABC_ERR_INVALID_STATE;
-    }
-    if (h->sum_gens == 0) {
-        set_error("%s: the summary holds no generation yet (n = 0)", who);
-        return KABC_ERR_INVALID_STATE;
-    }
-    const size_t nchD = (size_t)h->nchains * (size_t)S.D;
-    if (counts) {
-        static_assert(sizeof(uint64_t) == sizeof(unsigned long long), "the counts are 64-bit words");
-        KABC_HIP_CHECK(hipSetDevice(h->ctx->device));
-        hipStream_t s = h->ctx->stream;
-        KABC_HIP_CHECK(hipMemcpyAsync(counts, S.d_hist_counts, sizeof(uint64_t) * nchD * (size_t)(S.hist_B + 2),
-                                      hipMemcpyDeviceToHost, s));
-        KABC_HIP_CHECK(hipStreamSynchronize(s));
-    }
-    if (nbins) *nbins = S.hist_B;
-    if (lo) std::memcpy(lo, S.hist_range.data(), sizeof(double) * nchD);
-    if (hi) std::memcpy(hi, S.hist_range.data() + nchD, sizeof(double) * nchD);
-    return KABC_OK;
-}
-
-kabc_status_t kabc_ais_hist_get(kabc_ais_t* h, int32_t* nbins, uint64_t* counts, double* lo, double* hi) {
-    const char* who = "kabc_ais_hist_get";
-    if (kabc_status_t st = summary_check(h, who, true)) return st;
-    return hist_get_set(h, h->par, who, "kabc_ais_hist_begin", nbins, counts, lo, hi);
-}
-
-// ---- derived quantities g(theta) of the summarised trace (ais_derived_kernel.hpp) -------------------------
-
-kabc_status_t kabc_ais_derived_begin(kabc_ais_t* h, int32_t id, int32_t G, const double* params, int32_t nparams,
-                                     int32_t cov_mode, int32_t maxlag, int32_t nbins, const double* lo,
-                                     const double* hi) {
-    const char* who = "kabc_ais_derived_begin";
-    if (kabc_status_t st = summary_check(h, who, true)) return st;
-    if (G < 1 || G > KABC_MAX_DIM_DYN) {
-        set_error("%s: G = %d outside 1..%d", who, G, KABC_MAX_DIM_DYN);
-        return KABC_ERR_INVALID_ARG;
-    }
-    if (nparams < 0 || (nparams > 0 && !params)) {
-        set_error("%s: a NULL params array or a negative length", who);
-        return KABC_ERR_INVALID_ARG;
-    }
-    if (!derived_registered(id)) {
-        set_error("%s: %d is not a registered derived-quantity snippet (kabc_compile_derived)", who, id);
-        return KABC_ERR_INVALID_ARG;
-    }
-    if (maxlag < 0 || nbins < 0) {
-        set_error("%s: maxlag %d and nbins %d must be >= 0 (0: none)", who, maxlag, nbins);
-        return KABC_ERR_INVALID_ARG;
-    }
-    if (nbins > 0 && (!lo || !hi)) {
-        set_error("%s: lo and hi must be non-NULL ([chain][G] each) with nbins > 0", who);
-        return KABC_ERR_INVALID_ARG;
-    }
-    if (h->sum_gens != 0 || h->par.sum_pivot) {
-        set_error("%s: the open summary already holds generations; the derived set starts with the summary "
-                  "(kabc_ais_summary_begin, then this call)", who);
-        return KABC_ERR_INVALID_STATE;
-    }
-    int32_t mode = 0;
-    if (kabc_status_t st = set_check(h, G, true, cov_mode, who, &mode)) return st;
-    KABC_HIP_CHECK(hipSetDevice(h->ctx->device));
-    hipStream_t s = h->ctx->stream;
-    if (h->der_id) {  // (begin again: its buffers may still be read by queued work)
-        KABC_HIP_CHECK(hipStreamSynchronize(s));
-        derived_release(h);
-    }
-    // the map kernel now: a snippet that does not compile into it fails here, not inside an advance call
-    if (!derived_kernel(id, false)) return KABC_ERR_DEVICE;
-    kabc_status_t st = set_begin(h, h->der, G, mode);
-    if (st == KABC_OK && maxlag > 0) st = autocorr_begin_set(h, h->der, who, maxlag);
-    if (st == KABC_OK && nbins > 0) st = hist_begin_set(h, h->der, who, nbins, lo, hi);
-    if (st == KABC_OK) {
-        h->der_bufs.ctx = h->ctx;
-        hipError_t e = h->der_bufs.alloc(&h->d_der_done, (size_t)1);
-        if (e == hipSuccess && nparams > 0) e = h->der_bufs.alloc(&h->d_der_params, (size_t)nparams);
-        // (a pageable source: the copy has left `params` when the call returns)
-        if (e == hipSuccess && nparams > 0)
-            e = hipMemcpyAsync(h->d_der_params, params, sizeof(double) * nparams, hipMemcpyHostToDevice, s);
-        if (e != hipSuccess) {
-            derived_release(h);
-            KABC_HIP_CHECK(e);
-        }
-    }
-    if (st != KABC_OK) {
-        derived_release(h);
-        return st;
-    }
-    h->der_id = id;
-    h->der_nparams = nparams;
-    return KABC_OK;
-}
-
-kabc_status_t kabc_ais_derived_summary_get(kabc_ais_t* h, int64_t* n, double* pivot, double* sum1, double* sum2,
-                                           double* mean, double* cov, double* mn, double* mx) {
-    const char* who = "kabc_ais_derived_summary_get";
-    if (kabc_status_t st = summary_check(h, who, true)) return st;
-    if (kabc_status_t st = derived_check(h, who)) return st;
-    return summary_get_set(h, h->der, who, n, pivot, sum1, sum2, mean, cov, mn, mx);
-}
-
-kabc_status_t kabc_ais_derived_autocorr_get(kabc_ais_t* h, int32_t* nlags, double* lagsum, double* first,
-                                            double* last, double* acov, double* rho, double* tau, double* ess,
-                                            int32_t* window, int32_t* converged) {
-    const char* who = "kabc_ais_derived_autocorr_get";
-    if (kabc_status_t st = summary_check(h, who, true)) return st;
-    if (kabc_status_t st = derived_check(h, who)) return st;
-    return autocorr_get_set(h, h->der, who, "kabc_ais_derived_begin with maxlag > 0", nlags, lagsum, first, last,
-                            acov, rho, tau, ess, window, converged);
-}
-
-kabc_status_t kabc_ais_derived_hist_get(kabc_ais_t* h, int32_t* nbins, uint64_t* counts, double* lo, double* hi) {
-    const char* who = "kabc_ais_derived_hist_get";
-    if (kabc_status_t st = summary_check(h, who, true)) return st;
-    if (kabc_status_t st = derived_check(h, who)) return st;
-    return hist_get_set(h, h->der, who, "kabc_ais_derived_begin with nbins > 0", nbins, counts, lo, hi);
-}
-
-kabc_status_t kabc_hist_quantile(const uint64_t* counts, int32_t nbins, double lo, double hi, double mn, double mx,
-                                 const double* q, int32_t nq, double* out) {
-    if (!counts || (nq > 0 && (!q || !out))) {
-        set_error("kabc_hist_quantile: counts, q and out must be non-NULL");
-        return KABC_ERR_INVALID_ARG;
-    }
-    if (nbins < 1 || nbins > KABC_HIST_MAX_BINS) {
-        set_error("kabc_hist_quantile: nbins %d is outside 1 ... %d", nbins, KABC_HIST_MAX_BINS);
-        return KABC_ERR_INVALID_ARG;
-    }
-    if (!std::isfinite(lo) || !std::isfinite(hi) || !(lo < hi)) {
-        set_error("kabc_hist_quantile: the range [%g, %g) needs finite bounds with lo < hi", lo, hi);
-        return KABC_ERR_INVALID_ARG;
-    }
-    if (nq < 0) {
-        set_error("kabc_hist_quantile: nq = %d is negative", nq);
-        return KABC_ERR_INVALID_ARG;
-    }
-    for (int32_t i = 0; i < nq; ++i)
-        if (!(q[i] >= 0.0 && q[i] <= 1.0)) {
-            set_error("kabc_hist_quantile: q[%d] = %g is outside [0, 1]", i, q[i]);
-            return KABC_ERR_INVALID_ARG;
-        }
-    const int B = nbins;
-    uint64_t n = 0;
-    for (int j = 0; j < B + 2; ++j) n += counts[j];
-    if (n == 0) {
-        set_error("kabc_hist_quantile: the counts sum to 0 (n = 0)");
-        return KABC_ERR_INVALID_STATE;
-    }
-    const double span = hi - lo;
-    const double w = span / (double)B;
-    for (int32_t i = 0; i < nq; ++i) {
-        const double hq = q[i] * (double)n;
-        uint64_t cum = 0;
-        int j = 0;
-        for (; j < B + 1; ++j) {  // (h <= n: the last non-empty counter is located at the latest)
-            if (counts[j] > 0 && hq <= (double)(cum + counts[j])) break;
-            cum += counts[j];
-        }
-        double v;
-        if (j == 0) v = mn;
-        else if (j == B + 1) v = mx;
-        else {
-            const double num = hq - (double)cum;
-            const double f = num / (double)counts[j];
-            const double pos = (double)(j - 1) + f;
-            const double off = pos * w;
-            v = lo + off;
-            v = v > mn ? v : mn;
-            v = v < mx ? v : mx;
-        }
-        out[i] = v;
-    }
+    summary_release(h->sum);
     return KABC_OK;
 }
 
@@ -3023,7 +2264,7 @@ kabc_status_t kabc_ais_destroy(kabc_ais_t* h) {
     if (h->d_dbg) (void)hipFree(h->d_dbg);
     if (h->d_aux) (void)hipFree(h->d_aux);
     if (h->d_strace) (void)hipFree(h->d_strace);
-    summary_release(h);  // (back to the context's pool)
+    summary_release(h->sum);  // (back to the context's pool)
     timing_release(h);
     delete h;
     return KABC_OK;

@@ -66,6 +66,16 @@ inline hipError_t dev_malloc(T** p, size_t bytes) {
     return e;
 }
 
+// a size knob of the environment (tests, tuning) in `unit` bytes, else `dflt`; read at every call, as
+// the tests change it between handles
+inline size_t env_bytes(const char* name, size_t unit, size_t dflt) {
+    if (const char* e = std::getenv(name)) {
+        const long v = std::atol(e);
+        if (v > 0) return (size_t)v * unit;
+    }
+    return dflt;
+}
+
 // copy of the caller's components with the library-side fields of MvNormal components filled in
 // (device block pointer, D); every entry point resolves before it prepares or copies the prior
 kabc_status_t resolve_priors(kabc_ctx_t* ctx, const kabc_prior_t* prior, int D, kabc_prior_t* out);

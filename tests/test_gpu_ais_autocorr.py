@@ -95,6 +95,19 @@ def test_half_generation_course_odd_rows_several_chunks(k, monkeypatch, L):
     _check(k, _box(k, 3), 641, 150, 1, "halves", L)
 
 
+@pytest.mark.parametrize("N", [513, 1025])
+def test_row_tree_last_tile_of_one_entry(k, N):
+    """N = 512 j + 1: the last tile of the row tree's first level holds a single entry, and at 1025 the second
+    level combines an odd number (3) of run values; D = 3 keeps the planes' element stride in play"""
+    _check(k, _box(k, 3), N, 5, 1, "halves", 4)
+
+
+def test_row_tree_three_levels(k):
+    """N = 512 * 512 + 1: the first shape whose tree has three levels, and so reads back from both scratch levels
+    (a trace of 12.6 MB, planes of 25 MB)"""
+    _check(k, _gauss2(k), 512 * 512 + 1, 3, 1, "halves", 2)
+
+
 def test_both_drivers_give_the_same_bits(k, monkeypatch):
     a, _ = _check(k, _gauss2(k), 100, 25, 2, "small", 8)
     monkeypatch.setenv("KABC_AIS_SMALL", "0")

@@ -85,6 +85,18 @@ def test_half_generation_course_widest_full_shape(k):
     assert s.cov.shape == (16, 16) and s.sum2.shape == (16, 16)
 
 
+@pytest.mark.parametrize("N", [513, 1025])
+def test_row_tree_last_tile_of_one_entry(k, N):
+    """N = 512 j + 1: the last tile of the row tree's first level holds a single entry, and at 1025 the second
+    level combines an odd number (3) of run values"""
+    _check(k, _box(k, 3), N, 5, 1, "halves")
+
+
+def test_row_tree_three_levels(k):
+    """N = 512 * 512 + 1: the first shape whose tree has three levels, and so reads back from both scratch levels"""
+    _check(k, _box(k, 2, k.costs.GaussDist([1.0, -0.5])), 512 * 512 + 1, 3, 1, "halves")
+
+
 def test_diag_below_the_full_limit(k):
     s, _ = _check(k, _box(k, 3), 641, 9, 1, "halves", cov="diag")
     assert s.cov.shape == (3,)
