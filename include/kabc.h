@@ -443,6 +443,28 @@ kabc_status_t kabc_ais_wide_deal(const int32_t* simd, int32_t waves, int32_t chu
                                  uint32_t* masks);
 void kabc_ais_wide_shipped(int32_t geom[3]);
 
+/* ---- the tables of prebuilt kernels (verification only) --------------------------
+ * The library ships its AIS and smc kernels as tables of template instantiations, one table per
+ * family.  kabc_prebuilt_has answers from the tables themselves (no device): 1 where `family` holds a
+ * kernel for (cost_id, D, variant), 0 where it does not and for every argument out of range.  variant:
+ * AIS families, pcx = prior class (0 BOX, 1 SIMPLE, 2 GENERAL, 3 NORMAL) + 4 * (posterior kind - 1);
+ * smc families, 1 the kernels of simple priors, 0 the general ones.
+ * kabc_ctx_last_kernel: info[6] = {family, cost id, D, prior class (AIS) or simple flag (smc), posterior
+ * kind (AIS; 0 for smc), wavefronts per workgroup} of the last AIS or smc kernel launch enqueued on ctx
+ * when that kernel came from one of these tables; all zero when it was a model's own run-time compiled
+ * kernel, a cost plugin's or a run-time-dimension kernel, and before the first launch.  The launch paths
+ * record it on the host; a test reads it to prove which instantiation it ran. */
+enum {
+    KABC_PREBUILT_AIS_HALF = 1,   /* ais_half_kernel: one launch per half-generation            */
+    KABC_PREBUILT_AIS_WIDE = 2,   /* ais_half_wide_kernel: its wide geometry                    */
+    KABC_PREBUILT_AIS_SMALL = 3,  /* the one-workgroup kernel of small ensembles                */
+    KABC_PREBUILT_SMC_PHASES = 4, /* smc_mcmc_kernel: the kernel-per-phase driver's propose / accept */
+    KABC_PREBUILT_SMC_LOOP = 5,   /* the persistent cooperative loop kernel                     */
+    KABC_PREBUILT_SMC_SMALL = 6   /* the one-workgroup kernel of small ensembles                */
+};
+int32_t kabc_prebuilt_has(int32_t family, int32_t cost_id, int32_t D, int32_t variant);
+void kabc_ctx_last_kernel(kabc_ctx_t* ctx, int32_t info[6]);
+
 /* ---- working-memory probe (verification only) ----------------------------------
  * KABC_POISON_ALLOC (read once per process: unset, empty or 0 off; 1 byte 0xA5; 0xNN that byte) fills
  * every working buffer of the library with one byte before use.  The hook is silent, so tests prove it

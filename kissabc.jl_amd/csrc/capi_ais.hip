@@ -117,6 +117,16 @@ AisSmallLaunch find_ais_small_kernel(int cost_id, int D, int pc) {
 #undef KABC_SMALL_CASE
 }
 
+// kabc_prebuilt_has (capi_smc.hip) for the three AIS tables
+int32_t prebuilt_has_ais(int32_t family, int32_t cost_id, int32_t D, int32_t pcx) {
+    if (cost_id < 1 || cost_id >= KABC_COST__COUNT || D < 1 || D > KABC_MAX_DIM || pcx < 0 || pcx >= kAisVariants)
+        return 0;
+    if (family == KABC_PREBUILT_AIS_HALF) return find_ais_kernel(cost_id, D, pcx) ? 1 : 0;
+    if (family == KABC_PREBUILT_AIS_WIDE) return find_ais_wide_kernel(cost_id, D, pcx) ? 1 : 0;
+    if (family == KABC_PREBUILT_AIS_SMALL) return find_ais_small_kernel(cost_id, D, pcx) ? 1 : 0;
+    return 0;
+}
+
 template <int D>
 static void launch_init_d(const InitArgs& a, hipStream_t s, unsigned nchains) {
     const unsigned grid = (unsigned)((a.rows_owned + kInitBlock - 1) / kInitBlock);
@@ -207,6 +217,7 @@ struct kabc_ais {
     AisLaunch launch;      // half-generation kernel (a small-ensemble handle resolves it at first need)
     AisLaunch launch_wide; // its wide geometry, where `launch` is a prebuilt kernel that has one
     int32_t pc = 0;        // its prior class
+    int32_t half_pcx = -1; // the prebuilt table's variant `launch` / `launch_wide` came from, else -1
     // the one-workgroup driver of small ensembles (ais_small_kernel.hpp): kabc_ais_advance runs every
     // generation of a call in ONE launch; spec_state / spec_variant then describe THIS kernel
     bool small_ok = false;
@@ -364,6 +375,7 @@ static kabc_status_t ais_resolve_half(kabc_ais_t* h) {
         // user families: there are no other kernels (message set by the compilation / load)
         if (!fn && unit_required(h->unit)) return KABC_ERR_DEVICE;
     }
+    h->half_pcx = -1;
     if (!fn) {  // (no unit, or a specialisation that is not there (yet): the prebuilt kernels)
         int pc = h->pc;
         // (A/B runs: what the GENERAL class costs a SIMPLE / NORMAL prior -- the classes give the same bits)
@@ -371,6 +383,7 @@ static kabc_status_t ais_resolve_half(kabc_ais_t* h) {
             if (e[0] == 'g' && pc != kPriorBox) pc = kPriorGeneral;
         fn = find_ais_kernel(h->cost_id, h->D, pc + pk_off);
         if (fn) h->launch_wide = find_ais_wide_kernel(h->cost_id, h->D, pc + pk_off);
+        if (fn && h->cost_id < KABC_COST_USER) h->half_pcx = pc + pk_off;
         if (!fn && h->pc == kPriorNormal)  // plugins instantiate SIMPLE only
             fn = find_ais_kernel(h->cost_id, h->D, kPriorSimple + pk_off);
     }
@@ -1143,6 +1156,7 @@ static void ais_poll_spec(kabc_ais_t* h) {
         else {
             h->launch = AisLaunch(k.mod, &ais_half_geom, (unsigned)kAisBlock);
             h->launch_wide = nullptr;  // (the model's own kernels have the one geometry)
+            h->half_pcx = -1;
         }
         h->spec_state = KABC_SPEC_ACTIVE;
         h->spec_switch_at = h->launches;
@@ -1223,6 +1237,7 @@ static kabc_status_t launch_half_seg(kabc_ais_t* h, int32_t half, const kabc_ais
         a.t0 = h->t;
         a.nt = ntransitions;
         h->dyn(a, s, 0);
+        note_kernel(h->ctx, false, 0, 0, 0, 0, 0, 0);
     } else {
         AisArgs a;
         fill_args(a, h);
@@ -1276,7 +1291,11 @@ static kabc_status_t launch_half_seg(kabc_ais_t* h, int32_t half, const kabc_ais
                 a.aux = h->d_aux;
                 a.stride_aux = enqueue_aux(h, half, sg.first, sg.count, a.t0, nb, h->d_aux);
             }
-            (ais_use_wide(h, sg.count, nb) ? h->launch_wide : h->launch)(a, s, (unsigned)h->nchains);
+            const bool wide = ais_use_wide(h, sg.count, nb);
+            (wide ? h->launch_wide : h->launch)(a, s, (unsigned)h->nchains);
+            const int pcl = h->half_pcx % kPriorClasses;
+            note_kernel(h->ctx, h->half_pcx >= 0, wide ? KABC_PREBUILT_AIS_WIDE : KABC_PREBUILT_AIS_HALF, h->cost_id,
+                        h->D, pcl, h->posterior, wide ? ais_wide_waves_c(h->D, pcl) : kAisBlock / kWave);
         }
     }
     if (t_on && ++h->open_count >= h->timing_stride)
@@ -1484,6 +1503,8 @@ static kabc_status_t ais_small_run(kabc_ais_t* h, int64_t ngenerations, int32_t 
         }
         if (h->dsmall) KABC_HIP_CHECK(h->dsmall(ad, s, h->dplan));
         else h->small(a, s);
+        note_kernel(h->ctx, !h->dsmall && h->small.fn && h->cost_id < KABC_COST_USER, KABC_PREBUILT_AIS_SMALL,
+                    h->cost_id, h->D, h->small_pcx % kPriorClasses, h->posterior, kAisSmallWaves);
         if (t_on && ++h->open_count >= h->timing_stride)
             if (kabc_status_t st = timing_close_pair(h)) return st;
         KABC_HIP_CHECK(hipGetLastError());

@@ -226,6 +226,18 @@ void kabc_smc_default_opts(kabc_smc_opts_t* o) {
     o->max_iterations = 0;
 }
 
+// the tables of prebuilt kernels, as their find_* functions answer (no device)
+int32_t kabc_prebuilt_has(int32_t family, int32_t cost_id, int32_t D, int32_t variant) {
+    if (family >= KABC_PREBUILT_AIS_HALF && family <= KABC_PREBUILT_AIS_SMALL)
+        return prebuilt_has_ais(family, cost_id, D, variant);
+    if (cost_id < 1 || cost_id >= KABC_COST__COUNT || D < 1 || D > KABC_MAX_DIM || (variant != 0 && variant != 1))
+        return 0;
+    if (family == KABC_PREBUILT_SMC_PHASES) return find_smc_kernel(cost_id, D, variant == 1) ? 1 : 0;
+    if (family == KABC_PREBUILT_SMC_LOOP) return find_smc_loop_kernel(cost_id, D, variant == 1) ? 1 : 0;
+    if (family == KABC_PREBUILT_SMC_SMALL) return find_smc_small_kernel(cost_id, D, variant == 1) ? 1 : 0;
+    return 0;
+}
+
 // kabc_smc_dist_stats: how the calling thread's last sharded run was driven
 static thread_local int64_t tl_dist_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 
@@ -371,6 +383,7 @@ kabc_status_t SmcRun::exchange(int b, bool with_slots) {
 void SmcRun::run_pass(hipStream_t st) {
     if (dyn) {
         dyn_fn(da, st, 0);
+        note_kernel(ctx, false, 0, 0, 0, 0, 0, 0);
         return;
     }
     if (!mcmc_final) {  // the kernel-per-phase driver runs: the model's own kernel if it is there
@@ -379,6 +392,8 @@ void SmcRun::run_pass(hipStream_t st) {
     }
     if (auxW && aux_ring == 1) launch_aux_prepass(cost->id, xa, st, 1);
     mcmc(ma, st);
+    note_kernel(ctx, mcmc.fn && cost->id < KABC_COST_USER, KABC_PREBUILT_SMC_PHASES, cost->id, D, simple ? 1 : 0, 0,
+                kSmcBlock / kWave);
 }
 
 kabc_status_t SmcRun::look() {  // the control block
@@ -963,6 +978,8 @@ kabc_status_t run_small(SmcRun& r) {
     for (int64_t launches = 0;; ++launches) {
         if (auxW) launch_aux_prepass(r.cost->id, r.xa, s, (unsigned)NR);
         small_fn(sm, s);
+        note_kernel(r.ctx, small_fn.fn && r.cost->id < KABC_COST_USER, KABC_PREBUILT_SMC_SMALL, r.cost->id, r.D,
+                    r.simple ? 1 : 0, 0, kSmallBlock / kWave);
         KABC_HIP_CHECK(hipGetLastError());
         r.small_launches = launches + 1;
         if (launches == 0) KABC_HIP_CHECK(hipEventRecord(r.ev.b, s));
@@ -1030,6 +1047,8 @@ kabc_status_t run_loop(SmcRun& r) {
         set_error("cooperative launch of the smc loop kernel failed: %s", hipGetErrorString(le));
         return KABC_ERR_DEVICE;
     }
+    note_kernel(r.ctx, loop_fn.fn && r.cost->id < KABC_COST_USER, KABC_PREBUILT_SMC_LOOP, r.cost->id, r.D,
+                r.simple ? 1 : 0, 0, kLoopBlock / kWave);
     KABC_HIP_CHECK(hipEventRecord(r.ev.b, s));
     KABC_HIP_CHECK(hipMemcpyAsync(&r.hc, r.ctrl, sizeof r.hc, hipMemcpyDeviceToHost, s));
     KABC_HIP_CHECK(hipStreamSynchronize(s));

@@ -106,9 +106,23 @@ struct kabc_ctx {
     // cancel_h, the polling kernels read it through cancel_d
     uint32_t* cancel_h = nullptr;
     uint32_t* cancel_d = nullptr;
+    // kabc_ctx_last_kernel (verification only): the last prebuilt AIS / smc launch, note_kernel below
+    int32_t last_kernel[6] = {};
 };
 
 namespace kabc {
+// The host launch paths of capi_ais.hip / capi_smc.hip record which kernel they enqueue: {family
+// (KABC_PREBUILT_*), cost id, D, prior class or simple flag, posterior kind, waves per workgroup} of a
+// kernel of the prebuilt tables, all zero for anything else (a model's own run-time compiled kernel, a cost
+// plugin's, a run-time-dimension kernel).
+inline void note_kernel(kabc_ctx_t* ctx, bool prebuilt, int family, int cost_id, int D, int variant, int kind,
+                        int waves) {
+    const int32_t v[6] = {family, cost_id, D, variant, kind, waves};
+    for (int i = 0; i < 6; ++i) ctx->last_kernel[i] = prebuilt ? v[i] : 0;
+}
+// kabc_prebuilt_has for the three AIS tables (capi_ais.hip, where their find_* functions live)
+int32_t prebuilt_has_ais(int32_t family, int32_t cost_id, int32_t D, int32_t pcx);
+
 // device buffers of one run-to-completion call (kabc_smc_run, kabc_pfilter_run), released on every
 // return path
 struct DevBufs {
