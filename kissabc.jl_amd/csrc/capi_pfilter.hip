@@ -4,14 +4,20 @@
 // kabc_pfilter_run_from: the same run started from a state and / or leaving one.
 // kabc_pfilter_run_batch: many independent runs, one workgroup each, as one launch grid
 // (pfilter_small_kernel.hpp), or one after another through kabc_pfilter_run.
+//
+// Layout of the single-run driver: pf_prepare decides once per call (prior, refusals, course, kernels, every
+// environment knob) into a PfPlan; pf_run_once makes one attempt over buffers of its own -- the state upload or
+// the initial draw, ONE course (pf_small_course: the one-workgroup kernel; pf_loop_course: four iterations per
+// host look; pf_passes_course: a launch per attempt, KABC_PF_PASSES=1), then pf_finish, the only epilogue.
+// pfilter_run_impl repeats the attempt with cooperative select launches when a course reports that an ordinary
+// one timed out.  pf_decode maps every device error code to its status and message.
 #include <cmath>
 #include <cstdlib>
 #include <string>
 #include <vector>
 
 #define KABC_PFILTER_UNIT 1
-#include "host_common.hpp"
-#include "plugin_registry.hpp"
+#include "population_host.hpp"
 #include "pfilter_kernels.hpp"
 #include "pfilter_small_kernel.hpp"
 
@@ -119,189 +125,405 @@ static kabc_status_t pf_check_state(const PfMode& mode, int32_t D, const kabc_pf
     return KABC_OK;
 }
 
-// force_coop: the run is repeated with cooperative launches of the select kernel after an ordinary
-// launch did not become co-resident in time (several large runs or another tenant holding the CUs)
-static kabc_status_t pfilter_run_impl(kabc_ctx_t* ctx, const kabc_prior_t* prior, int32_t D,
-                                      const kabc_cost_t* cost, const kabc_pfilter_opts_t* o,
-                                      kabc_pfilter_result_t* res, const PfMode& mode, bool force_coop) {
-    const kabc_pfilter_state_t* const from = mode.from;
-    kabc_pfilter_state_t* const to = mode.to;
-    // length(prior) > KABC_MAX_DIM: the run-time-dimension instantiation (D = 0) of the kernels,
-    // prior components as device arrays
-    std::vector<kabc_prior_t> resolved((size_t)D);  // MvNormal components: device block, D
-    if (kabc_status_t st = resolve_priors(ctx, prior, D, resolved.data())) return st;
-    prior = resolved.data();
-    const bool dyn = D > KABC_MAX_DIM;
-    PriorSet P;
-    std::memset(&P, 0, sizeof P);
-    std::vector<PriorDev> Pdyn((size_t)(dyn ? D : 0));
-    bool prior_ok = true;
-    if (dyn)
-        for (int k = 0; k < D && prior_ok; ++k) prior_ok = prepare_prior(prior[k], Pdyn[k]);
-    else
-        prior_ok = prepare_priors(prior, D, P);
-    if (!prior_ok) {
-        set_error("invalid prior parameters");
-        return KABC_ERR_INVALID_ARG;
+namespace {
+
+// kabc_pfilter_run's own messages, and the one place a device error code becomes a verdict.  PfCtrl::error and
+// SmcCtrl::error hold the select kernel's codes (1, 2: the quantile is undefined; 3: a device-wide barrier timed
+// out) or 9 (a particle left unreplaced); the initial draw's failure (AbcdeCtrl::error, PfBatchRec::error == 1)
+// comes in as kPfErrInit.
+const char* const kPfExhausted = "pfilter: the prior never produced a finite (cost, logpdf) pair for some particle";
+const char* const kPfUnreplaced = "pfilter: a particle was not replaced after 2^24 proposals";
+const char* const kPfNanCost = "pfilter: quantile of the costs is undefined (NaN or empty)";
+const char* const kPfWedged = "pfilter: a device-wide barrier of a cooperative launch timed out after 5 s (the device is wedged)";
+constexpr int kPfErrInit = -1, kPfErrTimeOut = 3, kPfErrUnreplaced = 9;
+struct PfVerdict {
+    kabc_status_t status;
+    const char* msg;
+};
+PfVerdict pf_decode(int code) {
+    switch (code) {
+        case 0: return {KABC_OK, nullptr};
+        case kPfErrInit: return {KABC_ERR_RETRY_EXHAUSTED, kPfExhausted};
+        case kPfErrUnreplaced: return {KABC_ERR_RETRY_EXHAUSTED, kPfUnreplaced};
+        case kPfErrTimeOut: return {KABC_ERR_DEVICE, kPfWedged};
+        default: return {KABC_ERR_NAN_COST, kPfNanCost};
     }
-    if (!cost_dim_ok_rt(cost->id, D)) {
-        set_error("DeviceCost id %d does not accept D = %d", cost->id, D);
-        return KABC_ERR_UNSUPPORTED;
-    }
+}
+kabc_status_t pf_fail(int code) {
+    const PfVerdict v = pf_decode(code);
+    set_error("%s", v.msg);
+    return v.status;
+}
+
+bool env_first_is(const char* name, char c) {
+    const char* e = std::getenv(name);
+    return e && e[0] == c;
+}
+
+// what a call decides once, before anything is allocated
+struct PfPlan {
+    kabc_ctx_t* ctx = nullptr;
+    const kabc_cost_t* cost = nullptr;
+    const kabc_pfilter_opts_t* o = nullptr;
+    int32_t D = 0;
+    int64_t N = 0;
+    PopPrior prior;
+    enum Course { kSmall, kLoop, kPasses } course = kLoop;
+    bool time_out_hook = false;  // KABC_SMC_SELECT_TIME_OUT (tests): the first look of an ordinary-launch attempt counts as timed out
     AbcdeLaunch f_init;
     PfLaunch f_att;
-    {
-        const CostPlugin* pl = cost->id >= KABC_COST_USER ? find_plugin(cost->id) : nullptr;
-        if (dyn && pl && !pl->rtc) {
-            set_error("pfilter with length(prior) = %d > %d: built-in DeviceCosts or a user cost in the hipRTC "
-                      "form (kabc_compile_cost_plugin)", D, KABC_MAX_DIM);
-            return KABC_ERR_UNSUPPORTED;
-        }
-    }
+    PfSmallLaunchFn f_small = nullptr;
+};
+
+kabc_status_t pf_prepare(kabc_ctx_t* ctx, const kabc_prior_t* prior, int32_t D, const kabc_cost_t* cost,
+                         const kabc_pfilter_opts_t* o, PfPlan& p) {
+    p.ctx = ctx;
+    p.cost = cost;
+    p.o = o;
+    p.D = D;
+    if (kabc_status_t st = prepare_pop_prior(ctx, prior, D, cost->id, p.prior)) return st;
+    if (kabc_status_t st = refuse_hipcc_plugin_dyn("pfilter", cost->id, D)) return st;
     // (run-time compiled kernels are loaded on the CURRENT device)
     KABC_HIP_CHECK(hipSetDevice(ctx->device));
-    const int64_t N = kabc_pfilter_nparticles(o->nparticles, o->q, D);
+    p.N = kabc_pfilter_nparticles(o->nparticles, o->q, D);
     // Up to 256 particles (the reference's default is 100) with a built-in cost: the whole loop in one
     // launch of ONE workgroup (pf_small_kernel; KABC_PF_SMALL=0 or KABC_PF_PASSES=1: the launches per
     // phase).  At this size a model's own kernels would buy nothing: none are asked for.
-    bool small = false;
-    {
-        const char* e = std::getenv("KABC_PF_SMALL");
-        const char* pe = std::getenv("KABC_PF_PASSES");
-        small = N <= (int64_t)kPfSmallBlock && cost->id < KABC_COST_USER && !(e && e[0] == '0') && !(pe && pe[0] == '1');
-    }
+    const bool passes = env_first_is("KABC_PF_PASSES", '1');  // one launch per attempt (the former scheme)
+    bool small = p.N <= (int64_t)kPfSmallBlock && cost->id < KABC_COST_USER && !env_first_is("KABC_PF_SMALL", '0') && !passes;
+    p.time_out_hook = std::getenv("KABC_SMC_SELECT_TIME_OUT") != nullptr;
     ModelUnit* unit = nullptr;
-    if (kabc_status_t st = model_unit_for(prior, D, cost->id, &unit, !small)) return st;
+    if (kabc_status_t st = model_unit_for(p.prior.raw.data(), D, cost->id, &unit, !small)) return st;
     if (unit && unit_required(unit)) small = false;  // (user prior families: only their unit knows them)
-    if (unit) {  // user prior families / a specialised model (plugin_registry.hpp)
-        const PluginKernel ki = unit_kernel(unit, kPfAbcdeInit, D, 0), ka = unit_kernel(unit, kPfAttempt, D, 0);
-        if (ki.mod) f_init = AbcdeLaunch(ki.mod, &abcde_geom, (unsigned)kAbcdeBlock);
-        if (ka.mod) f_att = PfLaunch(ka.mod, &pf_geom, (unsigned)kPfBlock);
-        if ((!f_init || !f_att) && unit_required(unit)) return KABC_ERR_DEVICE;
-        // (a specialisation that is not there (yet): what is missing comes from below, same bits)
+    p.course = passes ? PfPlan::kPasses : small ? PfPlan::kSmall : PfPlan::kLoop;
+    // the prebuilt kernels: the D = 0 instantiations beyond KABC_MAX_DIM, else the tables' entries
+    const std::make_integer_sequence<int, KABC_MAX_DIM> dims{};
+    const bool dyn = D > KABC_MAX_DIM;
+    AbcdeLaunchFn b_init = &pf_l_init<0>;
+    PfLaunchFn b_att = &pf_l_attempt<0>;
+    if (!dyn) {
+        b_init = pf_pick_init(D, dims);
+        b_att = pf_pick_attempt(D, dims);
     }
-    if (!f_init || !f_att) {
-        AbcdeLaunch b_init;
-        PfLaunch b_att;
-        if (dyn && cost->id < KABC_COST_USER) {
-            b_init = AbcdeLaunch(&pf_l_init<0>);
-            b_att = PfLaunch(&pf_l_attempt<0>);
-        } else if (const CostPlugin* p = find_plugin(cost->id)) {
-            const PluginKernel ki = plugin_kernel(p, kPfAbcdeInit, D, 0), ka = plugin_kernel(p, kPfAttempt, D, 0);
-            b_init = ki.host ? AbcdeLaunch((AbcdeLaunchFn)ki.host)
-                             : ki.mod ? AbcdeLaunch(ki.mod, &abcde_geom, (unsigned)kAbcdeBlock) : AbcdeLaunch();
-            b_att = ka.host ? PfLaunch((PfLaunchFn)ka.host)
-                            : ka.mod ? PfLaunch(ka.mod, &pf_geom, (unsigned)kPfBlock) : PfLaunch();
-            if (!b_init || !b_att) {
-                set_error("cost plugin has no pfilter kernels for D = %d", D);
-                return KABC_ERR_UNSUPPORTED;
-            }
-        } else {
-            b_init = pf_pick_init(D, std::make_integer_sequence<int, KABC_MAX_DIM>{});
-            b_att = pf_pick_attempt(D, std::make_integer_sequence<int, KABC_MAX_DIM>{});
-        }
-        if (!f_init) f_init = b_init;
-        if (!f_att) f_att = b_att;
-    }
-    KABC_HIP_CHECK(hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
+    p.f_small = dyn ? &pf_l_small<0> : pf_pick_small(D, dims);
+    if (kabc_status_t st = resolve_pop_kernel(unit, cost->id, kPfAbcdeInit, D, &abcde_geom, (unsigned)kAbcdeBlock, b_init,
+                                              "pfilter", &p.f_init))
+        return st;
+    return resolve_pop_kernel(unit, cost->id, kPfAttempt, D, &pf_geom, (unsigned)kPfBlock, b_att, "pfilter", &p.f_att);
+}
+
+// the device buffers of one attempt and the argument structs over them
+struct PfAttempt {
     DevBufs bufs;
-    bufs.ctx = ctx;
-    double *th, *Cc, *lpi, *d_params = nullptr, *d_data = nullptr, *d_out, *d_cout;
-    uint8_t *ones, *ok, *pending;
+    hipStream_t s = nullptr;
+    bool force_coop = false;  // the select kernel by cooperative launches (the repeated attempt)
+    double *th = nullptr, *Cc = nullptr, *lpi = nullptr, *d_out = nullptr, *d_cout = nullptr;
+    uint8_t *ok = nullptr, *pending = nullptr;
+    SmcCtrl* sel = nullptr;
+    PfCtrl* pctrl = nullptr;
+    SmcSelectArgs sa;
+    unsigned selG = 0;
+    PfArgs pa;
+};
+
+// what a course leaves: the loop's scalars, the control block as the host read it last (its counters go into
+// the result), and two verdicts -- stopped by kabc_ctx_cancel; an ordinary select launch timed out
+struct PfOutcome {
+    int64_t iters = 0;
+    double eps = INFINITY, eff = NAN;  // (iteration 0: Inf, NaN)
+    bool cancelled = false, timed_out = false;
+    PfCtrl last;
+};
+
+// the host's look at the control block(s) behind what is enqueued
+kabc_status_t pf_look(const PfAttempt& a, PfCtrl* hp, SmcCtrl* hsel = nullptr) {
+    KABC_HIP_CHECK(hipGetLastError());
+    KABC_HIP_CHECK(hipMemcpyAsync(hp, a.pctrl, sizeof *hp, hipMemcpyDeviceToHost, a.s));
+    if (hsel) KABC_HIP_CHECK(hipMemcpyAsync(hsel, a.sel, sizeof *hsel, hipMemcpyDeviceToHost, a.s));
+    KABC_HIP_CHECK(hipStreamSynchronize(a.s));
+    return KABC_OK;
+}
+
+void pf_print_iteration(const PfPlan& p, long long iters, double eps, double eff) {
+    if (p.o->verbose) fprintf(stderr, "(iters, ϵ, eff) = (%lld, %.17g, %.17g)\n", iters, eps, eff);
+}
+
+// :280-294 (same initial-draw loop as ABCDE, its own stream domains)
+kabc_status_t pf_initial_draw(const PfPlan& p, const PfAttempt& a, AbcdeCtrl* actrl, const kabc_prior_t* d_raw) {
+    AbcdeArgs ia;
+    std::memset(&ia, 0, sizeof ia);
+    ia.theta[0] = a.th;
+    ia.delta[0] = a.Cc;
+    ia.lpi[0] = a.lpi;
+    ia.ctrl = actrl;
+    ia.cost_params = a.pa.cost_params;
+    ia.cost_data = a.pa.cost_data;
+    ia.cost_ndata = p.cost->ndata;
+    ia.N = p.N;
+    ia.seed = p.o->seed;
+    ia.cost_id = p.cost->id;
+    ia.dom_init = KABC_DOM_PF_INIT;
+    ia.dom_init_cost = KABC_DOM_PF_INIT_COST;
+    ia.prior = p.prior.set;
+    ia.D_rt = p.D;
+    ia.dprior = a.pa.dprior;
+    ia.draw = d_raw;
+    if (p.D <= KABC_MAX_DIM) std::memcpy(ia.raw, p.prior.raw.data(), sizeof(kabc_prior_t) * p.D);
+    p.f_init(ia, a.s);
+    KABC_HIP_CHECK(hipGetLastError());
+    AbcdeCtrl hc;
+    KABC_HIP_CHECK(hipMemcpyAsync(&hc, actrl, sizeof hc, hipMemcpyDeviceToHost, a.s));
+    KABC_HIP_CHECK(hipStreamSynchronize(a.s));
+    return hc.error ? pf_fail(kPfErrInit) : KABC_OK;
+}
+
+// the whole loop in launches of ONE workgroup (verbose runs: a launch per iteration, to print it)
+kabc_status_t pf_small_course(const PfPlan& p, const PfMode& mode, const PfAttempt& a, PfOutcome& out) {
+    PfSmallArgs sm;
+    std::memset(&sm, 0, sizeof sm);
+    sm.pf = a.pa;
+    sm.pf.pending = nullptr;
+    sm.pf.idxok = nullptr;
+    sm.pf.sel = nullptr;
+    sm.q = p.o->q;
+    sm.eff_tol = p.o->eff_tol;
+    sm.epstol = p.o->epstol;
+    sm.max_iters = p.o->max_iters;
+    sm.iters_this_launch = p.o->verbose ? 1 : 0;
+    sm.cancel = mode.poll ? p.ctx->cancel_d : nullptr;
+    PfCtrl& hp = out.last;
+    do {
+        p.f_small(sm, a.s);
+        if (kabc_status_t st = pf_look(a, &hp)) return st;
+        if (hp.error) return pf_fail(hp.error);
+        pf_print_iteration(p, hp.iters, hp.eps, hp.eff);
+    } while (!hp.done);
+    out.cancelled = hp.done == 2;  // (stopped at an iteration boundary by kabc_ctx_cancel)
+    out.iters = hp.iters;
+    out.eps = hp.eps;
+    out.eff = hp.eff;
+    return KABC_OK;
+}
+
+// the select kernel, then the marks of the bad particles: the head of an iteration of the two courses below
+kabc_status_t pf_select_and_mark(PfAttempt& a, int64_t N, int64_t iteration) {
+    KABC_HIP_CHECK(launch_select(a.sa, a.selG, a.s, a.force_coop));
+    hipLaunchKernelGGL(pf_mark_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, a.s, a.pending, a.ok, a.pctrl,
+                       a.sel, N);
+    a.pa.iteration = (uint64_t)iteration;  // (the iteration index of the streams: it continues from the state)
+    a.pa.attempt = 0u;
+    return KABC_OK;
+}
+
+// Default: every bad particle's rejection loop inside one launch, the stop tests on the device,
+// FOUR iterations enqueued per host round trip (kernels of iterations after the last are
+// no-ops); verbose runs look after every iteration, to print it.
+kabc_status_t pf_loop_course(const PfPlan& p, const PfMode& mode, PfAttempt& a, PfOutcome& out) {
+    const kabc_pfilter_opts_t* o = p.o;
+    const bool coop = select_cooperative(a.force_coop);
+    const int kIterBatch = o->verbose ? 1 : 4;
+    PfCtrl& hp = out.last;
+    int64_t iters = out.iters;
+    do {
+        for (int b = 0; b < kIterBatch; ++b) {
+            if (kabc_status_t st = pf_select_and_mark(a, p.N, ++iters)) return st;
+            a.pa.loop_attempts = 1;
+            p.f_att(a.pa, a.s);
+            hipLaunchKernelGGL(pf_iter_end_kernel, dim3(1), dim3(1), 0, a.s, a.pctrl, a.sel, p.N, o->eff_tol, o->epstol,
+                               o->max_iters);
+        }
+        if (kabc_status_t st = pf_look(a, &hp)) return st;
+        if (!coop && hp.error == 0 && p.time_out_hook) hp.error = kPfErrTimeOut;
+        if (hp.error == kPfErrTimeOut && !coop) {
+            out.timed_out = true;
+            return KABC_OK;
+        }
+        if (hp.error) return pf_fail(hp.error);
+        pf_print_iteration(p, hp.iters, hp.eps, hp.eff);
+        // (the host waits here anyway: kabc_ctx_cancel is looked at on the boundary of the batch's last iteration)
+        out.cancelled = !hp.done && mode.poll && cancel_pending(p.ctx);
+    } while (!hp.done && !out.cancelled);
+    out.iters = hp.iters;
+    out.eps = hp.eps;
+    out.eff = hp.eff;
+    return KABC_OK;
+}
+
+// KABC_PF_PASSES=1: a launch per attempt, eight per host round trip, the stop tests on the host
+kabc_status_t pf_passes_course(const PfPlan& p, const PfMode& mode, PfAttempt& a, PfOutcome& out) {
+    const kabc_pfilter_opts_t* o = p.o;
+    const bool coop = select_cooperative(a.force_coop);
+    PfCtrl& hp = out.last;
+    SmcCtrl hsel;
+    while (true) {
+        if (kabc_status_t st = pf_select_and_mark(a, p.N, ++out.iters)) return st;
+        a.pa.loop_attempts = 0;
+        uint32_t attempt = 0;
+        while (true) {
+            for (int g = 0; g < 8; ++g) {
+                a.pa.attempt = attempt++;
+                p.f_att(a.pa, a.s);
+            }
+            if (kabc_status_t st = pf_look(a, &hp, &hsel)) return st;
+            if (hsel.error == kPfErrTimeOut && !coop) {
+                out.timed_out = true;
+                return KABC_OK;
+            }
+            if (hsel.error) return pf_fail(hsel.error);
+            if (hp.remaining == 0) break;
+            if (attempt >= (1u << 24)) return pf_fail(kPfErrUnreplaced);
+        }
+        // NOTE passes enqueued after the last replacement are no-ops (nothing pending)
+        out.eps = hsel.eps;
+        const double nbad = (double)(p.N - hsel.ess);
+        out.eff = nbad / (double)hp.nreps;  // :327 (0/0 = NaN when nothing was bad, as in Julia)
+        pf_print_iteration(p, out.iters, out.eps, out.eff);
+        if (out.eff < o->eff_tol) break;
+        if (out.eps < o->epstol) break;
+        if (o->max_iters >= 0 && out.iters > o->max_iters) break;  // src/smc.jl:332; < 0 = Inf
+        if (!(hp.nreps > 0)) break;  // nothing left to refresh: eff is NaN forever
+        if (mode.poll && cancel_pending(p.ctx)) {  // (kabc_ctx_cancel takes effect at the iteration's end)
+            out.cancelled = true;
+            break;
+        }
+    }
+    return KABC_OK;
+}
+
+// the epilogue: the push_p'ed population, the copies to `res` and `to`, their scalars, the cancel verdict
+kabc_status_t pf_finish(const PfPlan& p, const PfMode& mode, const PfAttempt& a, const PfOutcome& out,
+                        kabc_pfilter_result_t* res) {
+    const int64_t N = p.N;
+    const int32_t D = p.D;
+    hipStream_t s = a.s;
+    kabc_pfilter_state_t* const to = mode.to;
+    SmcFinalArgs fa;
+    fa.theta[0] = fa.theta[1] = a.th;
+    fa.X[0] = fa.X[1] = a.Cc;
+    fa.ctrl = a.sel;
+    fa.out = a.d_out;
+    fa.Xout = a.d_cout;
+    fa.N = N;
+    fa.D = D;
+    fa.prior = p.prior.set;
+    fa.dprior = a.pa.dprior;
+    hipLaunchKernelGGL(smc_finalize_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, fa);
+    KABC_HIP_CHECK(hipGetLastError());
+    if (res->theta) KABC_HIP_CHECK(hipMemcpyAsync(res->theta, a.d_out, sizeof(double) * N * D, hipMemcpyDeviceToHost, s));
+    if (res->cost) KABC_HIP_CHECK(hipMemcpyAsync(res->cost, a.d_cout, sizeof(double) * N, hipMemcpyDeviceToHost, s));
+    if (to) {  // the population as the loop holds it (NOT push_p'ed)
+        KABC_HIP_CHECK(hipMemcpyAsync(to->theta, a.th, sizeof(double) * N * D, hipMemcpyDeviceToHost, s));
+        KABC_HIP_CHECK(hipMemcpyAsync(to->cost, a.Cc, sizeof(double) * N, hipMemcpyDeviceToHost, s));
+        KABC_HIP_CHECK(hipMemcpyAsync(to->logprior, a.lpi, sizeof(double) * N, hipMemcpyDeviceToHost, s));
+    }
+    KABC_HIP_CHECK(hipStreamSynchronize(s));
+    res->eps = out.eps;
+    res->eff = out.eff;
+    res->iterations = out.iters;
+    res->nreps = out.last.total_reps;
+    res->cost_evals = out.last.cost_evals;
+    if (to) {
+        to->nparticles = N;
+        to->D = D;
+        to->reserved = 0;
+        to->seed = p.o->seed;
+        to->iteration = out.iters;
+        to->eps = out.eps;
+        to->eff = out.eff;
+        to->nreps = out.last.total_reps;
+        to->cost_evals = out.last.cost_evals;
+    }
+    if (out.cancelled) {  // stopped after `iters` iterations: the result of max_iters = iters - 1
+        if (!cancel_take(p.ctx)) set_error("cancelled");
+        return KABC_ERR_CANCELLED;
+    }
+    return KABC_OK;
+}
+
+// One attempt, from its own buffers to the epilogue.  *timed_out (with KABC_OK): an ordinary select launch did
+// not become co-resident in time (several large runs or another tenant holding the CUs) and nothing was
+// written; the caller makes the attempt again with force_coop.
+kabc_status_t pf_run_once(const PfPlan& p, const PfMode& mode, bool force_coop, kabc_pfilter_result_t* res,
+                          bool* timed_out) {
+    *timed_out = false;
+    kabc_ctx_t* const ctx = p.ctx;
+    const kabc_pfilter_opts_t* const o = p.o;
+    const kabc_pfilter_state_t* const from = mode.from;
+    const int64_t N = p.N;
+    const int32_t D = p.D;
+    KABC_HIP_CHECK(hipSetDevice(ctx->device));
+    PfAttempt a;
+    a.s = ctx->stream;
+    a.force_coop = force_coop;
+    a.bufs.ctx = ctx;
+    hipStream_t s = a.s;
+    uint8_t* ones;
     int32_t* cidx;
-    SmcCtrl* sel;
-    PfCtrl* pctrl;
     AbcdeCtrl* actrl;
-    KABC_HIP_CHECK(bufs.alloc(&th, (size_t)N * D));
-    KABC_HIP_CHECK(bufs.alloc(&Cc, (size_t)N));
-    KABC_HIP_CHECK(bufs.alloc(&lpi, (size_t)N));
-    KABC_HIP_CHECK(bufs.alloc(&d_out, (size_t)N * D));
-    KABC_HIP_CHECK(bufs.alloc(&d_cout, (size_t)N));
-    KABC_HIP_CHECK(bufs.alloc(&ones, (size_t)N));
-    KABC_HIP_CHECK(bufs.alloc(&ok, (size_t)N));
-    KABC_HIP_CHECK(bufs.alloc(&pending, (size_t)N));
-    KABC_HIP_CHECK(bufs.alloc(&cidx, (size_t)N));
-    KABC_HIP_CHECK(bufs.alloc(&sel, 1));
-    KABC_HIP_CHECK(bufs.alloc(&pctrl, 1));
-    KABC_HIP_CHECK(bufs.alloc(&actrl, 1));
+    KABC_HIP_CHECK(a.bufs.alloc(&a.th, (size_t)N * D));
+    KABC_HIP_CHECK(a.bufs.alloc(&a.Cc, (size_t)N));
+    KABC_HIP_CHECK(a.bufs.alloc(&a.lpi, (size_t)N));
+    KABC_HIP_CHECK(a.bufs.alloc(&a.d_out, (size_t)N * D));
+    KABC_HIP_CHECK(a.bufs.alloc(&a.d_cout, (size_t)N));
+    KABC_HIP_CHECK(a.bufs.alloc(&ones, (size_t)N));
+    KABC_HIP_CHECK(a.bufs.alloc(&a.ok, (size_t)N));
+    KABC_HIP_CHECK(a.bufs.alloc(&a.pending, (size_t)N));
+    KABC_HIP_CHECK(a.bufs.alloc(&cidx, (size_t)N));
+    KABC_HIP_CHECK(a.bufs.alloc(&a.sel, 1));
+    KABC_HIP_CHECK(a.bufs.alloc(&a.pctrl, 1));
+    KABC_HIP_CHECK(a.bufs.alloc(&actrl, 1));
     KABC_HIP_CHECK(hipMemsetAsync(ones, 1, (size_t)N, s));
-    KABC_HIP_CHECK(hipMemsetAsync(sel, 0, sizeof(SmcCtrl), s));
-    KABC_HIP_CHECK(hipMemsetAsync(pctrl, 0, sizeof(PfCtrl), s));  // (a continued run: the state's counters, below)
+    KABC_HIP_CHECK(hipMemsetAsync(a.sel, 0, sizeof(SmcCtrl), s));
+    KABC_HIP_CHECK(hipMemsetAsync(a.pctrl, 0, sizeof(PfCtrl), s));  // (a continued run: the state's counters, below)
     KABC_HIP_CHECK(hipMemsetAsync(actrl, 0, sizeof(AbcdeCtrl), s));
-    PriorDev* d_prior = nullptr;
-    kabc_prior_t* d_raw = nullptr;
-    if (dyn) {
-        KABC_HIP_CHECK(bufs.alloc(&d_prior, (size_t)D));
-        KABC_HIP_CHECK(bufs.alloc(&d_raw, (size_t)D));
-        KABC_HIP_CHECK(hipMemcpyAsync(d_prior, Pdyn.data(), sizeof(PriorDev) * D, hipMemcpyHostToDevice, s));
-        KABC_HIP_CHECK(hipMemcpyAsync(d_raw, prior, sizeof(kabc_prior_t) * D, hipMemcpyHostToDevice, s));
-    }
-    if (cost->nparams > 0) {
-        KABC_HIP_CHECK(bufs.alloc(&d_params, (size_t)cost->nparams));
-        KABC_HIP_CHECK(hipMemcpyAsync(d_params, cost->params, sizeof(double) * cost->nparams,
-                                      hipMemcpyHostToDevice, s));
-    }
-    if (cost->ndata > 0) {
-        KABC_HIP_CHECK(bufs.alloc(&d_data, (size_t)cost->ndata));
-        KABC_HIP_CHECK(hipMemcpyAsync(d_data, cost->data, sizeof(double) * cost->ndata,
-                                      hipMemcpyHostToDevice, s));
-    }
+    PopInputs in;
+    if (kabc_status_t st = upload_pop_inputs(a.bufs, s, p.prior, p.cost, in)) return st;
+    PfArgs& pa = a.pa;
+    std::memset(&pa, 0, sizeof pa);
+    pa.theta = a.th;
+    pa.C = a.Cc;
+    pa.lpi = a.lpi;
+    pa.pending = a.pending;
+    pa.idxok = cidx;
+    pa.sel = a.sel;
+    pa.ctrl = a.pctrl;
+    pa.cost_params = in.params;
+    pa.cost_data = in.data;
+    pa.cost_ndata = p.cost->ndata;
+    pa.N = N;
+    pa.seed = o->seed;
+    pa.cost_id = p.cost->id;
+    pa.proposal_width = o->proposal_width;
+    pa.prior = p.prior.set;
+    pa.D_rt = D;
+    pa.dprior = in.prior;
     // the loop's counters: zeros, or the state's (pf_small_kernel starts from *pctrl, pf_iter_end_kernel and
     // the attempt kernels count on from it)
-    PfCtrl hp;
+    PfOutcome out;
+    PfCtrl& hp = out.last;
     std::memset(&hp, 0, sizeof hp);
     if (from) {
-        hp.iters = (long long)from->iteration;
-        hp.eps = from->eps;
-        hp.eff = from->eff;
+        out.iters = hp.iters = (long long)from->iteration;
+        out.eps = hp.eps = from->eps;
+        out.eff = hp.eff = from->eff;
         hp.total_reps = (unsigned long long)from->nreps;
         hp.cost_evals = (unsigned long long)from->cost_evals;
-        KABC_HIP_CHECK(hipMemcpyAsync(pctrl, &hp, sizeof hp, hipMemcpyHostToDevice, s));
-        KABC_HIP_CHECK(hipMemcpyAsync(th, from->theta, sizeof(double) * N * D, hipMemcpyHostToDevice, s));
-        KABC_HIP_CHECK(hipMemcpyAsync(Cc, from->cost, sizeof(double) * N, hipMemcpyHostToDevice, s));
-        KABC_HIP_CHECK(hipMemcpyAsync(lpi, from->logprior, sizeof(double) * N, hipMemcpyHostToDevice, s));
-        KABC_HIP_CHECK(hipStreamSynchronize(s));  // (hp is written again below)
+        KABC_HIP_CHECK(hipMemcpyAsync(a.pctrl, &hp, sizeof hp, hipMemcpyHostToDevice, s));
+        KABC_HIP_CHECK(hipMemcpyAsync(a.th, from->theta, sizeof(double) * N * D, hipMemcpyHostToDevice, s));
+        KABC_HIP_CHECK(hipMemcpyAsync(a.Cc, from->cost, sizeof(double) * N, hipMemcpyHostToDevice, s));
+        KABC_HIP_CHECK(hipMemcpyAsync(a.lpi, from->logprior, sizeof(double) * N, hipMemcpyHostToDevice, s));
+        KABC_HIP_CHECK(hipStreamSynchronize(s));  // (hp is written again by the course's looks)
+    } else if (kabc_status_t st = pf_initial_draw(p, a, actrl, in.raw)) {
+        return st;
     }
-    // :280-294 (same initial-draw loop as ABCDE, its own stream domains)
-    if (!from) {
-        AbcdeArgs a;
-        std::memset(&a, 0, sizeof a);
-        a.theta[0] = th;
-        a.delta[0] = Cc;
-        a.lpi[0] = lpi;
-        a.ctrl = actrl;
-        a.cost_params = d_params;
-        a.cost_data = d_data;
-        a.cost_ndata = cost->ndata;
-        a.N = N;
-        a.seed = o->seed;
-        a.cost_id = cost->id;
-        a.dom_init = KABC_DOM_PF_INIT;
-        a.dom_init_cost = KABC_DOM_PF_INIT_COST;
-        a.prior = P;
-        a.D_rt = D;
-        a.dprior = d_prior;
-        a.draw = d_raw;
-        if (!dyn) std::memcpy(a.raw, prior, sizeof(kabc_prior_t) * D);
-        f_init(a, s);
-        KABC_HIP_CHECK(hipGetLastError());
-        AbcdeCtrl hc;
-        KABC_HIP_CHECK(hipMemcpyAsync(&hc, actrl, sizeof hc, hipMemcpyDeviceToHost, s));
-        KABC_HIP_CHECK(hipStreamSynchronize(s));
-        if (hc.error) {
-            set_error("pfilter: the prior never produced a finite (cost, logpdf) pair for some particle");
-            return KABC_ERR_RETRY_EXHAUSTED;
-        }
-    }
-    SmcSelectArgs sa;
-    sa.Xbuf[0] = Cc;
-    sa.Xbuf[1] = Cc;
+    SmcSelectArgs& sa = a.sa;
+    sa.Xbuf[0] = a.Cc;
+    sa.Xbuf[1] = a.Cc;
     sa.alive = ones;
-    sa.alive_out = ok;
+    sa.alive_out = a.ok;
     sa.ridx = nullptr;
     sa.cidx = cidx;
-    sa.ctrl = sel;
+    sa.ctrl = a.sel;
     sa.N = N;
     sa.alpha = o->q;
     sa.min_r_ess = 1.0;
@@ -309,223 +531,43 @@ static kabc_status_t pfilter_run_impl(kabc_ctx_t* ctx, const kabc_prior_t* prior
     sa.mode = 1;
     sa.part = nullptr;  // pfilter's kernels do not produce the partials: select scans C
     sa.npart = 0;
-    KABC_HIP_CHECK(bufs.alloc(&sa.scratch, 1));
+    KABC_HIP_CHECK(a.bufs.alloc(&sa.scratch, 1));
     KABC_HIP_CHECK(hipMemsetAsync(sa.scratch, 0, sizeof(SmcSelScratch), s));
-    const unsigned selG = select_blocks(N);
-    auto do_select = [&](hipStream_t st) -> hipError_t { return launch_select(sa, selG, st, force_coop); };
-    PfArgs pa;
-    std::memset(&pa, 0, sizeof pa);
-    pa.theta = th;
-    pa.C = Cc;
-    pa.lpi = lpi;
-    pa.pending = pending;
-    pa.idxok = cidx;
-    pa.sel = sel;
-    pa.ctrl = pctrl;
-    pa.cost_params = d_params;
-    pa.cost_data = d_data;
-    pa.cost_ndata = cost->ndata;
-    pa.N = N;
-    pa.seed = o->seed;
-    pa.cost_id = cost->id;
-    pa.proposal_width = o->proposal_width;
-    pa.prior = P;
-    pa.D_rt = D;
-    pa.dprior = d_prior;
-    // (the host's `iters` feeds pa.iteration, the iteration index of the streams: it continues from the state)
-    int64_t iters = from ? from->iteration : 0;
-    double eps = from ? from->eps : INFINITY, eff = from ? from->eff : NAN;  // (iteration 0: Inf, NaN)
-    SmcCtrl hsel;
-    const char* pf_env = std::getenv("KABC_PF_PASSES");  // =1: one launch per attempt (the former scheme)
-    const bool pf_loop = !(pf_env && pf_env[0] == '1');
-    // a continued run: the stop tests of :330-332 and of "nothing was bad" below, on the state's (eps, eff,
+    a.selG = select_blocks(N);
+    // a continued run: the stop tests of :330-332 and of "nothing was bad", on the state's (eps, eff,
     // iteration) with this call's options, before the first new iteration (not on the initial draw)
-    bool cancelled = false;
     bool ended = from && from->iteration > 0 &&
                  (from->eff < o->eff_tol || from->eps < o->epstol ||
                   (o->max_iters >= 0 && from->iteration > o->max_iters) || from->eff != from->eff);
     // kabc_ctx_cancel during the initial draw: the result is that draw, the state has iteration 0
-    if (!ended && mode.poll && cancel_pending(ctx)) cancelled = ended = true;
-    // Default: every bad particle's rejection loop inside one launch, the stop tests on the device,
-    // FOUR iterations enqueued per host round trip (kernels of iterations after the last are
-    // no-ops); verbose runs look after every iteration, to print it.
-    bool batched_done = ended;
-    if (!ended && small && pf_loop) {
-        PfSmallArgs sm;
-        std::memset(&sm, 0, sizeof sm);
-        sm.pf = pa;
-        sm.pf.pending = nullptr;
-        sm.pf.idxok = nullptr;
-        sm.pf.sel = nullptr;
-        sm.q = o->q;
-        sm.eff_tol = o->eff_tol;
-        sm.epstol = o->epstol;
-        sm.max_iters = o->max_iters;
-        sm.iters_this_launch = o->verbose ? 1 : 0;
-        sm.cancel = mode.poll ? ctx->cancel_d : nullptr;
-        const PfSmallLaunchFn f_small = dyn ? &pf_l_small<0> : pf_pick_small(D, std::make_integer_sequence<int, KABC_MAX_DIM>{});
-        while (true) {
-            f_small(sm, s);
-            KABC_HIP_CHECK(hipGetLastError());
-            KABC_HIP_CHECK(hipMemcpyAsync(&hp, pctrl, sizeof hp, hipMemcpyDeviceToHost, s));
-            KABC_HIP_CHECK(hipStreamSynchronize(s));
-            if (hp.error == 9) {
-                set_error("pfilter: a particle was not replaced after 2^24 proposals");
-                return KABC_ERR_RETRY_EXHAUSTED;
-            }
-            if (hp.error) {
-                set_error("pfilter: quantile of the costs is undefined (NaN or empty)");
-                return KABC_ERR_NAN_COST;
-            }
-            if (o->verbose)
-                fprintf(stderr, "(iters, ϵ, eff) = (%lld, %.17g, %.17g)\n", (long long)hp.iters, hp.eps, hp.eff);
-            if (hp.done) break;
-        }
-        cancelled = hp.done == 2;  // (stopped at an iteration boundary by kabc_ctx_cancel)
-        iters = hp.iters;
-        eps = hp.eps;
-        eff = hp.eff;
-        batched_done = true;
-    }
-    while (pf_loop && !batched_done) {
-        const int kIterBatch = o->verbose ? 1 : 4;
-        for (int b = 0; b < kIterBatch; ++b) {
-            ++iters;
-            KABC_HIP_CHECK(do_select(s));
-            hipLaunchKernelGGL(pf_mark_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s,
-                               pending, ok, pctrl, sel, N);
-            pa.iteration = (uint64_t)iters;
-            pa.attempt = 0u;
-            pa.loop_attempts = 1;
-            f_att(pa, s);
-            hipLaunchKernelGGL(pf_iter_end_kernel, dim3(1), dim3(1), 0, s, pctrl, sel, N, o->eff_tol,
-                               o->epstol, o->max_iters);
-        }
-        KABC_HIP_CHECK(hipGetLastError());
-        KABC_HIP_CHECK(hipMemcpyAsync(&hp, pctrl, sizeof hp, hipMemcpyDeviceToHost, s));
-        KABC_HIP_CHECK(hipStreamSynchronize(s));
-        if (!select_cooperative(force_coop) && hp.error == 0 && std::getenv("KABC_SMC_SELECT_TIME_OUT")) hp.error = 3;  // (test hook)
-        if (hp.error == 3) {
-            if (!select_cooperative(force_coop)) {  // an ordinary launch that did not become co-resident in time: the same run, cooperatively
-                return pfilter_run_impl(ctx, prior, D, cost, o, res, mode, true);
-            }
-            set_error("pfilter: a device-wide barrier of a cooperative launch timed out after 5 s (the device is wedged)");
-            return KABC_ERR_DEVICE;
-        }
-        if (hp.error == 9) {
-            set_error("pfilter: a particle was not replaced after 2^24 proposals");
-            return KABC_ERR_RETRY_EXHAUSTED;
-        }
-        if (hp.error) {
-            set_error("pfilter: quantile of the costs is undefined (NaN or empty)");
-            return KABC_ERR_NAN_COST;
-        }
-        if (o->verbose)
-            fprintf(stderr, "(iters, ϵ, eff) = (%lld, %.17g, %.17g)\n", (long long)hp.iters, hp.eps, hp.eff);
-        // (the host waits here anyway: kabc_ctx_cancel is looked at on the boundary of the batch's last iteration)
-        cancelled = !hp.done && mode.poll && cancel_pending(ctx);
-        if (hp.done || cancelled) {
-            iters = hp.iters;
-            eps = hp.eps;
-            eff = hp.eff;
-            batched_done = true;
-            break;
+    if (!ended && mode.poll && cancel_pending(ctx)) out.cancelled = ended = true;
+    if (!ended) {
+        const kabc_status_t st = p.course == PfPlan::kSmall  ? pf_small_course(p, mode, a, out)
+                                 : p.course == PfPlan::kLoop ? pf_loop_course(p, mode, a, out)
+                                                             : pf_passes_course(p, mode, a, out);
+        if (st) return st;
+        if (out.timed_out) {
+            *timed_out = true;
+            return KABC_OK;
         }
     }
-    while (!batched_done) {
-        ++iters;
-        KABC_HIP_CHECK(do_select(s));
-        hipLaunchKernelGGL(pf_mark_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s,
-                           pending, ok, pctrl, sel, N);
-        pa.iteration = (uint64_t)iters;
-        uint32_t attempt = 0;
-        while (true) {
-            pa.loop_attempts = 0;  // (KABC_PF_PASSES=1: a launch per attempt, eight per host round trip)
-            for (int g = 0; g < 8; ++g) {
-                pa.attempt = attempt++;
-                f_att(pa, s);
-            }
-            KABC_HIP_CHECK(hipGetLastError());
-            KABC_HIP_CHECK(hipMemcpyAsync(&hp, pctrl, sizeof hp, hipMemcpyDeviceToHost, s));
-            KABC_HIP_CHECK(hipMemcpyAsync(&hsel, sel, sizeof hsel, hipMemcpyDeviceToHost, s));
-            KABC_HIP_CHECK(hipStreamSynchronize(s));
-            if (hsel.error == 3) {
-                if (!select_cooperative(force_coop)) {  // an ordinary launch that did not become co-resident in time: the same run, cooperatively
-                    return pfilter_run_impl(ctx, prior, D, cost, o, res, mode, true);
-                }
-                set_error("pfilter: a device-wide barrier of a cooperative launch timed out after 5 s (the device is wedged)");
-                return KABC_ERR_DEVICE;
-            }
-            if (hsel.error) {
-                set_error("pfilter: quantile of the costs is undefined (NaN or empty)");
-                return KABC_ERR_NAN_COST;
-            }
-            if (hp.remaining == 0) break;
-            if (attempt >= (1u << 24)) {
-                set_error("pfilter: a particle was not replaced after 2^24 proposals");
-                return KABC_ERR_RETRY_EXHAUSTED;
-            }
-        }
-        // NOTE passes enqueued after the last replacement are no-ops (nothing pending)
-        eps = hsel.eps;
-        const double nbad = (double)(N - hsel.ess);
-        eff = nbad / (double)hp.nreps;  // :327 (0/0 = NaN when nothing was bad, as in Julia)
-        if (o->verbose)
-            fprintf(stderr, "(iters, ϵ, eff) = (%lld, %.17g, %.17g)\n", (long long)iters, eps, eff);
-        if (eff < o->eff_tol) break;
-        if (eps < o->epstol) break;
-        if (o->max_iters >= 0 && iters > o->max_iters) break;  // src/smc.jl:332; < 0 = Inf
-        if (!(hp.nreps > 0)) break;  // nothing left to refresh: eff is NaN forever
-        if (mode.poll && cancel_pending(ctx)) {  // (kabc_ctx_cancel takes effect at the iteration's end)
-            cancelled = true;
-            break;
-        }
-    }
-    SmcFinalArgs fa;
-    fa.theta[0] = fa.theta[1] = th;
-    fa.X[0] = fa.X[1] = Cc;
-    fa.ctrl = sel;
-    fa.out = d_out;
-    fa.Xout = d_cout;
-    fa.N = N;
-    fa.D = D;
-    fa.prior = P;
-    fa.dprior = d_prior;
-    hipLaunchKernelGGL(smc_finalize_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, fa);
-    KABC_HIP_CHECK(hipGetLastError());
-    if (res->theta)
-        KABC_HIP_CHECK(hipMemcpyAsync(res->theta, d_out, sizeof(double) * N * D,
-                                      hipMemcpyDeviceToHost, s));
-    if (res->cost)
-        KABC_HIP_CHECK(hipMemcpyAsync(res->cost, d_cout, sizeof(double) * N, hipMemcpyDeviceToHost, s));
-    if (to) {  // the population as the loop holds it (NOT push_p'ed)
-        KABC_HIP_CHECK(hipMemcpyAsync(to->theta, th, sizeof(double) * N * D, hipMemcpyDeviceToHost, s));
-        KABC_HIP_CHECK(hipMemcpyAsync(to->cost, Cc, sizeof(double) * N, hipMemcpyDeviceToHost, s));
-        KABC_HIP_CHECK(hipMemcpyAsync(to->logprior, lpi, sizeof(double) * N, hipMemcpyDeviceToHost, s));
-    }
-    KABC_HIP_CHECK(hipStreamSynchronize(s));
-    res->eps = eps;
-    res->eff = eff;
-    res->iterations = iters;
-    res->nreps = hp.total_reps;
-    res->cost_evals = hp.cost_evals;
-    if (to) {
-        to->nparticles = N;
-        to->D = D;
-        to->reserved = 0;
-        to->seed = o->seed;
-        to->iteration = iters;
-        to->eps = eps;
-        to->eff = eff;
-        to->nreps = hp.total_reps;
-        to->cost_evals = hp.cost_evals;
-    }
-    if (cancelled) {  // stopped after `iters` iterations: the result of max_iters = iters - 1
-        if (!cancel_take(ctx)) set_error("cancelled");
-        return KABC_ERR_CANCELLED;
-    }
-    return KABC_OK;
+    return pf_finish(p, mode, a, out, res);
 }
+
+kabc_status_t pfilter_run_impl(kabc_ctx_t* ctx, const kabc_prior_t* prior, int32_t D, const kabc_cost_t* cost,
+                               const kabc_pfilter_opts_t* o, kabc_pfilter_result_t* res, const PfMode& mode) {
+    PfPlan plan;
+    if (kabc_status_t st = pf_prepare(ctx, prior, D, cost, o, plan)) return st;
+    // an attempt whose ordinary select launch timed out has released its buffers; the same run is made again,
+    // cooperatively, from the state or the initial draw (every draw is counter-based).  A time-out of a
+    // cooperative attempt is an error of its own (pf_decode).
+    bool timed_out = false;
+    kabc_status_t st = pf_run_once(plan, mode, false, res, &timed_out);
+    if (timed_out) st = pf_run_once(plan, mode, true, res, &timed_out);
+    return st;
+}
+
+}  // namespace
 
 // the checks that need neither the context nor the device, the states, a cancel request pending at entry
 static kabc_status_t pfilter_run_entry(kabc_ctx_t* ctx, const kabc_prior_t* prior, int32_t D,
@@ -550,7 +592,7 @@ static kabc_status_t pfilter_run_entry(kabc_ctx_t* ctx, const kabc_prior_t* prio
     // a request made while ctx was idle: nothing is launched, `result` and `to` stay as they are
     if (mode.poll && cancel_take(ctx)) return KABC_ERR_CANCELLED;
     if (mode.to) mode.to->iteration = -1;  // (until the result is filled)
-    return pfilter_run_impl(ctx, prior, D, cost, o, res, mode, false);
+    return pfilter_run_impl(ctx, prior, D, cost, o, res, mode);
 }
 
 extern "C" {
@@ -583,16 +625,6 @@ namespace {
 // how the calling thread's last kabc_pfilter_run_batch was driven (kabc_pfilter_batch_stats)
 thread_local int64_t tl_pf_batch_stats[4] = {0, 0, 0, 0};
 
-// kabc_pfilter_run's own messages
-const char* const kPfExhausted = "pfilter: the prior never produced a finite (cost, logpdf) pair for some particle";
-const char* const kPfUnreplaced = "pfilter: a particle was not replaced after 2^24 proposals";
-const char* const kPfNanCost = "pfilter: quantile of the costs is undefined (NaN or empty)";
-
-bool env_is_zero(const char* name) {
-    const char* e = std::getenv(name);
-    return e && e[0] == '0';
-}
-
 // The launch grid: workgroup r runs run r from its initial draw to its output.  *grid = false (and
 // KABC_OK) when there is no kernel for the pair: the caller runs the batch one run after another.
 // A non-OK return: the batch as a whole failed (message set).
@@ -603,19 +635,12 @@ kabc_status_t pf_run_grid(kabc_ctx_t* ctx, const kabc_prior_t* prior, int32_t D,
     const kabc_cost_t* cost = &costs[0];
     const int64_t N = kabc_pfilter_nparticles(o->nparticles, o->q, D), NR = nruns;
     // the checks of kabc_pfilter_run that need the prior and the cost
-    std::vector<kabc_prior_t> resolved((size_t)D);  // MvNormal components: device block, D
-    if (kabc_status_t st = resolve_priors(ctx, prior, D, resolved.data())) return st;
-    prior = resolved.data();
+    PopPrior pp;
+    if (kabc_status_t st = prepare_pop_prior(ctx, prior, D, cost->id, pp)) return st;
+    prior = pp.raw.data();
     PfBatchArgs A;
     std::memset(&A, 0, sizeof A);
-    if (!prepare_priors(prior, D, A.prior)) {
-        set_error("invalid prior parameters");
-        return KABC_ERR_INVALID_ARG;
-    }
-    if (!cost_dim_ok_rt(cost->id, D)) {
-        set_error("DeviceCost id %d does not accept D = %d", cost->id, D);
-        return KABC_ERR_UNSUPPORTED;
-    }
+    A.prior = pp.set;
     // (run-time compiled kernels are loaded on the CURRENT device)
     KABC_HIP_CHECK(hipSetDevice(ctx->device));
     // a user prior family is known to its model unit only: those runs go one after another
@@ -690,7 +715,7 @@ kabc_status_t pf_run_grid(kabc_ctx_t* ctx, const kabc_prior_t* prior, int32_t D,
     A.N = (int32_t)N;
     A.nruns = (int32_t)NR;
     A.cost_id = cost->id;
-    A.spread = env_is_zero("KABC_PF_BATCH_SPREAD") ? 0 : 1;
+    A.spread = env_first_is("KABC_PF_BATCH_SPREAD", '0') ? 0 : 1;
     A.q = o->q;
     A.eff_tol = o->eff_tol;
     A.epstol = o->epstol;
@@ -771,7 +796,7 @@ kabc_status_t pf_run_grid(kabc_ctx_t* ctx, const kabc_prior_t* prior, int32_t D,
     for (int64_t r = 0; r < NR; ++r) {
         if (status[r] == KABC_OK) continue;
         const int e = hrec[(size_t)r].error;
-        set_error("run %lld: %s", (long long)r, e == 1 ? kPfExhausted : e == 9 ? kPfUnreplaced : e == 2 ? kPfNanCost : "cancelled");
+        set_error("run %lld: %s", (long long)r, e ? pf_decode(e == 1 ? kPfErrInit : e).msg : "cancelled");
         break;
     }
     return KABC_OK;
@@ -827,7 +852,7 @@ kabc_status_t pf_batch_impl(kabc_ctx_t* ctx, const kabc_prior_t* prior, int32_t 
         return KABC_ERR_INVALID_ARG;
     }
     bool grid = false;
-    if (!o->verbose && !env_is_zero("KABC_PF_BATCH") && D <= KABC_MAX_DIM &&
+    if (!o->verbose && !env_first_is("KABC_PF_BATCH", '0') && D <= KABC_MAX_DIM &&
         kabc_pfilter_nparticles(o->nparticles, o->q, D) <= (int64_t)kPfBatchBlock) {
         const kabc_status_t st = pf_run_grid(ctx, prior, D, costs, nruns, seeds, o, results, status, &grid);
         if (st) {  // (the batch as a whole failed: every run shares the verdict)

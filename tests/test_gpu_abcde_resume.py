@@ -237,6 +237,35 @@ def test_run_from_without_states_is_kabc_abcde_run(k, orc, gpu_ctx):
     assert (r.generations_run, r.nsims, bool(r.reached_eps)) == (7, plain.info["nsims"], plain.reached_eps)
 
 
+def test_a_run_that_fails_on_the_device_leaves_no_state(k, gpu_ctx):
+    """a user cost that is never finite: the initial draw gives up, the call fails with KABC_ERR_RETRY_EXHAUSTED and
+    its own message, and the `to` state it was given keeps the -1 a failed run leaves (through ctypes: the Python
+    error carries no result)"""
+    from kissabc_jl_amd import _cdefs as cd, _lib
+    from test_gpu_pfilter_batch import INF_SRC
+    lib = _lib.load()
+    pri = k.Factored(k.Normal(0, 5), k.Normal(0, 5))
+    cost = k.costs.UserCost(INF_SRC, dims=[2], params=[-1.0], name="inf_in_run")
+    N, D = 64, 2
+    o = cd.AbcdeOpts()
+    lib.kabc_abcde_default_opts(C.byref(o))
+    o.nparticles, o.generations, o.eps_target, o.seed = N, 20, 0.05, 9
+    theta, Cst = np.empty((N, D)), np.empty(N)
+    r = cd.AbcdeResult()
+    r.theta = theta.ctypes.data_as(cd.c_double_p)
+    r.cost = Cst.ctypes.data_as(cd.c_double_p)
+    to = k.AbcdeState._empty(N, D)
+    st_to = to._to_c()
+    st_to.generation = 7
+    cc = cost.to_c()
+    status = lib.kabc_abcde_run_from(gpu_ctx.handle, pri.to_c(), D, C.byref(cc), C.byref(o), None, C.byref(st_to),
+                                     C.byref(r))
+    assert status == cd.KABC_ERR_RETRY_EXHAUSTED
+    assert lib.kabc_last_error().decode() == \
+        "ABCDE: the prior never produced a finite (cost, logpdf) pair for some particle"
+    assert st_to.generation == -1
+
+
 # ---- kabc_ctx_cancel ------------------------------------------------------------------------------------------
 
 def test_cancel_pending_at_entry_launches_nothing(k):

@@ -188,6 +188,61 @@ def test_run_from_without_states_is_kabc_pfilter_run(k, orc, gpu_ctx):
     assert (r.eps, r.eff, r.iterations, r.nreps, r.cost_evals) == tuple(plain.info[key] for key in INFO[:5])
 
 
+def test_retry_after_a_select_time_out_with_states(k, orc, gpu_ctx, monkeypatch):
+    """KABC_SMC_SELECT_TIME_OUT=1 makes every ordinary-launch attempt of the loop course count as timed out, so each
+    call is made twice, the second time with cooperative select launches.  The repeated attempt starts from the
+    state again and is the one that fills `to`: 3 + 3 iterations under the hook are the 6 of the plain run"""
+    for name in ("KABC_PF_SMALL", "KABC_PF_PASSES", "KABC_SMC_SELECT_TIME_OUT", "KABC_SMC_COOPERATIVE"):
+        monkeypatch.delenv(name, raising=False)
+    pri, cost = _gauss(k)
+    N, kw = 300, dict(eff_tol=0.0, max_iters=5)
+    full = _run(k, pri, cost, N, 4, **kw)
+    ref = orc.pfilter(pri, cost, N, seed=4, return_state=True, **kw)
+    assert ref["iterations"] == 6
+    monkeypatch.setenv("KABC_SMC_SELECT_TIME_OUT", "1")
+    first = _run(k, pri, cost, N, 4, **dict(kw, max_iters=2))
+    st = first.info["state"]
+    assert st.iteration == first.info["iterations"] == 3 and st.seed == 4
+    cont = k.pfilter(pri, cost, resume=st, return_array=True, return_state=True, **kw)
+    monkeypatch.delenv("KABC_SMC_SELECT_TIME_OUT")
+    _same_result(cont, full)
+    _same_state(cont.info["state"], full.info["state"])
+    assert np.array_equal(_u64(cont.P), _u64(ref["P"])) and np.array_equal(_u64(cont.C), _u64(ref["C"]))
+    for key in ("eps", "eff", "iterations", "nreps", "cost_evals"):
+        assert _u64(cont.info[key]) == _u64(ref[key]), key
+    _same_state(cont.info["state"], ref["state"])
+
+
+def test_a_run_that_fails_on_the_device_leaves_no_state(k, gpu_ctx):
+    """a user cost that is never finite: the initial draw gives up, the call fails with KABC_ERR_RETRY_EXHAUSTED and
+    its own message, and the `to` state it was given keeps the -1 a failed run leaves (through ctypes: the Python
+    error carries no result)"""
+    from kissabc_jl_amd import _cdefs as cd, _lib
+    from test_gpu_pfilter_batch import INF_SRC
+    lib = _lib.load()
+    pri = k.Factored(k.Normal(0, 5), k.Normal(0, 5))
+    cost = k.costs.UserCost(INF_SRC, dims=[2], params=[-1.0], name="inf_in_run")
+    N, D = 64, 2
+    o = cd.PfilterOpts()
+    lib.kabc_pfilter_default_opts(C.byref(o))
+    o.nparticles, o.max_iters, o.seed = N, 12, 4
+    assert lib.kabc_pfilter_nparticles(N, o.q, D) == N
+    theta, Cst = np.empty((N, D)), np.empty(N)
+    r = cd.PfilterResult()
+    r.theta = theta.ctypes.data_as(cd.c_double_p)
+    r.cost = Cst.ctypes.data_as(cd.c_double_p)
+    to = k.PfilterState._empty(N, D)
+    st_to = to._to_c()
+    st_to.iteration = 7
+    cc = cost.to_c()
+    status = lib.kabc_pfilter_run_from(gpu_ctx.handle, pri.to_c(), D, C.byref(cc), C.byref(o), None, C.byref(st_to),
+                                       C.byref(r))
+    assert status == cd.KABC_ERR_RETRY_EXHAUSTED
+    assert lib.kabc_last_error().decode() == \
+        "pfilter: the prior never produced a finite (cost, logpdf) pair for some particle"
+    assert st_to.iteration == -1
+
+
 # ---- kabc_ctx_cancel ------------------------------------------------------------------------------------------
 
 def test_cancel_pending_at_entry_launches_nothing(k):
