@@ -1,10 +1,12 @@
 // abcde_kernels.hpp -- gfx950 kernels for ABCDE (src/smc.jl:347-430).
 // Not a hot path of the round: one thread per particle, D as the only template
 // parameter (the DeviceCost is dispatched at run time by kabc_cost_eval, which a
-// user plugin extends with its own branch).
+// user plugin extends with its own branch).  The reference's rules are the functions of
+// population_model.hpp; the kernels here are their schedules.
 #pragma once
 
 #include "dyn_model.hpp"
+#include "population_model.hpp"
 #ifndef __HIPCC_RTC__
 #include "launcher.hpp"
 #endif
@@ -118,9 +120,8 @@ __device__ __forceinline__ unsigned wm_quantile(const AbcdeArgs& A, unsigned c, 
 
 constexpr int kAbcdeBlock = 64;
 constexpr int kAbcdeScanMax = 4096;   // particles whose costs the generation kernel stages in LDS (32 KB)
-constexpr unsigned kAbcdeMaxInitTries = 100000u;
 
-// θs, logπ, Δs with the re-draw loop of :351-366
+// θs, logπ, Δs (pop_initial_draw) from the prior in global memory; ABCDE's or pfilter's stream domains
 template <int DT>
 __global__ void __launch_bounds__(kAbcdeBlock) abcde_init_kernel(const AbcdeArgs A) {
     const int64_t i = (int64_t)blockIdx.x * kAbcdeBlock + threadIdx.x;
@@ -129,27 +130,10 @@ __global__ void __launch_bounds__(kAbcdeBlock) abcde_init_kernel(const AbcdeArgs
     const int D = DimOf<DT>::get(A.D_rt);
     double x[CAP], xp[CAP];
     double lp = 0.0, dl = 0.0;
-    for (unsigned attempt = 0;; ++attempt) {
-        for (int k = 0; k < D; ++k) {
-            kabc_slotwin_t win = {A.seed, (uint64_t)attempt, (uint32_t)i, A.dom_init,
-                                  (uint32_t)k * KABC_SLOTS_PER_DIM};
-            // (a pointer INTO the components' array: a joint prior's sampler reaches component 0 from component k)
-            const kabc_prior_t* pr = DT ? &A.raw[k] : &A.draw[k];
-            x[k] = kabc_sample_prior(pr, &win);
-        }
-        lp = logpdf_push_n<DT>(A.prior, A.dprior, D, x, xp);
-        kabc_cost_rng_t rng = {A.seed, (uint64_t)attempt, (uint32_t)i, A.dom_init_cost, 0u};
-        // first pass: the cost is only evaluated when logπ is finite (:357-359);
-        // in the re-draw loop it always is (:364).  cost(θ.x): NOT push_p'ed.
-        const bool eval = (attempt > 0) || kabc_isfinite(lp);
-        dl = eval ? kabc_cost_eval(A.cost_id, x, D, A.cost_params, A.cost_data, A.cost_ndata, &rng)
-                  : KABC_NAN;
-        if (kabc_isfinite(dl) && kabc_isfinite(lp)) break;
-        if (attempt >= kAbcdeMaxInitTries) {
-            A.ctrl->error = 1;
-            break;
-        }
-    }
+    const auto logpdf = [&](const double* v, double* vp) { return logpdf_push_n<DT>(A.prior, A.dprior, D, v, vp); };
+    if (pop_initial_draw(A.seed, (uint32_t)i, A.dom_init, A.dom_init_cost, DT ? A.raw : A.draw, D, A.cost_id,
+                         A.cost_params, A.cost_data, A.cost_ndata, nullptr, logpdf, x, xp, lp, dl))
+        A.ctrl->error = 1;
     store_row_n<DT>(A.theta[0] + i * D, x, D);
     A.delta[0][i] = dl;
     A.lpi[0][i] = lp;
@@ -197,13 +181,10 @@ __global__ void __launch_bounds__(1024) abcde_extrema_kernel(const AbcdeArgs A, 
         }
         A.ctrl->eps_l = mn;
         A.ctrl->eps_h = mx;
-        A.ctrl->iters += 1;  // iters += 1 (:373): counted before the earlystop break (:379-381), as the reference does
-        if (A.earlystop && mx <= A.eps_target) {
-            A.ctrl->done = 1;
-        } else {
-            const double pop = mn + A.alpha * (mx - mn);
-            A.ctrl->eps_pop = (A.eps_target > pop) ? A.eps_target : pop;  // max(ϵ_target, ...)
-        }
+        A.ctrl->iters += 1;  // iters += 1 (:373)
+        double eps_pop;
+        if (abcde_generation_head(mn, mx, A.alpha, A.eps_target, A.earlystop, &eps_pop)) A.ctrl->done = 1;
+        else A.ctrl->eps_pop = eps_pop;
     }
 }
 
@@ -227,9 +208,8 @@ __global__ void __launch_bounds__(kDonorBlock) abcde_donor_kernel(const AbcdeArg
     double di = 0.0;
     if (i < N) {
         di = s_dl[i];
-        const bool skip = A.earlystop && di <= A.eps_target;                        // :384-386
-        const double eps = (di <= A.eps_target) ? A.eps_target : A.ctrl->eps_pop;   // :390
-        need = !skip && di > eps;
+        need = !abcde_skips(A.earlystop, di, A.eps_target) &&
+               abcde_needs_donor(di, abcde_particle_eps(di, A.eps_target, A.ctrl->eps_pop));
     }
     const int64_t per = (N + kDonorTeam - 1) / kDonorTeam;
     const int64_t lo = (int64_t)t * per < N ? (int64_t)t * per : N;
@@ -256,8 +236,7 @@ __global__ void __launch_bounds__(kDonorBlock) abcde_donor_kernel(const AbcdeArg
     const int total = __shfl(incl, kDonorTeam - 1, kDonorTeam);
     int found = -1;
     if (need) {  // total >= 1: the particle's own cost counts
-        const kabc_u128_t B0 = kabc_stream_block(A.seed, (uint32_t)i, g, 0u, KABC_DOM_ABCDE_MOVE);
-        int64_t m = (int64_t)kabc_index(kabc_lo64(B0), (uint64_t)total);
+        int64_t m = abcde_donor_rank(abcde_move_block(A.seed, (uint32_t)i, g, 0u), (uint64_t)total);
         const int excl = incl - c;
         if (m >= excl && m < incl) {  // this lane's range holds the m-th hit
             m -= excl;
@@ -292,7 +271,8 @@ __global__ void __launch_bounds__(kAbcdeBlock) abcde_gen_kernel(const AbcdeArgs 
     const double* __restrict__ DL = A.delta[cur];
     const double* __restrict__ LP = A.lpi[cur];
     unsigned long long sims = 0;
-    // scan path (no rank structure: N < 4096): the generation's costs in LDS -- every particle
+    // own scans (neither a rank structure nor abcde_donor_kernel's draws: the host chooses them below 4096
+    // particles only, capi_abcde.hip abcde_donor_scheme): the generation's costs in LDS -- every particle
     // walks all of them twice for its donor draw; from global memory those were two dependent
     // chains of N loads per thread (1000 particles: 167 us per generation, 16 us from LDS)
     __shared__ double s_dl[kAbcdeScanMax];
@@ -306,107 +286,88 @@ __global__ void __launch_bounds__(kAbcdeBlock) abcde_gen_kernel(const AbcdeArgs 
         double th[CAP];
         load_row_n<DT>(TH + i * D, th, D);
         double di = DL[i], li = LP[i];
-        const bool skip = A.earlystop && di <= A.eps_target;  // :384-386
-        if (!skip) {
+        if (!abcde_skips(A.earlystop, di, A.eps_target)) {
             const uint32_t w = (uint32_t)i;
-            const kabc_u128_t B0 = kabc_stream_block(A.seed, w, g, 0u, KABC_DOM_ABCDE_MOVE);
-            const kabc_u128_t B1 = kabc_stream_block(A.seed, w, g, 1u, KABC_DOM_ABCDE_MOVE);
+            const kabc_u128_t B0 = abcde_move_block(A.seed, w, g, 0u), B1 = abcde_move_block(A.seed, w, g, 1u);
             int64_t s = i;
-            const double eps = (di <= A.eps_target) ? A.eps_target : A.ctrl->eps_pop;  // :390
-            if (di > eps && A.sorted_delta) {
-                // s = rand(trng, (1:N)[Δs .<= Δs[i]])  (:392) through the rank structure:
-                // c = #{Δ <= Δ_i} by bisection of the sorted costs, then the m-th smallest
-                // index among the first c entries of the cost-sorted order
+            const double eps = abcde_particle_eps(di, A.eps_target, A.ctrl->eps_pop);
+            const bool need = abcde_needs_donor(di, eps);
+            if (need && A.sorted_delta) {
+                // the donor through the rank structure: c = #{Δ <= Δ_i} by bisection of the sorted costs,
+                // then the m-th smallest index among the first c entries of the cost-sorted order
                 int64_t lo = 0, hi = N;  // first position whose cost exceeds di
                 while (lo < hi) {
                     const int64_t mid = (lo + hi) >> 1;
                     if (A.sorted_delta[mid] <= di) lo = mid + 1;
                     else hi = mid;
                 }
-                const int64_t m = (int64_t)kabc_index(kabc_lo64(B0), (uint64_t)lo);
-                s = (int64_t)wm_quantile(A, (unsigned)lo, (unsigned)m);
-            } else if (di > eps && A.donor) {
-                s = (int64_t)A.donor[i];  // (abcde_donor_kernel: the same draw, scanned by a team)
-            } else if (di > eps) {
-                // the same by two scans (small N): the m-th index, in ascending order, whose
-                // cost does not exceed ours
-                // (two inlined instances, so that the LDS one reads with ds_read, not flat loads)
-                auto donor = [&](const double* __restrict__ dl) __attribute__((always_inline)) {
-                    // eight costs per step, loaded together: a step then costs one memory latency,
-                    // not eight (the element-by-element loops were chains of dependent loads)
-                    constexpr int U = 8;
-                    const int64_t NU = N - N % U;
-                    int c = 0;
-                    for (int64_t j = 0; j < NU; j += U) {
-                        double v[U];
+                s = (int64_t)wm_quantile(A, (unsigned)lo, (unsigned)abcde_donor_rank(B0, (uint64_t)lo));
+            } else if (need && A.donor) {
+                s = (int64_t)A.donor[i];  // (abcde_donor_kernel / abcde_donor_blocks_kernel: the same draw)
+            } else if (need && lds_scan) {
+                // the same by two scans of the costs in LDS: the m-th index, in ascending order, whose cost
+                // does not exceed ours.  Eight costs per step, loaded together: a step then costs one memory
+                // latency, not eight (the element-by-element loops were chains of dependent loads)
+                constexpr int U = 8;
+                const int64_t NU = N - N % U;
+                int c = 0;
+                for (int64_t j = 0; j < NU; j += U) {
+                    double v[U];
 #pragma unroll
-                        for (int u = 0; u < U; ++u) v[u] = dl[j + u];
+                    for (int u = 0; u < U; ++u) v[u] = s_dl[j + u];
 #pragma unroll
-                        for (int u = 0; u < U; ++u) c += (v[u] <= di) ? 1 : 0;
-                    }
-                    for (int64_t j = NU; j < N; ++j) c += (dl[j] <= di) ? 1 : 0;
-                    int64_t m = (int64_t)kabc_index(kabc_lo64(B0), (uint64_t)c);
-                    bool found = false;
-                    for (int64_t j = 0; j < NU && !found; j += U) {
-                        double v[U];
+                    for (int u = 0; u < U; ++u) c += (v[u] <= di) ? 1 : 0;
+                }
+                for (int64_t j = NU; j < N; ++j) c += (s_dl[j] <= di) ? 1 : 0;
+                int64_t m = abcde_donor_rank(B0, (uint64_t)c);
+                bool found = false;
+                for (int64_t j = 0; j < NU && !found; j += U) {
+                    double v[U];
 #pragma unroll
-                        for (int u = 0; u < U; ++u) v[u] = dl[j + u];
-                        int cnt = 0;
+                    for (int u = 0; u < U; ++u) v[u] = s_dl[j + u];
+                    int cnt = 0;
 #pragma unroll
-                        for (int u = 0; u < U; ++u) cnt += (v[u] <= di) ? 1 : 0;
-                        if (m < cnt) {  // the m-th hit is in this group
+                    for (int u = 0; u < U; ++u) cnt += (v[u] <= di) ? 1 : 0;
+                    if (m < cnt) {  // the m-th hit is in this group
 #pragma unroll
-                            for (int u = 0; u < U; ++u) {
-                                if (!found && v[u] <= di) {
-                                    if (m == 0) {
-                                        s = j + u;
-                                        found = true;
-                                    }
-                                    --m;
+                        for (int u = 0; u < U; ++u) {
+                            if (!found && v[u] <= di) {
+                                if (m == 0) {
+                                    s = j + u;
+                                    found = true;
                                 }
+                                --m;
                             }
-                        } else {
-                            m -= cnt;
                         }
+                    } else {
+                        m -= cnt;
                     }
-                    for (int64_t j = NU; j < N && !found; ++j) {
-                        if (dl[j] <= di) {
-                            if (m == 0) {
-                                s = j;
-                                found = true;
-                            }
-                            --m;
+                }
+                for (int64_t j = NU; j < N && !found; ++j) {
+                    if (s_dl[j] <= di) {
+                        if (m == 0) {
+                            s = j;
+                            found = true;
                         }
+                        --m;
                     }
-                };
-                if (lds_scan) donor(s_dl);
-                else donor(DL);
+                }
             }
-            // while a == s ... ; while b == a || b == s ...  (:394-401)
-            int64_t a = (int64_t)kabc_index(kabc_hi64(B0), (uint64_t)(N - 1));
-            a += (a >= s);
-            const int64_t lo = a < s ? a : s, hi = a < s ? s : a;
-            int64_t b = (int64_t)kabc_index(kabc_lo64(B1), (uint64_t)(N - 2));
-            b += (b >= lo);
-            b += (b >= hi);
+            int64_t a, b;
+            abcde_partners<int64_t>(B0, B1, s, N, a, b);
             double ts[CAP], ta[CAP], tb[CAP], tp[CAP], xp[CAP];
             load_row_n<DT>(TH + s * D, ts, D);
             load_row_n<DT>(TH + a * D, ta, D);
             load_row_n<DT>(TH + b * D, tb, D);
 #pragma unroll
-            for (int k = 0; k < D; ++k) tp[k] = ts[k] + (ta[k] - tb[k]) * A.gamma;  // :402
+            for (int k = 0; k < D; ++k) tp[k] = abcde_proposal(ts[k], ta[k], tb[k], A.gamma);
             const double lpp = logpdf_push_n<DT>(A.prior, A.dprior, D, tp, xp);
-            const double wp = lpp - li;
-            double mn = wp;
-            if (!(wp < 0.0)) mn = (wp != wp) ? wp : 0.0;  // min(0, w_prior), NaN propagates
-            const double lu = kabc_log_pn(kabc_u01(kabc_hi64(B1)));
-            if (!(lu > mn)) {  // log(rand) > min(0,w_prior) && continue  (:405)
+            if (pop_prior_gate(lpp, li, kabc_hi64(B1))) {
                 sims = 1;
                 kabc_cost_rng_t rng = {A.seed, g, w, KABC_DOM_ABCDE_COST, 0u};
                 const double dp = kabc_cost_eval(A.cost_id, tp, D, A.cost_params, A.cost_data,
                                                  A.cost_ndata, &rng);  // cost(θp.x), :408
-                const double thr = (eps > di) ? eps : di;  // max(ϵ, Δs[i])
-                if (dp <= thr) {
+                if (abcde_accepts(dp, eps, di)) {
                     di = dp;
                     li = lpp;
 #pragma unroll
@@ -446,7 +407,7 @@ __global__ void __launch_bounds__(256) abcde_final_kernel(const AbcdeFinalArgs A
     for (int k = 0; k < A.D; ++k) {
         const double v = A.theta[cur][i * A.D + k];
         const bool disc = A.dprior ? (A.dprior[k].discrete != 0) : (A.prior.c[k].discrete != 0);
-        A.out[i * A.D + k] = disc ? kabc_rint(v) : v;
+        A.out[i * A.D + k] = pop_output(v, disc);
     }
     A.dout[i] = A.delta[cur][i];
 }

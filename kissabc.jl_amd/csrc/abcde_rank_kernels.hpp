@@ -231,9 +231,8 @@ __global__ void __launch_bounds__(256) abcde_donor_blocks_kernel(const AbcdeArgs
     const int64_t N = A.N;
     const double* __restrict__ DL = A.delta[A.ctrl->cur];
     const double di = DL[i];
-    const bool skip = A.earlystop && di <= A.eps_target;                        // :384-386
-    const double eps = (di <= A.eps_target) ? A.eps_target : A.ctrl->eps_pop;   // :390
-    if (skip || !(di > eps)) {  // (wave-uniform: one particle per wavefront)
+    if (abcde_skips(A.earlystop, di, A.eps_target) ||
+        !abcde_needs_donor(di, abcde_particle_eps(di, A.eps_target, A.ctrl->eps_pop))) {  // (wave-uniform)
         if (lane == 0) donor[i] = (int32_t)i;
         return;
     }
@@ -267,8 +266,8 @@ __global__ void __launch_bounds__(256) abcde_donor_blocks_kernel(const AbcdeArgs
         if (lane >= off) incl += o;
     }
     const int total = __shfl(incl, kWave - 1, kWave);  // >= 1: the particle's own cost counts
-    const kabc_u128_t B0 = kabc_stream_block(A.seed, (uint32_t)i, (uint64_t)A.ctrl->iters, 0u, KABC_DOM_ABCDE_MOVE);
-    const int64_t m = (int64_t)kabc_index(kabc_lo64(B0), (uint64_t)total);
+    const int64_t m =
+        abcde_donor_rank(abcde_move_block(A.seed, (uint32_t)i, (uint64_t)A.ctrl->iters, 0u), (uint64_t)total);
     // the lane whose blocks hold the m-th hit names the block and the hit's rank inside it
     const int excl = incl - c;
     int tb = -1, tm = 0;

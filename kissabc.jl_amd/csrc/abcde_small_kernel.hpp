@@ -8,8 +8,8 @@
 //
 // The same draws and the same operation order as abcde_init_kernel + abcde_extrema_kernel + the scan
 // path of abcde_gen_kernel + abcde_final_kernel (abcde_kernels.hpp): run r is bit-identical to
-// kabc_abcde_run with seed = seeds[r].  The per-particle body is a copy of the generation kernel's, not
-// a shared function: here the frozen generation is read from LDS with 32-bit indices, there from global
+// kabc_abcde_run with seed = seeds[r].  Both evaluate the rules of population_model.hpp; what differs is
+// the schedule: here the frozen generation is read from LDS with 32-bit indices, there from global
 // memory (or a rank structure) with 64-bit ones.
 //   * the ensemble (θ [256][D], Δ, logπ), the prepared prior and the math table live in LDS for the
 //     whole launch; one θ buffer only (two do not fit at D = 16: 2 x 32 KB).  The reference's frozen
@@ -95,30 +95,16 @@ __global__ void __launch_bounds__(kAbcdeSmallBlock) abcde_small_kernel(const Abc
     if (tid == 0 && A.cancel) cw = __hip_atomic_load(A.cancel, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     __syncthreads();
 
-    // ---- θs, logπ, Δs with the re-draw loop of :351-366 (abcde_init_kernel)
+    // ---- θs, logπ, Δs (pop_initial_draw) from the prior and the math table in LDS
     if (in) {
         double x[D], xp[D];
         double lp = 0.0, dl = 0.0;
-        for (unsigned attempt = 0;; ++attempt) {
-            for (int k = 0; k < D; ++k) {
-                kabc_slotwin_t win = {seed, (uint64_t)attempt, (uint32_t)tid, KABC_DOM_ABCDE_INIT,
-                                      (uint32_t)k * KABC_SLOTS_PER_DIM};
-                // (a pointer INTO the components' array: a joint prior's sampler reaches component 0 from component k)
-                x[k] = kabc_sample_prior(&A.raw[k], &win);
-            }
-            lp = factored_logpdf_push<D>(s_prior, x, xp, s_logtab);
-            kabc_cost_rng_t rng = {seed, (uint64_t)attempt, (uint32_t)tid, KABC_DOM_ABCDE_INIT_COST, 0u};
-            rng.logtab = s_logtab;
-            // first pass: the cost is only evaluated when logπ is finite (:357-359);
-            // in the re-draw loop it always is (:364).  cost(θ.x): NOT push_p'ed.
-            const bool eval = (attempt > 0) || kabc_isfinite(lp);
-            dl = eval ? kabc_cost_eval(A.cost_id, x, D, cost_params, cost_data, A.cost_ndata, &rng) : KABC_NAN;
-            if (kabc_isfinite(dl) && kabc_isfinite(lp)) break;
-            if (attempt >= kAbcdeMaxInitTries) {
-                s_err = 1;
-                break;
-            }
-        }
+        const auto logpdf = [&](const double* v, double* vp) {
+            return factored_logpdf_push<D>(s_prior, v, vp, s_logtab);
+        };
+        if (pop_initial_draw(seed, (uint32_t)tid, KABC_DOM_ABCDE_INIT, KABC_DOM_ABCDE_INIT_COST, A.raw, D, A.cost_id,
+                             cost_params, cost_data, A.cost_ndata, s_logtab, logpdf, x, xp, lp, dl))
+            s_err = 1;
 #pragma unroll
         for (int k = 0; k < D; ++k) s_th[tid][k] = x[k];
         s_dl[tid] = dl;
@@ -153,10 +139,9 @@ __global__ void __launch_bounds__(kAbcdeSmallBlock) abcde_small_kernel(const Abc
             mx = s_mx[w] > mx ? s_mx[w] : mx;
         }
         if (tid == 0 && A.cancel) cw = __hip_atomic_load(A.cancel, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        iters += 1;  // iters += 1 (:373): counted before the earlystop break (:379-381), as the reference does
-        if (A.earlystop && mx <= A.eps_target) break;  // (uniform)
-        const double pop = mn + A.alpha * (mx - mn);
-        const double eps_pop = (A.eps_target > pop) ? A.eps_target : pop;  // max(ϵ_target, ...)
+        iters += 1;  // iters += 1 (:373)
+        double eps_pop;
+        if (abcde_generation_head(mn, mx, A.alpha, A.eps_target, A.earlystop, &eps_pop)) break;  // (uniform)
 
         // ================= one generation (:383-412) from the frozen ensemble
         double th[D];
@@ -166,20 +151,17 @@ __global__ void __launch_bounds__(kAbcdeSmallBlock) abcde_small_kernel(const Abc
             for (int k = 0; k < D; ++k) th[k] = s_th[tid][k];
             di = s_dl[tid];
             li = s_lp[tid];
-            const bool skip = A.earlystop && di <= A.eps_target;  // :384-386
-            if (!skip) {
+            if (!abcde_skips(A.earlystop, di, A.eps_target)) {
                 const uint32_t w = (uint32_t)tid;
                 const uint64_t g = (uint64_t)iters;  // (the streams of generation g are keyed by iters after += 1)
-                const kabc_u128_t B0 = kabc_stream_block(seed, w, g, 0u, KABC_DOM_ABCDE_MOVE);
-                const kabc_u128_t B1 = kabc_stream_block(seed, w, g, 1u, KABC_DOM_ABCDE_MOVE);
+                const kabc_u128_t B0 = abcde_move_block(seed, w, g, 0u), B1 = abcde_move_block(seed, w, g, 1u);
                 int s = tid;
-                const double eps = (di <= A.eps_target) ? A.eps_target : eps_pop;  // :390
-                if (di > eps) {
-                    // s = rand(trng, (1:N)[Δs .<= Δs[i]])  (:392): the m-th index, in ascending order,
-                    // whose cost does not exceed ours
+                const double eps = abcde_particle_eps(di, A.eps_target, eps_pop);
+                if (abcde_needs_donor(di, eps)) {
+                    // the donor by two scans: the m-th index, in ascending order, whose cost does not exceed ours
                     int c = 0;
                     for (int j = 0; j < N; ++j) c += (s_dl[j] <= di) ? 1 : 0;  // (broadcast reads)
-                    int m = (int)kabc_index(kabc_lo64(B0), (uint64_t)c);
+                    int m = (int)abcde_donor_rank(B0, (uint64_t)c);
                     for (int j = 0; j < N; ++j) {
                         if (s_dl[j] <= di) {
                             if (m == 0) {
@@ -190,29 +172,19 @@ __global__ void __launch_bounds__(kAbcdeSmallBlock) abcde_small_kernel(const Abc
                         }
                     }
                 }
-                // while a == s ... ; while b == a || b == s ...  (:394-401)
-                int a = (int)kabc_index(kabc_hi64(B0), (uint64_t)(N - 1));
-                a += (a >= s);
-                const int lo = a < s ? a : s, hi = a < s ? s : a;
-                int b = (int)kabc_index(kabc_lo64(B1), (uint64_t)(N - 2));
-                b += (b >= lo);
-                b += (b >= hi);
+                int a, b;
+                abcde_partners<int>(B0, B1, s, N, a, b);
                 double tp[D], xp[D];
 #pragma unroll
-                for (int k = 0; k < D; ++k) tp[k] = s_th[s][k] + (s_th[a][k] - s_th[b][k]) * A.gamma;  // :402
+                for (int k = 0; k < D; ++k) tp[k] = abcde_proposal(s_th[s][k], s_th[a][k], s_th[b][k], A.gamma);
                 const double lpp = factored_logpdf_push<D>(s_prior, tp, xp, s_logtab);
-                const double wp = lpp - li;
-                double mnw = wp;
-                if (!(wp < 0.0)) mnw = (wp != wp) ? wp : 0.0;  // min(0, w_prior), NaN propagates
-                const double lu = kabc_log_pn(kabc_u01(kabc_hi64(B1)));
-                if (!(lu > mnw)) {  // log(rand) > min(0,w_prior) && continue  (:405)
+                if (pop_prior_gate(lpp, li, kabc_hi64(B1))) {
                     sims += 1;
                     kabc_cost_rng_t rng = {seed, g, w, KABC_DOM_ABCDE_COST, 0u};
                     rng.logtab = s_logtab;
                     const double dp = kabc_cost_eval(A.cost_id, tp, D, cost_params, cost_data, A.cost_ndata,
                                                      &rng);  // cost(θp.x), :408
-                    const double thr = (eps > di) ? eps : di;  // max(ϵ, Δs[i])
-                    if (dp <= thr) {
+                    if (abcde_accepts(dp, eps, di)) {
                         di = dp;
                         li = lpp;
 #pragma unroll
@@ -239,7 +211,7 @@ __global__ void __launch_bounds__(kAbcdeSmallBlock) abcde_small_kernel(const Abc
 #pragma unroll
         for (int k = 0; k < D; ++k) {
             const double v = s_th[tid][k];
-            out[(int64_t)tid * D + k] = s_prior[k].discrete ? kabc_rint(v) : v;
+            out[(int64_t)tid * D + k] = pop_output(v, s_prior[k].discrete != 0);
         }
         const double dl = s_dl[tid];
         dout[tid] = dl;
@@ -267,7 +239,7 @@ __global__ void __launch_bounds__(kAbcdeSmallBlock) abcde_small_kernel(const Abc
         r.nsims = nsims;
         r.error = failed ? 1 : 0;
         r.cancelled = cancelled ? 1 : 0;
-        r.reached = (mx <= A.eps_target) ? 1 : 0;  // conv = maximum(Δs) <= ϵ_target
+        r.reached = abcde_reached(mx, A.eps_target) ? 1 : 0;
         r.pad = 0;
         A.rec[run] = r;
     }

@@ -3,8 +3,9 @@
 // here is one ATTEMPT of the rejection loop (:306-325) for every particle that is
 // still "bad": the host repeats passes until none is left.  Survivors are read-only
 // during an iteration and bad particles write only themselves, so passes are
-// race-free exactly as the reference's threaded loop is.  The one-workgroup kernel's quantile position
-// and value are the functions of smc_model.hpp.
+// race-free exactly as the reference's threaded loop is.  The reference's rules -- partners, scale, prior
+// gate, success, the one-workgroup selection, the end of an iteration -- are the functions of
+// population_model.hpp (the quantile's position and value: smc_model.hpp).
 #pragma once
 
 #include "kabc_device.hpp"
@@ -78,20 +79,20 @@ __global__ void pf_iter_end_kernel(PfCtrl* ctrl, SmcCtrl* sel, int64_t N, double
         sel->done = 1;
         return;
     }
-    if (ctrl->remaining != 0ull) {  // (2^24 proposals did not replace some particle)
-        ctrl->error = 9;
+    const long long iters = ctrl->iters + 1;
+    const double eps = sel->eps;
+    const PfIterEnd e = pf_iteration_end(ctrl->remaining, (unsigned long long)(N - sel->ess), ctrl->nreps, eps, iters,
+                                         eff_tol, epstol, max_iters);
+    if (e.error) {
+        ctrl->error = e.error;
         ctrl->done = 1;
         sel->done = 1;
         return;
     }
-    const long long iters = ctrl->iters + 1;
-    const double eps = sel->eps;
-    const double nbad = (double)(N - sel->ess);
-    const double eff = nbad / (double)ctrl->nreps;  // :327 (0/0 = NaN when nothing was bad, as in Julia)
     ctrl->iters = iters;
     ctrl->eps = eps;
-    ctrl->eff = eff;
-    if (eff < eff_tol || eps < epstol || (max_iters >= 0 && iters > max_iters) || !(ctrl->nreps > 0ull)) {
+    ctrl->eff = e.eff;
+    if (e.stop) {
         ctrl->done = 1;
         sel->done = 1;  // (the select kernels still enqueued become no-ops)
     }
@@ -112,40 +113,29 @@ __device__ __forceinline__ void pf_reject_loop(const PfArgs& A, int64_t i, uint6
     const uint32_t w = (uint32_t)i;
     const double lpi_i = A.lpi[i];
     for (uint32_t attempt = a0; attempt < a_end && !done; ++attempt) {
-        const uint64_t t = (A.iteration << 24) | (uint64_t)attempt;
-        const kabc_u128_t B0 = kabc_stream_block(A.seed, w, t, 0u, KABC_DOM_PF_MOVE);
-        const kabc_u128_t B1 = kabc_stream_block(A.seed, w, t, 1u, KABC_DOM_PF_MOVE);
-        const kabc_u128_t B2 = kabc_stream_block(A.seed, w, t, 2u, KABC_DOM_PF_MOVE);
-        // b=c=d=rand(idxok); while c==b ...; while d==b || d==c ...  (:309-311)
-        const int64_t pb = (int64_t)kabc_index(kabc_lo64(B0), nok);
-        int64_t pc = (int64_t)kabc_index(kabc_hi64(B0), nok - 1u);
-        pc += (pc >= pb);
-        const int64_t lo = pb < pc ? pb : pc, hi = pb < pc ? pc : pb;
-        int64_t pd = (int64_t)kabc_index(kabc_lo64(B1), nok - 2u);
-        pd += (pd >= lo);
-        pd += (pd >= hi);
+        const uint64_t t = pf_attempt_counter(A.iteration, attempt);
+        const kabc_u128_t B0 = pf_move_block(A.seed, w, t, 0u), B1 = pf_move_block(A.seed, w, t, 1u);
+        const kabc_u128_t B2 = pf_move_block(A.seed, w, t, 2u);
+        int64_t pb, pc, pd;
+        pf_partners(B0, B1, nok, pb, pc, pd);
         const int64_t b = idxok[pb], c = idxok[pc], d = idxok[pd];
         double z0, z1;
         kabc_normal_pair(kabc_lo64(B2), kabc_hi64(B2), &z0, &z1);
-        const double sc = z0 * A.proposal_width;  // randn(trng)*proposal_width
+        const double sc = pf_scale(z0, A.proposal_width);
         double tb[CAP], tc[CAP], td[CAP], p[CAP], xp[CAP];
         load_row_n<DT>(A.theta + b * D, tb, D);
         load_row_n<DT>(A.theta + c * D, tc, D);
         load_row_n<DT>(A.theta + d * D, td, D);
 #pragma unroll
-        for (int k = 0; k < D; ++k) p[k] = tb[k] + (td[k] - tc[k]) * sc;  // :312
+        for (int k = 0; k < D; ++k) p[k] = pf_proposal(tb[k], tc[k], td[k], sc);
         reps += 1;
         const double ll = logpdf_push_n<DT>(A.prior, A.dprior, D, p, xp);
-        const double wp = ll - lpi_i;
-        double mn = wp;
-        if (!(wp < 0.0)) mn = (wp != wp) ? wp : 0.0;  // min(0.0, ll - logπ[i])
-        const double lu = kabc_log_pn(kabc_u01(kabc_hi64(B1)));
-        if (!(lu > mn)) {  // :316-318
+        if (pop_prior_gate(ll, lpi_i, kabc_hi64(B1))) {
             kabc_cost_rng_t rng = {A.seed, t, w, KABC_DOM_PF_COST, 0u};
             const double Cp = kabc_cost_eval(A.cost_id, p, D, A.cost_params, A.cost_data,
                                              A.cost_ndata, &rng);  // cost(p.x): NOT push_p'ed
             evals += 1;
-            if (!(Cp > eps)) {  // :320-322
+            if (pf_succeeds(Cp, eps)) {
                 store_row_n<DT>(A.theta + i * D, p, D);
                 A.C[i] = Cp;
                 A.lpi[i] = ll;
@@ -181,8 +171,9 @@ __global__ void __launch_bounds__(kPfBlock) pf_attempt_kernel(const PfArgs A) {
 // built to rank 2^15..2^21 keys with 1024 threads, is the largest part.  Here ϵ = quantile(C, q)
 // (type 7) comes from rank counting -- every thread counts the keys before its own (N broadcast LDS
 // reads) and the two threads holding the bracketing order statistics publish them --, the survivor
-// list idxok from wave ballots, the rejection loops are pf_reject_loop as in the other scheme (same
-// attempt numbering, same draws), the stop tests are evaluated by every thread from the same words.
+// list idxok from wave ballots (pf_select_workgroup), the rejection loops are pf_reject_loop as in the other
+// scheme (same attempt numbering, same draws), the stop tests (pf_iteration_end) are evaluated by every thread
+// from the same words.
 // The particles stay in global memory (rows of up to 256 parameters); workgroup barriers order the
 // iterations.  Bit-identical to the launch-per-phase scheme and to the oracle.
 constexpr int kPfSmallBlock = 256;
@@ -218,57 +209,23 @@ __global__ void __launch_bounds__(kPfSmallBlock) pf_small_kernel(const PfSmallAr
     const bool poller = tid == kPfSmallBlock - 1;
     uint32_t cw = 0u;
     double Ci = in ? A.C[tid] : 0.0;
-    const unsigned long long below = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
     for (int launched = 0; S.iters_this_launch <= 0 || launched < S.iters_this_launch; ++launched) {
-        // ---- ϵ = quantile(C, q) over all particles (:298)
-        const unsigned long long nanb = __ballot(in && Ci != Ci);
-        if (lane == 0) s_cnt[wid] = (unsigned)__popcll(nanb);
-        const unsigned long long ki = in ? key_of(Ci) : ~0ull;
-        s_key[tid] = ki;
-        __syncthreads();
-        if (poller && S.cancel) cw = __hip_atomic_load(S.cancel, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        unsigned nn = 0;
-#pragma unroll
-        for (int w = 0; w < kPfSmallBlock / kWave; ++w) nn += s_cnt[w];
-        if (nn > 0u) {
+        // ---- ϵ = quantile(C, q) over all particles (:298), ok, idxok (:299-301)
+        const PfSelection sel = pf_select_workgroup(
+            Ci, in ? key_of(Ci) : ~0ull, in, N, S.q, kPfSmallBlock / kWave, s_key, s_cnt, s_idx, s_ab, [&] {
+                if (poller && S.cancel) cw = __hip_atomic_load(S.cancel, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            });
+        if (sel.nan) {
             c.error = 1;
             c.done = 1;
             break;
         }
-        unsigned rank = 0;  // keys before mine in (key, index) order
-#pragma unroll 4
-        for (int j = 0; j < N; ++j) {
-            const unsigned long long kj = s_key[j];  // (broadcast read)
-            rank += (kj < ki || (kj == ki && j < tid)) ? 1u : 0u;
-        }
-        const long long n = N;
-        long long jq;
-        double gq;
-        smc_quantile_pos(n, S.q, &jq, &gq);
-        if (in) {
-            if ((long long)rank == jq - 1) s_ab[0] = Ci;
-            if ((long long)rank == (n == 1 ? 0 : jq)) s_ab[1] = Ci;
-        }
-        __syncthreads();
-        const double qa = s_ab[0], qb = s_ab[1];
-        const double eps = smc_quantile_value(qa, qb, gq);
-        // ---- ok = !(C > ϵ) as the select kernel writes it, idxok ascending (:299-301)
-        const bool ok = in && Ci <= eps;
-        const unsigned long long okb = __ballot(ok);
-        if (lane == 0) s_cnt[wid] = (unsigned)__popcll(okb);
-        __syncthreads();
-        unsigned nok = 0, before = 0;
-#pragma unroll
-        for (int w = 0; w < kPfSmallBlock / kWave; ++w) {
-            before += (w < wid) ? s_cnt[w] : 0u;
-            nok += s_cnt[w];
-        }
-        if (ok) s_idx[before + (unsigned)__popcll(okb & below)] = tid;
-        __syncthreads();
+        const double eps = sel.eps;
+        const unsigned nok = sel.nok;
         // ---- every bad particle's rejection loop (:302-325)
         A.iteration = (uint64_t)(c.iters + 1);
         unsigned long long reps = 0, evals = 0, done = 0;
-        if (in && !ok) pf_reject_loop<DT>(A, tid, (uint64_t)nok, eps, s_idx, 0u, 1u << 24, reps, evals, done, &Ci);
+        if (in && !sel.ok) pf_reject_loop<DT>(A, tid, (uint64_t)nok, eps, s_idx, 0u, 1u << 24, reps, evals, done, &Ci);
         const unsigned long long sr = wave_sum(reps), se = wave_sum(evals), sd = wave_sum(done);
         if (lane == 0) {
             s_red[0][wid] = sr;
@@ -284,21 +241,23 @@ __global__ void __launch_bounds__(kPfSmallBlock) pf_small_kernel(const PfSmallAr
             nev += s_red[1][w];
             ndone += s_red[2][w];
         }
-        // ---- end of the iteration (:326-333), as pf_iter_end_kernel
+        // ---- end of the iteration (:326-333)
         c.cost_evals += nev;
         c.total_reps += nreps;
         c.nreps = nreps;
         const unsigned long long nbad = (unsigned long long)N - nok;
         c.remaining = nbad - ndone;
-        if (c.remaining != 0ull) {  // (2^24 proposals did not replace some particle)
-            c.error = 9;
+        const PfIterEnd e =
+            pf_iteration_end(c.remaining, nbad, nreps, eps, c.iters + 1, S.eff_tol, S.epstol, S.max_iters);
+        if (e.error) {
+            c.error = e.error;
             c.done = 1;
             break;
         }
         c.iters += 1;
         c.eps = eps;
-        c.eff = (double)nbad / (double)nreps;  // :327 (0/0 = NaN when nothing was bad, as in Julia)
-        if (c.eff < S.eff_tol || eps < S.epstol || (S.max_iters >= 0 && c.iters > S.max_iters) || !(nreps > 0ull)) {
+        c.eff = e.eff;
+        if (e.stop) {
             c.done = 1;
             break;
         }

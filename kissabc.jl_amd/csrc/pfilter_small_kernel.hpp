@@ -7,16 +7,17 @@
 //
 // The same draws and the same operation order as abcde_init_kernel (pfilter's stream domains) +
 // pf_small_kernel / pf_reject_loop + smc_finalize_kernel: run r is bit-identical to kabc_pfilter_run
-// with seed = seeds[r].
+// with seed = seeds[r].  All of them evaluate the rules of population_model.hpp; this file is their
+// schedule over a population in LDS.
 //   * θ [256][D], C, logπ, the rank keys, idxok, the prepared prior and the math table live in LDS for
 //     the whole launch.  LDS per workgroup: 256 * 8 * D (rows) + 4 KB (C, logπ) + 2 KB (keys) + 1 KB
 //     (idxok) + the prior (64 B per component) + the math table; profiles/pfilter_batch_resources.txt
 //     has the totals per D.  At D = 2 15.6 KB, at D = 16 45 KB: by LDS ten and three runs fit the
-//     160 KB of a CU.  The registers bind first: 298-326 VGPRs (arch + acc) from D = 2 on, so a SIMD
+//     160 KB of a CU.  The registers bind first: 284-352 VGPRs (arch + acc) from D = 2 on, so a SIMD
 //     holds one of the kernel's wavefronts and a CU four -- two runs of 100 particles (two wavefronts
 //     each) share a CU, a run of 256 has it alone;
-//   * ϵ = quantile(C, q) (type 7) by rank counting, ok = C <= ϵ, idxok from wave ballots: the
-//     arithmetic of pf_small_kernel (the quantile's position and value: smc_model.hpp);
+//   * ϵ = quantile(C, q) (type 7) by rank counting, ok = C <= ϵ, idxok from wave ballots:
+//     pf_select_workgroup, the function pf_small_kernel calls;
 //   * THE REJECTION PHASE (:304-325) is parallel over ATTEMPTS.  Every draw of attempt a of particle i
 //     is addressed by (seed, i, iteration << 24 | a, domain); the survivors are read-only during an
 //     iteration and a bad particle writes only itself: any lane can evaluate any (particle, attempt)
@@ -144,31 +145,17 @@ __global__ void __launch_bounds__(kPfBatchBlock) pf_batch_kernel(const PfBatchAr
     // (thread 0: requested here, decided on at the end of the first iteration)
     if (tid == 0 && A.cancel) cw = __hip_atomic_load(A.cancel, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 
-    // ---- θs, logπ, C with the re-draw loop of :280-294 (abcde_init_kernel, pfilter's domains)
+    // ---- θs, logπ, C (pop_initial_draw, pfilter's domains) from the prior and the math table in LDS
     double Ci = 0.0;
     if (in) {
         double x[D], xp[D];
         double lp = 0.0, dl = 0.0;
-        for (unsigned attempt = 0;; ++attempt) {
-            for (int k = 0; k < D; ++k) {
-                kabc_slotwin_t win = {seed, (uint64_t)attempt, (uint32_t)tid, KABC_DOM_PF_INIT,
-                                      (uint32_t)k * KABC_SLOTS_PER_DIM};
-                // (a pointer INTO the components' array: a joint prior's sampler reaches component 0 from component k)
-                x[k] = kabc_sample_prior(&A.raw[k], &win);
-            }
-            lp = factored_logpdf_push<D>(s_prior, x, xp, s_logtab);
-            kabc_cost_rng_t rng = {seed, (uint64_t)attempt, (uint32_t)tid, KABC_DOM_PF_INIT_COST, 0u};
-            rng.logtab = s_logtab;
-            // first pass: the cost is only evaluated when logπ is finite; in the re-draw loop it
-            // always is.  cost(θ.x): NOT push_p'ed.
-            const bool eval = (attempt > 0) || kabc_isfinite(lp);
-            dl = eval ? kabc_cost_eval(A.cost_id, x, D, cost_params, cost_data, A.cost_ndata, &rng) : KABC_NAN;
-            if (kabc_isfinite(dl) && kabc_isfinite(lp)) break;
-            if (attempt >= kAbcdeMaxInitTries) {
-                s_err = 1;
-                break;
-            }
-        }
+        const auto logpdf = [&](const double* v, double* vp) {
+            return factored_logpdf_push<D>(s_prior, v, vp, s_logtab);
+        };
+        if (pop_initial_draw(seed, (uint32_t)tid, KABC_DOM_PF_INIT, KABC_DOM_PF_INIT_COST, A.raw, D, A.cost_id,
+                             cost_params, cost_data, A.cost_ndata, s_logtab, logpdf, x, xp, lp, dl))
+            s_err = 1;
 #pragma unroll
         for (int k = 0; k < D; ++k) s_th[tid][k] = x[k];
         s_C[tid] = dl;
@@ -179,47 +166,16 @@ __global__ void __launch_bounds__(kPfBatchBlock) pf_batch_kernel(const PfBatchAr
     if (s_err != 0) c.error = 1;
 
     while (c.error == 0) {
-        // ---- ϵ = quantile(C, q) over all particles (:298), as pf_small_kernel
-        const unsigned long long nanb = __ballot(in && Ci != Ci);
-        if (lane == 0) s_cnt[wid] = (unsigned)__popcll(nanb);
-        const unsigned long long ki = in ? key_of(Ci) : ~0ull;
-        s_key[tid] = ki;
-        __syncthreads();
-        unsigned nn = 0;
-        for (int w = 0; w < nwaves; ++w) nn += s_cnt[w];
-        if (nn > 0u) {
+        // ---- ϵ = quantile(C, q) over all particles (:298), ok, idxok (:299-301)
+        const PfSelection sel =
+            pf_select_workgroup(Ci, in ? key_of(Ci) : ~0ull, in, N, A.q, nwaves, s_key, s_cnt, s_idx, s_ab, [] {});
+        if (sel.nan) {
             c.error = 2;
             break;
         }
-        unsigned rank = 0;  // keys before mine in (key, index) order
-#pragma unroll 4
-        for (int j = 0; j < N; ++j) {
-            const unsigned long long kj = s_key[j];  // (broadcast read)
-            rank += (kj < ki || (kj == ki && j < tid)) ? 1u : 0u;
-        }
-        const long long n = N;
-        long long jq;
-        double gq;
-        smc_quantile_pos(n, A.q, &jq, &gq);
-        if (in) {
-            if ((long long)rank == jq - 1) s_ab[0] = Ci;
-            if ((long long)rank == (n == 1 ? 0 : jq)) s_ab[1] = Ci;
-        }
-        __syncthreads();
-        const double qa = s_ab[0], qb = s_ab[1];
-        const double eps = smc_quantile_value(qa, qb, gq);
-        // ---- ok = !(C > ϵ) as the select kernel writes it, idxok ascending (:299-301)
-        const bool ok = in && Ci <= eps;
-        const unsigned long long okb = __ballot(ok);
-        if (lane == 0) s_cnt[wid] = (unsigned)__popcll(okb);
-        __syncthreads();
-        unsigned nok = 0, before = 0;
-        for (int w = 0; w < nwaves; ++w) {
-            before += (w < wid) ? s_cnt[w] : 0u;
-            nok += s_cnt[w];
-        }
-        if (ok) s_idx[before + (unsigned)__popcll(okb & below)] = tid;
-        __syncthreads();
+        const double eps = sel.eps;
+        const unsigned nok = sel.nok;
+        const bool ok = sel.ok;
         // ---- every bad particle's rejection loop (:302-325)
         const uint64_t iteration = (uint64_t)(c.iters + 1);
         unsigned long long reps = 0, evals = 0, done = 0;
@@ -239,39 +195,28 @@ __global__ void __launch_bounds__(kPfBatchBlock) pf_batch_kernel(const PfBatchAr
                 double p[D];
                 double ll = 0.0, Cp = 0.0;
                 const int i = wid * kWave + pl;
-                if (active) {  // one proposal, the expressions and the order of pf_reject_loop
+                if (active) {  // one proposal, as pf_reject_loop makes it
                     const uint32_t w = (uint32_t)i;
-                    const uint64_t t = (iteration << 24) | (uint64_t)attempt;
-                    const kabc_u128_t B0 = kabc_stream_block(seed, w, t, 0u, KABC_DOM_PF_MOVE);
-                    const kabc_u128_t B1 = kabc_stream_block(seed, w, t, 1u, KABC_DOM_PF_MOVE);
-                    const kabc_u128_t B2 = kabc_stream_block(seed, w, t, 2u, KABC_DOM_PF_MOVE);
-                    // b=c=d=rand(idxok); while c==b ...; while d==b || d==c ...  (:309-311)
-                    const int64_t pb = (int64_t)kabc_index(kabc_lo64(B0), (uint64_t)nok);
-                    int64_t pc = (int64_t)kabc_index(kabc_hi64(B0), (uint64_t)nok - 1u);
-                    pc += (pc >= pb);
-                    const int64_t lo = pb < pc ? pb : pc, hi = pb < pc ? pc : pb;
-                    int64_t pd = (int64_t)kabc_index(kabc_lo64(B1), (uint64_t)nok - 2u);
-                    pd += (pd >= lo);
-                    pd += (pd >= hi);
+                    const uint64_t t = pf_attempt_counter(iteration, attempt);
+                    const kabc_u128_t B0 = pf_move_block(seed, w, t, 0u), B1 = pf_move_block(seed, w, t, 1u);
+                    const kabc_u128_t B2 = pf_move_block(seed, w, t, 2u);
+                    int64_t pb, pc, pd;
+                    pf_partners(B0, B1, (uint64_t)nok, pb, pc, pd);
                     const int b = s_idx[pb], cc = s_idx[pc], d = s_idx[pd];
                     double z0, z1;
                     kabc_normal_pair(kabc_lo64(B2), kabc_hi64(B2), &z0, &z1);
-                    const double sc = z0 * A.proposal_width;  // randn(trng)*proposal_width
+                    const double sc = pf_scale(z0, A.proposal_width);
                     double xp[D];
 #pragma unroll
-                    for (int k = 0; k < D; ++k) p[k] = s_th[b][k] + (s_th[d][k] - s_th[cc][k]) * sc;  // :312
+                    for (int k = 0; k < D; ++k) p[k] = pf_proposal(s_th[b][k], s_th[cc][k], s_th[d][k], sc);
                     ll = factored_logpdf_push<D>(s_prior, p, xp, s_logtab);
-                    const double wp = ll - s_lp[i];
-                    double mn = wp;
-                    if (!(wp < 0.0)) mn = (wp != wp) ? wp : 0.0;  // min(0.0, ll - logπ[i])
-                    const double lu = kabc_log_pn(kabc_u01(kabc_hi64(B1)));
-                    if (!(lu > mn)) {  // :316-318
+                    if (pop_prior_gate(ll, s_lp[i], kabc_hi64(B1))) {
                         kabc_cost_rng_t rng = {seed, t, w, KABC_DOM_PF_COST, 0u};
                         rng.logtab = s_logtab;
                         Cp = kabc_cost_eval(A.cost_id, p, D, cost_params, cost_data, A.cost_ndata,
                                             &rng);  // cost(p.x): NOT push_p'ed
                         pass = true;
-                        success = !(Cp > eps);  // :320-322
+                        success = pf_succeeds(Cp, eps);
                     }
                 }
                 const unsigned long long sb = __ballot(success), mb = __ballot(pass);
@@ -340,20 +285,21 @@ __global__ void __launch_bounds__(kPfBatchBlock) pf_batch_kernel(const PfBatchAr
             nev += s_red[1][w];
             ndone += s_red[2][w];
         }
-        // ---- end of the iteration (:326-333), as pf_iter_end_kernel
+        // ---- end of the iteration (:326-333)
         c.cost_evals += nev;
         c.total_reps += nreps;
         c.nreps = nreps;
         const unsigned long long nbad = (unsigned long long)N - nok;
-        if (nbad - ndone != 0ull) {  // (2^24 proposals did not replace some particle)
-            c.error = 9;
+        const PfIterEnd e =
+            pf_iteration_end(nbad - ndone, nbad, nreps, eps, c.iters + 1, A.eff_tol, A.epstol, A.max_iters);
+        if (e.error) {
+            c.error = e.error;
             break;
         }
         c.iters += 1;
         c.eps = eps;
-        c.eff = (double)nbad / (double)nreps;  // :327 (0/0 = NaN when nothing was bad, as in Julia)
-        if (c.eff < A.eff_tol || eps < A.epstol || (A.max_iters >= 0 && c.iters > A.max_iters) || !(nreps > 0ull))
-            break;
+        c.eff = e.eff;
+        if (e.stop) break;
         if (s_stop) {  // (uniform) stop at this iteration boundary (kabc_ctx_cancel)
             c.cancelled = 1;
             break;
@@ -367,7 +313,7 @@ __global__ void __launch_bounds__(kPfBatchBlock) pf_batch_kernel(const PfBatchAr
 #pragma unroll
         for (int k = 0; k < D; ++k) {
             const double v = s_th[tid][k];
-            out[k] = s_prior[k].discrete ? kabc_rint(v) : v;
+            out[k] = pop_output(v, s_prior[k].discrete != 0);
         }
         A.cout[run * (int64_t)N + tid] = s_C[tid];
     }

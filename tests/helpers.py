@@ -424,3 +424,52 @@ def witness_dsel2(Xa, alpha, eps_1, eps_2, eps_now, N):
     if eps_now == 0.0:
         return 7
     return 0
+
+
+# ---- the re-draw loop of the initial population (src/smc.jl:351-366 ABCDE, :280-294 pfilter):
+# cases in which rows of the first draw are rejected and drawn again (test_abcde.py, test_pfilter.py,
+# test_gpu_abcde_batch.py, test_gpu_pfilter_batch.py)
+REDRAW_SEED = 7
+
+
+def redraw_case(k, p_inf=0.5):
+    """NoisyBanana(0.5) returns +Inf with probability 1/2 from the cost's own stream: about half of the
+    rows of the initial population are drawn again, some of them several times.  p_inf = 0: the same
+    problem without re-draws."""
+    return k.Factored(k.Normal(0, 5), k.Normal(0, 5)), k.costs.NoisyBanana(p_inf)
+
+
+REDRAW_USER_SRC = """
+KABC_HD double kabc_user_cost(const double* x, int D, const double* params, const double* data,
+                              int64_t ndata, kabc_cost_rng_t* rng) {
+    // params[1] > 0: no finite distance on the half space x[0] < 0
+    if (params[1] > 0.0 && x[0] < 0.0) return KABC_INF;
+    double s = 0.0;
+    for (int k = 0; k < D; ++k) s += kabc_fabs(x[k] - params[0]);
+    return s;
+}
+"""
+
+
+def redraw_user_case(k, orc, inf_branch=True, D=17):
+    """the run-time-dimension kernels (length(prior) > 16) with a user cost that is +Inf on half of the
+    prior's mass; inf_branch = False: the same cost without that branch"""
+    cost = k.costs.UserCost(REDRAW_USER_SRC, dims=[D], params=[0.5, 1.0 if inf_branch else 0.0],
+                            name="redraw_half_space")
+    orc.register_user_cost(cost)
+    return k.Factored(*[k.Normal(0, 2)] * D), cost
+
+
+def bits_equal(a, b):
+    a, b = np.ascontiguousarray(a, dtype=np.float64), np.ascontiguousarray(b, dtype=np.float64)
+    return a.shape == b.shape and np.array_equal(a.view(np.uint64), b.view(np.uint64))
+
+
+def assert_redraws_happen(run0, case, case_plain):
+    """run0(prior, cost) -> the oracle's initial population (generations = 0 / max_iters = 0): the case is
+    informative when at least one of its rows differs from the row drawn without the Inf branch"""
+    with_inf, plain = run0(*case)["P"], run0(*case_plain)["P"]
+    assert with_inf.shape == plain.shape
+    changed = int(np.any(with_inf.view(np.uint64) != plain.view(np.uint64), axis=1).sum())
+    assert changed >= 1, "no row of the initial population was drawn again"
+    return changed

@@ -3,6 +3,8 @@ there, so parity is oracle-vs-device (bit-exact) plus sanity on known posteriors
 import numpy as np
 import pytest
 
+from helpers import REDRAW_SEED, assert_redraws_happen, bits_equal, redraw_case, redraw_user_case
+
 
 def _cases(k):
     N2 = k.Factored(k.Normal(0, 5), k.Normal(0, 5))
@@ -112,3 +114,47 @@ def test_abcde_medium_donor_draws_bit_exact(k, orc, gpu_ctx, monkeypatch, N, kw)
         r = k.ABCDE(pri, cost, 0.5, nparticles=N, seed=11, return_array=True, **kw)
         assert np.array_equal(r.P, ref["P"]) and np.array_equal(r.C, ref["C"]), env
         assert r.info["generations_run"] == ref["generations_run"] and r.info["nsims"] == ref["nsims"], env
+
+
+REDRAW_KW = dict(generations=15)
+
+
+def _abcde_same_bits(got, ref, what):
+    assert bits_equal(got.P, ref["P"]) and bits_equal(got.C, ref["C"]), what
+    assert got.reached_ϵ == ref["reached_eps"], what
+    assert got.info["generations_run"] == ref["generations_run"] and got.info["nsims"] == ref["nsims"], what
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("N,env", [(3, {}), (50, {}), (257, {}), (300, {"KABC_ABCDE_DONOR": "0"}),
+                                   (50, {"KABC_ABCDE_SMALL": "0"})],
+                         ids=["n3", "n50", "n257_teams", "n300_own_scans", "n50_launch_per_generation"])
+def test_abcde_initial_redraws_bit_exact(k, orc, gpu_ctx, monkeypatch, N, env):
+    """The initial draw goes past attempt 0 and succeeds (src/smc.jl:351-366: the cost only where logπ is
+    finite on the first pass, always afterwards): a cost that is +Inf half of the time, on the one-workgroup
+    kernel (its smallest ensemble too), the teams, the generation kernel's own scans, and abcde_init_kernel
+    at a size the one-workgroup kernel would otherwise take.  Bit for bit the oracle's run."""
+    for name in ("KABC_ABCDE_DONOR", "KABC_ABCDE_SMALL", "KABC_ABCDE_BLOCKS_FROM", "KABC_ABCDE_RANK"):
+        monkeypatch.delenv(name, raising=False)
+    for name, v in env.items():
+        monkeypatch.setenv(name, v)
+    run0 = lambda pri, cost: orc.abcde(pri, cost, 0.5, nparticles=N, generations=0, seed=REDRAW_SEED)  # noqa: E731
+    assert_redraws_happen(run0, redraw_case(k), redraw_case(k, 0.0))
+    pri, cost = redraw_case(k)
+    ref = orc.abcde(pri, cost, 0.5, nparticles=N, seed=REDRAW_SEED, **REDRAW_KW)
+    assert ref["generations_run"] == 15 and np.all(np.isfinite(ref["C"]))
+    got = k.ABCDE(pri, cost, 0.5, nparticles=N, seed=REDRAW_SEED, return_array=True, **REDRAW_KW)
+    _abcde_same_bits(got, ref, (N, env))
+
+
+@pytest.mark.gpu
+def test_abcde_initial_redraws_run_time_dimension_bit_exact(k, orc, gpu_ctx):
+    """the same through the run-time-dimension kernels (17 parameters) and a run-time compiled cost that
+    is +Inf on the half space x[0] < 0"""
+    kw = dict(nparticles=64, generations=15, seed=REDRAW_SEED)
+    pri, cost = redraw_user_case(k, orc)
+    ref = orc.abcde(pri, cost, 10.0, **kw)
+    assert not np.any(ref["P"][:, 0] < 0)
+    plain = orc.abcde(*redraw_user_case(k, orc, inf_branch=False), 10.0, **kw)
+    assert not bits_equal(ref["P"], plain["P"])
+    _abcde_same_bits(k.ABCDE(pri, cost, 10.0, return_array=True, **kw), ref, "d17")

@@ -10,6 +10,8 @@ import time
 import numpy as np
 import pytest
 
+from helpers import REDRAW_SEED, assert_redraws_happen, redraw_case
+
 pytestmark = pytest.mark.gpu
 
 SEEDS5 = [1, 977, 2 ** 40 + 3, 123456789, 0x9E3779B97F4A7C15 % (1 << 63)]
@@ -85,6 +87,25 @@ def test_batch_equals_single_runs(k, orc, gpu_ctx, monkeypatch, name):
     base = out[0].P.__array_interface__["data"][0]
     for r in range(5):
         assert out[r].P.__array_interface__["data"][0] == base + r * out[0].P.nbytes
+
+
+def test_batch_initial_redraws_bit_exact(k, orc, gpu_ctx, monkeypatch):
+    """every run's initial draw goes past attempt 0 (a cost that is +Inf half of the time, src/smc.jl:351-366):
+    5 seeds at 50 particles in one launch, each run the oracle's"""
+    monkeypatch.delenv("KABC_ABCDE_SMALL", raising=False)
+    kw = dict(nparticles=50, generations=15)
+    seeds = [REDRAW_SEED] + SEEDS5[1:]
+    for s in seeds:
+        run0 = lambda pri, cost: orc.abcde(pri, cost, 0.5, nparticles=50, generations=0, seed=s)  # noqa: E731
+        assert_redraws_happen(run0, redraw_case(k), redraw_case(k, 0.0))
+    prior, cost = redraw_case(k)
+    out = k.ABCDE_batch(prior, cost, 0.5, 5, seeds=seeds, return_array=True, **kw)
+    assert out.info["course"] == "grid" and out.info["launches"] == 1, out.info
+    for r in range(5):
+        ref = orc.abcde(prior, cost, 0.5, seed=seeds[r], **kw)
+        assert np.array_equal(out[r].P.view(np.uint64), ref["P"].view(np.uint64)), r
+        assert np.array_equal(out[r].C.view(np.uint64), ref["C"].view(np.uint64)), r
+        _same_as_oracle(out[r], ref, r)
 
 
 def test_thousand_runs_one_grid(k, gpu_ctx):

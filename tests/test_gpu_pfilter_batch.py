@@ -11,6 +11,8 @@ import time
 import numpy as np
 import pytest
 
+from helpers import REDRAW_SEED, assert_redraws_happen, redraw_case
+
 pytestmark = pytest.mark.gpu
 
 SEEDS5 = [1, 977, 2 ** 40 + 3, 123456789, 0x9E3779B97F4A7C15 % (1 << 63)]
@@ -118,6 +120,27 @@ def test_batch_equals_single_runs(k, orc, gpu_ctx, monkeypatch, name, spread):
     for r in range(5):
         assert out[r].P.__array_interface__["data"][0] == base + r * out[0].P.nbytes
         assert out[r].C.__array_interface__["data"][0] == cbase + r * out[0].C.nbytes
+
+
+@pytest.mark.parametrize("spread", ["spread", "one-lane-per-particle"])
+def test_batch_initial_redraws_bit_exact(k, orc, gpu_ctx, monkeypatch, spread):
+    """every run's initial draw goes past attempt 0 (a cost that is +Inf half of the time, src/smc.jl:280-294):
+    5 seeds at 50 particles in one launch, each run the oracle's"""
+    monkeypatch.delenv("KABC_PF_BATCH", raising=False)
+    if spread == "spread":
+        monkeypatch.delenv("KABC_PF_BATCH_SPREAD", raising=False)
+    else:
+        monkeypatch.setenv("KABC_PF_BATCH_SPREAD", "0")
+    seeds = [REDRAW_SEED] + SEEDS5[1:]
+    for s in seeds:
+        run0 = lambda pri, cost: orc.pfilter(pri, cost, 50, max_iters=0, seed=s)  # noqa: E731
+        assert_redraws_happen(run0, redraw_case(k), redraw_case(k, 0.0))
+    prior, cost = redraw_case(k)
+    out = k.pfilter_batch(prior, cost, 50, 5, seeds=seeds, max_iters=8, return_array=True)
+    assert out.info["course"] == "grid" and out.info["launches"] == 1, out.info
+    assert out.info["status"] == [0] * 5
+    for r in range(5):
+        _same_as_oracle(out[r], orc.pfilter(prior, cost, 50, seed=seeds[r], max_iters=8), (spread, r))
 
 
 def test_thousand_runs_one_grid(k, gpu_ctx, monkeypatch):

@@ -3,6 +3,8 @@ there, so parity is oracle-vs-device (bit-exact) plus sanity on a known posterio
 import numpy as np
 import pytest
 
+from helpers import REDRAW_SEED, assert_redraws_happen, bits_equal, redraw_case, redraw_user_case
+
 
 def _cases(k):
     N2 = k.Factored(k.Normal(0, 5), k.Normal(0, 5))
@@ -97,3 +99,42 @@ def test_pfilter_small_ensembles_bit_exact(k, orc, gpu_ctx, monkeypatch, capfd, 
     if kw.get("verbose"):
         lines = [ln for ln in err.splitlines() if ln.startswith("(iters, ")]
         assert len(lines) == ref["iterations"] and lines[-1].startswith(f"(iters, ϵ, eff) = ({ref['iterations']}, ")
+
+
+def _pfilter_same_bits(got, ref, what):
+    assert bits_equal(got.P, ref["P"]) and bits_equal(got.C, ref["C"]), what
+    for f in ("eps", "iterations", "nreps", "cost_evals"):
+        assert got.info[f] == ref[f], (what, f, got.info, ref[f])
+    assert got.info["eff"] == ref["eff"] or (np.isnan(got.info["eff"]) and np.isnan(ref["eff"])), what
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("N,small", [(5, "1"), (5, "0"), (50, "1"), (50, "0"), (257, "0")],
+                         ids=["raised_13-one-workgroup", "raised_13-launch-per-phase", "n50-one-workgroup",
+                              "n50-launch-per-phase", "n257-launch-per-phase"])
+def test_pfilter_initial_redraws_bit_exact(k, orc, gpu_ctx, monkeypatch, N, small):
+    """The initial draw goes past attempt 0 and succeeds (src/smc.jl:280-294): a cost that is +Inf half of
+    the time, under both KABC_PF_SMALL settings (257 particles are beyond the one-workgroup course).  Bit for
+    bit the oracle's run."""
+    monkeypatch.delenv("KABC_PF_PASSES", raising=False)
+    monkeypatch.setenv("KABC_PF_SMALL", small)
+    run0 = lambda pri, cost: orc.pfilter(pri, cost, N, max_iters=0, seed=REDRAW_SEED)  # noqa: E731
+    assert_redraws_happen(run0, redraw_case(k), redraw_case(k, 0.0))
+    pri, cost = redraw_case(k)
+    ref = orc.pfilter(pri, cost, N, max_iters=8, seed=REDRAW_SEED)
+    assert ref["iterations"] == 9 and np.all(np.isfinite(ref["C"]))
+    got = k.pfilter(pri, cost, N, max_iters=8, seed=REDRAW_SEED, return_array=True)
+    _pfilter_same_bits(got, ref, (N, small))
+
+
+@pytest.mark.gpu
+def test_pfilter_initial_redraws_run_time_dimension_bit_exact(k, orc, gpu_ctx):
+    """the same through the run-time-dimension kernels (17 parameters) and a run-time compiled cost that
+    is +Inf on the half space x[0] < 0"""
+    kw = dict(max_iters=8, seed=REDRAW_SEED)
+    pri, cost = redraw_user_case(k, orc)
+    ref = orc.pfilter(pri, cost, 64, **kw)
+    assert not np.any(ref["P"][:, 0] < 0)
+    plain = orc.pfilter(*redraw_user_case(k, orc, inf_branch=False), 64, **kw)
+    assert not bits_equal(ref["P"], plain["P"])
+    _pfilter_same_bits(k.pfilter(pri, cost, 64, return_array=True, **kw), ref, "d17")
