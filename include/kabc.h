@@ -453,14 +453,26 @@ void kabc_ais_wide_shipped(int32_t geom[3]);
  * kind (AIS; 0 for smc), wavefronts per workgroup} of the last AIS or smc kernel launch enqueued on ctx
  * when that kernel came from one of these tables; all zero when it was a model's own run-time compiled
  * kernel, a cost plugin's or a run-time-dimension kernel, and before the first launch.  The launch paths
- * record it on the host; a test reads it to prove which instantiation it ran. */
+ * record it on the host; a test reads it to prove which instantiation it ran.
+ * The two population samplers (ABCDE, pfilter) ship one instantiation per D = 1..KABC_MAX_DIM of each kernel,
+ * the built-in cost behind a run-time switch: their families hold (cost_id, D, variant 0) wherever the cost
+ * accepts D (kabc_cost_dim_ok), and no other variant.  For them info[6] = {family, cost id, D, sub-course,
+ * 0, wavefronts per workgroup}.  sub-course: ABCDE_GEN, the donor draw of the generations (0 the generation
+ * kernel's own scans, 1 teams of sixteen lanes in front of it, 2 sorted blocks, 3 the wavelet matrix);
+ * PF_PHASES, 0 the rejection loop inside the attempt kernel, 1 a launch per attempt (KABC_PF_PASSES=1);
+ * 0 for the one-workgroup families.  A call that is refused before its first launch leaves info as it was. */
 enum {
     KABC_PREBUILT_AIS_HALF = 1,   /* ais_half_kernel: one launch per half-generation            */
     KABC_PREBUILT_AIS_WIDE = 2,   /* ais_half_wide_kernel: its wide geometry                    */
     KABC_PREBUILT_AIS_SMALL = 3,  /* the one-workgroup kernel of small ensembles                */
     KABC_PREBUILT_SMC_PHASES = 4, /* smc_mcmc_kernel: the kernel-per-phase driver's propose / accept */
     KABC_PREBUILT_SMC_LOOP = 5,   /* the persistent cooperative loop kernel                     */
-    KABC_PREBUILT_SMC_SMALL = 6   /* the one-workgroup kernel of small ensembles                */
+    KABC_PREBUILT_SMC_SMALL = 6,  /* the one-workgroup kernel of small ensembles                */
+    KABC_PREBUILT_ABCDE_GEN = 7,  /* abcde_init_kernel + abcde_gen_kernel: kabc_abcde_run's launches */
+    KABC_PREBUILT_ABCDE_SMALL = 8, /* abcde_small_kernel: the grid course of kabc_abcde_run_batch */
+    KABC_PREBUILT_PF_PHASES = 9,  /* abcde_init_kernel (pfilter's domains) + pf_attempt_kernel  */
+    KABC_PREBUILT_PF_SMALL = 10,  /* pf_small_kernel: the whole loop in one workgroup           */
+    KABC_PREBUILT_PF_BATCH = 11   /* pf_batch_kernel: the grid course of kabc_pfilter_run_batch */
 };
 int32_t kabc_prebuilt_has(int32_t family, int32_t cost_id, int32_t D, int32_t variant);
 void kabc_ctx_last_kernel(kabc_ctx_t* ctx, int32_t info[6]);

@@ -259,18 +259,21 @@ def math_probe(name, x, ctx=None):
 
 
 # the tables of prebuilt kernels (include/kabc.h KABC_PREBUILT_*)
-PREBUILT_FAMILY = {"AIS_HALF": 1, "AIS_WIDE": 2, "AIS_SMALL": 3, "SMC_PHASES": 4, "SMC_LOOP": 5, "SMC_SMALL": 6}
+PREBUILT_FAMILY = {"AIS_HALF": 1, "AIS_WIDE": 2, "AIS_SMALL": 3, "SMC_PHASES": 4, "SMC_LOOP": 5, "SMC_SMALL": 6,
+                   "ABCDE_GEN": 7, "ABCDE_SMALL": 8, "PF_PHASES": 9, "PF_SMALL": 10, "PF_BATCH": 11}
 
 
 def prebuilt_has(family, cost_id, D, variant):
     """kabc_prebuilt_has (verification only; no device): does the table `family` hold a kernel for
-    (cost id, D, variant)?  variant: AIS, pcx = prior class + 4 * (posterior kind - 1); smc, 1 simple, 0 general."""
+    (cost id, D, variant)?  variant: AIS, pcx = prior class + 4 * (posterior kind - 1); smc, 1 simple, 0 general;
+    ABCDE and pfilter, 0."""
     return bool(load().kabc_prebuilt_has(PREBUILT_FAMILY.get(family, family), int(cost_id), int(D), int(variant)))
 
 
 def last_kernel(ctx=None):
     """kabc_ctx_last_kernel (verification only): (family, cost id, D, prior class or simple flag, posterior
-    kind, waves per workgroup) of the last prebuilt AIS / smc launch on the context; zeros for any other kernel."""
+    kind, waves per workgroup) of the last prebuilt AIS / smc launch on the context; zeros for any other kernel.
+    ABCDE and pfilter: (family, cost id, D, sub-course, 0, waves per workgroup), include/kabc.h."""
     info = (C.c_int32 * 6)()
     ctx = ctx or default_context()
     load().kabc_ctx_last_kernel(ctx.handle, info)

@@ -54,6 +54,17 @@ static AbcdeSmallLaunchFn pick_small(int D, std::integer_sequence<int, Ds...>) {
     return f[D - 1];
 }
 
+// kabc_prebuilt_has (capi_smc.hip) for the two ABCDE tables: the entries the drivers pick, one per D, each
+// serving every built-in cost that accepts D (kabc_cost_eval's run-time switch)
+int32_t prebuilt_has_abcde(int32_t family, int32_t cost_id, int32_t D, int32_t variant) {
+    if (cost_id < 1 || cost_id >= KABC_COST__COUNT || D < 1 || D > KABC_MAX_DIM || variant != 0) return 0;
+    const std::make_integer_sequence<int, KABC_MAX_DIM> dims{};
+    bool entry = false;
+    if (family == KABC_PREBUILT_ABCDE_GEN) entry = pick_init(D, dims) && pick_gen(D, dims);
+    if (family == KABC_PREBUILT_ABCDE_SMALL) entry = pick_small(D, dims) != nullptr;
+    return entry && kabc_cost_dim_ok(cost_id, D) ? 1 : 0;
+}
+
 }  // namespace kabc
 
 using namespace kabc;
@@ -312,6 +323,9 @@ kabc_status_t abcde_enqueue(AbcdeRun& r) {
     const int64_t n_gen = r.o->generations > g_first ? r.o->generations - g_first : 0;
     const uint32_t* const cancel_word = r.poll ? r.ctx->cancel_d : nullptr;
     const unsigned db_blocks = (unsigned)((N + kDbBlock - 1) / kDbBlock);
+    // (kabc_ctx_last_kernel: the table's entries, not a unit's, a plugin's or the D = 0 instantiations)
+    note_kernel(r.ctx, r.f_init.fn && r.f_gen.fn && r.cost->id < KABC_COST_USER && r.D <= KABC_MAX_DIM,
+                KABC_PREBUILT_ABCDE_GEN, r.cost->id, r.D, (int)r.donor, 0, kAbcdeBlock / kWave);
     struct BlockEvents {
         hipEvent_t ev[2] = {nullptr, nullptr};
         ~BlockEvents() {
@@ -563,6 +577,8 @@ kabc_status_t abcde_run_grid(kabc_ctx_t* ctx, const kabc_prior_t* prior, int32_t
     A.eps_target = o->eps_target;
     A.alpha = o->alpha;
     A.gamma = o->proposal_width * 2.38 / std::sqrt((double)(2 * D));
+    note_kernel(ctx, f.fn && cost->id < KABC_COST_USER, KABC_PREBUILT_ABCDE_SMALL, cost->id, D, 0, 0,
+                (int)(abcde_small_block(N) / kWave));
     f(A, s);
     KABC_HIP_CHECK(hipGetLastError());
     tl_abcde_batch_stats[1] = 1;

@@ -416,7 +416,7 @@ kabc_status_t kabc_ctx_cancel(kabc_ctx_t* ctx) {
     return KABC_OK;
 }
 
-// the last prebuilt AIS / smc kernel launch on ctx (note_kernel, host_common.hpp)
+// the last prebuilt AIS / smc / ABCDE / pfilter kernel launch on ctx (note_kernel, host_common.hpp)
 void kabc_ctx_last_kernel(kabc_ctx_t* ctx, int32_t info[6]) {
     if (!info) return;
     for (int i = 0; i < 6; ++i) info[i] = ctx ? ctx->last_kernel[i] : 0;

@@ -91,6 +91,20 @@ PfBatchLaunchFn pf_pick_batch(int D, std::integer_sequence<int, Ds...>) {
 }
 }  // namespace
 
+namespace kabc {
+// kabc_prebuilt_has (capi_smc.hip) for the three pfilter tables: the entries the drivers pick, one per D, each
+// serving every built-in cost that accepts D (kabc_cost_eval's run-time switch)
+int32_t prebuilt_has_pfilter(int32_t family, int32_t cost_id, int32_t D, int32_t variant) {
+    if (cost_id < 1 || cost_id >= KABC_COST__COUNT || D < 1 || D > KABC_MAX_DIM || variant != 0) return 0;
+    const std::make_integer_sequence<int, KABC_MAX_DIM> dims{};
+    bool entry = false;
+    if (family == KABC_PREBUILT_PF_PHASES) entry = pf_pick_init(D, dims) && pf_pick_attempt(D, dims);
+    if (family == KABC_PREBUILT_PF_SMALL) entry = pf_pick_small(D, dims) != nullptr;
+    if (family == KABC_PREBUILT_PF_BATCH) entry = pf_pick_batch(D, dims) != nullptr;
+    return entry && kabc_cost_dim_ok(cost_id, D) ? 1 : 0;
+}
+}  // namespace kabc
+
 // kabc_pfilter_run_from's states (from: the one the run continues from, NULL: the initial draw; to: the one
 // it leaves, NULL: none), and whether the call observes kabc_ctx_cancel: the one-after-another course of
 // kabc_pfilter_run_batch looks between two runs itself and runs each of them without
@@ -244,6 +258,13 @@ kabc_status_t pf_look(const PfAttempt& a, PfCtrl* hp, SmcCtrl* hsel = nullptr) {
     return KABC_OK;
 }
 
+// kabc_ctx_last_kernel for the two courses of launches per phase: the tables' entries, not a unit's, a
+// plugin's or the D = 0 instantiations.  passes: 1 a launch per attempt, 0 the loop in the attempt kernel.
+void pf_note_phases(const PfPlan& p, int passes) {
+    note_kernel(p.ctx, p.f_init.fn && p.f_att.fn && p.cost->id < KABC_COST_USER && p.D <= KABC_MAX_DIM,
+                KABC_PREBUILT_PF_PHASES, p.cost->id, p.D, passes, 0, kPfBlock / kWave);
+}
+
 void pf_print_iteration(const PfPlan& p, long long iters, double eps, double eff) {
     if (p.o->verbose) fprintf(stderr, "(iters, ϵ, eff) = (%lld, %.17g, %.17g)\n", iters, eps, eff);
 }
@@ -292,6 +313,8 @@ kabc_status_t pf_small_course(const PfPlan& p, const PfMode& mode, const PfAttem
     sm.iters_this_launch = p.o->verbose ? 1 : 0;
     sm.cancel = mode.poll ? p.ctx->cancel_d : nullptr;
     PfCtrl& hp = out.last;
+    // (the course is taken with a built-in cost only: pf_prepare)
+    note_kernel(p.ctx, p.D <= KABC_MAX_DIM, KABC_PREBUILT_PF_SMALL, p.cost->id, p.D, 0, 0, kPfSmallBlock / kWave);
     do {
         p.f_small(sm, a.s);
         if (kabc_status_t st = pf_look(a, &hp)) return st;
@@ -324,6 +347,7 @@ kabc_status_t pf_loop_course(const PfPlan& p, const PfMode& mode, PfAttempt& a, 
     const int kIterBatch = o->verbose ? 1 : 4;
     PfCtrl& hp = out.last;
     int64_t iters = out.iters;
+    pf_note_phases(p, 0);
     do {
         for (int b = 0; b < kIterBatch; ++b) {
             if (kabc_status_t st = pf_select_and_mark(a, p.N, ++iters)) return st;
@@ -355,6 +379,7 @@ kabc_status_t pf_passes_course(const PfPlan& p, const PfMode& mode, PfAttempt& a
     const bool coop = select_cooperative(a.force_coop);
     PfCtrl& hp = out.last;
     SmcCtrl hsel;
+    pf_note_phases(p, 1);
     while (true) {
         if (kabc_status_t st = pf_select_and_mark(a, p.N, ++out.iters)) return st;
         a.pa.loop_attempts = 0;
@@ -720,6 +745,8 @@ kabc_status_t pf_run_grid(kabc_ctx_t* ctx, const kabc_prior_t* prior, int32_t D,
     A.eff_tol = o->eff_tol;
     A.epstol = o->epstol;
     A.proposal_width = o->proposal_width;
+    note_kernel(ctx, f.fn && cost->id < KABC_COST_USER, KABC_PREBUILT_PF_BATCH, cost->id, D, 0, 0,
+                (int)(pf_batch_block(N) / kWave));
     f(A, s);
     KABC_HIP_CHECK(hipGetLastError());
     tl_pf_batch_stats[1] = 1;

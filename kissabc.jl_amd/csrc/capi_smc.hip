@@ -230,6 +230,10 @@ void kabc_smc_default_opts(kabc_smc_opts_t* o) {
 int32_t kabc_prebuilt_has(int32_t family, int32_t cost_id, int32_t D, int32_t variant) {
     if (family >= KABC_PREBUILT_AIS_HALF && family <= KABC_PREBUILT_AIS_SMALL)
         return prebuilt_has_ais(family, cost_id, D, variant);
+    if (family == KABC_PREBUILT_ABCDE_GEN || family == KABC_PREBUILT_ABCDE_SMALL)
+        return prebuilt_has_abcde(family, cost_id, D, variant);
+    if (family >= KABC_PREBUILT_PF_PHASES && family <= KABC_PREBUILT_PF_BATCH)
+        return prebuilt_has_pfilter(family, cost_id, D, variant);
     if (cost_id < 1 || cost_id >= KABC_COST__COUNT || D < 1 || D > KABC_MAX_DIM || (variant != 0 && variant != 1))
         return 0;
     if (family == KABC_PREBUILT_SMC_PHASES) return find_smc_kernel(cost_id, D, variant == 1) ? 1 : 0;

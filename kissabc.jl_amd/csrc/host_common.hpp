@@ -106,7 +106,7 @@ struct kabc_ctx {
     // cancel_h, the polling kernels read it through cancel_d
     uint32_t* cancel_h = nullptr;
     uint32_t* cancel_d = nullptr;
-    // kabc_ctx_last_kernel (verification only): the last prebuilt AIS / smc launch, note_kernel below
+    // kabc_ctx_last_kernel (verification only): the last prebuilt AIS / smc / ABCDE / pfilter launch, note_kernel below
     int32_t last_kernel[6] = {};
 };
 
@@ -114,7 +114,8 @@ namespace kabc {
 // The host launch paths of capi_ais.hip / capi_smc.hip record which kernel they enqueue: {family
 // (KABC_PREBUILT_*), cost id, D, prior class or simple flag, posterior kind, waves per workgroup} of a
 // kernel of the prebuilt tables, all zero for anything else (a model's own run-time compiled kernel, a cost
-// plugin's, a run-time-dimension kernel).
+// plugin's, a run-time-dimension kernel).  capi_abcde.hip / capi_pfilter.hip: `variant` is the sub-course
+// within the family (ABCDE_GEN: the donor scheme; PF_PHASES: 0 loop in kernel, 1 a launch per attempt), kind 0.
 inline void note_kernel(kabc_ctx_t* ctx, bool prebuilt, int family, int cost_id, int D, int variant, int kind,
                         int waves) {
     const int32_t v[6] = {family, cost_id, D, variant, kind, waves};
@@ -122,6 +123,9 @@ inline void note_kernel(kabc_ctx_t* ctx, bool prebuilt, int family, int cost_id,
 }
 // kabc_prebuilt_has for the three AIS tables (capi_ais.hip, where their find_* functions live)
 int32_t prebuilt_has_ais(int32_t family, int32_t cost_id, int32_t D, int32_t pcx);
+// ... for the two ABCDE tables (capi_abcde.hip) and the three of pfilter (capi_pfilter.hip)
+int32_t prebuilt_has_abcde(int32_t family, int32_t cost_id, int32_t D, int32_t variant);
+int32_t prebuilt_has_pfilter(int32_t family, int32_t cost_id, int32_t D, int32_t variant);
 
 // device buffers of one run-to-completion call (kabc_smc_run, kabc_pfilter_run), released on every
 // return path

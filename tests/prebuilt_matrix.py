@@ -1,8 +1,12 @@
-"""The matrix of prebuilt kernel instantiations (csrc/ais_inst.hip, csrc/smc_inst.hip) as test cases: for
-every (cost id, D, prior class, posterior kind) one model, for every (cost id, D, simple / general) one smc
-problem.  Builders depend on nothing but that tuple.  A helper module, used by
+"""The matrix of prebuilt kernel instantiations (csrc/ais_inst.hip, csrc/smc_inst.hip, the per-D tables of
+csrc/capi_abcde.hip and csrc/capi_pfilter.hip) as test cases: for every (cost id, D, prior class, posterior
+kind) one model, for every (cost id, D, simple / general) one smc problem and one problem of the two
+population samplers (ABCDE, pfilter).  Builders depend on nothing but that tuple.  A helper module, used by
 test_prebuilt_matrix_cases.py (CPU: the tables' contents; the cases are informative on the oracle alone),
-test_gpu_ais_prebuilt_matrix.py and test_gpu_smc_prebuilt_matrix.py (the kernels against the oracle)."""
+test_gpu_ais_prebuilt_matrix.py, test_gpu_smc_prebuilt_matrix.py, test_gpu_abcde_prebuilt_matrix.py and
+test_gpu_pfilter_prebuilt_matrix.py (the kernels against the oracle)."""
+import math
+
 import numpy as np
 
 MAX_DIM = 16
@@ -15,7 +19,11 @@ KERNELIZED, THRESHOLD, COMMON = 1, 2, 3
 KIND_NAME = {KERNELIZED: "KERNELIZED", THRESHOLD: "THRESHOLD", COMMON: "COMMON"}
 AIS_FAMILIES = ("AIS_HALF", "AIS_WIDE", "AIS_SMALL")
 SMC_FAMILIES = ("SMC_PHASES", "SMC_LOOP", "SMC_SMALL")
-FAMILY_ID = {"AIS_HALF": 1, "AIS_WIDE": 2, "AIS_SMALL": 3, "SMC_PHASES": 4, "SMC_LOOP": 5, "SMC_SMALL": 6}
+ABCDE_FAMILIES = ("ABCDE_GEN", "ABCDE_SMALL")
+PF_FAMILIES = ("PF_PHASES", "PF_SMALL", "PF_BATCH")
+POP_FAMILIES = ABCDE_FAMILIES + PF_FAMILIES
+FAMILY_ID = {"AIS_HALF": 1, "AIS_WIDE": 2, "AIS_SMALL": 3, "SMC_PHASES": 4, "SMC_LOOP": 5, "SMC_SMALL": 6,
+             "ABCDE_GEN": 7, "ABCDE_SMALL": 8, "PF_PHASES": 9, "PF_SMALL": 10, "PF_BATCH": 11}
 # the shapes of the GPU sweeps.  AIS: 13 sub-steps end on a single-sub-step chunk for K = 3, 4 and 6 and pass
 # the 8 sub-steps from which the NegativeBinomial table is staged.  AIS_HALF: 65 rows per half, a full
 # 64-row workgroup and one of one row.  AIS_WIDE: 129 rows per half, the second batch of the wide workgroup
@@ -28,6 +36,28 @@ AIS_ENV = {"AIS_HALF": {"KABC_AIS_SMALL": "0", "KABC_AIS_WIDE": "0"},
 SMC_N = {"SMC_PHASES": 300, "SMC_LOOP": 300, "SMC_SMALL": 101}
 SMC_ENV = {"SMC_PHASES": {"KABC_SMC_LOOP": "0"}, "SMC_LOOP": {"KABC_SMC_LOOP": "1"}, "SMC_SMALL": {}}
 SMC_SEED, SMC_ITERATIONS = 1, 3
+# The population samplers.  A family's sweep makes one or more "legs" per case: (environment, keywords).
+# ABCDE_GEN: 130 particles are three 64-lane workgroups, the last of two particles, and take the generation
+# kernel's own scans for the donor draw; 257 put abcde_donor_kernel's teams in front of it, the last team range
+# holding one particle.  ABCDE_SMALL: 65 particles are two wavefronts, the second of one lane; three runs, one
+# launch.  PF_SMALL: 130 particles in the one-workgroup kernel; eff_tol = 0 keeps a poor early efficiency from
+# ending the run before max_iters does.  PF_PHASES: the same call on the loop-in-kernel course and on the
+# launch-per-attempt course.  PF_BATCH: 65 particles; from D = 12 on N q <= 4 length(prior) raises N to 70..93.
+POP_SEED, POP_SEEDS = 1, (1, 2, 3)
+ABCDE_EPS, ABCDE_GENERATIONS = 0.0, 4
+PF_Q, PF_MAX_ITERS = 0.7, 3
+ABCDE_ENV_CLEARED = ("KABC_ABCDE_DONOR", "KABC_ABCDE_BLOCKS_FROM", "KABC_ABCDE_RANK", "KABC_ABCDE_SMALL")
+PF_ENV_CLEARED = ("KABC_PF_SMALL", "KABC_PF_PASSES", "KABC_PF_BATCH", "KABC_PF_BATCH_SPREAD")
+_PF_KW = dict(max_iters=PF_MAX_ITERS, eff_tol=0.0)
+POP_LEGS = {
+    "ABCDE_GEN": [({}, dict(nparticles=130, generations=ABCDE_GENERATIONS, seed=POP_SEED)),
+                  ({}, dict(nparticles=257, generations=ABCDE_GENERATIONS, seed=POP_SEED))],
+    "ABCDE_SMALL": [({}, dict(nparticles=65, generations=ABCDE_GENERATIONS))],
+    "PF_SMALL": [({}, dict(N=130, seed=POP_SEED, **_PF_KW))],
+    "PF_PHASES": [({"KABC_PF_SMALL": "0"}, dict(N=130, seed=POP_SEED, **_PF_KW)),
+                  ({"KABC_PF_SMALL": "0", "KABC_PF_PASSES": "1"}, dict(N=130, seed=POP_SEED, **_PF_KW))],
+    "PF_BATCH": [({}, dict(N=65, **_PF_KW))],
+}
 
 
 def pcx(cls, kind):
@@ -61,6 +91,8 @@ def wide_waves(D, cls):
 
 
 def rule_has(family, cost, D, variant):
+    if family in POP_FAMILIES:   # (one instantiation per D, the cost behind a run-time switch)
+        return cost_dim_ok(cost, D) and variant == 0
     if family in SMC_FAMILIES:
         return cost_dim_ok(cost, D) and variant in (0, 1)
     if not 0 <= variant < 12:
@@ -90,6 +122,29 @@ def smc_expected_kernel(family, cost, D, simple):
     if family == "SMC_LOOP" and cost == 4:
         family = "SMC_PHASES"
     return (FAMILY_ID[family], cost, D, int(simple), 0, {"SMC_PHASES": 1, "SMC_LOOP": 4, "SMC_SMALL": 4}[family])
+
+
+def pf_effective_n(N, D, q=PF_Q):
+    """kabc_pfilter_nparticles (src/smc.jl:276-279): N q <= 4 length(prior) raises N"""
+    return math.ceil((4 * D + 1) / q) if N * q <= 4 * D else N
+
+
+def pop_expected_kernel(family, cost, D, env, kw):
+    """kabc_ctx_last_kernel after a leg of the case: {family, cost, D, sub-course, 0, waves per workgroup}.
+    The sub-course: ABCDE_GEN, the donor scheme by size with the knobs unset (capi_abcde.hip
+    abcde_donor_scheme: 0 the generation kernel's scans below 256 particles, 1 the teams up to 4096);
+    PF_PHASES, 1 with KABC_PF_PASSES=1, else 0."""
+    if family == "ABCDE_GEN":
+        N = kw["nparticles"]
+        assert N < 1536, N   # (sorted blocks and the wavelet matrix: not these shapes)
+        return (FAMILY_ID[family], cost, D, 1 if N >= 256 else 0, 0, 1)
+    if family == "ABCDE_SMALL":
+        return (FAMILY_ID[family], cost, D, 0, 0, -(-kw["nparticles"] // 64))
+    if family == "PF_PHASES":
+        return (FAMILY_ID[family], cost, D, 1 if env.get("KABC_PF_PASSES") == "1" else 0, 0, 1)
+    if family == "PF_SMALL":
+        return (FAMILY_ID[family], cost, D, 0, 0, 4)
+    return (FAMILY_ID[family], cost, D, 0, 0, -(-pf_effective_n(kw["N"], D) // 64))
 
 
 # ---- builders -------------------------------------------------------------------------------------------
@@ -190,6 +245,16 @@ def smc_case(k, cost_id, D, simple, family):
                                                                max_iterations=SMC_ITERATIONS)
 
 
+def pop_case(k, cost_id, D, simple, family):
+    """(prior, cost, legs) of a population-sampler case; a leg is (environment, keywords of k.ABCDE /
+    k.ABCDE_batch / k.pfilter / k.pfilter_batch and of the oracle's run; the batch families run POP_SEEDS)"""
+    return smc_prior(k, D, simple), cost(k, cost_id, D), POP_LEGS[family]
+
+
+def pop_name(family, cost_id, D, simple):
+    return f"({family}, {COSTS[cost_id]}, D={D}, {'simple' if simple else 'general'})"
+
+
 # ---- the grid ---------------------------------------------------------------------------------------------
 def grid_ids():
     """(cost, D) over the full grid, cost 1..11 x D 1..16"""
@@ -208,6 +273,7 @@ def tuple_name(family, cost_id, D, cls, kind):
 # family's cases (asserted by test_prebuilt_matrix_cases.py)
 AIS_UNINFORMATIVE = {}
 SMC_UNINFORMATIVE = {}
+POP_UNINFORMATIVE = {}
 
 
 # ---- informativeness, on the oracle alone -------------------------------------------------------------------
@@ -223,3 +289,23 @@ def smc_informative(orc, k, cost_id, D, simple, family):
     """the oracle's run of the case: its iteration log"""
     p, c, kw = smc_case(k, cost_id, D, simple, family)
     return orc.smc(p, c, **kw)
+
+
+def pop_seeds(family, kw):
+    """the seeds a leg runs: its own, or the three of the batch families"""
+    return (kw["seed"],) if "seed" in kw else POP_SEEDS
+
+
+def abcde_informative(orc, prior, cost, kw, seed):
+    """the oracle's run of one ABCDE leg and seed: (generations run, the share of particles whose row differs
+    from the run of no generations, i.e. from the initial draw)"""
+    kw = dict(kw, seed=seed)
+    ref = orc.abcde(prior, cost, ABCDE_EPS, **kw)
+    ref0 = orc.abcde(prior, cost, ABCDE_EPS, **dict(kw, generations=0))
+    return ref["generations_run"], float(np.mean(np.any(ref["P"] != ref0["P"], axis=1)))
+
+
+def pf_informative(orc, prior, cost, kw, seed):
+    """the oracle's run of one pfilter leg and seed"""
+    kw = dict(kw, seed=seed)
+    return orc.pfilter(prior, cost, kw.pop("N"), **kw)

@@ -1,18 +1,22 @@
 """CPU: the tables of prebuilt kernels (kabc_prebuilt_has, no device) against the written rules, and the
 cases of the GPU sweeps (prebuilt_matrix.py) on the oracle alone: a case in which nothing is accepted, or
 everything is, cannot see a wrong kernel."""
+import math
+
 import pytest
 
 import prebuilt_matrix as pm
 
-FAMILIES = pm.AIS_FAMILIES + pm.SMC_FAMILIES
+FAMILIES = pm.AIS_FAMILIES + pm.SMC_FAMILIES + pm.POP_FAMILIES
 # what csrc/ais_inst.hip and csrc/smc_inst.hip instantiate: 68 (cost, D) pairs; x 12 variants; the wide
-# kernel's 26 pairs x 12; x 9 without the SIMPLE class; x 2 flavours of each smc driver
-TOTALS = {"AIS_HALF": 816, "AIS_WIDE": 312, "AIS_SMALL": 612, "SMC_PHASES": 136, "SMC_LOOP": 136, "SMC_SMALL": 136}
+# kernel's 26 pairs x 12; x 9 without the SIMPLE class; x 2 flavours of each smc driver.  The population
+# samplers: one instantiation per D, every cost that accepts D behind its run-time switch, 68 pairs
+TOTALS = {"AIS_HALF": 816, "AIS_WIDE": 312, "AIS_SMALL": 612, "SMC_PHASES": 136, "SMC_LOOP": 136, "SMC_SMALL": 136,
+          "ABCDE_GEN": 68, "ABCDE_SMALL": 68, "PF_PHASES": 68, "PF_SMALL": 68, "PF_BATCH": 68}
 
 
 def _variants(family):
-    return range(12) if family in pm.AIS_FAMILIES else range(2)
+    return range(12) if family in pm.AIS_FAMILIES else range(1) if family in pm.POP_FAMILIES else range(2)
 
 
 @pytest.mark.parametrize("family", FAMILIES)
@@ -27,7 +31,8 @@ def test_table_is_the_written_rule(k, family):
                 assert has == pm.rule_has(family, c, D, v), (family, c, D, v)
                 total += has
     assert total == TOTALS[family]
-    assert not _lib.prebuilt_has(0, 1, 1, 0) and not _lib.prebuilt_has(7, 1, 1, 0)
+    assert not _lib.prebuilt_has(0, 1, 1, 0) and not _lib.prebuilt_has(12, 1, 1, 0)
+    assert sorted(pm.FAMILY_ID.values()) == list(range(1, 12)) and pm.FAMILY_ID == _lib.PREBUILT_FAMILY
 
 
 def test_twelve_wave_rule_edges():
@@ -102,6 +107,76 @@ def test_smc_cases_are_informative(k, orc, family):
     assert n_cases == TOTALS[family]
     assert n_excused <= 0.05 * n_cases
     assert all(reason for reason in pm.SMC_UNINFORMATIVE.values())
+
+
+def test_pop_table_entries_are_the_grid():
+    """each population-sampler family holds the (cost, D) pairs grid_ids() accepts, and the sweeps' expected
+    tuples are one per entry and leg-specific sub-course: both donor schemes of ABCDE_GEN, both PF_PHASES courses"""
+    for family in pm.POP_FAMILIES:
+        held = [cd for cd in pm.grid_ids() if pm.rule_has(family, *cd, 0)]
+        assert len(held) == TOTALS[family] == 68
+        subs = {pm.pop_expected_kernel(family, 1, 1, env, kw)[3] for env, kw in pm.POP_LEGS[family]}
+        assert subs == ({0, 1} if family in ("ABCDE_GEN", "PF_PHASES") else {0}), family
+    # the batch sweep crosses pfilter's N q <= 4 length(prior) rule between D = 11 and D = 12
+    assert [pm.pf_effective_n(65, D) for D in (11, 12, 16)] == [65, 70, 93]
+    assert pm.pop_expected_kernel("PF_BATCH", 1, 16, {}, dict(N=65))[5] == 2
+
+
+def _pop_cases(family):
+    for c, D in pm.grid_ids():
+        for simple in (1, 0):
+            if pm.rule_has(family, c, D, 0):
+                yield c, D, simple, pm.pop_name(family, c, D, simple)
+
+
+@pytest.mark.parametrize("family", pm.ABCDE_FAMILIES)
+def test_abcde_cases_are_informative(k, orc, family):
+    """at every shape (and seed of the batch) of the GPU sweep: all four generations run, and between a tenth
+    and nine tenths of the particles have left the row of their initial draw"""
+    n_cases = n_excused = 0
+    for c, D, simple, name in _pop_cases(family):
+        n_cases += 1
+        if name in pm.POP_UNINFORMATIVE:
+            n_excused += 1
+            continue
+        prior, cost, legs = pm.pop_case(k, c, D, simple, family)
+        for _, kw in legs:
+            for seed in pm.pop_seeds(family, kw):
+                gens, moved = pm.abcde_informative(orc, prior, cost, kw, seed)
+                print(name, kw["nparticles"], seed, gens, moved)
+                assert gens == pm.ABCDE_GENERATIONS, name
+                assert 0.1 <= moved <= 0.9, (name, kw["nparticles"], seed, moved)
+    assert n_cases == 2 * TOTALS[family]
+    assert n_excused <= 0.05 * n_cases
+    assert all(reason for reason in pm.POP_UNINFORMATIVE.values())
+
+
+@pytest.mark.parametrize("family", pm.PF_FAMILIES)
+def test_pfilter_cases_are_informative(k, orc, family):
+    """at every shape (and seed of the batch) of the GPU sweep: max_iters + 1 iterations run; some proposals
+    fail the prior's Metropolis gate and some pass (nreps > cost_evals > 0); at least 0.3 replacements per
+    particle were proposed; eps is finite"""
+    n_cases = n_excused = 0
+    for c, D, simple, name in _pop_cases(family):
+        n_cases += 1
+        if name in pm.POP_UNINFORMATIVE:
+            n_excused += 1
+            continue
+        prior, cost, legs = pm.pop_case(k, c, D, simple, family)
+        kw = legs[0][1]   # (the legs of a family differ by their environment only: one oracle run)
+        assert all(leg_kw == kw for _, leg_kw in legs)
+        n_eff = pm.pf_effective_n(kw["N"], D)
+        for seed in pm.pop_seeds(family, kw):
+            ref = pm.pf_informative(orc, prior, cost, kw, seed)
+            print(name, seed, {f: ref[f] for f in ("iterations", "nreps", "cost_evals", "eps", "eff")})
+            assert ref["P"].shape == (n_eff, D), name
+            assert ref["iterations"] == pm.PF_MAX_ITERS + 1, name
+            assert ref["nreps"] > ref["cost_evals"] > 0, (name, seed, ref["nreps"], ref["cost_evals"])
+            assert ref["nreps"] >= 0.3 * n_eff, (name, seed, ref["nreps"])
+            assert math.isfinite(ref["eps"]), (name, seed)
+    assert n_cases == 2 * TOTALS[family]
+    assert n_excused <= 0.05 * n_cases
+    assert all(reason for reason in pm.POP_UNINFORMATIVE.values())
 
 
 def test_smc_priors_are_what_the_dispatch_calls_simple(k):
