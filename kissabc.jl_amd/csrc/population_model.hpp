@@ -105,9 +105,11 @@ __device__ __forceinline__ void abcde_partners(const kabc_u128_t& B0, const kabc
 __device__ __forceinline__ double abcde_proposal(double ts, double ta, double tb, double gamma) {
     return ts + (ta - tb) * gamma;
 }
-// Δp <= max(ϵ, Δs[i])  (:409)
+// Δp <= max(ϵ, Δs[i])  (:409).  Julia's max keeps a NaN: a NaN ϵ (ϵ_pop = ϵ_l + α(ϵ_h - ϵ_l) is NaN when
+// ϵ_h - ϵ_l overflows with α = 0, and whenever a cost of -Inf was accepted) accepts nothing.  Δs[i] is never
+// NaN: a NaN Δp is refused here, and the initial draw keeps finite costs only.
 __device__ __forceinline__ bool abcde_accepts(double dp, double eps, double di) {
-    const double thr = (eps > di) ? eps : di;
+    const double thr = (eps != eps || eps > di) ? eps : di;
     return dp <= thr;
 }
 

@@ -1355,7 +1355,8 @@ int32_t orc_abcde_run_from(const kabc_prior_t* prior, int32_t D, const kabc_cost
             if (lu > mn) continue; /* :405 */
             nsims += 1;
             double dp = orc_cost_eval(cost, D, tp, seed, (uint32_t)i, (uint64_t)iters, KABC_DOM_ABCDE_COST);
-            double thr = eps > dl[i] ? eps : dl[i];
+            /* :409 dp <= max(ϵ, Δs[i]): Julia's max keeps a NaN, so a NaN ϵ accepts nothing */
+            double thr = (eps != eps || eps > dl[i]) ? eps : dl[i];
             if (dp <= thr) {
                 ndl[i] = dp;
                 nlp[i] = lpp;
@@ -1482,6 +1483,12 @@ int32_t orc_pfilter_run_from(const kabc_prior_t* prior, int32_t D, const kabc_co
     }
     while (!ended) {
         iters += 1;
+        /* :299 quantile(C, q) throws on a NaN (one accepted by `Cp > ϵ` being false, :320): the library's error */
+        for (int64_t i = 0; i < N; ++i)
+            if (kabc_isnan(Cc[i])) {
+                rc = fail(KABC_ERR_NAN_COST, "pfilter: quantile of the costs is undefined (NaN or empty)");
+                goto done;
+            }
         memcpy(tmp, Cc, sizeof(double) * N);
         qsort(tmp, N, sizeof(double), cmp_double);
         quantile_sorted(tmp, N, o->q, &eps); /* ϵ = quantile(C, q) */

@@ -473,3 +473,215 @@ def assert_redraws_happen(run0, case, case_plain):
     changed = int(np.any(with_inf.view(np.uint64) != plain.view(np.uint64), axis=1).sum())
     assert changed >= 1, "no row of the initial population was drawn again"
     return changed
+
+
+# ---- one generation of ABCDE (src/smc.jl:371-414) and one iteration of pfilter (:297-333) on a table cost
+# (tests/population_scenarios.py), written from the reference and the documented stream layout
+# (include/kabc_philox.h, the comments of csrc/population_model.hpp), not from the oracle or the kernels
+# (test_population_cost_edges.py, test_gpu_population_cost_edges.py)
+def philox_py(ctr, key, rounds):
+    """Philox4x32-R written a third time, from the published round function (Salmon et al. SC'11):
+    multiply two counter words by the two constants, swap / xor with the round key, bump the key."""
+    x, kk = list(ctr), list(key)
+    M0, M1, W0, W1, mask = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85, 0xffffffff
+    for r in range(rounds):
+        if r:
+            kk = [(kk[0] + W0) & mask, (kk[1] + W1) & mask]
+        p0, p1 = M0 * x[0], M1 * x[2]
+        x = [(p1 >> 32) ^ x[1] ^ kk[0], p1 & mask, (p0 >> 32) ^ x[3] ^ kk[1], p0 & mask]
+    return x
+
+
+DOM_ABCDE_INIT, DOM_ABCDE_MOVE, DOM_PF_INIT, DOM_PF_MOVE = 9, 11, 13, 15     # (include/kabc_philox.h)
+
+
+def stream_blocks(seed, walkers, t, slot, domain, rounds):
+    """philox_py over an array of walkers: the block (seed, walker, t, slot, domain) of each as its two 64-bit
+    words (lo, hi).  counter = (walker, t lo32, slot, domain | t hi24 << 8), key = (seed lo32, seed hi32);
+    uint64 arithmetic holds the product of two 32-bit words."""
+    u, mask, s32 = np.uint64, np.uint64(0xffffffff), np.uint64(32)
+    w = np.asarray(walkers, dtype=np.uint64)
+    t = int(t)
+    x = [w.copy(), np.full_like(w, t & 0xffffffff), np.full_like(w, slot), np.full_like(w, domain | ((t >> 32) << 8))]
+    k0, k1 = seed & 0xffffffff, seed >> 32
+    for r in range(rounds):
+        if r:
+            k0, k1 = (k0 + 0x9E3779B9) & 0xffffffff, (k1 + 0xBB67AE85) & 0xffffffff
+        p0, p1 = u(0xD2511F53) * x[0], u(0xCD9E8D57) * x[2]
+        x = [(p1 >> s32) ^ x[1] ^ u(k0), p1 & mask, (p0 >> s32) ^ x[3] ^ u(k1), p0 & mask]
+    return (x[1] << s32) | x[0], (x[3] << s32) | x[2]
+
+
+def stream_index(r, n):
+    """kabc_index: floor(r n / 2^64) of each 64-bit word, in Python integers; n a count or one per word"""
+    n = np.broadcast_to(np.asarray(n), np.shape(r))
+    return np.array([(int(a) * int(b)) >> 64 for a, b in zip(r, n)], dtype=np.int64)
+
+
+def jl_max(a, b):
+    """Julia's max of two doubles: a NaN is kept, max(-0.0, 0.0) = 0.0"""
+    if a != a or b != b:
+        return math.nan
+    if a == b:
+        return b if math.copysign(1.0, a) < 0 else a
+    return a if a > b else b
+
+
+def jl_extrema(v):
+    """Julia's extrema: (NaN, NaN) with a NaN among the values"""
+    v = np.asarray(v, dtype=np.float64)
+    if np.isnan(v).any():
+        return math.nan, math.nan
+    return float(v.min()), float(v.max())
+
+
+def kth_smallest_of_prefix(seq, r, k):
+    """the k[q]-th smallest (from 0) of seq[:r[q]] for every query q, seq a permutation of 0 .. n - 1: the
+    queries walk the bits of the answer from the top, the sequence stably partitioned by each bit in turn
+    (test_population_cost_edges.py checks it against np.sort(seq[:r])[k])"""
+    cur = np.asarray(seq, dtype=np.int64)
+    lo, hi, k = np.zeros(len(r), dtype=np.int64), np.array(r, dtype=np.int64), np.array(k, dtype=np.int64)
+    ans = np.zeros(len(r), dtype=np.int64)
+    for bit in range(max(1, int(cur.size - 1).bit_length()) - 1, -1, -1):
+        one = ((cur >> bit) & 1).astype(bool)
+        z = np.concatenate([[0], np.cumsum(~one)])        # zeros among cur[:p]
+        zl, zh = z[lo], z[hi]
+        up = k >= zh - zl                                 # the answer has this bit set
+        k = np.where(up, k - (zh - zl), k)
+        lo, hi = np.where(up, z[-1] + lo - zl, zl), np.where(up, z[-1] + hi - zh, zh)
+        ans |= up.astype(np.int64) << bit
+        cur = np.concatenate([cur[~one], cur[one]])
+    return ans
+
+
+class TableProblem:
+    """cost(x) = table[x[0]] under x[0] ~ DiscreteUniform(0, M - 1), as population_scenarios.SOURCE computes it:
+    the index is x[0] truncated towards zero and clamped; push_p rounds to nearest-even (src/types.jl:29-32)
+    and the log-prior is `lp0` on the integers 0 .. M - 1 and -Inf elsewhere.  normal_pairs: the library's
+    Box-Muller of two stream words (the oracle's orc.normal_pairs), used for pfilter's scale only."""
+
+    def __init__(self, table, lp0, seed, rounds, normal_pairs):
+        self.table = np.asarray(table, dtype=np.float64)
+        self.M, self.lp0, self.seed, self.rounds, self.normal_pairs = self.table.size, float(lp0), int(seed), rounds, normal_pairs
+
+    def cost(self, x):
+        return self.table[np.clip(np.trunc(x), 0, self.M - 1).astype(np.int64)]
+
+    def in_support(self, x):
+        r = np.rint(x)
+        return (r >= 0) & (r <= self.M - 1)
+
+
+def abcde_step(pb, st, *, eps_target, alpha, earlystop, proposal_width=1.0):
+    """One pass of the loop of src/smc.jl:371-420 on the state st = dict(theta [N], C, logpi, generation,
+    nsims): the next state (a new dict; "broke": the earlystop break of :377-379, which moves nothing and
+    draws nothing) with "w", the witnesses of what the generation met.
+
+    The draws of particle i in generation g = st["generation"] + 1 are the blocks 0 and 1 of the stream
+    (seed, i, g, DOM_ABCDE_MOVE): block 0 lo the donor's position among (1:N)[Δs .<= Δs[i]], block 0 hi the
+    partner a among the N - 1 others of s, block 1 lo the partner b among the N - 2 others of s and a (an
+    index at or above an excluded one moves up by one), block 1 hi the uniform of :403.  With this prior
+    w_prior is 0 or -Inf (asserted), so log(rand) > min(0, w_prior) is false for 0 -- rand < 1 -- and true
+    for -Inf: the uniform's bits decide nothing."""
+    th, C, lp = (np.asarray(st[f], dtype=np.float64) for f in ("theta", "C", "logpi"))
+    N, g = C.size, st["generation"] + 1
+    assert np.all(lp == pb.lp0) and not np.isnan(C).any()
+    el, eh = jl_extrema(C)                                                   # :376
+    w = dict(n_donor=0, neg_donor=False, zero_needs_donor=False, tie_frac=0.0, inf_eval=False, nan_refused=0,
+             neg_inf_state=bool(np.isneginf(C).any()), eps_pop_nan=False, span_overflow=False)
+    if earlystop and eh <= eps_target:                                       # :377-379
+        return dict(st, broke=True, w=w)
+    with np.errstate(over="ignore", invalid="ignore"):
+        span = np.float64(eh) - np.float64(el)
+        pop = np.float64(el) + np.float64(alpha) * span
+    eps_pop = jl_max(float(eps_target), float(pop))                          # :380
+    w["eps_pop_nan"] = eps_pop != eps_pop
+    w["span_overflow"] = bool(np.isfinite(el) and np.isfinite(eh) and np.isinf(span))
+    w["tie_frac"] = float(np.unique(C, return_counts=True)[1].max()) / N
+    active = ~(C <= eps_target) if earlystop else np.ones(N, dtype=bool)     # :382-384
+    eps_i = np.where(C <= eps_target, float(eps_target), eps_pop)            # :388
+    with np.errstate(invalid="ignore"):
+        need = active & (C > eps_i)                                          # :389
+    idx = np.arange(N)
+    lo0, hi0 = stream_blocks(pb.seed, idx, g, 0, DOM_ABCDE_MOVE, pb.rounds)
+    lo1, _ = stream_blocks(pb.seed, idx, g, 1, DOM_ABCDE_MOVE, pb.rounds)
+    s = idx.copy()
+    who = np.flatnonzero(need)                                               # :390
+    if who.size:    # (1:N)[Δs .<= Δs[i]] is the first `count` entries of the stable order by cost, in index order
+        order = np.argsort(C, kind="stable")
+        count = np.searchsorted(C[order], C[who], side="right")
+        s[who] = kth_smallest_of_prefix(order, count, stream_index(lo0[who], count))
+    w["n_donor"] = int(need.sum())
+    w["neg_donor"] = bool(need.any() and el < 0)         # (the donors' set holds the minimum)
+    zeros = C == 0.0
+    w["zero_needs_donor"] = bool((need & zeros).any() and np.signbit(C[zeros]).any() and not np.signbit(C[zeros]).all())
+    a = stream_index(hi0, N - 1)                                             # :392-395
+    a += a >= s
+    b = stream_index(lo1, N - 2)                                             # :396-399
+    first, second = np.minimum(a, s), np.maximum(a, s)
+    b += b >= first
+    b += b >= second
+    gamma = proposal_width * 2.38 / math.sqrt(2.0 * 1)                       # :368, length(prior) = 1
+    tp = th[s] + (th[a] - th[b]) * gamma                                     # :400
+    ok = pb.in_support(tp)
+    lpp = np.where(ok, pb.lp0, -np.inf)                                      # :401
+    go = active & ok                                                         # :402-403
+    dp = pb.cost(tp)                                                         # :405
+    with np.errstate(invalid="ignore"):
+        acc = go & (dp <= np.maximum(eps_i, C))                              # :406 (np.maximum keeps a NaN, as Julia's max)
+    w["inf_eval"] = bool((go & np.isposinf(dp)).any())
+    w["nan_refused"] = int((go & np.isnan(dp)).sum())
+    assert not (acc & np.isnan(dp)).any()
+    return dict(theta=np.where(acc, tp, th), C=np.where(acc, dp, C), logpi=np.where(acc, lpp, lp), generation=g,
+                nsims=st["nsims"] + int(go.sum()), broke=False, w=w)
+
+
+def pfilter_step(pb, st, *, q, proposal_width=0.75):
+    """One pass of the loop of src/smc.jl:297-333 on the state st = dict(theta [N], C, logpi, iteration,
+    nreps, cost_evals): the next state with this iteration's "eps", "eff", "nok", "nbad" and "max_attempts".
+    quantile7 raises ValueError on a NaN cost, as Statistics.quantile does.
+
+    Attempt k (from 0) of particle i in iteration it = st["iteration"] + 1 draws from the blocks 0..2 of the
+    stream (seed, i, (it << 24) | k, DOM_PF_MOVE): block 0 lo the position of b in idxok, block 0 hi that of c
+    among the others of b, block 1 lo that of d among the others of b and c, block 1 hi the uniform of :316
+    (deciding nothing here, as in abcde_step), block 2 the normal pair whose first is randn.  The bad
+    particles read ok particles only and write themselves only, so their order does not matter."""
+    th, C, lp = (np.array(st[f], dtype=np.float64) for f in ("theta", "C", "logpi"))
+    it = st["iteration"] + 1
+    assert np.all(lp == pb.lp0)
+    eps = quantile7(C, q)                                                    # :299
+    with np.errstate(invalid="ignore"):
+        bad = C > eps                                                        # :300
+    idxok, pending = np.flatnonzero(~bad), np.flatnonzero(bad)               # :301-302
+    nok, nbad = idxok.size, pending.size
+    nreps = evals = attempt = 0
+    while pending.size:
+        assert nok >= 3, "b, c and d cannot be distinct: the reference never leaves :309-311"
+        assert attempt < 1 << 24
+        t = (it << 24) | attempt
+        lo0, hi0 = stream_blocks(pb.seed, pending, t, 0, DOM_PF_MOVE, pb.rounds)
+        lo1, _ = stream_blocks(pb.seed, pending, t, 1, DOM_PF_MOVE, pb.rounds)
+        lo2, hi2 = stream_blocks(pb.seed, pending, t, 2, DOM_PF_MOVE, pb.rounds)
+        jb = stream_index(lo0, nok)                                          # :309-311
+        jc = stream_index(hi0, nok - 1)
+        jc += jc >= jb
+        first, second = np.minimum(jb, jc), np.maximum(jb, jc)
+        jd = stream_index(lo1, nok - 2)
+        jd += jd >= first
+        jd += jd >= second
+        b, c, d = idxok[jb], idxok[jc], idxok[jd]
+        z = pb.normal_pairs(np.stack([lo2, hi2], axis=1).ravel())[:, 0]
+        p = th[b] + (th[d] - th[c]) * (z * proposal_width)                   # :312
+        nreps += pending.size                                                # :313
+        ok = pb.in_support(p)                                                # :315-318
+        Cp = pb.cost(p)                                                      # :319
+        evals += int(ok.sum())
+        with np.errstate(invalid="ignore"):
+            done = ok & ~(Cp > eps)                                          # :320-322
+        i = pending[done]
+        th[i], C[i], lp[i] = p[done], Cp[done], pb.lp0                       # :323-325
+        pending = pending[~done]
+        attempt += 1
+    eff = nbad / nreps if nreps else math.nan                                # :328 (0/0)
+    return dict(theta=th, C=C, logpi=lp, iteration=it, nreps=st["nreps"] + nreps, cost_evals=st["cost_evals"] + evals,
+                eps=eps, eff=eff, nok=nok, nbad=nbad, max_attempts=attempt)

@@ -6,6 +6,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from helpers import philox_py as _philox_py   # (the Python Philox lives with the population restatements)
 from helpers import ulp_diff
 
 rng = np.random.default_rng(1)
@@ -19,19 +20,6 @@ def test_philox_kat_oracle_restatement(orc):
     assert orc.philox([0x243f6a88, 0x85a308d3, 0x13198a2e, 0x03707344],
                       [0xa4093822, 0x299f31d0]) == \
         [0xd16cfe09, 0x94fdcceb, 0x5001e420, 0x24126ea1]
-
-
-def _philox_py(ctr, key, rounds):
-    """Philox4x32-R written a third time, from the published round function (Salmon et al. SC'11):
-    multiply two counter words by the two constants, swap / xor with the round key, bump the key."""
-    x, kk = list(ctr), list(key)
-    M0, M1, W0, W1, mask = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85, 0xffffffff
-    for r in range(rounds):
-        if r:
-            kk = [(kk[0] + W0) & mask, (kk[1] + W1) & mask]
-        p0, p1 = M0 * x[0], M1 * x[2]
-        x = [(p1 >> 32) ^ x[1] ^ kk[0], p1 & mask, (p0 >> 32) ^ x[3] ^ kk[1], p0 & mask]
-    return x
 
 
 def test_philox_round_count_is_a_contract_parameter(orc):
