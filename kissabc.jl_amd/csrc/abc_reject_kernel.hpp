@@ -8,13 +8,18 @@
 // KABC_DOM_EVAL_COST).  The arithmetic below is THOSE device functions, called the way those kernels call them;
 // this file only decides where a row lives (LDS instead of global memory) and which rows are stored.
 //
+// This header holds the ONE copy of the rules that abc_reject_batch_kernel.hpp shares (it is also the header the
+// hipRTC form of a user cost compiles): the row rule (reject_draw_row), the output sink (RejectOut, reject_store,
+// reject_append), the log-table prologue, the tile geometry and the dispatch over the built-in costs.
+//
 // abc_reject_kernel<COST> (the fused course): a lane owns a row.  It draws the row into the workgroup's LDS tile
 // (rows D | 1 words apart as in cost_eval_kernel.hpp, run-time D, the row behind its LDS pointer; no other lane
 // touches it, so the tile needs no barrier), projects it, sums its log-prior and evaluates its cost.  A workgroup
 // walks tiles of blockDim.x rows with a grid stride.
 // abc_reject_compact_kernel (defined in capi_abc_reject.hip, the one file that launches it; the phases course: user
-// prior families, joint priors, MvNormal, rows too long for the tile): the rows, log-priors and costs were written to global memory by the kernels of kabc_prior_predictive;
-// a lane reads the cost of its row and appends the row the same way.
+// prior families, joint priors, MvNormal, rows too long for the tile): the rows, log-priors and costs were written
+// to global memory by the kernels of kabc_prior_predictive; a lane reads the cost of its row and appends the row
+// the same way.
 //
 // Compaction (reject_append): a wave-level ballot of the accepting lanes (wave64: a 64-bit mask) gives each its
 // rank within the wavefront (mbcnt); the wavefronts' counts meet in LDS, lane 0 of the workgroup takes ONE
@@ -31,6 +36,18 @@ namespace kabc {
 constexpr int kRejectBlock = kEvalBlock;
 constexpr int kRejectMaxWaves = kRejectBlock / kWave;
 
+// where accepted rows go: one record buffer (stored as arrays) and one cursor per batch of launches
+struct RejectOut {
+    int32_t* run;                // [capacity]: the record's run (kabc_abc_reject_batch only, else unused)
+    int64_t* index;              // [capacity]
+    double* cost;                // [capacity]
+    double* lp;                  // [capacity]
+    double* theta;               // [capacity][D]
+    unsigned long long* cursor;  // records appended so far (zeroed by the host); keeps counting past capacity
+    int64_t capacity;
+    int32_t D;
+};
+
 struct AbcRejectArgs {
     const PriorDev* prior;    // [D] prepared components (fused course)
     const kabc_prior_t* raw;  // [D] raw components (fused course)
@@ -40,23 +57,52 @@ struct AbcRejectArgs {
     const double* theta_in;   // phases course: [nrows][D], [nrows], [nrows] of this launch
     const double* lp_in;
     const double* cost_in;
-    double* out_theta;        // [capacity][D]
-    double* out_cost;         // [capacity]
-    double* out_lp;           // [capacity]
-    int64_t* out_index;       // [capacity]
-    unsigned long long* cursor;  // rows appended so far (zeroed by the host); keeps counting past capacity
-    int64_t capacity;
+    RejectOut out;
     int64_t nrows;            // rows of this launch
     int64_t row0;             // index (relative to first_row) of the launch's first row
     uint64_t seed;
     double tau;               // accept iff cost <= tau (NaN never)
     uint32_t walker0;         // first_row + row0
-    int32_t D, cost_id;
+    int32_t cost_id;
 };
 
-// `acc` lanes append their row (x: D words, stride 1) -- called by EVERY lane of the workgroup (two barriers)
-__device__ __forceinline__ void reject_append(const AbcRejectArgs& A, bool acc, const double* x, double c, double lp,
-                                              int64_t index, unsigned* s_wcnt, unsigned long long* s_wbase) {
+// The row rule: row `walker` of `seed` drawn into x[0..D), projected; returns its log-prior.
+__device__ __forceinline__ double reject_draw_row(const kabc_prior_t* raw, const PriorDev* prior, int D, uint64_t seed,
+                                                  uint32_t walker, double* x) {
+    double lp = 0.0;
+    // rand(prior): prior_rand_kernel's loop (attempt 0, a pointer INTO the raw array)
+    for (int k = 0; k < D; ++k) {
+        kabc_slotwin_t win = {seed, 0ull, walker, KABC_DOM_EVAL_DRAW, (uint32_t)k * KABC_SLOTS_PER_DIM};
+        x[k] = kabc_sample_prior(&raw[k], &win);
+    }
+    // push_p, then logpdf(Factored, x) of the pushed row: prior_logpdf_kernel's modes 1 and 0
+    for (int k = 0; k < D; ++k) {
+        const PriorDev q = prior[k];
+        const double xv = q.discrete ? kabc_rint(x[k]) : x[k];
+        x[k] = xv;
+        const double l = comp_logpdf(q.kind, q, xv);
+        lp = (k == 0) ? l : lp + l;
+    }
+    return lp;
+}
+
+// one record (x: D words, stride 1) at `slot`; RUN: the record carries its run
+template <bool RUN>
+__device__ __forceinline__ void reject_store(const RejectOut& O, unsigned long long slot, int run, const double* x,
+                                             double c, double lp, int64_t index) {
+    if (slot >= (unsigned long long)O.capacity) return;  // (counted, not stored: the host repeats the range)
+    double* __restrict__ dst = O.theta + slot * (unsigned long long)O.D;
+    for (int k = 0; k < O.D; ++k) dst[k] = x[k];
+    if constexpr (RUN) O.run[slot] = run;
+    O.index[slot] = index;
+    O.cost[slot] = c;
+    O.lp[slot] = lp;
+}
+
+// `acc` lanes append their record -- called by EVERY lane of the workgroup (two barriers)
+template <bool RUN>
+__device__ __forceinline__ void reject_append(const RejectOut& O, bool acc, int run, const double* x, double c,
+                                              double lp, int64_t index, unsigned* s_wcnt, unsigned long long* s_wbase) {
     const int tid = threadIdx.x, wave = tid / kWave, nwaves = (blockDim.x + kWave - 1) / kWave;
     const unsigned long long m = __builtin_amdgcn_ballot_w64(acc);
     const unsigned lo = (unsigned)m, hi = (unsigned)(m >> 32);
@@ -67,7 +113,7 @@ __device__ __forceinline__ void reject_append(const AbcRejectArgs& A, bool acc, 
         unsigned total = 0;
         for (int w = 0; w < nwaves; ++w) total += s_wcnt[w];
         // (device scope: the workgroups of a launch sit on eight XCDs with private L2s)
-        unsigned long long base = total ? atomicAdd(A.cursor, (unsigned long long)total) : 0ull;
+        unsigned long long base = total ? atomicAdd(O.cursor, (unsigned long long)total) : 0ull;
         for (int w = 0; w < nwaves; ++w) {
             s_wbase[w] = base;
             base += s_wcnt[w];
@@ -75,13 +121,16 @@ __device__ __forceinline__ void reject_append(const AbcRejectArgs& A, bool acc, 
     }
     __syncthreads();
     if (!acc) return;
-    const unsigned long long slot = s_wbase[wave] + rank;
-    if (slot >= (unsigned long long)A.capacity) return;  // (counted, not stored: the host repeats the range)
-    double* __restrict__ dst = A.out_theta + slot * (unsigned long long)A.D;
-    for (int k = 0; k < A.D; ++k) dst[k] = x[k];
-    A.out_cost[slot] = c;
-    A.out_lp[slot] = lp;
-    A.out_index[slot] = index;
+    reject_store<RUN>(O, s_wbase[wave] + rank, run, x, c, lp, index);
+}
+
+// the prologue of a kernel whose cost reads the log table: the workgroup's LDS copy of it
+template <bool TAB>
+__device__ __forceinline__ void reject_stage_log_table(double* s_logtab) {
+    if constexpr (TAB) {
+        for (int j = threadIdx.x; j < KABC_MATH_TAB_WORDS; j += blockDim.x) s_logtab[j] = kabc_log_tab[j];
+        __syncthreads();
+    }
 }
 
 template <int COST>
@@ -92,11 +141,8 @@ __global__ void __launch_bounds__(kRejectBlock) abc_reject_kernel(const AbcRejec
     __shared__ unsigned s_wcnt[kRejectMaxWaves];
     __shared__ unsigned long long s_wbase[kRejectMaxWaves];
     const int tid = threadIdx.x, nthreads = blockDim.x;
-    const int D = A.D, Dp = cost_eval_stride(D);
-    if constexpr (kTab) {
-        for (int j = tid; j < KABC_MATH_TAB_WORDS; j += nthreads) s_logtab[j] = kabc_log_tab[j];
-        __syncthreads();
-    }
+    const int D = A.out.D, Dp = cost_eval_stride(D);
+    reject_stage_log_table<kTab>(s_logtab);
     double* x = reject_rows + tid * Dp;
     const int64_t ntiles = (A.nrows + nthreads - 1) / nthreads;
     for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {  // (a workgroup-uniform trip count)
@@ -105,34 +151,24 @@ __global__ void __launch_bounds__(kRejectBlock) abc_reject_kernel(const AbcRejec
         double c = 0.0, lp = 0.0;
         if (row < A.nrows) {
             const uint32_t walker = A.walker0 + (uint32_t)row;
-            // rand(prior): prior_rand_kernel's loop (attempt 0, a pointer INTO the raw array)
-            for (int k = 0; k < D; ++k) {
-                kabc_slotwin_t win = {A.seed, 0ull, walker, KABC_DOM_EVAL_DRAW, (uint32_t)k * KABC_SLOTS_PER_DIM};
-                x[k] = kabc_sample_prior(&A.raw[k], &win);
-            }
-            // push_p, then logpdf(Factored, x) of the pushed row: prior_logpdf_kernel's modes 1 and 0
-            for (int k = 0; k < D; ++k) {
-                const PriorDev q = A.prior[k];
-                const double xv = q.discrete ? kabc_rint(x[k]) : x[k];
-                x[k] = xv;
-                const double l = comp_logpdf(q.kind, q, xv);
-                lp = (k == 0) ? l : lp + l;
-            }
+            lp = reject_draw_row(A.raw, A.prior, D, A.seed, walker, x);
             c = cost_eval_item<COST>(A.cost_id, x, D, A.cost_params, A.cost_data, A.cost_ndata, A.seed, 0ull, walker,
                                      kTab ? s_logtab : nullptr);
             acc = c <= A.tau;
         }
-        reject_append(A, acc, x, c, lp, A.row0 + row, s_wcnt, s_wbase);
+        reject_append<false>(A.out, acc, 0, x, c, lp, A.row0 + row, s_wcnt, s_wbase);
     }
 }
 
 #ifndef __HIPCC_RTC__  // (the host side)
 // Launch geometry.  Fused: a workgroup of kRejectBlock lanes when their rows fit the LDS budget of
 // cost_eval_kernel.hpp, else one wavefront when 64 rows fit (D <= 111), else the shape takes the phases course
-// (block == 0).  The grid is capped: a workgroup walks several tiles, the log table is staged once.
+// (block == 0).  The grid is capped at about kRejectMaxGrid workgroups: a workgroup walks several tiles, the log
+// table is staged once.  The batch kernel puts its groups in the grid's second dimension.
 constexpr unsigned kRejectMaxGrid = 2048;  // (8 workgroups per CU)
 struct RejectGeom {
-    unsigned grid, block, lds;
+    dim3 grid;
+    unsigned block, lds;
 };
 inline unsigned reject_fused_block(int D) {
     const size_t row = (size_t)cost_eval_stride(D) * sizeof(double);
@@ -140,22 +176,41 @@ inline unsigned reject_fused_block(int D) {
     if (row * kWave <= kEvalLdsBudget) return kWave;
     return 0u;
 }
-inline RejectGeom reject_geom(int64_t nrows, unsigned block, int D) {
+inline RejectGeom reject_geom(int64_t nrows, unsigned block, int D, int ngroups = 1) {
     RejectGeom G;
     G.block = block;
     const int64_t tiles = (nrows + block - 1) / block;
-    G.grid = (unsigned)(tiles < (int64_t)kRejectMaxGrid ? tiles : (int64_t)kRejectMaxGrid);
+    const int64_t gx = ((int64_t)kRejectMaxGrid + ngroups - 1) / ngroups;  // (>= 1: at most 65535 groups)
+    G.grid = dim3((unsigned)(tiles < gx ? tiles : gx), (unsigned)ngroups, 1u);
     G.lds = (unsigned)((size_t)block * cost_eval_stride(D) * sizeof(double));
     return G;
 }
 
-using RejectLaunchFn = void (*)(const AbcRejectArgs&, unsigned, hipStream_t);
-template <int COST>
-inline void launch_abc_reject(const AbcRejectArgs& a, unsigned block, hipStream_t s) {
-    const RejectGeom G = reject_geom(a.nrows, block, a.D);
-    if (G.grid == 0) return;
-    hipLaunchKernelGGL((abc_reject_kernel<COST>), dim3(G.grid), dim3(G.block), G.lds, s, a);
+// Dispatch over the built-in costs.  A kernel family names its Args and its kernel<COST>; pick_reject<Family>
+// returns the launcher of cost `id` (nullptr: none).
+template <class Args>
+using RejectLaunchFn = void (*)(const Args&, int ngroups, unsigned block, hipStream_t);
+template <class Args, void (*KERNEL)(Args)>
+inline void reject_launch(const Args& a, int ngroups, unsigned block, hipStream_t s) {
+    if (a.nrows < 1 || ngroups < 1) return;
+    const RejectGeom G = reject_geom(a.nrows, block, a.out.D, ngroups);
+    hipLaunchKernelGGL(KERNEL, G.grid, dim3(G.block), G.lds, s, a);
 }
+template <class Family, int... Cs>
+RejectLaunchFn<typename Family::Args> pick_reject(int id, std::integer_sequence<int, Cs...>) {
+    RejectLaunchFn<typename Family::Args> f = nullptr;
+    ((id == Cs + 1 ? (void)(f = &reject_launch<typename Family::Args, Family::template kernel<Cs + 1>>) : (void)0), ...);
+    return f;
+}
+template <class Family>
+RejectLaunchFn<typename Family::Args> pick_reject(int id) {
+    return pick_reject<Family>(id, std::make_integer_sequence<int, KABC_COST__COUNT - 1>{});
+}
+struct AbcRejectFamily {
+    using Args = AbcRejectArgs;
+    template <int COST>
+    static constexpr auto kernel = &abc_reject_kernel<COST>;
+};
 #endif
 
 }  // namespace kabc

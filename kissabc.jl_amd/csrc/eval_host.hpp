@@ -1,6 +1,7 @@
 // eval_host.hpp -- host-side pieces shared by the entry points that run a DeviceCost over rows of the
-// (seed, first_row + i) stream: kabc_cost_eval / kabc_prior_predictive (capi_cost_eval.hip) and kabc_abc_reject
-// (capi_abc_reject.hip).  The argument checks that need no device, the rows of one launch, event timing.
+// (seed, first_row + i) stream: kabc_cost_eval / kabc_prior_predictive (capi_cost_eval.hip), kabc_abc_reject
+// (capi_abc_reject.hip) and kabc_abc_reject_batch (capi_abc_reject_batch.hip), the last two through reject_host.hpp.
+// The argument checks that need no device, the rows of one launch, event timing.
 #pragma once
 #include <vector>
 
