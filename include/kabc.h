@@ -443,6 +443,13 @@ kabc_status_t kabc_ais_wide_deal(const int32_t* simd, int32_t waves, int32_t chu
                                  uint32_t* masks);
 void kabc_ais_wide_shipped(int32_t geom[3]);
 
+/* ---- symmetric-box flag of the AIS half-generation kernels (verification only) ----
+ * A prior whose components are all continuous Uniform(-a_k, a_k), 2 <= D <= 8, is tested for support
+ * with one comparison per component, |y_k| <= a_k, instead of two (csrc/ais_kernels.hpp
+ * box_is_symmetric; same lanes, same results).  kabc_ais_box_sym needs no device: *sym receives the
+ * flag an AIS handle for prior[D] hands its kernels, 1 or 0. */
+kabc_status_t kabc_ais_box_sym(const kabc_prior_t* prior, int32_t D, int32_t* sym);
+
 /* ---- the tables of prebuilt kernels (verification only) --------------------------
  * The library ships its AIS and smc kernels as tables of template instantiations, one table per
  * family.  kabc_prebuilt_has answers from the tables themselves (no device): 1 where `family` holds a

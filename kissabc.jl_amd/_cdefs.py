@@ -164,6 +164,7 @@ PROTOTYPES = {
     "kabc_ais_wide_deal": (C.c_int, [C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32,
                                      C.POINTER(C.c_uint32)]),
     "kabc_ais_wide_shipped": (None, [C.POINTER(C.c_int32)]),
+    "kabc_ais_box_sym": (C.c_int, [C.POINTER(Prior), C.c_int32, C.POINTER(C.c_int32)]),
     "kabc_prebuilt_has": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "kabc_ctx_last_kernel": (None, [VP, C.POINTER(C.c_int32)]),
     "kabc_host_alloc": (C.c_int, [C.c_size_t, C.POINTER(VP)]),

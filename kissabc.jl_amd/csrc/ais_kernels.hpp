@@ -41,6 +41,8 @@ struct AisArgs {
     double reps;            // RN(1/eps) for kabc_div_rc
     double box_lp;          // prior class BOX: the in-support log-density (ordered sum of c0)
     int32_t ablate;         // PROBES=1 builds only (KABC_ABLATE): 1 no consumer, 2 no producers, 64 HW_ID, 128 barrier time
+    int32_t box_sym;        // prior class BOX: 1 = every bound pair is (-hi, hi) (box_is_symmetric); in the
+                            // padding behind `ablate`, so that every other field keeps its offset
     const PriorDev* prior;  // [D] prepared components, device memory (scalar-loaded)
     // batched independent chains (MCMCThreads, src/KissABC.jl:96-104,108): blockIdx.y = chain.
     // Chain c works on x_act + c * stride_act, x_comp + c * stride_comp, lp/ll + c * stride_own,
@@ -264,7 +266,18 @@ struct BoxPrior {
     const double* hi;   // LDS, [D]
     uint32_t dmask;     // bit k: component k is discrete (push_p rounds)
     double lp;          // in-support log-density
+    uint32_t sym;       // wave-uniform: lo[k] == -hi[k] for every k (box_is_symmetric on the host); 0 = unknown
 };
+
+// The condition under which the continuous BOX test may run as |y_k| <= hi_k (box_contains_sym):
+// every component continuous, every bound pair (-hi, hi), and a dimension whose test is a v_cmpx
+// chain.  Evaluated on the host, once per handle; kabc_ais_box_sym is its C entry for the tests.
+inline bool box_is_symmetric(const double* lo, const double* hi, uint32_t dmask, int D) {
+    if (dmask != 0u || D < 2 || D > 8) return false;
+    for (int k = 0; k < D; ++k)
+        if (!(lo[k] == -hi[k])) return false;  // (NaN bounds: not symmetric)
+    return true;
+}
 
 // y inside the box [lo, hi]^D as ONE v_cmpx chain (D = 2..8, the sizes whose bounds live in
 // registers): every comparison narrows EXEC itself, so the 2D s_and_b64 that combine ordinary
@@ -272,11 +285,17 @@ struct BoxPrior {
 // a dependent VALU -> SALU -> VALU chain (C3: 155.4 -> 149.6 us per launch at ntransitions =
 // 100).  Lanes still enabled at the end are inside the box; EXEC is restored before the
 // statement ends.  NaN compares false, as `y >= lo && y <= hi` does.  The surviving EXEC is handed
-// back as the boolean itself (inverse ballot): a flag register set under the narrowed EXEC and
-// compared afterwards was three VALU instructions more.
+// back as the lane mask, which KABC_BOX_LANE turns into the boolean itself (inverse ballot): a flag
+// register set under the narrowed EXEC and compared afterwards was three VALU instructions more.
+// The caller that counts the lanes inside takes the mask as it is (loglike's `evm`).
 #define KABC_BOXP(k) \
     "v_cmpx_ge_f64_e32 vcc, %[y" #k "], %[l" #k "]\n\tv_cmpx_le_f64_e32 vcc, %[y" #k "], %[h" #k "]\n\t"
 #define KABC_BOXO(k) [y##k] "v"(y[k]), [l##k] "v"(lo[k]), [h##k] "v"(hi[k])
+// the box (-hi, hi)^D: y >= -hi && y <= hi is |y| <= hi, ONE comparison per component (|.| is a
+// source modifier, so the VOP3 form).  Exactly the general chain's lanes: -y <= hi is y >= -hi, a
+// NaN compares false either way, and +-0 are inside both.
+#define KABC_BOXS(k) "v_cmpx_le_f64_e64 vcc, |%[y" #k "]|, %[h" #k "]\n\t"
+#define KABC_BOXSO(k) [y##k] "v"(y[k]), [h##k] "v"(hi[k])
 #if __has_builtin(__builtin_amdgcn_inverse_ballot_w64)
 #define KABC_BOX_ASM(BODY, ...)                                                                   \
     unsigned long long saved, inside;                                                             \
@@ -284,7 +303,8 @@ struct BoxPrior {
                  : [in] "=&s"(inside), [sv] "=&s"(saved)                                          \
                  : __VA_ARGS__                                                                    \
                  : "vcc");                                                                        \
-    return __builtin_amdgcn_inverse_ballot_w64(inside);
+    return inside;
+#define KABC_BOX_LANE(m) __builtin_amdgcn_inverse_ballot_w64(m)
 #else  // (a hipRTC older than the one hipcc ships with -- the copy bundled with PyTorch, say)
 #define KABC_BOX_ASM(BODY, ...)                                                                   \
     unsigned flag = 0;                                                                            \
@@ -293,58 +313,111 @@ struct BoxPrior {
                  : [fl] "+v"(flag), [sv] "=&s"(saved)                                             \
                  : __VA_ARGS__                                                                    \
                  : "vcc");                                                                        \
-    return flag != 0u;
+    return __builtin_amdgcn_ballot_w64(flag != 0u);
+#define KABC_BOX_LANE(m) \
+    ((((m) >> __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u))) & 1ull) != 0ull)
 #endif
 template <int D>
-__device__ __forceinline__ bool box_contains(const double* y, const double* lo, const double* hi);
+__device__ __forceinline__ unsigned long long box_contains(const double* y, const double* lo, const double* hi);
 template <>
-__device__ __forceinline__ bool box_contains<2>(const double* y, const double* lo, const double* hi) {
+__device__ __forceinline__ unsigned long long box_contains<2>(const double* y, const double* lo, const double* hi) {
     KABC_BOX_ASM(KABC_BOXP(0) KABC_BOXP(1), KABC_BOXO(0), KABC_BOXO(1))
 }
 template <>
-__device__ __forceinline__ bool box_contains<3>(const double* y, const double* lo, const double* hi) {
+__device__ __forceinline__ unsigned long long box_contains<3>(const double* y, const double* lo, const double* hi) {
     KABC_BOX_ASM(KABC_BOXP(0) KABC_BOXP(1) KABC_BOXP(2), KABC_BOXO(0), KABC_BOXO(1), KABC_BOXO(2))
 }
 template <>
-__device__ __forceinline__ bool box_contains<4>(const double* y, const double* lo, const double* hi) {
+__device__ __forceinline__ unsigned long long box_contains<4>(const double* y, const double* lo, const double* hi) {
     KABC_BOX_ASM(KABC_BOXP(0) KABC_BOXP(1) KABC_BOXP(2) KABC_BOXP(3), KABC_BOXO(0), KABC_BOXO(1), KABC_BOXO(2),
                  KABC_BOXO(3))
 }
 template <>
-__device__ __forceinline__ bool box_contains<5>(const double* y, const double* lo, const double* hi) {
+__device__ __forceinline__ unsigned long long box_contains<5>(const double* y, const double* lo, const double* hi) {
     KABC_BOX_ASM(KABC_BOXP(0) KABC_BOXP(1) KABC_BOXP(2) KABC_BOXP(3) KABC_BOXP(4), KABC_BOXO(0), KABC_BOXO(1),
                  KABC_BOXO(2), KABC_BOXO(3), KABC_BOXO(4))
 }
 template <>
-__device__ __forceinline__ bool box_contains<6>(const double* y, const double* lo, const double* hi) {
+__device__ __forceinline__ unsigned long long box_contains<6>(const double* y, const double* lo, const double* hi) {
     KABC_BOX_ASM(KABC_BOXP(0) KABC_BOXP(1) KABC_BOXP(2) KABC_BOXP(3) KABC_BOXP(4) KABC_BOXP(5), KABC_BOXO(0),
                  KABC_BOXO(1), KABC_BOXO(2), KABC_BOXO(3), KABC_BOXO(4), KABC_BOXO(5))
 }
 template <>
-__device__ __forceinline__ bool box_contains<7>(const double* y, const double* lo, const double* hi) {
+__device__ __forceinline__ unsigned long long box_contains<7>(const double* y, const double* lo, const double* hi) {
     KABC_BOX_ASM(KABC_BOXP(0) KABC_BOXP(1) KABC_BOXP(2) KABC_BOXP(3) KABC_BOXP(4) KABC_BOXP(5) KABC_BOXP(6),
                  KABC_BOXO(0), KABC_BOXO(1), KABC_BOXO(2), KABC_BOXO(3), KABC_BOXO(4), KABC_BOXO(5), KABC_BOXO(6))
 }
 template <>
-__device__ __forceinline__ bool box_contains<8>(const double* y, const double* lo, const double* hi) {
+__device__ __forceinline__ unsigned long long box_contains<8>(const double* y, const double* lo, const double* hi) {
     KABC_BOX_ASM(KABC_BOXP(0) KABC_BOXP(1) KABC_BOXP(2) KABC_BOXP(3) KABC_BOXP(4) KABC_BOXP(5) KABC_BOXP(6)
                      KABC_BOXP(7),
                  KABC_BOXO(0), KABC_BOXO(1), KABC_BOXO(2), KABC_BOXO(3), KABC_BOXO(4), KABC_BOXO(5), KABC_BOXO(6),
                  KABC_BOXO(7))
 }
+template <int D>
+__device__ __forceinline__ unsigned long long box_contains_sym(const double* y, const double* hi);
+template <>
+__device__ __forceinline__ unsigned long long box_contains_sym<2>(const double* y, const double* hi) {
+    KABC_BOX_ASM(KABC_BOXS(0) KABC_BOXS(1), KABC_BOXSO(0), KABC_BOXSO(1))
+}
+template <>
+__device__ __forceinline__ unsigned long long box_contains_sym<3>(const double* y, const double* hi) {
+    KABC_BOX_ASM(KABC_BOXS(0) KABC_BOXS(1) KABC_BOXS(2), KABC_BOXSO(0), KABC_BOXSO(1), KABC_BOXSO(2))
+}
+template <>
+__device__ __forceinline__ unsigned long long box_contains_sym<4>(const double* y, const double* hi) {
+    KABC_BOX_ASM(KABC_BOXS(0) KABC_BOXS(1) KABC_BOXS(2) KABC_BOXS(3), KABC_BOXSO(0), KABC_BOXSO(1), KABC_BOXSO(2),
+                 KABC_BOXSO(3))
+}
+template <>
+__device__ __forceinline__ unsigned long long box_contains_sym<5>(const double* y, const double* hi) {
+    KABC_BOX_ASM(KABC_BOXS(0) KABC_BOXS(1) KABC_BOXS(2) KABC_BOXS(3) KABC_BOXS(4), KABC_BOXSO(0), KABC_BOXSO(1),
+                 KABC_BOXSO(2), KABC_BOXSO(3), KABC_BOXSO(4))
+}
+template <>
+__device__ __forceinline__ unsigned long long box_contains_sym<6>(const double* y, const double* hi) {
+    KABC_BOX_ASM(KABC_BOXS(0) KABC_BOXS(1) KABC_BOXS(2) KABC_BOXS(3) KABC_BOXS(4) KABC_BOXS(5), KABC_BOXSO(0),
+                 KABC_BOXSO(1), KABC_BOXSO(2), KABC_BOXSO(3), KABC_BOXSO(4), KABC_BOXSO(5))
+}
+template <>
+__device__ __forceinline__ unsigned long long box_contains_sym<7>(const double* y, const double* hi) {
+    KABC_BOX_ASM(KABC_BOXS(0) KABC_BOXS(1) KABC_BOXS(2) KABC_BOXS(3) KABC_BOXS(4) KABC_BOXS(5) KABC_BOXS(6),
+                 KABC_BOXSO(0), KABC_BOXSO(1), KABC_BOXSO(2), KABC_BOXSO(3), KABC_BOXSO(4), KABC_BOXSO(5), KABC_BOXSO(6))
+}
+template <>
+__device__ __forceinline__ unsigned long long box_contains_sym<8>(const double* y, const double* hi) {
+    KABC_BOX_ASM(KABC_BOXS(0) KABC_BOXS(1) KABC_BOXS(2) KABC_BOXS(3) KABC_BOXS(4) KABC_BOXS(5) KABC_BOXS(6)
+                     KABC_BOXS(7),
+                 KABC_BOXSO(0), KABC_BOXSO(1), KABC_BOXSO(2), KABC_BOXSO(3), KABC_BOXSO(4), KABC_BOXSO(5), KABC_BOXSO(6),
+                 KABC_BOXSO(7))
+}
 #undef KABC_BOX_ASM
+#undef KABC_BOXSO
+#undef KABC_BOXS
 #undef KABC_BOXO
 #undef KABC_BOXP
 
+// Which instantiations of ais_half_body take the trimmed consumer sub-step (symmetric box chain,
+// carried lp + ll, n_eval by add-with-carry): the BOX class with its bounds in registers.  Every other
+// class keeps the earlier form -- it has no chain to halve, and one more live value or scalar pair
+// made kernels that are short of registers spill (profiles/ais_wide4.md: 30 of 1128 instantiations
+// gained spilled VGPRs or scratch with the trimmed form everywhere).  So does the one BOX kernel that
+// spilled before: gauss_dist at D = 8 bound to 168 registers (`regs168`: the twelve-wave geometry).
+constexpr bool ais_trim_c(int cost, int D, int pc, bool regs168) {
+    return pc == kPriorBox && D >= 2 && D <= 8 && !(regs168 && D == 8 && cost == KABC_COST_GAUSS_DIST);
+}
+
 // loglike(density, push_p(density, y)) -- src/types.jl:51-58, :84-91
-template <int D, int COST, int PC>
+// TRIM (ais_trim_c below): the continuous BOX test may take the symmetric chain, and `evm` receives
+// `ev` as a lane mask.  Without it this is the code every other caller has always had.
+template <int D, int COST, int PC, bool TRIM = false>
 __device__ __forceinline__ void loglike(const PriorDev* __restrict__ P, const BoxPrior& B,
                                         const GaussBoxPrior& GB,
                                         int posterior, double eps, double reps, const double* y,
                                         const double* cost_params, const double* cost_data,
                                         int64_t ndata, kabc_cost_rng_t* rng, double& lp,
                                         double& ll, bool& ev, const double* logtab = kabc_log_tab,
-                                        const double* nbtab = nullptr) {
+                                        const double* nbtab = nullptr, unsigned long long* evm = nullptr) {
     double yp[D];
     // A cheap deterministic cost is evaluated for every lane and selected afterwards: the
     // divergent region around it (exec save / branch / restore) costs the consumer wave more
@@ -368,9 +441,14 @@ __device__ __forceinline__ void loglike(const PriorDev* __restrict__ P, const Bo
             hi[k] = B.hi[k];
         }
         bool in = true;
+        [[maybe_unused]] unsigned long long inm = 0;  // the lanes inside, where the test is a v_cmpx chain
         if (__builtin_amdgcn_readfirstlane((int)B.dmask) == 0) {  // wave-uniform (a scalar branch): all components continuous, push_p = identity
-            if constexpr (D >= 2 && D <= 8) in = box_contains<D>(y, lo, hi);
-            else {
+            if constexpr (D >= 2 && D <= 8) {
+                // (a scalar branch around the chain alone: the cost below is ONE copy for both)
+                if (TRIM && __builtin_amdgcn_readfirstlane((int)B.sym) != 0) inm = box_contains_sym<D>(y, hi);
+                else inm = box_contains<D>(y, lo, hi);
+                in = KABC_BOX_LANE(inm);
+            } else {
 #pragma unroll
                 for (int k = 0; k < D; ++k) in = in && (y[k] >= lo[k]) && (y[k] <= hi[k]);
             }
@@ -380,8 +458,9 @@ __device__ __forceinline__ void loglike(const PriorDev* __restrict__ P, const Bo
                 // (outside the box the reference's values are lp = -Inf, ll = -/+Inf: an invalid
                 // log-density that accept() rejects.  Here the caller gates on `ev` instead and
                 // lp / ll are left as computed -- no selects on the consumer's issue stream)
-                lp = B.lp;
+                lp = B.lp;  // (an accepted BOX state's logprior is B.lp on every path: kLpOfBox relies on it)
                 ev = in;
+                if constexpr (TRIM) *evm = inm;
                 const double c = eval_cost<COST, D>(y, cost_params, cost_data, ndata, rng);
                 if (posterior == KABC_POSTERIOR_KERNELIZED) {
                     const double q = kabc_div_rc(c, eps, reps);
@@ -402,8 +481,9 @@ __device__ __forceinline__ void loglike(const PriorDev* __restrict__ P, const Bo
             }
             if constexpr (kCheap) {
                 // finished here too: the two paths then meet on (lp, ll, ev) only, not on yp
-                lp = B.lp;
+                lp = B.lp;  // (kLpOfBox, as above)
                 ev = in;
+                if constexpr (TRIM) *evm = __builtin_amdgcn_ballot_w64(in);
                 const double c = eval_cost<COST, D>(yp, cost_params, cost_data, ndata, rng);
                 if (posterior == KABC_POSTERIOR_KERNELIZED) {
                     const double q = kabc_div_rc(c, eps, reps);
@@ -414,7 +494,7 @@ __device__ __forceinline__ void loglike(const PriorDev* __restrict__ P, const Bo
                 return;
             }
         }
-        lp = in ? B.lp : -KABC_INF;
+        lp = in ? B.lp : -KABC_INF;  // (kLpOfBox, as above: accepted means `in`)
     } else if constexpr (PC == kPriorSimple || PC == kPriorNormal) {
         bool in;
         double sum;
@@ -432,6 +512,7 @@ __device__ __forceinline__ void loglike(const PriorDev* __restrict__ P, const Bo
         lp = factored_logpdf_push<D, false>(P, y, yp, logtab, nbtab);
     }
     ev = kabc_isfinite(lp);
+    if constexpr (TRIM) *evm = __builtin_amdgcn_ballot_w64(ev);
     if (posterior == KABC_POSTERIOR_KERNELIZED) {
         if constexpr (kCheap) {
             const double c = eval_cost<COST, D>(yp, cost_params, cost_data, ndata, rng);
@@ -763,6 +844,16 @@ __device__ __forceinline__ void ais_half_body(const AisArgs& A0) {
         ll = A.ll[r];
         if (!ld_valid(PK, lp, ll)) err = 2;  // accept(): "old log-density is invalid"
     }
+    // lp + ll of the CURRENT state (kernelized accept): part of the state, formed here and in the
+    // accept region -- the same addition of the same operands, once per accept instead of once
+    // per sub-step
+    constexpr bool kTrim = ais_trim_c(COST, D, PC, G::kWide && G::kOneRowSet) && PK != KABC_POSTERIOR_COMMON;
+    [[maybe_unused]] double lsum = lp + ll;
+    // BOX class, kernelized: an accepted state's logprior is the box's constant (loglike), and the
+    // sub-steps read the old one through lsum only -- lp is set once, after the loop, for the lanes
+    // that accepted at all
+    constexpr bool kLpOfBox = kTrim && PK == KABC_POSTERIOR_KERNELIZED;
+    constexpr bool kSumState = kTrim && PK == KABC_POSTERIOR_KERNELIZED;
 
     // the table's loads are issued here and land in LDS right before the barrier below
     // (768 threads: one word per thread of the first 512 -- wave-uniform)
@@ -793,7 +884,8 @@ __device__ __forceinline__ void ais_half_body(const AisArgs& A0) {
     // no registers to spare
     constexpr bool kBoxRegs = (PC == kPriorBox) && D <= 8;
     double blo[kBoxRegs ? D : 1], bhi[kBoxRegs ? D : 1];
-    const BoxPrior box = {kBoxRegs ? blo : sbox_lo, kBoxRegs ? bhi : sbox_hi, dmask, A.box_lp};
+    const BoxPrior box = {kBoxRegs ? blo : sbox_lo, kBoxRegs ? bhi : sbox_hi, dmask, A.box_lp,
+                          (uint32_t)A.box_sym};
 
     // while the table's loads are in flight the producers expand the two Philox blocks
     // every lane of their first sub-step needs (they depend on nothing else)
@@ -1082,11 +1174,23 @@ __device__ __forceinline__ void ais_half_body(const AisArgs& A0) {
                     }
                     double nlp, nll;
                     bool ev;
-                    loglike<D, COST, PC>(sprior, box, gbox, PK, A.eps, A.reps, y, cparams,
-                                         A.cost_data, A.cost_ndata, &rng, nlp, nll, ev, slogtab,
-                                         kNbTabs > 0 ? snb : nullptr);
+                    [[maybe_unused]] unsigned long long evm = 0;  // kTrim: `ev` as a lane mask
+                    loglike<D, COST, PC, kTrim>(sprior, box, gbox, PK, A.eps, A.reps, y, cparams,
+                                                A.cost_data, A.cost_ndata, &rng, nlp, nll, ev, slogtab,
+                                                kNbTabs > 0 ? snb : nullptr, &evm);
                     __builtin_amdgcn_sched_barrier(0);
-                    n_eval += ev ? 1u : 0u;
+                    if constexpr (!kTrim) {
+                        n_eval += ev ? 1u : 0u;
+                    } else {
+                        // n_eval += ev as ONE VALU instruction: the lane's bit of the mask is the
+                        // carry-in of an add with carry (hipcc forms v_cndmask 0/1 + v_add_u32).  A count
+                        // per WAVE (s_bcnt1 of the mask into a scalar) does not stay scalar: the sub-step
+                        // sits inside the divergent `active` region, so the sum is a per-lane value to hipcc.
+                        unsigned long long cout;
+                        asm("v_addc_co_u32_e64 %[n], %[co], 0, %[n], %[m]"
+                            : [n] "+v"(n_eval), [co] "=&s"(cout)
+                            : [m] "s"(evm));
+                    }
                     // accept(...)  src/types.jl:62-75, :96-104
                     // (the old state's validity is checked once, before the first sub-step: it
                     // can only change through an accept, which requires a valid new state)
@@ -1100,8 +1204,10 @@ __device__ __forceinline__ void ais_half_body(const AisArgs& A0) {
                     const bool valid = ev && ld_valid(PK, nlp, nll);
                     const double e = -logu;  // randexp(rng)
                     bool acc;
+                    [[maybe_unused]] double nsum = 0.0;
                     if (PK == KABC_POSTERIOR_KERNELIZED) {
-                        const double lW = corr + (nlp + nll) - (lp + ll);
+                        nsum = nlp + nll;
+                        const double lW = kSumState ? corr + nsum - lsum : corr + nsum - (lp + ll);
                         acc = valid && (-e <= lW);
                     } else if (PK == KABC_POSTERIOR_COMMON) {
                         const double lW = corr + nll - ll;  // src/types.jl:127
@@ -1115,8 +1221,9 @@ __device__ __forceinline__ void ais_half_body(const AisArgs& A0) {
                     if (acc) {
 #pragma unroll
                         for (int k = 0; k < D; ++k) x[k] = y[k];
-                        lp = nlp;
+                        if constexpr (!kLpOfBox) lp = nlp;
                         ll = nll;
+                        if constexpr (kSumState) lsum = nsum;
                         n_acc += 1u;
                     }
                     // (no code: pins the state to ONE set of registers here.  Without it hipcc
@@ -1182,6 +1289,9 @@ __device__ __forceinline__ void ais_half_body(const AisArgs& A0) {
     if (consumer) {
         if (active) {
             store_row<D>(A.x_act + row * D, x);
+            if constexpr (kLpOfBox) {
+                if (n_acc != 0u) lp = A.box_lp;
+            }
             A.lp[r] = lp;
             A.ll[r] = ll;
             if (A.trace) {

@@ -237,6 +237,7 @@ struct kabc_ais {
     int64_t spec_switch_at = -1;    // launches that ran before the switch, -1
     std::chrono::steady_clock::time_point spec_next_poll;
     double box_lp = 0.0;
+    int32_t box_sym = 0;            // BOX class: the box is (-hi, hi)^D (box_symmetric below)
     bool initialised = false;
     // sample-trace streaming: device chunks filled in rotation by the kernels and
     // drained to the caller's buffer on a copy stream while the next chunks compute
@@ -467,6 +468,21 @@ static kabc_status_t ais_validate(kabc_ctx_t* ctx, const kabc_model_t* m, kabc_a
     return KABC_OK;
 }
 
+// BoxPrior::sym of prepared components (ais_kernels.hpp box_is_symmetric): every one a continuous
+// Uniform(-a, a), 2 <= D <= 8.  The bounds and the discrete flags are the ones the kernel stages.
+static int32_t box_symmetric(const PriorDev* c, int D) {
+    if (D < 1 || D > KABC_MAX_DIM) return 0;
+    double lo[KABC_MAX_DIM], hi[KABC_MAX_DIM];
+    uint32_t dmask = 0;
+    for (int k = 0; k < D; ++k) {
+        if (c[k].kind != KABC_PRIOR_UNIFORM && c[k].kind != KABC_PRIOR_DISCRETE_UNIFORM) return 0;
+        lo[k] = c[k].p[0];
+        hi[k] = c[k].p[1];
+        dmask |= (c[k].discrete ? 1u : 0u) << k;
+    }
+    return box_is_symmetric(lo, hi, dmask, D) ? 1 : 0;
+}
+
 // the prepared components, their class for the half-generation kernel (ais_kernels.hpp) and the BOX
 // class's in-support log-density
 static kabc_status_t ais_prepare_prior(kabc_ais_t* h, const kabc_model_t* m) {
@@ -500,6 +516,7 @@ static kabc_status_t ais_prepare_prior(kabc_ais_t* h, const kabc_model_t* m) {
     // exactly as logpdf(d::Factored, x) does (src/priors.jl:30-36)
     h->box_lp = h->prior.c[0].c0;
     for (int k = 1; k < h->D && !dyn; ++k) h->box_lp += h->prior.c[k].c0;
+    h->box_sym = (!dyn && h->pc == kPriorBox) ? box_symmetric(h->prior.c, h->D) : 0;
     return KABC_OK;
 }
 
@@ -740,6 +757,7 @@ static void fill_args(A& a, const kabc_ais_t* h) {
         a.prior = h->d_prior;
     }
     if constexpr (!aux && !dyn && !dsm && !init) a.box_lp = h->box_lp;
+    if constexpr (std::is_same_v<A, AisArgs>) a.box_sym = h->box_sym;
     if constexpr (!aux && !small) a.posterior = h->posterior;
     if constexpr (dyn || dsm || init) a.cost_id = h->cost_id;
     if constexpr (dyn || dsm) a.D = h->D;
@@ -1320,6 +1338,16 @@ kabc_status_t kabc_ais_wide_deal(const int32_t* simd, int32_t waves, int32_t chu
         sd |= (uint64_t)simd[w] << (4 * w);
     }
     for (int p = 0; p < waves - kWideBatches; ++p) masks[p] = wide_deal_mask(sd, waves, chunk, nc, p);
+    return KABC_OK;
+}
+// the flag the half-generation kernels get for a prior (no device needed): the handle's own rule
+kabc_status_t kabc_ais_box_sym(const kabc_prior_t* prior, int32_t D, int32_t* sym) {
+    PriorSet ps;
+    if (!sym || !prepare_priors(prior, D, ps)) {
+        set_error("kabc_ais_box_sym: bad argument (D 1..%d components with valid parameters)", KABC_MAX_DIM);
+        return KABC_ERR_INVALID_ARG;
+    }
+    *sym = box_symmetric(ps.c, D);
     return KABC_OK;
 }
 void kabc_ais_wide_shipped(int32_t geom[3]) {
