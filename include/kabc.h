@@ -438,9 +438,15 @@ kabc_status_t kabc_math_probe(kabc_ctx_t* ctx, int32_t fn, int64_t n, const doub
  * kabc_ais_wide_deal needs no device: simd[waves] are SIMD ids 0..15, nc the tasks per chunk of a
  * consumer's SIMD (< 0: equal shares); masks[waves - 2] receives each producer's tasks, bit
  * 2 si + b = sub-step si of batch b.  kabc_ais_wide_shipped: geom[3] = {waves, chunk, nc} of the
- * kernel the library ships. */
+ * kernel the library ships.  kabc_ais_wide_deal_table: for the placement every measured workgroup
+ * got (waves w, w + 4, w + 8 on one SIMD, the consumers apart, neither of waves 2, 3 beside one) the
+ * kernel takes a table formed at compile time instead of running the function; *expected = 1 when
+ * simd[] is such a placement (the kernel's own test), masks[waves - 2] = that table -- for the
+ * shipped (waves, chunk, nc) = (12, 6, 2) and (8, 4, 1), anything else KABC_ERR_INVALID_ARG. */
 kabc_status_t kabc_ais_wide_deal(const int32_t* simd, int32_t waves, int32_t chunk, int32_t nc,
                                  uint32_t* masks);
+kabc_status_t kabc_ais_wide_deal_table(const int32_t* simd, int32_t waves, int32_t chunk, int32_t nc,
+                                       uint32_t* masks, int32_t* expected);
 void kabc_ais_wide_shipped(int32_t geom[3]);
 
 /* ---- symmetric-box flag of the AIS half-generation kernels (verification only) ----

@@ -163,6 +163,8 @@ PROTOTYPES = {
                                     C.POINTER(C.c_uint8), C.POINTER(C.c_int32)]),
     "kabc_ais_wide_deal": (C.c_int, [C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32,
                                      C.POINTER(C.c_uint32)]),
+    "kabc_ais_wide_deal_table": (C.c_int, [C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32,
+                                           C.POINTER(C.c_uint32), C.POINTER(C.c_int32)]),
     "kabc_ais_wide_shipped": (None, [C.POINTER(C.c_int32)]),
     "kabc_ais_box_sym": (C.c_int, [C.POINTER(Prior), C.c_int32, C.POINTER(C.c_int32)]),
     "kabc_prebuilt_has": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),

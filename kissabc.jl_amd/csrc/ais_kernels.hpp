@@ -131,9 +131,12 @@ constexpr int kChunk = 3;    // sub-steps per record buffer = number of producer
 //                       sub-steps x 2 batches = 2K tasks, dealt to the producers by where the
 //                       hardware PLACED them (wide_deal_mask below): the producers on a consumer's
 //                       SIMD take NC tasks per chunk between them, the producer-only waves split
-//                       the rest (NC < 0: equal shares whatever the placement).  The table is
-//                       derived once per launch from the SIMD ids the waves publish in LDS; a
-//                       placement it does not expect gets equal shares.  A record is a pure
+//                       the rest (NC < 0: equal shares whatever the placement).  The table of the
+//                       placement every measured workgroup got is a compile-time constant, taken
+//                       after one scalar test of the SIMD ids the waves publish in LDS
+//                       (WideDealTable); any other placement runs the function and gets equal
+//                       shares.  The launch's RAGGED chunk is its first (ch0 in the body): a short
+//                       chunk 0 is one task per producer.  A record is a pure
 //                       function of (seed, walker, t, slot): which wave writes it, and when, cannot
 //                       change a value.  W = 12 is three waves per SIMD: its kernel is bound to 168
 //                       registers per lane, so its consumer keeps ONE set of partner-row registers
@@ -167,7 +170,7 @@ struct WideGeom {
 #else
 #define KABC_DEAL_UNROLL
 #endif
-__host__ __device__ __forceinline__ uint32_t wide_deal_mask(uint64_t sd, int W, int K, int nc, int me) {
+__host__ __device__ __forceinline__ constexpr uint32_t wide_deal_mask(uint64_t sd, int W, int K, int nc, int me) {
     const int NPROD = W - kWideBatches, NT = 2 * K, beside = W / 4 - 1;
     const uint32_t sc0 = (uint32_t)sd & 15u, sc1 = (uint32_t)(sd >> 4) & 15u;
     uint32_t cot = 0;  // bit p: producer p shares its SIMD with a consumer
@@ -186,7 +189,7 @@ __host__ __device__ __forceinline__ uint32_t wide_deal_mask(uint64_t sd, int W, 
         int seen = 0, seen0 = 0, seen1 = 0;
     KABC_DEAL_UNROLL
         for (int p = 0; p < NPROD; ++p) {
-            int n;
+            int n = 0;  // (set on both branches; a constexpr function's variables are initialised)
             if ((cot >> p) & 1u) {
                 const bool on0 = ((uint32_t)(sd >> (4 * (kWideBatches + p))) & 15u) == sc0;
                 const int k = on0 ? seen0 : seen1;  // (this one is the k-th producer beside its consumer)
@@ -215,6 +218,40 @@ __host__ __device__ __forceinline__ uint32_t wide_deal_mask(uint64_t sd, int W, 
     return mine;
 }
 #undef KABC_DEAL_UNROLL
+
+// The placement the hardware has given every workgroup measured (profiles/ais_wide3.md, the four
+// rotations): waves w, w + 4, w + 8 on one SIMD, neither of waves 2, 3 beside a consumer, the two
+// consumers apart.  wide_deal_mask reads a placement only through WHICH producers sit beside WHICH
+// consumer, and here those are the producers p with (p + 2) % 4 = 0 and 1 whatever the rotation: one
+// table per geometry, formed at compile time by the function itself (WideDealTable).  The kernel
+// takes it after this one scalar test and runs the function for any other placement.
+__host__ __device__ __forceinline__ constexpr bool wide_placement_expected(uint64_t sd, int W) {
+    const uint64_t four = sd & 0xffffull;
+    uint64_t rep = 0;
+    for (int q = 0; q < W / 4; ++q) rep |= four << (16 * q);
+    const uint32_t s0 = (uint32_t)four & 15u, s1 = (uint32_t)(four >> 4) & 15u;
+    const uint32_t s2 = (uint32_t)(four >> 8) & 15u, s3 = (uint32_t)(four >> 12) & 15u;
+    return sd == rep && s0 != s1 && s2 != s0 && s2 != s1 && s3 != s0 && s3 != s1;
+}
+template <int W, int K, int NC>
+struct WideDealTable {
+    static constexpr int kProd = W - kWideBatches;
+    static_assert(2 * K <= 16 && kProd <= 12, "a producer's tasks in 16 bits, four producers to a word");
+    static constexpr uint64_t kPlaced = 0x321032103210ull & ((1ull << (4 * W)) - 1ull);  // (wave w on SIMD w % 4)
+    static_assert(wide_placement_expected(kPlaced, W), "the table's own placement is the expected one");
+    static constexpr uint64_t word(int q) {
+        uint64_t v = 0;
+        for (int p = 4 * q; p < 4 * q + 4 && p < kProd; ++p)
+            v |= (uint64_t)wide_deal_mask(kPlaced, W, K, NC, p) << (16 * (p - 4 * q));
+        return v;
+    }
+    // (three s_cselect, a shift and a mask on immediates: no table in memory)
+    __host__ __device__ static __forceinline__ uint32_t of(int me) {
+        constexpr uint64_t w0 = word(0), w1 = word(1), w2 = word(2);
+        const uint64_t w = me < 4 ? w0 : me < 8 ? w1 : w2;
+        return (uint32_t)(w >> (16 * (me & 3))) & 0xffffu;
+    }
+};
 
 template <int D>
 struct RecGeom {
@@ -807,7 +844,31 @@ __device__ __forceinline__ void ais_half_body(const AisArgs& A0) {
     // (the second batch of the last wide workgroup may be empty)
     const int n_active = rem >= kBatch ? kBatch : (G::kWide && rem < 0) ? 0 : (int)rem;
     const uint32_t w_base = A.id_base + (uint32_t)(A.row_first + r0);
-    const int nchunks = (A.nt + CH - 1) / CH;
+    // wide geometry: the SHORT chunk comes first.  Chunk 0 holds the launch's first ch0 sub-steps,
+    // every later chunk CH but possibly the last.  A short chunk 0 (nt = 100, CH = 6: four sub-steps
+    // = 8 tasks) is one task for each of eight producers, so the consumers leave the prologue after
+    // ONE fill and the first full chunk is filled while they compute; a full first chunk (12 tasks
+    // for 10 producers) kept both consumers at the barrier for a second fill in a row.
+    //   nt not a multiple of CH: ch0 = ((nt - 1) mod CH) + 1, the ragged chunk moved from the
+    //       launch's end to its start -- same chunk count, same barriers.
+    //   nt = m CH, m > 1: ch0 = CH - 2 and the last chunk holds 2 -- one chunk and one barrier more,
+    //       and still 0.5 us per launch less than a full first chunk (profiles/ais_wide5.md).
+    //   nt <= CH: the one chunk there is.
+    // A record is a pure function of (seed, walker, t, slot): which chunk carries a sub-step cannot
+    // change a value.
+    // kWideCut: the wide kernels that take all this and the prologue steps below -- every prior class
+    // but SIMPLE.  Its D = 7, 8 kernels on eight waves spill already, and each step moved one or another
+    // of them by a spilled VGPR or more (profiles/ais_wide5.md); the class keeps the prologue it had:
+    // full chunks first, the ragged one last, the table from wide_deal_mask.
+    constexpr bool kWideCut = G::kWide && PC != kPriorSimple;
+    const bool split_full = kWideCut && CH > 2 && A.nt > CH && A.nt % CH == 0;
+    const int nchunks = (A.nt + CH - 1) / CH + (split_full ? 1 : 0);
+    [[maybe_unused]] const int ch0 = !kWideCut ? CH : split_full ? CH - 2 : (A.nt - 1) % CH + 1;
+    // first sub-step of chunk c
+    auto chunk_first = [&](int c) __attribute__((always_inline)) {
+        if constexpr (kWideCut) return c == 0 ? 0 : ch0 + (c - 1) * CH;
+        else return c * CH;
+    };
     const bool consumer = G::kWide ? wave < NBAT : wave == 0;
     // KABC_ABLATE=128 (with debug records on): cycles each wave spends at the barriers
     const bool tprobe = (KABL & 128) && A.dbg;
@@ -871,9 +932,21 @@ __device__ __forceinline__ void ais_half_body(const AisArgs& A0) {
         sbox_hi[threadIdx.x] = A.prior[threadIdx.x].p[1];
     }
     uint32_t dmask = 0, gmask = 0;
-    for (int k = 0; k < D; ++k) {
-        dmask |= (A.prior[k].discrete ? 1u : 0u) << k;
-        gmask |= (gaussbox_is_gauss(A.prior[k].kind) ? 1u : 0u) << k;
+    if constexpr (kWideCut) {
+        // lane k reads component k, a ballot makes the masks: ONE load and one wait.  As D scalar
+        // loads (the loop below) the wide kernel, short of scalar registers, ran them one at a time
+        // -- s_load_dword, s_waitcnt, v_writelane into a spill lane, eight times over at D = 8, each a
+        // cache line of its own -- in front of the first barrier.
+        static_assert(D <= kWave, "one lane per component");
+        const int kl = lane < D ? lane : 0;
+        const int32_t disc = A.prior[kl].discrete, kind = A.prior[kl].kind;
+        dmask = (uint32_t)__ballot(lane < D && disc != 0);
+        if constexpr (kGaussBox) gmask = (uint32_t)__ballot(lane < D && gaussbox_is_gauss(kind));
+    } else {
+        for (int k = 0; k < D; ++k) {
+            dmask |= (A.prior[k].discrete ? 1u : 0u) << k;
+            gmask |= (gaussbox_is_gauss(A.prior[k].kind) ? 1u : 0u) << k;
+        }
     }
     if constexpr (kGaussBox) {
         if (threadIdx.x < D) gaussbox_stage(sgb[threadIdx.x], A.prior[threadIdx.x]);
@@ -889,12 +962,26 @@ __device__ __forceinline__ void ais_half_body(const AisArgs& A0) {
 
     // while the table's loads are in flight the producers expand the two Philox blocks
     // every lane of their first sub-step needs (they depend on nothing else)
-    // (not in the wide geometry: its launches are long, and a producer's first task is the table's)
+    // (the wide geometry: the same for the task of chunk 0 that the table of the expected placement
+    // gives this wave first -- WideDealTable needs no SIMD word, so the task is known before the
+    // barrier that publishes them; the blocks are used if the placement then is the expected one)
     [[maybe_unused]] kabc_u128_t pro01[2] = {};
+    [[maybe_unused]] int pro_task = -1;  // wide: the task pro01 belongs to (scalar)
     if constexpr (!G::kWide) {
         if (wave > 0 && wave - 1 < A.nt && lane < n_active) {
             const uint32_t w = w_base + (uint32_t)lane;
             const uint64_t t = A.t0 + (uint64_t)(wave - 1);
+            pro01[0] = kabc_stream_block(A.seed, w, t, 0u, KABC_DOM_AIS_MOVE);
+            pro01[1] = kabc_stream_block(A.seed, w, t, 1u, KABC_DOM_AIS_MOVE);
+        }
+    } else if (kWideCut && wave >= NBAT) {
+        const int task = __builtin_ctz(WideDealTable<NBAT + NPROD, CH, G::kNC>::of(wave - NBAT) | 0x10000u);
+        const int si = task >> 1, b = task & 1;
+        const int64_t left = A.rows_owned - (r0_wg + b * kBatch);
+        if (si < ch0 && left > 0) {  // (scalar)
+            pro_task = task;  // (every lane draws, as in produce_substep)
+            const uint32_t w = A.id_base + (uint32_t)(A.row_first + r0_wg + b * kBatch) + (uint32_t)lane;
+            const uint64_t t = A.t0 + (uint64_t)si;
             pro01[0] = kabc_stream_block(A.seed, w, t, 0u, KABC_DOM_AIS_MOVE);
             pro01[1] = kabc_stream_block(A.seed, w, t, 1u, KABC_DOM_AIS_MOVE);
         }
@@ -947,14 +1034,22 @@ __device__ __forceinline__ void ais_half_body(const AisArgs& A0) {
             sprior[threadIdx.x].p[2] = (nb_on && slot < kNbTabs) ? (double)slot : -1.0;
         }
     }
-    if constexpr (kBoxRegs) {  // per-lane copies from LDS (vector registers: scalar ones ran
-                               // out and spilled when these were loaded as uniform values)
+    // per-lane copies from LDS (vector registers: scalar ones ran out and spilled when these were
+    // loaded as uniform values).  The wide geometry's CONSUMERS (kWideCut) load them in their own branch: only
+    // they read the box, and a producer that carries its first task's two Philox blocks (pro01)
+    // across the barrier above has no room for 32 registers it never uses -- loaded here, the
+    // headline kernel spilled two VGPRs.
+    constexpr bool kBoxLate = kWideCut;
+    auto load_box = [&]() __attribute__((always_inline)) {
+        if constexpr (kBoxRegs) {
 #pragma unroll
-        for (int k = 0; k < D; ++k) {
-            blo[k] = sbox_lo[k];
-            bhi[k] = sbox_hi[k];
+            for (int k = 0; k < D; ++k) {
+                blo[k] = sbox_lo[k];
+                bhi[k] = sbox_hi[k];
+            }
         }
-    }
+    };
+    if constexpr (!kBoxLate) load_box();
 
     // The stream seed as a VECTOR-register value for the producers: the ten Philox round keys
     // derived from it are loop-invariant either way, but as scalars they took twenty of the scalar
@@ -976,8 +1071,10 @@ __device__ __forceinline__ void ais_half_body(const AisArgs& A0) {
     // (wave-uniform and, outside the probes build, a compile-time constant)
     const bool pro_rows = !G::kWide && !(KABL & 5);
     // wide geometry: this producer's tasks of a chunk, bit 2 si + b = sub-step si of batch b, so that
-    // each batch's earliest sub-steps come first.  Every wave derives the same table from the same
-    // LDS words -- scalar code, once per launch; shares and SIMD ids packed four bits apiece.
+    // each batch's earliest sub-steps come first.  Every wave reads the same LDS words (SIMD ids packed
+    // four bits apiece) and takes the same table: the compile-time one in the expected placement, else
+    // wide_deal_mask's -- a scalar program of a dozen dependent loops that cost every launch about 1 us
+    // when all waves ran it (profiles/ais_wide5.md).
     [[maybe_unused]] uint32_t my_tasks = 0;
     if constexpr (G::kWide) {
         static_assert(4 * (NBAT + NPROD) <= 64, "the SIMD ids of a workgroup's waves, four bits apiece");
@@ -985,7 +1082,13 @@ __device__ __forceinline__ void ais_half_body(const AisArgs& A0) {
 #pragma unroll
         for (int w = 0; w < NBAT + NPROD; ++w)
             sd |= (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)ssimd[w]) << (4 * w);
-        my_tasks = wide_deal_mask(sd, NBAT + NPROD, CH, G::kNC, wave - NBAT);
+        // the expected placement (every workgroup measured): the compile-time table
+        if (kWideCut && wide_placement_expected(sd, NBAT + NPROD)) {
+            my_tasks = WideDealTable<NBAT + NPROD, CH, G::kNC>::of(wave - NBAT);
+        } else {
+            pro_task = -1;  // (the blocks expanded ahead were another wave's task's)
+            my_tasks = wide_deal_mask(sd, NBAT + NPROD, CH, G::kNC, wave - NBAT);
+        }
     }
     // PRODUCER: sub-step si (transition s of the launch) of batch b into record buffer `buf`, by
     // producer wave pw
@@ -998,21 +1101,23 @@ __device__ __forceinline__ void ais_half_body(const AisArgs& A0) {
         if constexpr (kPre > 0)
             produce_cost_normals<kPre>(seed_v, A.t0 + (uint64_t)s, wb, lane, spre[buf][b][si], slogtab);
     };
-    // wide geometry: this wave's tasks of the chunk whose first sub-step is `sbase`
-    [[maybe_unused]] auto fill_tasks = [&](int buf, int sbase) __attribute__((always_inline)) {
+    // wide geometry: this wave's tasks of the chunk of `len` sub-steps whose first one is `sbase`
+    // (pre_task: the task whose first two blocks are in pro01, or -1)
+    [[maybe_unused]] auto fill_tasks = [&](int buf, int sbase, int len, int pre_task) __attribute__((always_inline)) {
 #pragma unroll 1
         for (uint32_t m = my_tasks; m != 0u; m &= m - 1u) {
             const int task = __builtin_ctz(m);
             const int si = task >> 1, b = task & 1;
             const int64_t rb = r0_wg + b * kBatch, left = A.rows_owned - rb;
-            if (sbase + si < A.nt && left > 0)  // (scalar; an empty second batch has no tasks)
+            // (scalar; an empty second batch has no tasks)
+            if ((kWideCut ? si < len : sbase + si < A.nt) && left > 0)
                 fill(buf, b, si, sbase + si, wave - NBAT, rb, left >= kBatch ? kBatch : (int)left,
-                     A.id_base + (uint32_t)(A.row_first + rb), nullptr, NoMid());
+                     A.id_base + (uint32_t)(A.row_first + rb), task == pre_task ? pro01 : nullptr, NoMid());
         }
     };
     // prologue: producers fill chunk 0
     if constexpr (G::kWide) {
-        if (!consumer && !(KABL & 4)) fill_tasks(0, 0);
+        if (!consumer && !(KABL & 4)) fill_tasks(0, 0, ch0, pro_task);
     } else if (wave > 0) {
         const int si = wave - 1;
         if (si < A.nt && !(KABL & 4)) {
@@ -1039,10 +1144,11 @@ __device__ __forceinline__ void ais_half_body(const AisArgs& A0) {
     if (!consumer) {
 #pragma unroll 1
         for (int c = 0; c < nchunks; ++c) {
-            const int s0 = c * CH;
+            [[maybe_unused]] const int s0 = c * CH;
             if constexpr (G::kWide) {
-                // PRODUCER: this wave's tasks of the next chunk
-                if (!(KABL & 2)) fill_tasks((c + 1) & 1, s0 + CH);
+                // PRODUCER: this wave's tasks of the next chunk (full, or the 2 sub-steps that end a whole number of chunks)
+                const int sn = chunk_first(c + 1);
+                if (!(KABL & 2)) fill_tasks((c + 1) & 1, sn, A.nt - sn < CH ? A.nt - sn : CH, -1);
             } else {
                 // PRODUCER: sub-step (s0 + kChunk + wave - 1) of the next chunk
                 const int si = wave - 1;
@@ -1052,6 +1158,7 @@ __device__ __forceinline__ void ais_half_body(const AisArgs& A0) {
             KABC_TIMED_BARRIER();
         }
     } else {
+        if constexpr (kBoxLate) load_box();
 #ifndef KABC_NO_REG_PARAMS
         // the cost's leading parameters in registers for the whole launch (cost_reg_params)
         constexpr int kRP = cost_reg_params(COST, D);
@@ -1070,11 +1177,12 @@ __device__ __forceinline__ void ais_half_body(const AisArgs& A0) {
         const bool dbg_on = __builtin_amdgcn_readfirstlane(A.dbg != nullptr ? 1 : 0) != 0;
 #pragma unroll 1
         for (int c = 0; c < nchunks; ++c) {
-            const int s0 = c * CH;
+            const int s0 = chunk_first(c);
             if (active && !(KABL & 1)) {
                 // CONSUMER
                 const RecBuf<D, CH>& R = rec[(KABL & 2) ? 0 : (c & 1)][bmine];
-                const int ns = (A.nt - s0 < CH) ? (A.nt - s0) : CH;
+                // (wide: chunk 0 is the short one, ch0 sub-steps)
+                const int ns = (kWideCut && c == 0) ? ch0 : (A.nt - s0 < CH) ? (A.nt - s0) : CH;
                 // partner rows: (pa, pb) serve this sub-step, (na, nb) are the next one's, in
                 // flight while this one computes.  Both rows are fetched for every lane
                 // whatever its move (bb defaults to a): no divergence around the loads.

@@ -1186,15 +1186,18 @@ static void ais_poll_spec(kabc_ais_t* h) {
 // Which geometry a launch of `nt` sub-steps over `rows` owned rows takes.  The wide kernel exists for
 // the prebuilt costs whose records fit the LDS (ais_wide_ok_c) and needs two full batches; single-chain,
 // unsharded handles only (ais_can_wide).  By default it is taken where it was measured to win
-// (profiles/ais_wide3.md; ais_wide.md for the eight-wave kernel): from kAisWideFrom sub-steps on (its
-// prologue is longer: 26.0 against 24.9 us at 16 sub-steps, 32.2 against 32.8 at 24), and only where the
+// (profiles/ais_wide5.md; ais_wide3.md and ais_wide.md before its prologue was cut): from kAisWideFrom
+// sub-steps on (C3: 20.3 against 20.5 us at 12 sub-steps, 23.5 against 24.8 at 16, 30.1 against 32.5 at
+// 24; nothing smaller than 12 was compared; the SIMPLE prior class, whose wide kernels keep the longer
+// prologue they had (ais_kernels.hpp kWideCut), keeps the 24 measured for that prologue: 26.0 against
+// 24.9 us at 16 sub-steps, 32.2 against 32.8 at 24, profiles/ais_wide3.md), and only where the
 // existing geometry would put two workgroups on every compute unit, i.e. at least two batches per
 // unit -- below that a batch of the existing geometry has its unit to itself, the wide one packs two
 // on half as many units, and nobody has measured that.  KABC_AIS_WIDE=0 keeps the existing geometry,
 // =1 takes the wide one wherever it can run, =2 does the same and makes a launch that cannot take
 // it an error, raised before anything is enqueued (read per launch: the tests flip it).  Same bits
 // either way.
-constexpr int32_t kAisWideFrom = 24;
+constexpr int32_t kAisWideFrom = 12, kAisWideFromSimple = 24;
 static bool ais_can_wide(const kabc_ais_t* h, int64_t rows) {
     return h->launch_wide && h->nchains == 1 && h->world == 1 && !h->comm && rows >= kWideBatches * kBatch;
 }
@@ -1212,7 +1215,8 @@ static bool ais_use_wide(const kabc_ais_t* h, int64_t rows, int32_t nt) {
     if (!ais_can_wide(h, rows)) return false;
     const char* e = std::getenv("KABC_AIS_WIDE");
     if (e && e[0]) return e[0] != '0';
-    return nt >= kAisWideFrom && rows >= ais_wide_min_rows();
+    const bool simple = h->half_pcx >= 0 && h->half_pcx % kPriorClasses == kPriorSimple;
+    return nt >= (simple ? kAisWideFromSimple : kAisWideFrom) && rows >= ais_wide_min_rows();
 }
 
 // one launch: `ntransitions` transitions for the owned rows of segment `sg` of `half`
@@ -1338,6 +1342,30 @@ kabc_status_t kabc_ais_wide_deal(const int32_t* simd, int32_t waves, int32_t chu
         sd |= (uint64_t)simd[w] << (4 * w);
     }
     for (int p = 0; p < waves - kWideBatches; ++p) masks[p] = wide_deal_mask(sd, waves, chunk, nc, p);
+    return KABC_OK;
+}
+// the kernel's scalar test of a placement and the compile-time table it then takes (WideDealTable):
+// the two geometries the library ships
+kabc_status_t kabc_ais_wide_deal_table(const int32_t* simd, int32_t waves, int32_t chunk, int32_t nc,
+                                       uint32_t* masks, int32_t* expected) {
+    const bool w12 = waves == kWideW && chunk == kWideK && nc == kWideNC;
+    const bool w8 = waves == kWideW8 && chunk == kWideK8 && nc == kWideNC8;
+    if (!simd || !masks || !expected || !(w12 || w8)) {
+        set_error("kabc_ais_wide_deal_table: bad argument ((waves, chunk, nc) = (%d, %d, %d) or (%d, %d, %d))",
+                  kWideW, kWideK, kWideNC, kWideW8, kWideK8, kWideNC8);
+        return KABC_ERR_INVALID_ARG;
+    }
+    uint64_t sd = 0;
+    for (int w = 0; w < waves; ++w) {
+        if (simd[w] < 0 || simd[w] > 15) {
+            set_error("kabc_ais_wide_deal_table: SIMD id %d of wave %d is not in 0..15", (int)simd[w], w);
+            return KABC_ERR_INVALID_ARG;
+        }
+        sd |= (uint64_t)simd[w] << (4 * w);
+    }
+    *expected = wide_placement_expected(sd, waves) ? 1 : 0;
+    for (int p = 0; p < waves - kWideBatches; ++p)
+        masks[p] = w12 ? WideDealTable<kWideW, kWideK, kWideNC>::of(p) : WideDealTable<kWideW8, kWideK8, kWideNC8>::of(p);
     return KABC_OK;
 }
 // the flag the half-generation kernels get for a prior (no device needed): the handle's own rule
