@@ -136,7 +136,8 @@ int32_t kabc_version(void);
  * 0 kabc_prior_t, 1 kabc_cost_t, 2 kabc_model_t, 3 kabc_stats_t, 4 kabc_smc_opts_t,
  * 5 kabc_smc_iter_t, 6 kabc_smc_result_t, 7 kabc_abcde_opts_t, 8 kabc_abcde_result_t,
  * 9 kabc_pfilter_opts_t, 10 kabc_pfilter_result_t; -1 beyond, except the second block
- * 32 kabc_reject_opts_t, 33 kabc_reject_result_t.  A binding that mirrors the
+ * 32 kabc_reject_opts_t, 33 kabc_reject_result_t, 35 kabc_pmc_opts_t, 36 kabc_pmc_gen_t,
+ * 37 kabc_pmc_result_t (34 stays -1).  A binding that mirrors the
  * structs by hand (ctypes, Julia `struct`) checks itself against this at load time. */
 int32_t kabc_abi_sizeof(int32_t which);
 /* offsetof() of the field-th member (declaration order, from 0) of the which-th struct (the
@@ -421,6 +422,138 @@ kabc_status_t kabc_abc_reject_batch(kabc_ctx_t* ctx, const kabc_prior_t* prior, 
                                     const double* eps, const kabc_reject_opts_t* opts,
                                     kabc_reject_result_t* results, kabc_status_t* status);
 void kabc_reject_batch_stats(int64_t out[4]);
+
+/* ---- ABC population Monte Carlo on the device -----------------------------------------
+ * Beaumont, Cornuet, Marin, Robert (2009): a sequence of rejection samplers, each proposing from a Gaussian
+ * mixture around the previous population; the importance weights make generation g an exact weighted sample of
+ * prior x 1[cost <= eps_g].  The result is a pure function of (prior, cost, opts): everything below is fp64 in
+ * the functions of kabc_math.h, mul then add (no contraction), sums in the stated order starting from 0.0.
+ * tests/abc_pmc_oracle.py restates it in numpy; the kernels agree with it bit for bit.
+ *
+ * A population is N = nparticles rows theta[N][D] in index order with costs C, log-priors lp, normalised
+ * weights w and, per particle, `index`: its row in its generation's proposal stream.
+ *
+ * GENERATION 0 is kabc_abc_reject in threshold mode, bit for bit: (prior, cost, eps = eps_0, n_accept = N, seed,
+ * first_row = 0, max_draws); w_i = 1 / N, ess = 1 / sum_i w_i^2 (i ascending).  Exhausted: the run ends with
+ * KABC_OK, generations_run = 0, stop = KABC_PMC_STOP_EXHAUSTED.
+ *
+ * GENERATION g >= 1, from generation g - 1 (theta, w):
+ *  1. moments (i ascending): mu_k = sum_i w_i theta_ik; c_kl = sum_i (w_i (theta_ik - mu_k)) (theta_il - mu_l);
+ *     Sigma = scale c (every entry: scale * c_kl); kernel = KABC_PMC_KERNEL_DIAG sets Sigma_kl = 0.0 for k != l.
+ *  2. factor: kabc_mvn_prepare(D, mu, Sigma, blk) of include/kabc_mvnormal.h gives L and W = L^-1.  Non-zero:
+ *     the run ends with generation g - 1 as its result, stop = KABC_PMC_STOP_DEGENERATE.
+ *  3. cdf_j = cdf_{j-1} + w_j, j ascending, cdf_{-1} = 0.0.
+ *  4. proposal row r = 0, 1, 2, ... (r < 2^32: the walker word).  Stream (seed, walker = r, t = g, slot,
+ *     KABC_DOM_PMC_MOVE).  Slot 0: u = kabc_u01(lo64); the ancestor a = the number of j with
+ *     cdf_j <= u * cdf_{N-1}, at most N - 1 (a bisection of ceil(log2 N) steps).  Slot 1 + m:
+ *     (z_2m, z_2m+1) = kabc_normal_pair(lo64, hi64), m < ceil(D / 2).
+ *     x_k = theta_ak + acc_k, acc_k = sum_{m<=k} L[k][m] z_m (m ascending from 0.0: kabc_sample_prior's MvNormal
+ *     order).  Then push_p and the log-prior of the pushed row as in a row of kabc_abc_reject.  The cost is
+ *     replicate g of row r of kabc_cost_eval(cost, x, nrep = g + 1, seed, first_row = r): the stream (seed,
+ *     walker = r, t = g, KABC_DOM_EVAL_COST).  The row is accepted iff lp is finite and C <= eps_g (a NaN cost
+ *     never is).  Whether a row with a non-finite lp is simulated is not observable; the fused kernel skips it.
+ *  5. generation g is the first N accepted rows in index order, draws_g = the index of the N-th + 1.  Fewer than
+ *     N among max_draws rows: the run ends with generation g - 1 as its result, stop = KABC_PMC_STOP_EXHAUSTED.
+ *  6. weights: y = W (theta - mu) for the new population and for its ancestors (generation g - 1), y_k =
+ *     sum_{j<=k} W[k][j] (theta_j - mu_j) as kabc_mvn_logpdf_comp forms its z.  d2_ij = sum_k (y_ik - y_jk)^2
+ *     (k ascending; t = y_ik - y_jk, d2 = d2 + t * t).  P_ic = sum over the ancestors j of chunk c (KABC_PMC_CHUNK
+ *     = 256 consecutive j, ascending) of w_j * kabc_exp(-0.5 * d2_ij); S_i = sum_c P_ic (c ascending).  The
+ *     Gaussian's normalising constant is the same for every i and left out.  v_i = kabc_exp(lp_i - max lp) / S_i;
+ *     w_i = v_i / sum_i v_i; ess = 1 / sum_i w_i^2 (sums over i ascending).  An S_i or a sum of v that is 0 or
+ *     not finite: generation g - 1 is the result, stop = KABC_PMC_STOP_DEGENERATE.
+ *
+ * SCHEDULE.  Explicit (opts.eps != NULL): eps_g = eps[g], g < generations.  Adaptive (opts.eps == NULL): eps_0 =
+ * opts.eps0, eps_g = max(eps_target, Q_q(C_{g-1})), at most `generations` generations.  Q_q is Statistics.quantile
+ * ("type 7") on the sorted costs v[0..N): h = N q + (1 - q), j = trunc(h) held to [1, N - 1], gamma = h - j held
+ * to [0, 1], a = v[j-1], b = v[j]; a + gamma (b - a) when both are finite, else (1 - gamma) a + gamma b.
+ * After generation g is complete, in this order: adaptive and eps_g <= eps_target: stop = TARGET; g + 1 ==
+ * generations: stop = DONE; N / draws_g < min_rate: stop = MIN_RATE; adaptive and eps_{g+1} is NaN, or g + 1 >= 2
+ * and eps_{g+1} >= eps_g: stop = STALLED (before generation g + 1 runs).  In all four the result is generation g.
+ *
+ * result: theta, w, cost, logprior, index of the last complete generation; log[g] for every complete generation
+ * (generations_run of them); eps of the result generation; mean = mu and cov = c (step 1, unscaled, full) of the
+ * result generation.  generations_run == 0: the arrays are unspecified.
+ *
+ * course 0 (fused): one kernel per launch draws, projects, simulates, tests and compacts the proposal rows
+ * (csrc/abc_pmc_kernel.hpp, the structure of kabc_abc_reject's); course 1 (phases): a proposal kernel, the prior
+ * kernels, the evaluation kernel of kabc_cost_eval and a compaction kernel -- user prior families, joint priors, an
+ * MvNormal prior, user costs in the hipRTC form, and KABC_PMC_COURSE=phases.  The run rules (looks, overflow
+ * repeats under KABC_REJECT_CAPACITY, KABC_EVAL_ROWS) are kabc_abc_reject's.  The sums S_i come from
+ * csrc/pmc_weight_kernel.hpp: one launch over all chunks, or (small N; KABC_PMC_WEIGHT_SPLIT=0|1 forces either)
+ * one workgroup per chunk and a second step adding the partials in chunk order -- same bits.
+ *
+ * KABC_ERR_INVALID_ARG, checked before ctx is used: NULL arguments (result arrays included), D outside
+ * 1..KABC_MAX_DIM, nparticles < D + 2 or > 2^20, q outside (0, 1) (adaptive), scale <= 0 or NaN, a NaN eps / eps0 /
+ * eps_target / min_rate, max_draws < nparticles or > 2^32, generations < 1 or >= 2^24, kernel not 0 or 1.
+ * KABC_ERR_UNSUPPORTED: a prior with a discrete component (a Gaussian density is not a pmf); a cost plugin built
+ * by hipcc (as kabc_cost_eval).  kabc_ctx_cancel: pending at entry, nothing is launched; during the run:
+ * KABC_ERR_CANCELLED, stop = CANCELLED, and the result is the last complete generation (looked at between two
+ * looks of the proposal launches and between two slices of the weight kernel, each sized to about 100 ms). */
+#define KABC_PMC_CHUNK 256
+#define KABC_PMC_MAX_PARTICLES (1 << 20)
+enum { KABC_PMC_KERNEL_FULL = 0, KABC_PMC_KERNEL_DIAG = 1 };
+enum {
+    KABC_PMC_STOP_DONE = 0,
+    KABC_PMC_STOP_EXHAUSTED = 1,
+    KABC_PMC_STOP_DEGENERATE = 2,
+    KABC_PMC_STOP_TARGET = 3,
+    KABC_PMC_STOP_STALLED = 4,
+    KABC_PMC_STOP_MIN_RATE = 5,
+    KABC_PMC_STOP_CANCELLED = 6
+};
+
+typedef struct kabc_pmc_opts {
+    int64_t nparticles;   /* N                                                                  */
+    int64_t generations;  /* explicit: the length of eps; adaptive: generations run at most     */
+    const double* eps;    /* [generations]: the explicit schedule; NULL: adaptive               */
+    double eps0;          /* adaptive: eps of generation 0 (+Inf by default)                    */
+    double eps_target;    /* adaptive (-Inf by default)                                         */
+    double q;             /* adaptive: the quantile (0.5 by default)                            */
+    double scale;         /* Sigma = scale * weighted covariance (2.0 by default)               */
+    double min_rate;      /* 0.0 by default                                                     */
+    int64_t max_draws;    /* proposal rows of ONE generation at most, nparticles..2^32          */
+    int32_t kernel;       /* KABC_PMC_KERNEL_FULL / _DIAG                                       */
+    int32_t reserved;
+    uint64_t seed;
+} kabc_pmc_opts_t;
+
+typedef struct kabc_pmc_gen {
+    double eps;
+    int64_t draws;     /* draws_g                                                               */
+    double ess;
+    int64_t launches;  /* proposal launches of the generation, repeats after an overflow included */
+} kabc_pmc_gen_t;
+
+typedef struct kabc_pmc_result {
+    double* theta;     /* [nparticles][D], caller-allocated, like the next four                 */
+    double* w;         /* [nparticles]                                                          */
+    double* cost;      /* [nparticles]                                                          */
+    double* logprior;  /* [nparticles]                                                          */
+    int64_t* index;    /* [nparticles]                                                          */
+    kabc_pmc_gen_t* log; /* [opts.generations]                                                  */
+    double* mean;      /* [D]                                                                   */
+    double* cov;       /* [D][D]                                                                */
+    double eps;
+    int64_t generations_run;
+    int32_t stop;      /* KABC_PMC_STOP_*                                                       */
+    int32_t course;    /* 0 fused, 1 phases                                                     */
+    double kernel_ms;  /* proposal launches and weight kernel with KABC_EVAL_TIMING=1, else -1  */
+} kabc_pmc_result_t;
+
+/* sizeof / offsetof: kabc_abi_sizeof(35) kabc_pmc_opts_t, (36) kabc_pmc_gen_t, (37) kabc_pmc_result_t (34 stays
+ * -1: it closes the pair of kabc_abc_reject) */
+void kabc_pmc_default_opts(kabc_pmc_opts_t* opts);
+kabc_status_t kabc_abc_pmc(kabc_ctx_t* ctx, const kabc_prior_t* prior, int32_t D, const kabc_cost_t* cost,
+                           const kabc_pmc_opts_t* opts, kabc_pmc_result_t* result);
+/* Verification: step 6's S_i alone, host in and host out.  y_new [n_new][D], y_anc [n_anc][D], w_anc [n_anc],
+ * S_out [n_new]; 1 <= D <= KABC_MAX_DIM, 1 <= n_new, n_anc <= 2^20.  An S that is 0 comes back as 0. */
+kabc_status_t kabc_pmc_kernel_sums(kabc_ctx_t* ctx, int32_t D, int64_t n_new, const double* y_new, int64_t n_anc,
+                                   const double* y_anc, const double* w_anc, double* S_out);
+/* How the calling thread's last kabc_abc_pmc (generations g >= 1) or kabc_pmc_kernel_sums ran: out[0] device
+ * milliseconds of the proposal launches, [1] of the weight kernel (both 0 unless KABC_EVAL_TIMING=1 was in the
+ * environment), [2] host milliseconds spent in the rules between the kernels (moments, factor, CDF, whitening,
+ * weights, schedule), [3] launches of the weight kernel (slices). */
+void kabc_pmc_stats(double out[4]);
 
 /* ---- arithmetic-contract probe (verification only) ---------------------------
  * Evaluates one function of include/kabc_math.h on the device for n host inputs, so

@@ -67,6 +67,10 @@ typedef struct kabc_u128 {
  * from (seed, walker = first_row + i, attempt 0, KABC_DOM_EVAL_DRAW), as kabc_factored_rand draws it. */
 #define KABC_DOM_EVAL_COST 17u       /* cost(θ): src/types.jl:42,55; src/smc.jl:94 */
 #define KABC_DOM_EVAL_DRAW 18u       /* rand(prior) of the pilot simulation */
+/* kabc_abc_pmc (include/kabc.h): proposal row r of generation g draws its ancestor (slot 0) and its normals
+ * (slots 1 ...) from (seed, walker = r, t = g, KABC_DOM_PMC_MOVE); its cost is replicate g of row r under
+ * KABC_DOM_EVAL_COST */
+#define KABC_DOM_PMC_MOVE 19u
 
 /* a ^ b ^ c: one v_bitop3_b32 on gfx950 instead of two v_xor_b32 */
 #if defined(__HIP_DEVICE_COMPILE__)

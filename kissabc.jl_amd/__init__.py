@@ -8,7 +8,7 @@ from . import costs
 from ._cdefs import KABC_MAX_DIM
 from ._lib import Cancelled, Context, KabcError, LIB_PATH, default_context
 from .api import (ABCDE, ABCDE_batch, AIS, AisEnsemble, ApproxKernelizedPosterior, ApproxPosterior, CommonLogDensity,
-                  MCMCThreads, abc_reject, abc_reject_batch, compile_model, pfilter, pfilter_batch, prior_predictive, set_specialize,
+                  MCMCThreads, PmcResult, abc_pmc, abc_reject, abc_reject_batch, compile_model, pfilter, pfilter_batch, prior_predictive, set_specialize,
                   AbcdeState, ChainSummaries, Particles, PfilterState, PosteriorSummary, SmcState, sample, sample_batch, smc, smc_batch)
 from . import comm
 from .comm import Comm, EnsembleGroup
@@ -21,7 +21,7 @@ from .distributions import (Ar1Normal, Beta, Dirichlet, DiscreteUniform, Exponen
 
 __all__ = [
     "ABCDE", "ABCDE_batch", "AIS", "AisEnsemble", "ApproxKernelizedPosterior", "ApproxPosterior", "CommonLogDensity",
-    "MCMCThreads", "abc_reject", "abc_reject_batch", "pfilter", "pfilter_batch", "prior_predictive",
+    "MCMCThreads", "PmcResult", "abc_pmc", "abc_reject", "abc_reject_batch", "pfilter", "pfilter_batch", "prior_predictive",
     "AbcdeState", "ChainSummaries", "Particles", "PosteriorSummary", "PfilterState", "SmcState", "sample", "sample_batch", "smc", "smc_batch", "DeviceCost", "Derived", "costs", "Factored", "Uniform", "Normal",
     "Truncated", "truncated", "TruncatedNormal", "Beta", "DiscreteUniform", "NegativeBinomial",
     "Exponential", "Gamma", "LogNormal", "Product", "MvNormal", "MultivariateNormal", "Context", "KabcError", "Cancelled", "default_context", "LIB_PATH",

@@ -39,6 +39,15 @@ COST_GAUSS_DIST, COST_ROSENBROCK, COST_HIER_GAUSS_SIM, COST_NORMAL_MEANSTD_SIM, 
 DOM_AIS_INIT, DOM_AIS_INIT_COST, DOM_AIS_MOVE, DOM_AIS_COST, DOM_SMC_INIT, DOM_SMC_INIT_COST, \
     DOM_SMC_MOVE, DOM_SMC_COST = range(1, 9)
 DOM_EVAL_COST, DOM_EVAL_DRAW = 17, 18   # cost.evaluate / prior_predictive: replicate = t, row = walker
+DOM_PMC_MOVE = 19                       # abc_pmc: generation = t, proposal row = walker
+
+# kabc_abc_pmc
+KABC_PMC_CHUNK = 256
+KABC_PMC_MAX_PARTICLES = 1 << 20
+PMC_KERNEL_FULL, PMC_KERNEL_DIAG = 0, 1
+PMC_STOP_DONE, PMC_STOP_EXHAUSTED, PMC_STOP_DEGENERATE, PMC_STOP_TARGET, PMC_STOP_STALLED, PMC_STOP_MIN_RATE, \
+    PMC_STOP_CANCELLED = range(7)
+PMC_STOP_NAMES = ("done", "exhausted", "degenerate", "target", "stalled", "min_rate", "cancelled")
 
 c_double_p = C.POINTER(C.c_double)
 
@@ -143,6 +152,27 @@ class RejectResult(C.Structure):
 # kabc_abi_sizeof / kabc_abi_offsetof number of the two structs above (the second block of the numbering)
 ABI_REJECT_OPTS, ABI_REJECT_RESULT = 32, 33
 
+
+class PmcOpts(C.Structure):
+    _fields_ = [("nparticles", C.c_int64), ("generations", C.c_int64), ("eps", c_double_p), ("eps0", C.c_double),
+                ("eps_target", C.c_double), ("q", C.c_double), ("scale", C.c_double), ("min_rate", C.c_double),
+                ("max_draws", C.c_int64), ("kernel", C.c_int32), ("reserved", C.c_int32), ("seed", C.c_uint64)]
+
+
+class PmcGen(C.Structure):
+    _fields_ = [("eps", C.c_double), ("draws", C.c_int64), ("ess", C.c_double), ("launches", C.c_int64)]
+
+
+class PmcResult(C.Structure):
+    _fields_ = [("theta", c_double_p), ("w", c_double_p), ("cost", c_double_p), ("logprior", c_double_p),
+                ("index", C.POINTER(C.c_int64)), ("log", C.POINTER(PmcGen)), ("mean", c_double_p),
+                ("cov", c_double_p), ("eps", C.c_double), ("generations_run", C.c_int64), ("stop", C.c_int32),
+                ("course", C.c_int32), ("kernel_ms", C.c_double)]
+
+
+# ... and of the three structs of kabc_abc_pmc (34 stays -1)
+ABI_PMC_OPTS, ABI_PMC_GEN, ABI_PMC_RESULT = 35, 36, 37
+
 # every symbol include/kabc.h declares: name -> (restype, argtypes)
 VP = C.c_void_p
 PROTOTYPES = {
@@ -190,6 +220,12 @@ PROTOTYPES = {
                                         C.POINTER(C.c_uint64), c_double_p, C.POINTER(RejectOpts),
                                         C.POINTER(RejectResult), C.POINTER(C.c_int)]),
     "kabc_reject_batch_stats": (None, [C.POINTER(C.c_int64)]),
+    "kabc_pmc_default_opts": (None, [C.POINTER(PmcOpts)]),
+    "kabc_abc_pmc": (C.c_int, [VP, C.POINTER(Prior), C.c_int32, C.POINTER(Cost), C.POINTER(PmcOpts),
+                               C.POINTER(PmcResult)]),
+    "kabc_pmc_kernel_sums": (C.c_int, [VP, C.c_int32, C.c_int64, c_double_p, C.c_int64, c_double_p, c_double_p,
+                                       c_double_p]),
+    "kabc_pmc_stats": (None, [c_double_p]),
     "kabc_register_cost_plugin": (C.c_int, [C.c_char_p, C.POINTER(C.c_int32)]),
     "kabc_plugin_precompile": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "kabc_compile_cost_plugin": (C.c_int, [C.c_char_p, C.POINTER(C.c_int32), C.c_int32, C.c_int32,

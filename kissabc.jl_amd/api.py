@@ -1444,6 +1444,105 @@ def abc_reject(prior, cost, eps=None, n=None, *, draws=None, keep=None, seed=0, 
     return result()
 
 
+class PmcResult(collections.namedtuple("PmcResult", ["theta", "w", "C", "logprior", "eps", "info"])):
+    """abc_pmc's result: the last complete generation as a weighted sample -- `theta` [N][D], normalised weights
+    `w`, costs `C`, `logprior`, its `eps`; `.mean` / `.cov` are its weighted moments, `.ess` = 1 / sum w^2;
+    `.ϵ`/`.ε` alias `.eps`."""
+    __slots__ = ()
+
+    def __getattr__(self, name):
+        if name in ("\u03b5", "\u03f5"):
+            return self.eps
+        if name in ("mean", "cov"):
+            return self.info[name]
+        if name == "ess":
+            return float(1.0 / np.sum(self.w * self.w)) if self.w.size else math.nan
+        raise AttributeError(name)
+
+    def resample(self, n=None, seed=0):
+        """`n` (default N) equally weighted draws from the weighted sample, bundled like smc's `P` (one
+        Particles per parameter).  A host resample with numpy's generator: a convenience, not part of the
+        bit contract."""
+        n = len(self.w) if n is None else int(n)
+        pick = np.random.default_rng(seed).choice(len(self.w), size=n, p=self.w / self.w.sum())
+        return _bundle(self.theta[pick], self.info["scalar"])
+
+
+def abc_pmc(prior, cost, nparticles, *, eps=None, q=None, eps0=math.inf, eps_target=-math.inf, generations=None,
+            kernel="full", scale=2.0, max_draws=None, min_rate=0.0, seed=0, ctx=None):
+    """ABC population Monte Carlo on the GPU (Beaumont, Cornuet, Marin, Robert 2009; kabc_abc_pmc,
+    include/kabc.h): a sequence of rejection samplers, each proposing from a Gaussian mixture around the
+    previous population, with importance weights -- every generation is a weighted sample of
+    prior x 1[cost <= eps_g].  Generation 0 is `abc_reject(prior, cost, eps_0, nparticles, seed=seed)`.
+
+    Schedule: `eps=[...]` runs one generation per entry; without it the schedule is adaptive --
+    eps_0 = `eps0`, eps_g = max(eps_target, quantile(C_{g-1}, q)) (q = 0.5), at most `generations` (20)
+    generations, stopping at `eps_target` or when the quantile no longer falls.  `kernel`: "full" (scale x
+    the weighted covariance) or "diag".  `max_draws` bounds the proposals of ONE generation
+    (min(2^32, 10 000 N)); a generation that cannot be filled ends the run with the one before
+    (`info["stop"] == "exhausted"`), as does a singular covariance ("degenerate").  `min_rate`: stop after a
+    generation that accepted fewer than this share of its proposals.
+
+    Returns PmcResult(theta, w, C, logprior, eps, info); info: log (eps, draws, ess, launches per generation),
+    stop, generations_run, index (each particle's row in its generation's proposal stream:
+    `cost.evaluate(theta[i], nrep=g + 1, seed=seed, first_row=index[i])[g]` is C[i]), course, mean, cov, kernel_ms
+    and its parts proposal_kernel_ms / weight_kernel_ms (KABC_EVAL_TIMING=1), host_rules_ms, wall_ms.  Context.cancel() / Ctrl-C: Cancelled (its `.result` is the last complete generation) /
+    KeyboardInterrupt."""
+    from .costs import check_pmc_args
+    fac = as_factored(prior)
+    scalar = isinstance(prior, UnivariateDistribution)
+    D = len(fac)
+    N, eps_a, qv, G, kid, M = check_pmc_args(cost, fac, nparticles, eps, q, eps0, eps_target, generations, kernel,
+                                             scale, max_draws, min_rate)
+    lib = _lib.load()
+    ctx = ctx or _lib.default_context()
+    t0 = time.perf_counter()
+    o = cd.PmcOpts()
+    lib.kabc_pmc_default_opts(C.byref(o))
+    o.nparticles, o.generations, o.scale, o.min_rate, o.max_draws = N, G, float(scale), float(min_rate), M
+    o.kernel, o.seed = kid, int(seed)
+    if eps_a is not None:
+        o.eps = eps_a.ctypes.data_as(cd.c_double_p)
+    else:
+        o.eps0, o.eps_target, o.q = float(eps0), float(eps_target), qv
+    theta = _lib.result_empty((N, D))
+    w, Cst, lp = _lib.result_empty(N), _lib.result_empty(N), _lib.result_empty(N)
+    index = np.empty(N, dtype=np.int64)
+    mean, cov = np.full(D, math.nan), np.full((D, D), math.nan)
+    log = (cd.PmcGen * G)()
+    r = cd.PmcResult()
+    r.theta, r.w = theta.ctypes.data_as(cd.c_double_p), w.ctypes.data_as(cd.c_double_p)
+    r.cost, r.logprior = Cst.ctypes.data_as(cd.c_double_p), lp.ctypes.data_as(cd.c_double_p)
+    r.index = index.ctypes.data_as(C.POINTER(C.c_int64))
+    r.log = log
+    r.mean, r.cov = mean.ctypes.data_as(cd.c_double_p), cov.ctypes.data_as(cd.c_double_p)
+    cc = cost.to_c()
+
+    def result():
+        g = int(r.generations_run)
+        m = N if g else 0
+        st = (C.c_double * 4)()
+        lib.kabc_pmc_stats(st)
+        info = {"log": [dict(eps=log[i].eps, draws=int(log[i].draws), ess=log[i].ess, launches=int(log[i].launches))
+                        for i in range(g)],
+                "stop": cd.PMC_STOP_NAMES[r.stop], "generations_run": g, "index": index[:m],
+                "course": "phases" if r.course else "fused", "mean": mean, "cov": cov, "kernel_ms": r.kernel_ms,
+                "proposal_kernel_ms": st[0], "weight_kernel_ms": st[1], "host_rules_ms": st[2],
+                "weight_launches": int(st[3]), "wall_ms": (time.perf_counter() - t0) * 1e3, "scalar": scalar}
+        return PmcResult(theta[:m], w[:m], Cst[:m], lp[:m], r.eps, info)
+
+    with ctx.interruptible():
+        status = lib.kabc_abc_pmc(ctx.handle, fac.to_c(), D, C.byref(cc), C.byref(o), C.byref(r))
+        if status == cd.KABC_ERR_CANCELLED:
+            try:
+                _lib.check(status)
+            except _lib.Cancelled as e:
+                e.result = result()
+                raise
+        _lib.check(status)
+    return result()
+
+
 class RejectBatchResult(list):
     """abc_reject_batch's result: one RejectResult per run (a list), and `.info` about the whole call."""
 

@@ -123,6 +123,51 @@ def check_reject_args(cost, D, eps, n, draws, keep, first_row):
     return (0 if keep is not None else int(n)), (0 if draws is None else int(draws)), (0 if keep is None else int(keep))
 
 
+def check_pmc_args(cost, prior, nparticles, eps, q, eps0, eps_target, generations, kernel, scale, max_draws, min_rate):
+    """the refusals of abc_pmc that need no library; returns (N, eps array or None, q, generations, kernel id,
+    max_draws) as kabc_pmc_opts_t takes them (eps None: the adaptive schedule)"""
+    D = len(prior)
+    if not isinstance(cost, DeviceCost):
+        raise TypeError("`cost` must be a DeviceCost on the MI355X path")
+    if not 1 <= D <= cd.KABC_MAX_DIM:
+        raise ValueError(f"length(θ) = {D} outside 1..{cd.KABC_MAX_DIM}")
+    if cost.dim is not None and int(cost.dim) != D:
+        raise ValueError(f"{cost!r} takes rows of {int(cost.dim)} parameters, got {D}")
+    if any(getattr(c, "discrete", False) for c in prior.p):
+        raise ValueError("abc_pmc needs a continuous prior: a Gaussian proposal density is not a pmf")
+    N = int(nparticles)
+    if not D + 2 <= N <= cd.KABC_PMC_MAX_PARTICLES:
+        raise ValueError(f"nparticles = {N} outside D + 2 = {D + 2} .. 2^20")
+    if kernel not in ("full", "diag"):
+        raise ValueError('kernel must be "full" or "diag"')
+    if not float(scale) > 0.0:
+        raise ValueError("scale must be > 0")
+    if math.isnan(float(min_rate)):
+        raise ValueError("min_rate is NaN")
+    if eps is not None:
+        if q is not None:
+            raise ValueError("give either eps (an explicit schedule) or q (the adaptive one), not both")
+        eps = np.ascontiguousarray(np.asarray(eps, dtype=np.float64).ravel())
+        if eps.size < 1 or np.isnan(eps).any():
+            raise ValueError("eps is empty or holds a NaN")
+        if generations is not None and int(generations) != eps.size:
+            raise ValueError("generations must be len(eps) with an explicit schedule")
+        G = eps.size
+    else:
+        q = 0.5 if q is None else float(q)
+        if not 0.0 < q < 1.0:
+            raise ValueError("q outside (0, 1)")
+        if math.isnan(float(eps0)) or math.isnan(float(eps_target)):
+            raise ValueError("eps0 / eps_target is NaN")
+        G = 20 if generations is None else int(generations)
+    if not 1 <= G < 1 << 24:
+        raise ValueError("generations outside 1 .. 2^24 - 1")
+    M = min(1 << 32, 10_000 * N) if max_draws is None else int(max_draws)
+    if not N <= M <= 1 << 32:
+        raise ValueError("max_draws outside nparticles .. 2^32")
+    return N, eps, q, G, (cd.PMC_KERNEL_DIAG if kernel == "diag" else cd.PMC_KERNEL_FULL), M
+
+
 def check_reject_batch_args(costs, D, eps, n, nruns, seeds, draws, keep, first_row):
     """the refusals of abc_reject_batch that need no library; returns (cost_list, seeds or None, eps_list or
     None, n_accept, max_draws, keep): seeds None = one seed for every run, eps_list None = keep mode"""

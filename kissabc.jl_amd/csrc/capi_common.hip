@@ -224,6 +224,21 @@ kabc_status_t enqueue_prior_draw(hipStream_t s, void* m_rand, void* m_logpdf, co
     P.mode = 2;
     if (m_rand) KABC_HIP_CHECK(rtc_launch(m_rand, grid, block, &P, s));
     else hipLaunchKernelGGL(prior_rand_kernel, grid, block, 0, s, P);
+    KABC_HIP_CHECK(hipGetLastError());
+    return enqueue_prior_push_logpdf(s, m_logpdf, d_prep, d_raw, D, n, d_theta, d_lp);
+}
+
+kabc_status_t enqueue_prior_push_logpdf(hipStream_t s, void* m_logpdf, const PriorDev* d_prep, const kabc_prior_t* d_raw,
+                                        int D, int64_t n, double* d_theta, double* d_lp) {
+    PriorUtilArgs P;
+    std::memset(&P, 0, sizeof P);
+    P.prior = d_prep;
+    P.raw = d_raw;
+    P.n = n;
+    P.D = D;
+    const dim3 grid = prior_util_geom(P), block(256);
+    if (grid.x == 0) return KABC_OK;
+    P.out = d_theta;
     P.x = d_theta;
     P.mode = 1;
     if (m_logpdf) KABC_HIP_CHECK(rtc_launch(m_logpdf, grid, block, &P, s));
@@ -291,6 +306,10 @@ int32_t kabc_abi_sizeof(int32_t which) {
     // (a second block of the numbering: the structs of kabc_abc_reject; 0..10 is closed)
     if (which == 32) return (int32_t)sizeof(kabc_reject_opts_t);
     if (which == 33) return (int32_t)sizeof(kabc_reject_result_t);
+    // (34 stays -1; the structs of kabc_abc_pmc)
+    if (which == 35) return (int32_t)sizeof(kabc_pmc_opts_t);
+    if (which == 36) return (int32_t)sizeof(kabc_pmc_gen_t);
+    if (which == 37) return (int32_t)sizeof(kabc_pmc_result_t);
     return (which >= 0 && which < (int32_t)(sizeof sz / sizeof sz[0])) ? sz[which] : -1;
 }
 int32_t kabc_abi_offsetof(int32_t which, int32_t field) {
@@ -336,7 +355,23 @@ int32_t kabc_abi_offsetof(int32_t which, int32_t field) {
          KABC_OFF(kabc_reject_result_t, draws), KABC_OFF(kabc_reject_result_t, accepted_seen),
          KABC_OFF(kabc_reject_result_t, eps), KABC_OFF(kabc_reject_result_t, exhausted), KABC_OFF(kabc_reject_result_t, course),
          KABC_OFF(kabc_reject_result_t, launches), KABC_OFF(kabc_reject_result_t, kernel_ms)}};
+    static const std::vector<std::vector<int32_t>> off3 = {
+        {KABC_OFF(kabc_pmc_opts_t, nparticles), KABC_OFF(kabc_pmc_opts_t, generations), KABC_OFF(kabc_pmc_opts_t, eps),
+         KABC_OFF(kabc_pmc_opts_t, eps0), KABC_OFF(kabc_pmc_opts_t, eps_target), KABC_OFF(kabc_pmc_opts_t, q),
+         KABC_OFF(kabc_pmc_opts_t, scale), KABC_OFF(kabc_pmc_opts_t, min_rate), KABC_OFF(kabc_pmc_opts_t, max_draws),
+         KABC_OFF(kabc_pmc_opts_t, kernel), KABC_OFF(kabc_pmc_opts_t, reserved), KABC_OFF(kabc_pmc_opts_t, seed)},
+        {KABC_OFF(kabc_pmc_gen_t, eps), KABC_OFF(kabc_pmc_gen_t, draws), KABC_OFF(kabc_pmc_gen_t, ess),
+         KABC_OFF(kabc_pmc_gen_t, launches)},
+        {KABC_OFF(kabc_pmc_result_t, theta), KABC_OFF(kabc_pmc_result_t, w), KABC_OFF(kabc_pmc_result_t, cost),
+         KABC_OFF(kabc_pmc_result_t, logprior), KABC_OFF(kabc_pmc_result_t, index), KABC_OFF(kabc_pmc_result_t, log),
+         KABC_OFF(kabc_pmc_result_t, mean), KABC_OFF(kabc_pmc_result_t, cov), KABC_OFF(kabc_pmc_result_t, eps),
+         KABC_OFF(kabc_pmc_result_t, generations_run), KABC_OFF(kabc_pmc_result_t, stop),
+         KABC_OFF(kabc_pmc_result_t, course), KABC_OFF(kabc_pmc_result_t, kernel_ms)}};
 #undef KABC_OFF
+    if (which >= 35 && which <= 37) {  // (the structs of kabc_abc_pmc)
+        const std::vector<int32_t>& f3 = off3[(size_t)(which - 35)];
+        return (field >= 0 && field < (int32_t)f3.size()) ? f3[(size_t)field] : -1;
+    }
     if (which == 32 || which == 33) {  // (the second block: see kabc_abi_sizeof)
         const std::vector<int32_t>& f2 = off2[(size_t)(which - 32)];
         return (field >= 0 && field < (int32_t)f2.size()) ? f2[(size_t)field] : -1;

@@ -88,6 +88,9 @@ bool prepare_priors(const kabc_prior_t* prior, int D, PriorSet& out);
 kabc_status_t enqueue_prior_draw(hipStream_t s, void* m_rand, void* m_logpdf, const PriorDev* d_prep,
                                  const kabc_prior_t* d_raw, int D, int64_t n, uint64_t seed, uint32_t first_walker,
                                  uint32_t domain, double* d_theta, double* d_lp);
+// its last two steps alone, for rows that are already in d_theta (kabc_abc_pmc's proposal rows)
+kabc_status_t enqueue_prior_push_logpdf(hipStream_t s, void* m_logpdf, const PriorDev* d_prep, const kabc_prior_t* d_raw,
+                                        int D, int64_t n, double* d_theta, double* d_lp);
 
 }  // namespace kabc
 
